@@ -5,15 +5,21 @@ A "step" is one Arnoldi/Lanczos step of EPSSolve_KrylovSchur_Default: BVMatMultC
 BVOrthonormalizeColumn (CGS with refinement, all passes, scaling).
 
 What is timed.  ONE Krylov-Schur solve (nev=10, ncv=m=30, tol 1e-8, keep 0.5, largest magnitude) runs through
-warm-up, timed region and an instrumented tail without being restarted in between; the phase boundaries sit at restart
-boundaries of that solve (the solver's stopping-test callback, krylovschur.c:289), so the timed region is a whole number
-of restart cycles in steady state - expansion (k = 16..30 here), host projected solve, restart BVMultInPlace +
-BVCopyColumn - and its rate does not depend on --steps:
+warm-up, timed region and (--full) an instrumented tail without being restarted in between; the phase boundaries sit at
+the solver's stopping-test callback (krylovschur.c:289), so the timed region is made of restart cycles in steady state -
+expansion (k = 16..30 here), host projected solve, restart BVMultInPlace + BVCopyColumn:
   warm-up : the first cycle (k = 1..30) and whole cycles until at least --warmup steps (>= 45) have run;
-  timed   : whole cycles until at least max(--steps, --min-steps) steps have run (--min-steps 200 keeps the region
-            above 200 ms on one GPU); "steps" in the JSON line is the number actually timed;
-  tail    : the same number of steps again with HIP events on every kernel class (untimed): the per-kernel table.
+  timed   : exactly max(--steps, --min-steps) steps (--min-steps defaults to 0); the solver's step cap
+            (ks_eps_set_max_steps) cuts the last expansion short when that is not a whole number of cycles;
+            "steps" in the JSON line is the number timed;
+  tail    : (--full) the same number of steps again with HIP events on every kernel class (untimed): the per-kernel table.
 Inputs and workspace are resident in HBM when the timed region starts.
+
+A plain run measures the headline alone (with the update kernel's HIP events inside the timed region, as the roofline
+figure needs). --full adds everything else: the instrumented tail and its per-kernel tables, the measured copy ceiling,
+the rocprofv3 counter passes, the SpMV layouts, the general-layout and drop-in legs, configs C2 / C5, the CPU baseline
+and, for N>1, the per-rank breakdown and the side legs.
+--dump-outputs DIR writes what the solve handed its caller after the last timed step (see LastStep) as .npy files.
 
 Workload (config.workload):
   N=1 : BASELINE config 3 - 3-D 7-point Laplacian 216^3 (n = 10 077 696, nnz = 70 263 936)
@@ -52,9 +58,11 @@ class Phases:
     Every rank runs the same replicated control flow (identical step counts), so the boundaries - which hold a barrier -
     fall on the same restart everywhere without any extra collective."""
 
-    def __init__(self, ks, ctx, eps, barrier, warmup, steps, tail_steps, timed_classes):
+    def __init__(self, ks, ctx, eps, barrier, warmup, steps, tail_steps, timed_classes, exact=False, on_timed_end=None):
         self.ks, self.ctx, self.eps, self.barrier = ks, ctx, eps, barrier
         self.warmup, self.steps, self.tail_steps, self.timed_classes = warmup, steps, tail_steps, timed_classes
+        self.exact = exact                # True: exactly `steps` timed steps (the solver's step cap); False: whole cycles, at least `steps`
+        self.on_timed_end = on_timed_end  # called with the solver right after the timed region closes
         self.phase = 0
         self.base = 0                 # steps of earlier solves (a solve that converges inside the region is followed by a fresh one)
         self.marks = {}               # name -> (steps, passes, time)
@@ -96,8 +104,14 @@ class Phases:
                 self.ctx.prof_reset()
             self.phase = 1
             self._mark("t0", steps)
+            if self.exact:
+                self.eps.SetMaxSteps(steps + self.steps - self.base)
         elif self.phase == 1 and steps - self.marks["t0"][0] >= self.steps:
             self._mark("t1", steps)
+            if self.exact:
+                self.eps.SetMaxSteps(0)
+            if self.on_timed_end is not None:
+                self.on_timed_end(self.eps)
             if self.tail_steps > 0:
                 self.prof_timed = self.ctx.prof_get(by_variant=True) if self.timed_classes is not None else {}
                 self.ctx.prof_enable(True)
@@ -123,6 +137,8 @@ class Phases:
         solves = 0
         while self.phase < 3:
             self.eps.SetRandomSeed(seed + solves)
+            if self.exact:                # a solve that converged inside the timed region: the next one takes the steps left
+                self.eps.SetMaxSteps(self.marks["t0"][0] + self.steps - self.base if self.phase == 1 else 0)
             self.eps.Solve()
             self.base += self.eps.GetStats()["arnoldi_steps"]
             solves += 1
@@ -136,7 +152,14 @@ class Phases:
         starts = [s0] + ends[:-1]
         lens = [e - b for b, e in zip(starts, ends)]
         # column orthogonalised by a step = number of previous columns k; a cycle of L steps ends at column ncv: k = ncv-L+1 .. ncv
-        ksum = sum(L * (2 * ncv - L + 1) / 2.0 for L in lens)
+        last = [ncv] * len(lens)
+        if self.exact:                # ... except a last cycle the step cap cut short: it starts where the cycle before it started
+            at = [0] + [s for (_, s) in self.cycles]
+            i = at.index(s1)
+            before = at[i - 1] - at[i - 2]
+            if lens[-1] < before:
+                last[-1] = ncv - (before - lens[-1])
+        ksum = sum(L * (2 * e - L + 1) / 2.0 for L, e in zip(lens, last))
         return {"steps": s1 - s0, "seconds": t1 - t0, "gs_passes": p1 - p0, "cycles": len(lens), "cycle_steps": lens,
                 "mean_k": ksum / max(1, s1 - s0)}
 
@@ -298,7 +321,7 @@ def live_traffic(kname, limit=90.0):
                 env = dict(os.environ); env["TMPDIR"] = "/tmp"
                 # the interpreter itself directly behind "--" (no env / shell hop: the profiler's preloaded library has initialised the GPU by then)
                 cmd = ["rocprofv3", "--kernel-trace", "--pmc", ctr, "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-                       "--steps", "60", "--warmup", "20", "--min-steps", "60", "--no-cpu-baseline", "--no-configs", "--no-pmc"]
+                       "--steps", "60", "--warmup", "20", "--min-steps", "60", "--full", "--no-cpu-baseline", "--no-configs", "--no-pmc"]
                 try:
                     cp = subprocess.run(cmd, env=env, cwd="/tmp", stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=limit)
                     child[ctr] = (cp.returncode, " | ".join(cp.stderr.decode(errors="replace").strip().splitlines()[-3:])[-400:])
@@ -345,9 +368,11 @@ def measured_copy_ceiling(torch, gib=1.0, reps=10):
     return 2.0 * n * 8 / ms / 1e6
 
 
-def measure(ks, ctx, A, B, barrier, warmup, steps, min_steps, nev, ncv, ptype, prof=True, tail=True, setup=None, seed=0x12345678, timed_events=True):
+def measure(ks, ctx, A, B, barrier, warmup, steps, min_steps, nev, ncv, ptype, prof=True, tail=True, setup=None, seed=0x12345678, timed_events=True,
+            exact=False, on_timed_end=None):
     """Run the phased solve on (A, B); returns (Phases, timed dict). timed_events=False: no HIP events inside the timed region (a pair per
-    update launch costs a step of 100 us about 5 %); the per-kernel figures then come from the instrumented tail alone."""
+    update launch costs a step of 100 us about 5 %); the per-kernel figures then come from the instrumented tail alone. exact / on_timed_end:
+    see Phases."""
     eps = ks.EPS(ctx)
     eps.SetOperators(A, B)
     eps.SetProblemType(ptype)
@@ -356,11 +381,45 @@ def measure(ks, ctx, A, B, barrier, warmup, steps, min_steps, nev, ncv, ptype, p
     if setup:
         setup(eps)
     k_eff = max(steps, min_steps)
-    ph = Phases(ks, ctx, eps, barrier, max(warmup, ncv + ncv // 2), k_eff, k_eff if (prof and tail) else 0, UPD_CLASSES[:2] if (prof and timed_events) else None)
+    ph = Phases(ks, ctx, eps, barrier, max(warmup, ncv + ncv // 2), k_eff, k_eff if (prof and tail) else 0, UPD_CLASSES[:2] if (prof and timed_events) else None,
+                exact=exact, on_timed_end=on_timed_end)
     eps.SetStoppingTestFunction(ph)
     ph.run(seed)
     eps.SetStoppingTestFunction(None)
     return eps, ph, ph.timed(ncv)
+
+
+class LastStep:
+    """--dump-outputs: what the solve hands its caller after the last timed step, taken by EPSMonitor at the restart that closes the timed
+    region (before the instrumented tail, if any, moves on):
+      ritz_values         - the Ritz values of the projected problem (EPSMonitor's eigr, nest entries, in the solver's order);
+      error_estimates     - their error estimates up to the first unconverged one (EPSMonitor's errest[:nconv+1]);
+      basis_vector_sample - the basis vector the last step appended (column nest of the BV), a fixed seeded sample of this rank's rows.
+    All float64. Same arguments, same inputs: the matrix is a formula and the start vectors are seeded."""
+    SAMPLE_ROWS = 1 << 20            # 8 MB of the 80 MB vector of the 216^3 workload
+    SAMPLE_SEED = 20261016
+
+    def __init__(self):
+        self.eps, self.arrays = None, None
+
+    def arm(self, eps):
+        self.eps = eps
+        eps.MonitorSet(self._monitor)
+
+    def _monitor(self, its, nconv, eigr, eigi, errest):
+        if self.arrays is None:      # the first restart after arm() only; later ones are the tail's
+            self.arrays = {"ritz_values": eigr, "error_estimates": errest[:nconv + 1], "basis_vector": self.eps.GetBV().column(len(eigr))}
+
+    def write(self, path):
+        import numpy as np
+        if self.arrays is None:
+            raise RuntimeError("--dump-outputs: the solver never reached the end of the timed region")
+        os.makedirs(path, exist_ok=True)
+        x = self.arrays.pop("basis_vector")
+        rows = np.sort(np.random.default_rng(self.SAMPLE_SEED).choice(x.size, size=min(x.size, self.SAMPLE_ROWS), replace=False))
+        self.arrays["basis_vector_sample"] = x[rows]
+        for name, a in self.arrays.items():
+            np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def spmv_leg(ks, ctx, make_mat, reps=40):
@@ -599,7 +658,8 @@ def headline(world, steps, dt, warm_steps, t, args, workload, mat):
         "dtype": "f64", "data": "synthetic",
         "config": {"workload": workload, "rows_per_gpu": mat["n"], "nnz_per_gpu": mat["nnz"], "n_global": mat["N"], "nev": NEV, "ncv": NCV,
                    "orthog": "CGS, refine ifneeded eta=0.7071", "gs_passes_per_step": t["gs_passes"] / steps,
-                   "timed_region": "whole restart cycles of one continuing solve in steady state (after the first cycle and %d warm-up steps)" % warm_steps,
+                   "timed_region": "%d steps of one continuing solve in steady state from a restart on (after the first cycle and %d warm-up steps); "
+                                   "the solver's step cap ends the last cycle early when the steps are not a whole number of cycles" % (steps, warm_steps),
                    "steps_requested": args.steps, "min_steps": args.min_steps, "cycles": t["cycles"], "restarts": t["cycles"],
                    "steps_per_cycle": round(steps / t["cycles"], 2), "mean_k": round(t["mean_k"], 2), "timed_seconds": round(dt, 4),
                    "parallelism": "row-slab x%d" % world,
@@ -703,7 +763,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=60)
-    ap.add_argument("--min-steps", type=int, default=200, help="lower bound of the timed region in steps (>= 200 ms on one GPU)")
+    ap.add_argument("--min-steps", type=int, default=0, help="lower bound of the timed region in steps (200 keeps it above 200 ms on one GPU)")
     ap.add_argument("--side", type=int, default=216, help="grid side per GPU slab (216 -> 10 077 696 rows per GPU)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prof", action="store_true", help="disable the per-kernel HIP-event timing")
@@ -714,7 +774,11 @@ def main():
     ap.add_argument("--no-oneshot", action="store_true", help="N>1: skip the side legs that repeat the measurements with the one-shot allreduce")
     ap.add_argument("--no-side-legs", action="store_true", help="N>1: the weak headline only (no strong-scaling leg, no one-shot legs)")
     ap.add_argument("--side-legs", action="store_true", help=argparse.SUPPRESS)       # the side legs themselves (a child process of every rank)
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline as well (see the module docstring); the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the solve computed in its last timed step to DIR/<name>.npy (class LastStep)")
     args = ap.parse_args()
+    if max(args.steps, args.min_steps) < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args))
@@ -783,12 +847,13 @@ def main():
         dist.all_gather(parts, tt)
         return [p.cpu().tolist() for p in parts]
 
-    def run_leg(scaling, prof, peer_halo=False):
+    def run_leg(scaling, prof, peer_halo=False, tail=True, on_timed_end=None):
         """One phased measurement on this rank's slab of the weak or the strong problem; every rank leaves with all ranks' records, so dt (the
         maximum over the ranks, as the contract asks) and the breakdown are the same everywhere."""
         A, workload = slab_problem(ks, ctx, side, world, rank, scaling, force_dist)
         halo = A.set_halo("peer") if peer_halo else None          # collective: boundary entries straight into the neighbours' ghost mailboxes
-        eps, ph, t = measure(ks, ctx, A, None, barrier, args.warmup, args.steps, args.min_steps, NEV, NCV, ks.EPS_HEP, prof=prof)
+        eps, ph, t = measure(ks, ctx, A, None, barrier, args.warmup, args.steps, args.min_steps, NEV, NCV, ks.EPS_HEP, prof=prof, tail=tail, exact=True,
+                             on_timed_end=on_timed_end)
         tail_steps = (ph.marks["t2"][0] - ph.marks["t1"][0]) if "t2" in ph.marks else 0
         recs = gather_records(rank_record(ph, t, tail_steps))
         return {"A": A, "workload": workload, "eps": eps, "ph": ph, "t": t, "dt": max(r[0] for r in recs), "recs": recs, "tail_steps": tail_steps, "halo": halo,
@@ -844,14 +909,17 @@ def main():
         dist.barrier(); dist.destroy_process_group()
         return
 
-    weak = run_leg("weak", prof=not args.no_prof)
+    last = LastStep() if (args.dump_outputs and rank == 0) else None
+    weak = run_leg("weak", prof=not args.no_prof, tail=args.full, on_timed_end=last and last.arm)
+    if last is not None:
+        last.write(args.dump_outputs)
     A, eps, ph, t, dt, workload = weak["A"], weak["eps"], weak["ph"], weak["t"], weak["dt"], weak["workload"]
     steps = t["steps"]
     prof_timed, prof = ph.prof_timed, ph.prof_tail
     tail_steps = weak["tail_steps"]
 
     legs = None
-    if dist is not None and not args.no_side_legs:
+    if dist is not None and args.full and not args.no_side_legs:
         pt = torch.zeros(1, dtype=torch.int64, device="cpu" if rehearsal else "cuda")
         if rank == 0:
             pt[0] = free_port()
@@ -870,11 +938,11 @@ def main():
                                   "note": "the HIP runtime libksgpu.so is bound to in this process (torch's bundled copy when torch is installed: slepc_amd/_lib.py bind_hip_runtime)"}
         except Exception as e:       # noqa: BLE001
             out["hip_runtime"] = {"error": repr(e)}
-        if dist is not None:
+        if dist is not None and args.full:
             out["multi_gpu_breakdown"] = comm_breakdown(weak["recs"], steps, "weak")
         if prof_timed:
             rl = update_kernel_roofline(ks, prof_timed)
-            if rl:
+            if rl and args.full:
                 try:
                     cp = measured_copy_ceiling(torch)
                     rl["measured_copy_GBps"] = round(cp, 1)
@@ -891,6 +959,7 @@ def main():
                         rl["traffic_over_bytes_per_executed_launch"] = round(tb / rl["bytes_per_executed_launch"], 4)
                     else:
                         rl["traffic_live_note"] = tnote
+            if rl:
                 out["roofline"] = rl
         if prof:
             kernels = []
@@ -914,7 +983,7 @@ def main():
             out["kernel_classes_untimed_instrumented_pass"] = class_table(prof, tail_steps)
             out["kernels_untimed_instrumented_pass"] = kernels[:12]
         del eps
-        if world == 1 and not force_dist and not args.no_configs:
+        if args.full and world == 1 and not force_dist and not args.no_configs:
             try:
                 legs = {}
                 for fmt in ("dict", "odict", "sell", "csr", "csrregs", "csrvec"):
@@ -936,7 +1005,7 @@ def main():
                     Ag = ks.Mat.laplacian3d(ctx, side, side, side)
                 finally:
                     os.environ.pop("KSGPU_SPMV", None)
-                eg, phg, tg = measure(ks, ctx, Ag, None, barrier, args.warmup, args.steps, args.min_steps, NEV, NCV, ks.EPS_HEP, prof=False)
+                eg, phg, tg = measure(ks, ctx, Ag, None, barrier, args.warmup, args.steps, args.min_steps, NEV, NCV, ks.EPS_HEP, prof=False, exact=True)
                 out["value_general_layout"] = {"value": tg["steps"] / tg["seconds"], "unit": "steps/s", "ms_per_step": 1e3 * tg["seconds"] / tg["steps"], "steps": tg["steps"],
                                                "spmv_layout": Ag.layout(), "spmv_avg_us": out.get("spmv_layouts", {}).get("legs", {}).get("csr", {}).get("avg_us"),
                                                "note": "the headline's solve with KSGPU_SPMV=csr: MatMult through the CSR row-block kernel (12 B per nonzero, any "
@@ -952,7 +1021,7 @@ def main():
             except Exception as e:      # noqa: BLE001
                 out["dropin_slot_path"] = {"value": None, "error": repr(e)}
             out["configs"] = side_configs(ks, ctx, barrier, args)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(side)
             except Exception as e:       # noqa: BLE001 - the baseline must not take the GPU number down with it

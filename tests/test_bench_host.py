@@ -63,6 +63,88 @@ def test_phases_cover_whole_cycles_and_do_not_depend_on_the_requested_steps():
         assert eps.solves == 1                                   # one continuing solve
 
 
+class CappedEPS(FakeEPS):
+    """FakeEPS with the library's step cap (ks_eps_set_max_steps): an expansion is cut short at the cap and the solve stops there."""
+    def __init__(self, ncv): super().__init__(ncv); self.max_steps = 0; self.monitor = None
+    def SetMaxSteps(self, s): self.max_steps = s
+    def MonitorSet(self, f): self.monitor = f
+    def Solve(self):
+        self.solves += 1; self.steps = 0; its = 0
+        while True:
+            its += 1
+            L = self.ncv if its == 1 else self.ncv // 2
+            if self.max_steps:
+                L = min(L, self.max_steps - self.steps)
+            self.steps += L; self.total_steps += L
+            reason = self.cb(its, 10 ** 9, 0, 10)
+            if not reason and self.max_steps and self.steps >= self.max_steps:
+                reason = 2
+            if self.monitor:
+                self.monitor(its, 0, [float(self.total_steps)], [0.0], [1.0])
+            if reason:
+                return
+
+
+def test_phases_time_exactly_the_requested_steps():
+    """exact=True (the headline): the timed region starts on a restart after the warm-up and holds exactly the requested steps; the step cap
+    cuts the last expansion short when they are not a whole number of cycles, mean k counts that cycle from where it started, the tail still
+    repeats the region, and the hook at the end of the region runs once, before the tail."""
+    ks = types.SimpleNamespace(EPS_CONVERGED_USER=2)
+    clock = [0.0]
+
+    def barrier():
+        clock[0] += 1.0
+        return clock[0]
+    for want, tail in ((20, True), (7, False), (200, True), (300, False)):
+        eps = CappedEPS(30); ctx = FakeCtx(); ends = []
+        ph = bench.Phases(ks, ctx, eps, barrier, max(5, 45), want, want if tail else 0, bench.UPD_CLASSES[:2], exact=True,
+                          on_timed_end=lambda e: ends.append((e.total_steps, e.max_steps)))
+        eps.cb = ph
+        ph.run(1)
+        t = ph.timed(30)
+        assert ph.marks["t0"][0] == 45 and t["steps"] == want
+        full, part = divmod(want, 15)
+        assert t["cycle_steps"] == [15] * full + ([part] if part else [])
+        # k = 16..30 in a whole cycle, k = 16..15+part in the cut one
+        assert abs(t["mean_k"] - (full * 15 * 23.0 + sum(range(16, 16 + part))) / want) < 1e-12
+        assert t["gs_passes"] == 2 * want
+        assert ends == [(45 + want, 0)]                          # once, at the end of the region, with the cap already lifted
+        if tail:
+            assert ph.marks["t2"][0] - ph.marks["t1"][0] >= want
+        else:
+            assert "t2" not in ph.marks and eps.total_steps == 45 + want
+        assert eps.solves == 1
+
+
+def test_last_step_dump(tmp_path):
+    """--dump-outputs: the monitor call at the restart that closes the timed region is the one kept (the tail's later calls are not), and the
+    files are float64 .npy, the basis vector as a fixed sample of its rows, the same from run to run."""
+    import numpy as np
+    n = 3 * bench.LastStep.SAMPLE_ROWS
+    cols = {4: np.arange(n, dtype=np.float64), 5: -np.ones(n)}
+
+    class BV:
+        def column(self, j): return cols[j]
+
+    class EPS:
+        def MonitorSet(self, f): self.f = f
+        def GetBV(self): return BV()
+    written = []
+    for d in ("a", "b"):
+        last, eps = bench.LastStep(), EPS()
+        last.arm(eps)
+        eps.f(7, 1, np.array([4.0, 3.0, 2.0, 1.0]), np.zeros(4), np.array([1e-9, 1e-3, 0.5, 0.5]))
+        eps.f(8, 1, np.array([5.0, 4.0, 3.0, 2.0, 1.0]), np.zeros(5), np.ones(5))      # a later restart: ignored
+        last.write(str(tmp_path / d))
+        written.append({f: np.load(tmp_path / d / f) for f in ("ritz_values.npy", "error_estimates.npy", "basis_vector_sample.npy")})
+    a, b = written
+    assert a["ritz_values.npy"].tolist() == [4.0, 3.0, 2.0, 1.0] and a["error_estimates.npy"].tolist() == [1e-9, 1e-3]
+    s = a["basis_vector_sample.npy"]
+    assert s.dtype == np.float64 and s.size == bench.LastStep.SAMPLE_ROWS and np.all(np.diff(s) > 0) and s.max() < n
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+
+
 def test_self_launch_command(monkeypatch):
     seen = {}
 

@@ -675,7 +675,7 @@ def test_bench_n_gt_1_line_with_two_ranks_on_one_gpu():
     import json
     import subprocess
     env = dict(os.environ); env["BENCH_PROVIDER"] = "gloo"; env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--min-steps", "60", "--side", "96"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--min-steps", "60", "--side", "96", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
