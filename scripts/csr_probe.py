@@ -1,6 +1,6 @@
 """The general-matrix CSR kernels on the bench matrix (216^3 7-point Laplacian) and on ragged random matrices: us per product and
 CSR-algorithmic TB/s (SURVEY 8d bytes) for KSGPU_SPMV = csr (wave-per-64-rows row-block kernel; short rows: its LDS-DMA form), csrregs (the register-staged form also for short rows),
-csrblock (workgroup per 256 rows), csrvec, sell."""
+csrvec, sell."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -8,7 +8,7 @@ import slepc_amd as ks
 
 ctx = ks.Context(0)
 nx = int(sys.argv[1]) if len(sys.argv) > 1 else 216
-fmts = sys.argv[2].split(",") if len(sys.argv) > 2 else ["csr", "csrblock", "sell", "csrvec"]
+fmts = sys.argv[2].split(",") if len(sys.argv) > 2 else ["csr", "csrregs", "sell", "csrvec"]
 
 
 def timeit(A, reps=100):

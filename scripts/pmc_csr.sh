@@ -1,6 +1,6 @@
-# SQ / LDS / memory counters of the general-matrix CSR kernels on the 216^3 Laplacian: KSGPU_SPMV = csr (wave form), csrblock, sell
+# SQ / LDS / memory counters of the general-matrix CSR kernels on the 216^3 Laplacian: KSGPU_SPMV = csr (wave form), csrregs, sell
 R=$GRAFT_REPO_ROOT
-FMTS=${1:-"csr csrblock sell"}
+FMTS=${1:-"csr csrregs sell"}
 cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out/pmc_csr.txt
 : > $OUT

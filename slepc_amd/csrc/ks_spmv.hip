@@ -79,61 +79,22 @@ __global__ __launch_bounds__(SPMV_BLOCK) void k_spmv_csr(int nrows, const int *_
 }
 
 
-// ---- CSR, row blocks streamed through LDS ("coalesced CSR row-block loads") -----------------------------------------------------
-// A workgroup takes 256 consecutive rows; their entries are ONE contiguous run of col / val, which it streams in chunks of 1024
-// with fully coalesced nontemporal loads (lane e of a chunk loads entry e: no lane idles on a short row, no row length is a
-// multiple of anything), gathers x for each entry (4 independent gathers per lane in flight) and parks value and x in LDS;
-// then every row (= thread) runs the reference's own loop over its segment: acc = fma(val, x, acc) in entry order, so the
-// result has the bits of the SELL / dictionary kernels. LDS slots are skewed by one per 32 so that rows whose length is a
-// multiple of 32 do not put a whole wave on one bank. The general-matrix kernel: ragged rows, empty rows, rows longer than a
-// chunk; the CSR-vector kernel above keeps the small matrices and the compressed off-diagonal block.
-constexpr int CS_EPT = 4, CS_CHUNK = 256 * CS_EPT;    // 1024-entry chunks: 212 us on the 216^3 Laplacian (512: 224, 2048: 252)
-__device__ __forceinline__ int cs_slot(int e) { return e + (e >> 5); }
-__global__ __launch_bounds__(256) void k_spmv_csr_stream(int n, const int *__restrict__ rp, const int *__restrict__ col, const double *__restrict__ val,
-                                                         const double *__restrict__ x, double *__restrict__ y)
-{
-  __shared__ double sa[CS_CHUNK + CS_CHUNK / 32], sx[CS_CHUNK + CS_CHUNK / 32];
-  __shared__ int erange[2];
-  const int tid = threadIdx.x;
-  for (long long R0 = (long long)blockIdx.x * 256; R0 < n; R0 += (long long)gridDim.x * 256) {
-    const long long r = R0 + tid;
-    const bool has = r < n;
-    const int p0 = has ? ksk::ldstream(rp + r) : 0, p1 = has ? ksk::ldstream(rp + r + 1) : 0;
-    if (tid == 0) erange[0] = p0;
-    if (has && (r == n - 1 || tid == 255)) erange[1] = p1;
-    __syncthreads();
-    const int E0 = erange[0], E1 = erange[1];
-    double acc = 0.0;
-    for (int e0 = E0; e0 < E1; e0 += CS_CHUNK) {
-      int c[CS_EPT]; double a[CS_EPT];
-#pragma unroll
-      for (int u = 0; u < CS_EPT; u++) { const int e = e0 + u * 256 + tid; const bool ok = e < E1; c[u] = ok ? ksk::ldstream(col + e) : -1; a[u] = ok ? ksk::ldstream(val + e) : 0.0; }
-#pragma unroll
-      for (int u = 0; u < CS_EPT; u++) { const int sl = cs_slot(u * 256 + tid); sa[sl] = a[u]; sx[sl] = c[u] >= 0 ? x[c[u]] : 0.0; }
-      __syncthreads();
-      const int lo = max(p0, e0), hi = min(p1, e0 + CS_CHUNK);
-      for (int p = lo; p < hi; p++) { const int sl = cs_slot(p - e0); acc = fma(sa[sl], sx[sl], acc); }
-      __syncthreads();
-    }
-    if (has) __builtin_nontemporal_store(acc, y + r);
-    __syncthreads();                       // erange is rewritten by the next row block
-  }
-}
-
 // ---- CSR, row blocks streamed through LDS, one wave per 64 rows (no workgroup barrier) -------------------------------------------
-// The same idea with the wave as the unit. A wave takes 64 consecutive rows; their entries are ONE contiguous run of col / val, which it
+// The general-matrix kernel: ragged rows, empty rows, rows longer than a chunk; the CSR-vector kernel above keeps the small matrices and
+// the compressed off-diagonal block. A wave takes 64 consecutive rows; their entries are ONE contiguous run of col / val, which it
 // streams in chunks of 512 with fully coalesced nontemporal loads (lane l of step u loads entry 64 u + l) and parks in a wave-private piece
 // of LDS; then lane = row: every lane runs the reference's loop over its own row's segment, acc = fma(val, x, acc) in entry order - the
 // bits of the SELL / dictionary kernels. Nothing waits for another wave: LDS operations of one wave execute in order, so the hand-over
-// from the loading lanes to the row lanes needs no barrier (the workgroup form above spends four fifths of its wave cycles parked at
-// barriers and s_waitcnt, profiles/r03_pmc_csr_kernels.txt), and the col / val loads of the next chunk - of the same rows or of the
+// from the loading lanes to the row lanes needs no barrier (the workgroup-per-256-rows form it replaced, since removed, spent four fifths
+// of its wave cycles parked at barriers and s_waitcnt, profiles/r03_pmc_csr_kernels.txt), and the col / val loads of the next chunk - of the same rows or of the
 // wave's next 64, whose row pointers were loaded one group ahead - are issued before the row sums of this one. Workgroups on one XCD
 // (blockIdx % 8) take one contiguous eighth of the rows, so an XCD's L2 holds the part of x its rows gather from.
 // ROWSIDE: where x is gathered. false: by the loading lanes (lane = entry), (value, x) pairs go through LDS - every lane has work whatever
 // the row lengths. true: by the row lanes (lane = row) - (value, column) go through LDS and the 64 lanes of a gather instruction ask for the
 // same entry position of 64 consecutive rows, which for a banded or stencil-like matrix is a few cache lines where the entry-side gather
 // touches two to three times as many (216^3 Laplacian: the entry-side gathers cost 35 of 211 us, profiles/r03_csr_wave_variants.txt);
-// pays only while a chunk spans most of the wave's rows, i.e. for short rows: chosen at assembly from the mean row length.
+// pays only while a chunk spans most of the wave's rows, i.e. for short rows - which the LDS-DMA form below takes, so the row side of this
+// form is reached only through KSGPU_SPMV=csrregs; the entry side is the automatic choice above 16 entries per row on average.
 // (16-byte loads of four consecutive entries per lane were tried for the streams: fewer instructions, no faster, and the gathers of such a
 // lane assignment touch still more lines.)
 typedef __attribute__((address_space(3))) void ks_lds_void;          // operands of __builtin_amdgcn_global_load_lds (LDS-DMA)
@@ -258,8 +219,9 @@ __global__ __launch_bounds__(256, ROWSIDE ? 5 : 4) void k_spmv_csr_wave(int n, c
 // ---- the same with the col / val streams going STRAIGHT into LDS (global_load_lds_dwordx4: no register staging, no ds_write pass) ----
 // Row side only (short rows). A chunk of 512 entries is six LDS-DMA instructions per wave (four for the values: lane l of instruction i brings
 // entries 128 i + 2 l, + 1; two for the columns: 256 i + 4 l .. + 3) into a lane-linear image - the DMA's destination is base + lane x 16, so
-// the image cannot be skewed; rows whose length is a multiple of 16 would meet on one bank, which is why the register-staged form above stays
-// for those (chosen at assembly). The registers the staged form spends on two chunks in flight (48 of its 96) are free here: more waves per
+// the image cannot be skewed; rows whose length is a multiple of 16 meet on one bank (slower, not wrong). Chosen at assembly for up to 16 entries
+// per row on average (beyond that the entry-side register form is as fast or faster: profiles/r04_csr_lds_dma.txt); the row-side register form
+// measures against it through KSGPU_SPMV=csrregs. The registers the staged form spends on two chunks in flight (48 of its 96) are free here: more waves per
 // SIMD take over the latency hiding. A chunk starts on a multiple of four entries (16-byte aligned in both streams; up to three entries of
 // the rows before it are fetched and ignored).
 template <int CW_STEPS, int WPS, int GU>
@@ -890,7 +852,6 @@ int compact_offdiag_rows(ks_mat A)
   return KS_SUCCESS;
 }
 
-// Build the SELL-64 copy of the diagonal block when its padding is small (<= 12.5 % extra entries).
 // ---- XCD-sliced layout ---------------------------------------------------------------------------------------------
 // Measured on MI355X (scripts/micro/gather_xcd.hip): 1.6e8 random 8-byte gathers from a 40 MB vector take 2.83 ms when
 // every XCD gathers from all of it (each one a 128-B line from the Infinity Cache) and 1.23 ms when the workgroups of
@@ -973,7 +934,7 @@ __global__ void k_sum_parts(int n, const double *__restrict__ ypart, double *__r
 }
 
 
-// ---- binned product (ksgpu_internal.h: use_binned) ---------------------------------------------------------------------------------
+// ---- binned product (ksgpu_internal.h: bn_*) ----------------------------------------------------------------------------------------
 // Why: the product of a uniformly random matrix in a row-ordered layout pulls a 128-byte line of x through L2 -> L1 for every nonzero and
 // runs at that line rate (1.3 ms for config 5), however x is cut for the L2s. Here no random access leaves the CU: phase 1
 // gathers from a piece of x in LDS and streams the gathered values out in the order phase 2 wants them; phase 2 streams them back in with
@@ -983,14 +944,13 @@ constexpr int BN_CS_MAX = 9984;          // columns of a slice: 78 KB of LDS nex
 constexpr int BN_SEG_PAD = 8;            // a (slice, wave-bin) segment holds a multiple of 8 entries (padding: value 0 into the spare accumulator): every segment then
                                          // starts on a 64-byte boundary of G / the values in both orders. Against padding to pairs only, same box: gather 385 -> 343-357 us,
                                          // reduce 511 -> 493 us with 2.5 % more entries (profiles/r03_ab_binned.txt); 4: 370-377 / 508, 16: 346-362 / 497
-// phase 1: grid = slices, 1024 threads; LDS: x piece [cs], off1 row [wb + 1], off2t row [wb] (+ DMA: 2 KB per wave for the window's column codes)
-// DMA (round 4): the window's 1024 column codes come by two global_load_lds_dwordx4 per wave (16 bytes per lane) into a wave-private piece of LDS and the
-// lanes read their pairs from there. The register form (DMA = false, kept for reference) loads a pair per lane and instruction - 4 bytes per lane, and
+// phase 1: grid = slices, 1024 threads; LDS: x piece [cs], off1 row [wb + 1], off2t row [wb], 2 KB per wave for the window's column codes
+// Round 4: the window's 1024 column codes come by two global_load_lds_dwordx4 per wave (16 bytes per lane) into a wave-private piece of LDS and the
+// lanes read their pairs from there. The register form it replaced loaded a pair per lane and instruction - 4 bytes per lane, and
 // 4-byte-per-lane streaming loads top out at 0.7 - 2.4 TB/s on this part (profiles/r03_micro_load_width.txt). Worth 2 - 8 % of this kernel depending on the
 // box (334-350 against 363-365 us; 336-341 against 343-351): it stays bound by its store. A second buffer with the next window's codes in flight (counted
 // vmcnt behind the window's eight stores) measured no better than the register form: profiles/r04_binned_gather_dma.txt.
 // Slices start on multiples of 8 entries (every segment is padded to 8): the 16-byte DMA is aligned.
-template <bool DMA>
 __global__ __launch_bounds__(1024) void k_binned_gather(int n, int cs, int wb, int nwin, const long long *__restrict__ sbase, const unsigned short *__restrict__ col16,
                                                         const int *__restrict__ off1, const int *__restrict__ off2t, const int *__restrict__ wseg,
                                                         const double *__restrict__ x, double *__restrict__ G)
@@ -1005,27 +965,21 @@ __global__ __launch_bounds__(1024) void k_binned_gather(int n, int cs, int wb, i
   for (int i = tid; i <= wb; i += blockDim.x) o1[i] = off1[(size_t)s * (wb + 1) + i];
   for (int i = tid; i < wb; i += blockDim.x) o2[i] = off2t[(size_t)s * wb + i];
   __syncthreads();
-  const unsigned *cp = reinterpret_cast<const unsigned *>(col16 + sbase[s]);     // slices start at even positions: 4-byte aligned
   const unsigned short *cg = col16 + sbase[s];
   unsigned *cw = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(bn_lds) + ((((size_t)cs * 8 + (size_t)(2 * wb + 1) * 4) + 15) & ~(size_t)15)) + (size_t)w * 512;
   const int total = o1[wb];                                                       // a multiple of 8
   for (int win = w; win * 1024 < total; win += nw) {
     const int base = win * 1024;
     unsigned c[8];
-    if (DMA) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // the reads of the previous window's codes are done before the next ones may land
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // the reads of the previous window's codes are done before the next ones may land
 #pragma unroll
-      for (int i = 0; i < 2; i++) {
-        const int e8 = base + 512 * i + 8 * lane;
-        if (e8 < total) __builtin_amdgcn_global_load_lds((ks_glb_void *)(cg + e8), (ks_lds_void *)(cw + 256 * i), 16, 0, 2);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int k = 0; k < 8; k++) { const int e = base + k * 128 + 2 * lane; c[k] = e < total ? cw[k * 64 + lane] : 0u; }
-    } else {
-#pragma unroll
-    for (int k = 0; k < 8; k++) { const int e = base + k * 128 + 2 * lane; c[k] = e < total ? __builtin_nontemporal_load(cp + (e >> 1)) : 0u; }
+    for (int i = 0; i < 2; i++) {
+      const int e8 = base + 512 * i + 8 * lane;
+      if (e8 < total) __builtin_amdgcn_global_load_lds((ks_glb_void *)(cg + e8), (ks_lds_void *)(cw + 256 * i), 16, 0, 2);
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < 8; k++) { const int e = base + k * 128 + 2 * lane; c[k] = e < total ? cw[k * 64 + lane] : 0u; }
     const int lo = wseg[(size_t)s * nwin + win];
     int bnd[BN_MAXSEG], dlt[BN_MAXSEG];
 #pragma unroll
@@ -1094,24 +1048,43 @@ __global__ __launch_bounds__(256) void k_binned_reduce(int n, int wr, int ns, co
 }
 
 
-// Host-side build of the binned layout from the device CSR of the diagonal block (copied back once; the counting sort per wave-bin is cache
-// friendly and runs on a few threads).
-static int build_binned(ks_mat A)
+// The matrices the binned and XCD-sliced layouts are for: x well beyond an L2 and most entries far from the diagonal (nothing a row-ordered
+// sweep could reuse). Measured, 33 nnz/row uniformly random: x = 4 MB CSR 0.118 ms / sliced 0.128 ms; 8 MB 0.379 / 0.247; 16 MB 1.97 / 0.49;
+// 40 MB 2.90 / 1.37.
+int wide_scatter(ks_mat A, bool *wide)
 {
   ks_ctx ctx = A->ctx;
-  const char *force = getenv("KSGPU_SPMV");
-  if (force && strcmp(force, "binned")) return KS_SUCCESS;
   const int n = A->n;
-  if (n < 4096 || A->nnz_d == 0) return KS_SUCCESS;
-  if (!force) {
-    // the same matrices the XCD-sliced layout was built for: x well beyond an L2 and most entries far from the diagonal
-    if ((double)n * 8.0 < 6.0 * 1048576.0 || A->nnz_d < 8LL * n) return KS_SUCCESS;
-    unsigned long long *cnt = nullptr, h = 0;
-    KS_HIP(hipMalloc(&cnt, sizeof(unsigned long long))); KS_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(k_far_entries, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, n / 16, A->d_rowptr, A->d_col, cnt);
-    KS_HIP(hipMemcpyAsync(&h, cnt, sizeof(h), hipMemcpyDeviceToHost, ctx->stream)); KS_HIP(ks_sync(ctx)); hipFree(cnt);
-    if ((double)h < 0.5 * (double)A->nnz_d) return KS_SUCCESS;
-  }
+  *wide = false;
+  if (n < 4096 || A->nnz_d == 0 || (double)n * 8.0 < 6.0 * 1048576.0 || A->nnz_d < 8LL * n) return KS_SUCCESS;
+  unsigned long long *cnt = nullptr, h = 0;
+  KS_HIP(hipMalloc(&cnt, sizeof(unsigned long long))); KS_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), ctx->stream));
+  hipLaunchKernelGGL(k_far_entries, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, n / 16, A->d_rowptr, A->d_col, cnt);
+  KS_HIP(hipMemcpyAsync(&h, cnt, sizeof(h), hipMemcpyDeviceToHost, ctx->stream)); KS_HIP(ks_sync(ctx)); hipFree(cnt);
+  *wide = (double)h >= 0.5 * (double)A->nnz_d;
+  return KS_SUCCESS;
+}
+
+// The binned, XCD-sliced and dictionary layouts are the only copy of the diagonal block kept: its diagonal and infinity norm are taken from
+// the CSR arrays before those are released (local rows only: no collective inside the per-rank layout choice).
+int release_csr(ks_mat A)
+{
+  double *d = nullptr, nrm = 0.0;
+  KS_HIP(hipMalloc(&d, sizeof(double) * A->n));
+  int rc = ks_mat_get_diagonal_internal(A, d);
+  if (!rc) rc = ks_mat_norm_inf_local(A, &nrm);            // waits for the stream: the diagonal is complete too
+  if (rc) { hipFree(d); return rc; }
+  A->diag_cache = d; A->norm_inf_cache = nrm;
+  hipFree(A->d_col); hipFree(A->d_val); A->d_col = nullptr; A->d_val = nullptr;
+  return KS_SUCCESS;
+}
+
+// Host-side build of the binned layout from the device CSR of the diagonal block (copied back once; the counting sort per wave-bin is cache
+// friendly and runs on a few threads).
+int build_binned(ks_mat A)
+{
+  ks_ctx ctx = A->ctx;
+  const int n = A->n;
   // slices: a multiple of the CU count (a workgroup per slice, one resident per CU), each at most BN_CS_MAX columns
   const int ncu = std::max(ctx->num_cu, 1);
   const long long per_round = (long long)ncu * BN_CS_MAX;
@@ -1223,21 +1196,13 @@ static int build_binned(ks_mat A)
   KS_HIP(hipMalloc(&A->bn_g, sizeof(double) * std::max<long long>(entries, 1)));
   KS_HIP(hipMemset(A->bn_g, 0, sizeof(double) * std::max<long long>(entries, 1)));
   const int lds1 = cs * 8 + (2 * wb + 1) * 4 + 16 + 16 * 2048, lds2 = 4 * (wr + 1) * 8;      // (+ 2 KB of column codes per wave)
-  KS_HIP(hipFuncSetAttribute((const void *)k_binned_gather<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds1));
+  KS_HIP(hipFuncSetAttribute((const void *)k_binned_gather, hipFuncAttributeMaxDynamicSharedMemorySize, lds1));
   KS_HIP(hipFuncSetAttribute((const void *)k_binned_reduce, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));
-  // diagonal and infinity norm are taken from the CSR arrays before they are released
-  KS_HIP(hipMalloc(&A->diag_cache, sizeof(double) * n));
-  KS_CALL(ks_mat_get_diagonal_internal(A, A->diag_cache));
-  KS_HIP(ks_sync(ctx));
-  double nrm = 0.0;
-  KS_CALL(ks_mat_norm_inf_local(A, &nrm));
-  A->norm_inf_cache = nrm;
-  A->use_binned = true; A->bn_ns = ns; A->bn_cs = cs; A->bn_wb = wb; A->bn_wr = wr; A->bn_nwin = nwin; A->bn_entries = entries;
-  hipFree(A->d_col); hipFree(A->d_val); A->d_col = nullptr; A->d_val = nullptr;
+  KS_CALL(release_csr(A));
+  A->layout = KS_MAT_LAYOUT_BINNED; A->bn_ns = ns; A->bn_cs = cs; A->bn_wb = wb; A->bn_wr = wr; A->bn_nwin = nwin; A->bn_entries = entries;
   } catch (const std::exception &) {                    // out of host memory (or anything else the build throws): the other layouts take the matrix
     hipFree(A->bn_col16); hipFree(A->bn_row16); hipFree(A->bn_val); hipFree(A->bn_g); hipFree(A->bn_off1); hipFree(A->bn_off2t); hipFree(A->bn_wseg); hipFree(A->bn_sbase); hipFree(A->bn_off2); hipFree(A->bn_log2);
     A->bn_col16 = A->bn_row16 = nullptr; A->bn_val = A->bn_g = nullptr; A->bn_off1 = A->bn_off2t = A->bn_wseg = nullptr; A->bn_sbase = nullptr; A->bn_off2 = A->bn_log2 = nullptr;
-    hipFree(A->diag_cache); A->diag_cache = nullptr;
     (void)hipGetLastError();
   }
   return KS_SUCCESS;
@@ -1245,23 +1210,8 @@ static int build_binned(ks_mat A)
 
 int build_sliced(ks_mat A)
 {
-  if (A->use_binned) return KS_SUCCESS;
   ks_ctx ctx = A->ctx;
-  const char *force = getenv("KSGPU_SPMV");
-  if (force && strcmp(force, "sliced")) return KS_SUCCESS;
   const int n = A->n;
-  if (n < 4096 || A->nnz_d == 0) return KS_SUCCESS;
-  if (!force) {
-    // automatic choice: x larger than one XCD's L2 can hold next to the streamed entries and most entries far from the
-    // diagonal (nothing a row-ordered sweep could reuse). Measured, 33 nnz/row uniformly random: x = 4 MB CSR 0.118 ms /
-    // sliced 0.128 ms; 8 MB 0.379 / 0.247; 16 MB 1.97 / 0.49; 40 MB 2.90 / 1.37.
-    if ((double)n * 8.0 < 6.0 * 1048576.0 || A->nnz_d < 8LL * n) return KS_SUCCESS;
-    unsigned long long *cnt = nullptr, h = 0;
-    KS_HIP(hipMalloc(&cnt, sizeof(unsigned long long))); KS_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(k_far_entries, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, n / 16, A->d_rowptr, A->d_col, cnt);
-    KS_HIP(hipMemcpyAsync(&h, cnt, sizeof(h), hipMemcpyDeviceToHost, ctx->stream)); KS_HIP(ks_sync(ctx)); hipFree(cnt);
-    if ((double)h < 0.5 * (double)A->nnz_d) return KS_SUCCESS;
-  }
   const int max_slice_rows = 786432;   // 6 MiB of x per slice: the 5 MiB slices of the 40 MB probe ran at the L2 rate
   int P = (int)(((long long)n + 8LL * max_slice_rows - 1) / (8LL * max_slice_rows)); if (P < 1) P = 1;
   KS_CHECK(P <= 8, KS_ERR_SUP, "sliced SpMV layout supports up to %d local rows", 64 * max_slice_rows);
@@ -1286,26 +1236,17 @@ int build_sliced(ks_mat A)
   KS_HIP(hipMalloc(&A->sl_col, sizeof(int) * A->nnz_d)); KS_HIP(hipMalloc(&A->sl_val, sizeof(double) * A->nnz_d));
   hipLaunchKernelGGL(k_slice_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, S, sc, A->d_rowptr, A->d_col, A->d_val, A->sl_rowptr, A->sl_base, A->sl_col, A->sl_val);
   KS_HIP(hipMalloc(&A->ypart, sizeof(double) * 8 * (size_t)n));
-  // diagonal and infinity norm are taken from the CSR arrays before they are released
-  KS_HIP(hipMalloc(&A->diag_cache, sizeof(double) * n));
-  KS_CALL(ks_mat_get_diagonal_internal(A, A->diag_cache));
-  KS_HIP(ks_sync(ctx));
   KS_HIP(hipGetLastError());
-  double nrm = 0.0;
-  KS_CALL(ks_mat_norm_inf_local(A, &nrm));                 // local rows only: no collective inside the (per-rank) layout choice
-  A->norm_inf_cache = nrm;
-  A->use_sliced = true; A->nslice = S; A->slice_cols = sc;
-  hipFree(A->d_col); hipFree(A->d_val); A->d_col = nullptr; A->d_val = nullptr;
+  KS_CALL(release_csr(A));
+  A->layout = KS_MAT_LAYOUT_SLICED; A->nslice = S; A->slice_cols = sc;
   return KS_SUCCESS;
 }
 
-// Try the dictionary layout (see k_spmv_dict). Needs the CSR arrays of the diagonal block on the device.
-int build_dict(ks_mat A)
+// Try the dictionary layout (see k_spmv_dict); offsets_only: the offset-dictionary form at once. Needs the CSR arrays of the diagonal block on the device.
+int build_dict(ks_mat A, bool offsets_only)
 {
   ks_ctx ctx = A->ctx;
-  const char *force = getenv("KSGPU_SPMV");
-  if (force && strcmp(force, "dict") && strcmp(force, "odict")) return KS_SUCCESS;       // any other forced layout
-  bool value_mode = !(force && !strcmp(force, "odict"));                 // "odict" forces the offsets-only form
+  bool value_mode = !offsets_only;
   const int n = A->n;
   int *d_int = nullptr;
   KS_HIP(hipMalloc(&d_int, sizeof(int) * 4));
@@ -1357,7 +1298,7 @@ int build_dict(ks_mat A)
     KS_HIP(hipMalloc(&A->dc_off, sizeof(int) * 256));
     KS_HIP(hipMemcpy(A->dc_off, dof.data(), sizeof(int) * 256, hipMemcpyHostToDevice));
     A->dc_codes8 = codes8; codes8 = nullptr; A->dc_vals = vals_out; vals_out = nullptr;
-    A->use_odict = true; A->dict_w = W; A->dict_nval = 0; A->dict_noff = (int)offs.size();
+    A->layout = KS_MAT_LAYOUT_ODICT; A->dict_w = W; A->dict_nval = 0; A->dict_noff = (int)offs.size();
     cleanup();
     return KS_SUCCESS;
   }
@@ -1368,33 +1309,15 @@ int build_dict(ks_mat A)
   KS_HIP(hipMemcpy(A->dc_val, dv.data(), sizeof(double) * 256, hipMemcpyHostToDevice));
   KS_HIP(hipMemcpy(A->dc_off, dof.data(), sizeof(int) * 256, hipMemcpyHostToDevice));
   A->dc_codes = codes; codes = nullptr;
-  A->use_dict = true; A->dict_w = W; A->dict_nval = (int)vals.size(); A->dict_noff = (int)offs.size();
+  A->layout = KS_MAT_LAYOUT_DICT; A->dict_w = W; A->dict_nval = (int)vals.size(); A->dict_noff = (int)offs.size();
   cleanup();
   return KS_SUCCESS;
 }
 
-int build_sell(ks_mat A)
+// Build the SELL-64 copy of the diagonal block when its padding is small (<= 12.5 % extra entries) or it is forced.
+int build_sell(ks_mat A, bool forced)
 {
-  if (A->use_sliced || A->use_binned) return KS_SUCCESS;
   ks_ctx ctx = A->ctx;
-  const char *force = getenv("KSGPU_SPMV");
-  if (force && !strcmp(force, "csrvec")) { A->force_csr_vector = true; return KS_SUCCESS; }     // the CSR-vector kernel at any size (A/B against the row-block kernel)
-  if (force && !strcmp(force, "csrblock")) { A->force_csr_block = true; return KS_SUCCESS; }    // the workgroup-per-256-rows form of the row-block kernel (A/B against the wave form)
-  if (force && !strcmp(force, "csrregs")) { A->force_csr_regs = true; return KS_SUCCESS; }      // the register-staged form of the wave kernel also for short rows (A/B against the LDS-DMA form)
-  if (force && !strcmp(force, "csr")) return KS_SUCCESS;
-  if (A->n == 0 || A->nnz_d == 0) return KS_SUCCESS;
-  KS_CALL(build_dict(A));                                   // independent of the SELL decision below; needs the CSR arrays
-  if (A->use_dict || A->use_odict) {
-    // the dictionary form is the only copy kept: diagonal and infinity norm are taken from the CSR arrays before they go
-    KS_HIP(hipMalloc(&A->diag_cache, sizeof(double) * A->n));
-    KS_CALL(ks_mat_get_diagonal_internal(A, A->diag_cache));
-    double nrm = 0.0;
-    KS_CALL(ks_mat_norm_inf_local(A, &nrm));
-    KS_HIP(ks_sync(ctx));
-    A->norm_inf_cache = nrm; A->have_cache = true;
-    hipFree(A->d_col); hipFree(A->d_val); A->d_col = nullptr; A->d_val = nullptr;
-    return KS_SUCCESS;
-  }
   const int ns = (A->n + 63) / 64;
   int *width = nullptr;
   KS_HIP(hipMalloc(&width, sizeof(int) * (ns + 1)));
@@ -1407,17 +1330,49 @@ int build_sell(ks_mat A)
   KS_HIP(hipMemcpy(&total, A->s_ptr + ns, sizeof(int), hipMemcpyDeviceToHost));
   hipFree(width);
   const long long entries = (long long)total * 64;
-  const bool ok = (force && !strcmp(force, "sell")) || (double)entries <= 1.125 * (double)A->nnz_d + 64.0 * 64.0;
+  const bool ok = forced || (double)entries <= 1.125 * (double)A->nnz_d + 64.0 * 64.0;
   if (!ok || entries <= 0) { hipFree(A->s_len); hipFree(A->s_ptr); A->s_len = A->s_ptr = nullptr; return KS_SUCCESS; }
   KS_HIP(hipMalloc(&A->s_col, sizeof(int) * entries));
   KS_HIP(hipMalloc(&A->s_val, sizeof(double) * entries));
   hipLaunchKernelGGL(k_sell_fill, dim3((ns + 3) / 4), dim3(256), 0, ctx->stream, A->n, ns, A->d_rowptr, A->d_col, A->d_val, A->s_ptr, A->s_col, A->s_val);
   KS_HIP(ks_sync(ctx));
   KS_HIP(hipGetLastError());
-  A->use_sell = true; A->nslices = ns; A->s_entries = entries;
+  A->layout = KS_MAT_LAYOUT_SELL; A->nslices = ns; A->s_entries = entries;
   // the CSR copy of the diagonal block is no longer needed on the device
   hipFree(A->d_col); hipFree(A->d_val); A->d_col = nullptr; A->d_val = nullptr;
   return KS_SUCCESS;
+}
+
+// The device layout of the diagonal block, chosen at assembly by every creation path: wide-scatter matrices get the binned layout, or the
+// XCD-sliced one where the binned build declines; the others a dictionary form, SELL-64 when its padding is small, or CSR. KSGPU_SPMV=<name>
+// forces one (tests and A/B legs); a forced layout that cannot be built falls through to SELL-64 under the padding rule, or CSR.
+int choose_layout(ks_mat A)
+{
+  enum { AUTO, CSR, CSRVEC, CSRREGS, SELL, DICT, ODICT, BINNED, SLICED };
+  static const char *const names[] = {"", "csr", "csrvec", "csrregs", "sell", "dict", "odict", "binned", "sliced"};
+  const char *force = getenv("KSGPU_SPMV");
+  int want = AUTO;
+  if (force) {
+    want = -1;
+    for (int i = CSR; i <= SLICED; i++) if (!strcmp(force, names[i])) want = i;
+    KS_CHECK(want >= 0, KS_ERR_ARG_WRONG, "KSGPU_SPMV=%s: not one of csr, csrvec, csrregs, sell, dict, odict, binned, sliced", force);
+  }
+  bool wide = false;
+  if (want == AUTO) KS_CALL(wide_scatter(A, &wide));
+  const bool big = A->n >= 4096 && A->nnz_d > 0;
+  if (wide || (want == BINNED && big)) KS_CALL(build_binned(A));
+  if ((wide || (want == SLICED && big)) && A->layout == KS_MAT_LAYOUT_CSR) KS_CALL(build_sliced(A));
+  if (A->layout != KS_MAT_LAYOUT_CSR) return KS_SUCCESS;
+  if (want == CSR || want == CSRVEC || want == CSRREGS) {
+    A->csr_form = want == CSRVEC ? ks_mat_s::CSR_VEC : want == CSRREGS ? ks_mat_s::CSR_REGS : ks_mat_s::CSR_AUTO;
+    return KS_SUCCESS;
+  }
+  if (A->n == 0 || A->nnz_d == 0) return KS_SUCCESS;
+  if (want == AUTO || want == DICT || want == ODICT) {
+    KS_CALL(build_dict(A, want == ODICT));
+    if (A->layout != KS_MAT_LAYOUT_CSR) return release_csr(A);
+  }
+  return build_sell(A, want == SELL);
 }
 
 } // namespace
@@ -1432,7 +1387,7 @@ int ks_mat_mult_dot_fused(ks_mat A, ks_bv bv, const double *x, int jy, bool gate
   const int ncols = bv->nc + jy + 1;
   const double *Vb = ks_bv_col(bv, -bv->nc);
   double *y = ks_bv_col(bv, jy);
-  if (!A->use_dict || A->shell_mult || ks_is_multi(ctx) || A->n_orows > 0 || bv->matrix || A->n != bv->n) return KS_SUCCESS;
+  if (A->layout != KS_MAT_LAYOUT_DICT || A->shell_mult || ks_is_multi(ctx) || A->n_orows > 0 || bv->matrix || A->n != bv->n) return KS_SUCCESS;
   if (ncols < 1 || ncols > KS_MAX_COLS || bv->ld % 2 || (((uintptr_t)Vb) & 15) || (((uintptr_t)y) & 15)) return KS_SUCCESS;
   if (!ksk::ks_basis_is_cache_resident((size_t)(bv->nc + bv->m), (size_t)bv->ld)) return KS_SUCCESS;
   if (ctx->dbg.no_spmv_dot) return KS_SUCCESS;        // test hook: the separate launches, to compare bits
@@ -1505,9 +1460,7 @@ extern "C" int ks_mat_create_csr_flags(ks_ctx ctx, int n_local, int row_start, i
   }
   int rc = build_halo_plan(A, garray);
   if (!rc) rc = compact_offdiag_rows(A);
-  if (!rc) rc = build_binned(A);
-  if (!rc) rc = build_sliced(A);
-  if (!rc) rc = build_sell(A);
+  if (!rc) rc = choose_layout(A);
   if (rc) { ks_mat_destroy(A); return rc; }
   if (flags & KS_MAT_KEEP_CSR) {
     try { A->k_rowptr.assign(rowptr, rowptr + n_local + 1); A->k_col.assign(col, col + nnz); A->k_val.assign(val, val + nnz); }
@@ -1567,7 +1520,7 @@ extern "C" int ks_mat_create_laplacian3d(ks_ctx ctx, int nx, int ny, int nz, int
   if (ctx->comm.size == 1 && !garray.empty()) { ks_mat_destroy(A); KS_FAIL(KS_ERR_ARG_INCOMP, "a partial slab needs a multi-rank communicator"); }
   rc = build_halo_plan(A, garray);
   if (!rc) rc = compact_offdiag_rows(A);
-  if (!rc) rc = build_sell(A);
+  if (!rc) rc = choose_layout(A);
   if (rc) { ks_mat_destroy(A); return rc; }
   *out = A;
   return KS_SUCCESS;
@@ -1594,7 +1547,7 @@ extern "C" int ks_mat_create_laplacian2d(ks_ctx ctx, int n, int m, ks_mat *out)
   hipLaunchKernelGGL(k_lap2d_fill, dim3(nb), dim3(256), 0, ctx->stream, n, m, A->d_rowptr, A->d_col, A->d_val);
   KS_HIP(ks_sync(ctx));
   A->lanes_per_row = pick_lanes(A->nnz_d, A->n);
-  { int rc = build_sell(A); if (rc) { ks_mat_destroy(A); return rc; } }
+  { int rc = choose_layout(A); if (rc) { ks_mat_destroy(A); return rc; } }
   *out = A;
   return KS_SUCCESS;
 }
@@ -1630,7 +1583,7 @@ extern "C" int ks_mat_shell_set_enqueue_only(ks_mat A, int flag)
 extern "C" int ks_mat_get_layout(ks_mat A, int *layout)     // storage of the diagonal block: KS_MAT_LAYOUT_*
 {
   KS_CHECK(A && layout, KS_ERR_ARG_NULL, "NULL argument");
-  *layout = A->shell_mult ? KS_MAT_LAYOUT_SHELL : A->use_binned ? KS_MAT_LAYOUT_BINNED : (A->use_sliced ? KS_MAT_LAYOUT_SLICED : (A->use_dict ? KS_MAT_LAYOUT_DICT : (A->use_odict ? KS_MAT_LAYOUT_ODICT : (A->use_sell ? KS_MAT_LAYOUT_SELL : KS_MAT_LAYOUT_CSR))));
+  *layout = A->shell_mult ? KS_MAT_LAYOUT_SHELL : A->layout;
   return KS_SUCCESS;
 }
 extern "C" int ks_mat_get_sizes(ks_mat A, int *n_local, int *n_global, long long *nnz_local)
@@ -1645,7 +1598,7 @@ extern "C" int ks_mat_get_sizes(ks_mat A, int *n_local, int *n_global, long long
 // y = A x.  Multi-rank: pack boundary entries, exchange with the neighbours (RCCL send/recv over xGMI),
 // diagonal block product, then the off-diagonal rows add their ghost contributions.
 // a row scaling can ride in the product's last pass: the binned layout on a rank without off-diagonal rows (their contribution is added afterwards)
-bool ks_mat_can_rowscale(ks_mat A) { return A && !A->shell_mult && A->use_binned && A->n_orows == 0; }
+bool ks_mat_can_rowscale(ks_mat A) { return A && !A->shell_mult && A->layout == KS_MAT_LAYOUT_BINNED && A->n_orows == 0; }
 
 int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *rowscale)
 {
@@ -1677,76 +1630,80 @@ int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *row
   }
   {
     const double csr_bytes = 12.0 * A->nnz + 4.0 * (A->n + 1) + 16.0 * A->n;                    // what the CSR algorithm moves
-    KsProfScope ps(ctx, KS_K_SPMV, csr_bytes, A->use_binned ? 18 : A->use_dict ? 16 : (A->use_odict ? 17 : (A->use_sell ? 8 : 0)),   // variant 16: k_spmv_dict, 17: k_spmv_odict, 8: k_spmv_sell<8>, 0: k_spmv_csr
-                   A->use_binned ? 28.0 * A->bn_entries + 16.0 * A->n + 12.0 * A->nnz_o
-                   : A->use_dict ? (2.0 * A->dict_w + 16.0) * A->n + 12.0 * A->nnz_o
-                   : (A->use_odict ? 8.0 * A->nnz_d + (A->dict_w + 16.0) * A->n + 12.0 * A->nnz_o : -1.0));   // the dictionary layouts' own compulsory bytes
-    if (A->use_binned) {
-      hipLaunchKernelGGL(k_binned_gather<true>, dim3((unsigned)A->bn_ns), dim3(1024), (size_t)A->bn_cs * 8 + (size_t)(2 * A->bn_wb + 1) * 4 + 16 + 16 * 2048, ctx->stream,
+    int variant = 0; double own = -1.0;        // variant 18: k_binned_*, 16: k_spmv_dict, 17: k_spmv_odict, 8: k_spmv_sell<8>, 0: k_spmv_csr; the layout's own compulsory bytes
+    switch (A->layout) {
+    case KS_MAT_LAYOUT_BINNED: variant = 18; own = 28.0 * A->bn_entries + 16.0 * A->n + 12.0 * A->nnz_o; break;
+    case KS_MAT_LAYOUT_DICT: variant = 16; own = (2.0 * A->dict_w + 16.0) * A->n + 12.0 * A->nnz_o; break;
+    case KS_MAT_LAYOUT_ODICT: variant = 17; own = 8.0 * A->nnz_d + (A->dict_w + 16.0) * A->n + 12.0 * A->nnz_o; break;
+    case KS_MAT_LAYOUT_SELL: variant = 8; break;
+    }
+    KsProfScope ps(ctx, KS_K_SPMV, csr_bytes, variant, own);
+    switch (A->layout) {
+    case KS_MAT_LAYOUT_BINNED:
+      hipLaunchKernelGGL(k_binned_gather, dim3((unsigned)A->bn_ns), dim3(1024), (size_t)A->bn_cs * 8 + (size_t)(2 * A->bn_wb + 1) * 4 + 16 + 16 * 2048, ctx->stream,
                          A->n, A->bn_cs, A->bn_wb, A->bn_nwin, A->bn_sbase, A->bn_col16, A->bn_off1, A->bn_off2t, A->bn_wseg, x, A->bn_g);
       hipLaunchKernelGGL(k_binned_reduce, dim3((unsigned)(A->bn_wb / 4)), dim3(256), (size_t)4 * (A->bn_wr + 1) * 8, ctx->stream, A->n, A->bn_wr, A->bn_ns, A->bn_log2, A->bn_off2,
                          A->bn_g, A->bn_val, A->bn_row16, y, rowscale);
-    } else if (A->use_sliced) {
+      break;
+    case KS_MAT_LAYOUT_SLICED: {
       const int per_xcd = std::max(1, std::min((A->n + 255) / 256, (ctx->num_cu / 8) * 8));       // 8 resident workgroups per CU of the XCD
       hipLaunchKernelGGL(k_spmv_sliced, dim3((unsigned)(8 * per_xcd)), dim3(256), 0, ctx->stream, A->n, A->nslice, A->sl_rowptr, A->sl_base, A->sl_col, A->sl_val, x, A->ypart);
       hipLaunchKernelGGL(k_sum_parts, dim3((unsigned)std::min((A->n + 255) / 256, ctx->num_cu * 8)), dim3(256), 0, ctx->stream, A->n, A->ypart, y);
-    } else if (A->use_dict) {
-      const int dremap_env = 1, dmul = 64;
+      break;
+    }
+    case KS_MAT_LAYOUT_DICT:
+    case KS_MAT_LAYOUT_ODICT: {
       const long long groups = ((long long)A->n + SPMV_BLOCK - 1) / SPMV_BLOCK;
-      long long nblk = std::max<long long>(1, std::min<long long>(groups, (long long)ctx->num_cu * dmul));
-      const int dremap = (dremap_env && nblk >= 64) ? 1 : 0;               // small matrices: nothing to pin
-      if (dremap) nblk = std::min<long long>((nblk + 7) / 8, (groups + 7) / 8) * 8;
+      long long nblk = std::max<long long>(1, std::min<long long>(groups, (long long)ctx->num_cu * 64));
+      const int remap = nblk >= 64 ? 1 : 0;               // small matrices: nothing to pin
+      if (remap) nblk = std::min<long long>((nblk + 7) / 8, (groups + 7) / 8) * 8;
       const dim3 gr((unsigned)nblk);
-      if (A->dict_w == 8) hipLaunchKernelGGL((k_spmv_dict<8>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, dremap);
-      else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmv_dict<32>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, dremap);
-      else hipLaunchKernelGGL((k_spmv_dict<16>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, dremap);
-    } else if (A->use_odict) {
-      const int oremap_env = 1, omul = 64;
-      const long long groups = ((long long)A->n + SPMV_BLOCK - 1) / SPMV_BLOCK;
-      long long nblk = std::max<long long>(1, std::min<long long>(groups, (long long)ctx->num_cu * omul));
-      const int oremap = (oremap_env && nblk >= 64) ? 1 : 0;
-      if (oremap) nblk = std::min<long long>((nblk + 7) / 8, (groups + 7) / 8) * 8;
-      if (A->dict_w == 8) hipLaunchKernelGGL((k_spmv_odict<8>), dim3((unsigned)nblk), dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, x, y, oremap);
-      else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmv_odict<32>), dim3((unsigned)nblk), dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, x, y, oremap);
-      else hipLaunchKernelGGL((k_spmv_odict<16>), dim3((unsigned)nblk), dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, x, y, oremap);
-    } else if (A->use_sell) {
-      const int remap_env = 1;   // each XCD one contiguous range of slices: 179 -> 172 us on the 216^3 Laplacian
+      if (A->layout == KS_MAT_LAYOUT_DICT) {
+        if (A->dict_w == 8) hipLaunchKernelGGL((k_spmv_dict<8>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, remap);
+        else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmv_dict<32>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, remap);
+        else hipLaunchKernelGGL((k_spmv_dict<16>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, remap);
+      } else if (A->dict_w == 8) hipLaunchKernelGGL((k_spmv_odict<8>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, x, y, remap);
+      else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmv_odict<32>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, x, y, remap);
+      else hipLaunchKernelGGL((k_spmv_odict<16>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, x, y, remap);
+      break;
+    }
+    case KS_MAT_LAYOUT_SELL: {
       const long long groups = ((long long)A->nslices + 3) / 4;
-      long long blocks = std::min<long long>(groups, (long long)ctx->num_cu * 16);
-      const int bmul = 4096;   // one 256-row group per block measured fastest
-      blocks = std::min<long long>(groups, (long long)ctx->num_cu * bmul);
-      const dim3 gr((unsigned)std::max<long long>(blocks, 1));
-      const int remap = (remap_env && blocks == groups && blocks >= 64) ? 1 : 0;     // only with one slice group per workgroup (a strided loop would interleave the ranges again)
-      hipLaunchKernelGGL((k_spmv_sell<4>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->nslices, A->s_ptr, A->s_len, A->s_col, A->s_val, x, y, remap);
-    } else if (A->n >= 2048 && !A->force_csr_vector && !A->force_csr_block) {
-      // 4 or 5 workgroups of 4 waves per CU (registers; forcing 6 spills: 259 us); a multiple of 8 so that every XCD gets its eighth of the rows
-      const long long NG = ((long long)A->n + 255) / 256;
-      const bool rowside = A->nnz_d <= 12LL * A->n;          // short rows: gather on the row side (register-staged form)
-      const bool dma = A->nnz_d <= 16LL * A->n && !A->force_csr_regs;      // the LDS-DMA form gathers on the row side up to 16 entries per row on average
-      long long nb = std::min<long long>(NG, (long long)ctx->num_cu * (rowside ? 5 : 4));
-      const int remap = nb >= 64 ? 1 : 0;
-      if (remap) nb = (nb / 8) * 8;
-      if (dma) {
-        // short rows: the LDS-DMA form (six workgroups of four waves per CU: 144 KB of LDS; 33 registers). 216^3 Laplacian: 191 us against the
-        // register-staged form's 207 on the same box (profiles/r04_csr_lds_dma.txt)
-        // 64 rows of up to 8 entries fit one 512-entry chunk; up to 12 entries one of 768 (9 KB of LDS per wave: four workgroups per CU), up to 16 one of
-        // 1024 (three per CU) - a second chunk per row group is a second serialised DMA wait (rows of 9: 56.6 -> 48.2 us with the wider chunk; beyond
-        // 16 entries per row the entry-side register form is as fast or faster: profiles/r04_csr_lds_dma.txt)
-        const bool wide = A->nnz_d > 8LL * A->n;
-        const bool wider = A->nnz_d > 12LL * A->n;
-        long long nd = std::min<long long>(NG, (long long)ctx->num_cu * (wider ? 3 : wide ? 4 : 6));
-        const int rd = nd >= 64 ? 1 : 0;
-        if (rd) nd = (nd / 8) * 8;
-        if (wider) hipLaunchKernelGGL((k_spmv_csr_wave_dma<16, 3, 8>), dim3((unsigned)nd), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, rd);
-        else if (wide) hipLaunchKernelGGL((k_spmv_csr_wave_dma<12, 4, 8>), dim3((unsigned)nd), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, rd);
-        else hipLaunchKernelGGL((k_spmv_csr_wave_dma<8, 6, 8>), dim3((unsigned)nd), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, rd);
-      } else if (rowside) hipLaunchKernelGGL((k_spmv_csr_wave<true, 8>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, remap);
-      else hipLaunchKernelGGL((k_spmv_csr_wave<false, 8>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, remap);
-    } else if (A->n >= 2048 && !A->force_csr_vector) {
-      const unsigned nb = (unsigned)std::min<long long>(((long long)A->n + 255) / 256, (long long)ctx->num_cu * 8);
-      hipLaunchKernelGGL(k_spmv_csr_stream, dim3(nb), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, x, y);
-    } else
-      launch_spmv<false, false>(ctx->stream, ctx->num_cu, A->lanes_per_row, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, nullptr);
+      const long long blocks = std::min<long long>(groups, (long long)ctx->num_cu * 4096);     // one 256-row group per block measured fastest
+      // each XCD one contiguous range of slices (179 -> 172 us on the 216^3 Laplacian), only with one slice group per workgroup (a strided
+      // loop would interleave the ranges again)
+      const int remap = (blocks == groups && blocks >= 64) ? 1 : 0;
+      hipLaunchKernelGGL((k_spmv_sell<4>), dim3((unsigned)std::max<long long>(blocks, 1)), dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->nslices, A->s_ptr, A->s_len, A->s_col, A->s_val, x, y, remap);
+      break;
+    }
+    default:                                   // CSR
+      if (A->n >= 2048 && A->csr_form != ks_mat_s::CSR_VEC) {
+        // 4 or 5 workgroups of 4 waves per CU (registers; forcing 6 spills: 259 us); a multiple of 8 so that every XCD gets its eighth of the rows
+        const long long NG = ((long long)A->n + 255) / 256;
+        const bool rowside = A->nnz_d <= 12LL * A->n;          // short rows: gather on the row side (register-staged form)
+        const bool dma = A->nnz_d <= 16LL * A->n && A->csr_form != ks_mat_s::CSR_REGS;      // the LDS-DMA form gathers on the row side up to 16 entries per row on average
+        long long nb = std::min<long long>(NG, (long long)ctx->num_cu * (rowside ? 5 : 4));
+        const int remap = nb >= 64 ? 1 : 0;
+        if (remap) nb = (nb / 8) * 8;
+        if (dma) {
+          // short rows: the LDS-DMA form (six workgroups of four waves per CU: 144 KB of LDS; 33 registers). 216^3 Laplacian: 191 us against the
+          // register-staged form's 207 on the same box (profiles/r04_csr_lds_dma.txt)
+          // 64 rows of up to 8 entries fit one 512-entry chunk; up to 12 entries one of 768 (9 KB of LDS per wave: four workgroups per CU), up to 16 one of
+          // 1024 (three per CU) - a second chunk per row group is a second serialised DMA wait (rows of 9: 56.6 -> 48.2 us with the wider chunk; beyond
+          // 16 entries per row the entry-side register form is as fast or faster: profiles/r04_csr_lds_dma.txt)
+          const bool wide = A->nnz_d > 8LL * A->n;
+          const bool wider = A->nnz_d > 12LL * A->n;
+          long long nd = std::min<long long>(NG, (long long)ctx->num_cu * (wider ? 3 : wide ? 4 : 6));
+          const int rd = nd >= 64 ? 1 : 0;
+          if (rd) nd = (nd / 8) * 8;
+          if (wider) hipLaunchKernelGGL((k_spmv_csr_wave_dma<16, 3, 8>), dim3((unsigned)nd), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, rd);
+          else if (wide) hipLaunchKernelGGL((k_spmv_csr_wave_dma<12, 4, 8>), dim3((unsigned)nd), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, rd);
+          else hipLaunchKernelGGL((k_spmv_csr_wave_dma<8, 6, 8>), dim3((unsigned)nd), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, rd);
+        } else if (rowside) hipLaunchKernelGGL((k_spmv_csr_wave<true, 8>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, remap);
+        else hipLaunchKernelGGL((k_spmv_csr_wave<false, 8>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, remap);
+      } else
+        launch_spmv<false, false>(ctx->stream, ctx->num_cu, A->lanes_per_row, A->n, A->d_rowptr, A->d_col, A->d_val, x, y, nullptr);
+    }
     if (overlap) KS_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_halo, 0));          // also when this rank has no off-diagonal rows: keeps the two streams in step
     if (A->n_orows > 0)
       launch_spmv<true, true>(ctx->stream, ctx->num_cu, 2, A->n_orows, A->o_rowptr, A->o_col, A->o_val, A->ghost, y, A->o_rows);
@@ -1779,9 +1736,9 @@ int ks_mat_get_diagonal_internal(ks_mat A, double *d)
   ks_ctx ctx = A->ctx;
   KS_CHECK(!A->shell_mult, KS_ERR_SUP, "a matrix-free operator has no stored diagonal");
   if (A->n == 0) return KS_SUCCESS;
-  if (A->use_sliced || A->use_binned || A->have_cache) { KS_HIP(hipMemcpyAsync(d, A->diag_cache, sizeof(double) * A->n, hipMemcpyDeviceToDevice, ctx->stream)); return KS_SUCCESS; }
+  if (A->diag_cache) { KS_HIP(hipMemcpyAsync(d, A->diag_cache, sizeof(double) * A->n, hipMemcpyDeviceToDevice, ctx->stream)); return KS_SUCCESS; }
   const unsigned nb = (unsigned)((A->n + 255) / 256);
-  if (A->use_sell) hipLaunchKernelGGL(k_diag_sell, dim3(nb), dim3(256), 0, ctx->stream, A->n, A->s_ptr, A->s_len, A->s_col, A->s_val, d);
+  if (A->layout == KS_MAT_LAYOUT_SELL) hipLaunchKernelGGL(k_diag_sell, dim3(nb), dim3(256), 0, ctx->stream, A->n, A->s_ptr, A->s_len, A->s_col, A->s_val, d);
   else hipLaunchKernelGGL(k_diag_csr, dim3(nb), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, d);
   KS_HIP(hipGetLastError());
   return KS_SUCCESS;
@@ -1816,13 +1773,13 @@ __global__ void k_rowabs_rows(int nrows, const int *__restrict__ rows, const int
 int ks_mat_norm_inf_local(ks_mat A, double *val)          // this rank's rows only
 {
   ks_ctx ctx = A->ctx;
-  if (A->use_sliced || A->use_binned || A->have_cache) { *val = A->norm_inf_cache; return KS_SUCCESS; }     // taken before the CSR arrays were released
+  if (A->diag_cache) { *val = A->norm_inf_cache; return KS_SUCCESS; }     // taken before the CSR arrays were released
   double local = 0.0;
   if (A->n > 0) {
     double *w = nullptr;
     KS_HIP(hipMalloc(&w, sizeof(double) * A->n));
     const unsigned nb = (unsigned)((A->n + 255) / 256);
-    if (A->use_sell) hipLaunchKernelGGL(k_rowabs_sell, dim3(nb), dim3(256), 0, ctx->stream, A->n, A->s_ptr, A->s_len, A->s_val, w);
+    if (A->layout == KS_MAT_LAYOUT_SELL) hipLaunchKernelGGL(k_rowabs_sell, dim3(nb), dim3(256), 0, ctx->stream, A->n, A->s_ptr, A->s_len, A->s_val, w);
     else hipLaunchKernelGGL(k_rowabs_csr, dim3(nb), dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_val, w, 0);
     if (A->n_orows > 0) hipLaunchKernelGGL(k_rowabs_rows, dim3((unsigned)((A->n_orows + 255) / 256)), dim3(256), 0, ctx->stream, A->n_orows, A->o_rows, A->o_rowptr, A->o_val, w);
     std::vector<double> h(A->n);

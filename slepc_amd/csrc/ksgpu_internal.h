@@ -152,34 +152,32 @@ struct ks_mat_s {
   // diagonal block (columns owned by this rank, LOCAL column indices)
   int *d_rowptr = nullptr; int *d_col = nullptr; double *d_val = nullptr; long long nnz_d = 0;
   int lanes_per_row = 8;
-  bool force_csr_vector = false;   // KSGPU_SPMV=csrvec
-  bool force_csr_regs = false, force_csr_block = false;    // KSGPU_SPMV=csrblock
+  // device layout of the diagonal block, chosen at assembly (choose_layout, ks_spmv.hip): a KS_MAT_LAYOUT_* value (SHELL is shell_mult's)
+  int layout = KS_MAT_LAYOUT_CSR;
+  enum CsrForm : unsigned char { CSR_AUTO, CSR_VEC, CSR_REGS } csr_form = CSR_AUTO;   // the CSR kernel KSGPU_SPMV=csrvec / csrregs forces
   // sliced-ELL copy of the diagonal block (slice = 64 rows = one wavefront), chosen at assembly when the
   // padding it needs is small; val/col stored column-major inside a slice: entry j of row 64s+lane at (sp[s]+j)*64+lane
-  bool use_sell = false;
   int nslices = 0; int *s_ptr = nullptr; int *s_len = nullptr; int *s_col = nullptr; double *s_val = nullptr; long long s_entries = 0;
   // dictionary ELL (few distinct values and few distinct column offsets, rows of at most 32 entries): 2 bytes per entry
-  bool use_dict = false; int dict_w = 0; int dict_nval = 0, dict_noff = 0;
+  int dict_w = 0; int dict_nval = 0, dict_noff = 0;
   unsigned short *dc_codes = nullptr; double *dc_val = nullptr; int *dc_off = nullptr;
   // offset-dictionary ELL: any values, few distinct column offsets: 1 byte per entry for the index, values in SELL order
-  bool use_odict = false; unsigned char *dc_codes8 = nullptr; double *dc_vals = nullptr;
-  bool have_cache = false;                    // diag_cache / norm_inf_cache hold MatGetDiagonal / the infinity norm (CSR arrays released)
+  unsigned char *dc_codes8 = nullptr; double *dc_vals = nullptr;
   // XCD-sliced copy of the diagonal block for wide-scatter matrices (columns spread over a vector much larger than one
   // XCD's 4 MiB L2): the columns are cut into nslice = 8*P ranges; slice s is a CSR of its own (rows 0..n-1) and is
   // multiplied only by workgroups with blockIdx % 8 == s % 8, i.e. on one XCD, whose L2 then holds that range of x.
   // Every XCD writes a partial y; a second kernel adds the eight partials in fixed order.
-  bool use_sliced = false;
   int nslice = 0, slice_cols = 0;
   int *sl_rowptr = nullptr; int *sl_col = nullptr; double *sl_val = nullptr; long long *sl_base = nullptr;   // [nslice][n+1], entries, device offsets [nslice+1]
   double *ypart = nullptr;                    // [8][n]
-  double *diag_cache = nullptr; double norm_inf_cache = -1.0;   // kept because the CSR arrays are released after slicing
+  // MatGetDiagonal / the infinity norm, taken before the binned, sliced and dictionary layouts release the CSR arrays (non-null: released)
+  double *diag_cache = nullptr; double norm_inf_cache = -1.0;
   // Binned ("propagation blocking") copy of the diagonal block for wide-scatter matrices, the successor of the XCD-sliced one: the product
   // runs in two streaming phases with every random access in LDS. Columns are cut into bn_ns slices of bn_cs, rows into bn_wb wave-bins of
   // bn_wr. Entries are stored twice over: the 16-bit slice-local column in SLICE-major order (slice, wave-bin, row), the value and the 16-bit
   // bin-local row in BIN-major order (wave-bin, slice, row); a (slice, wave-bin) segment is contiguous in both, holds a multiple of 8
   // entries (padding entries with value 0 where needed) and so starts on a 64-byte boundary of the 8-byte streams. Phase 1 (a workgroup per slice, its piece of x in LDS) writes G = x[col] in bin-major
   // order; phase 2 (a wave per wave-bin, its rows of y in LDS) streams G, val and row and adds val * G into its rows.
-  bool use_binned = false;
   int bn_ns = 0, bn_cs = 0, bn_wb = 0, bn_wr = 0, bn_nwin = 0;
   long long bn_entries = 0;                   // entries incl. padding
   unsigned short *bn_col16 = nullptr, *bn_row16 = nullptr;

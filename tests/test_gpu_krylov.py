@@ -319,6 +319,75 @@ def test_spmv_binned_layout(ctx, monkeypatch):
     assert abs(A.get_diagonal()[12345] - Ao.to_scipy().diagonal()[12345]) < 1e-13
 
 
+SPMV_OVERRIDES = ("csr", "csrvec", "csrregs", "sell", "dict", "odict", "binned", "sliced")
+
+
+def _layout_choice_table(ctx, monkeypatch):
+    """Mat.layout() of a small corpus of matrices under the automatic choice and under every accepted KSGPU_SPMV name."""
+    import slepc_amd as ks
+    rng = np.random.default_rng(33)
+
+    def ragged(n, mean):
+        lens = np.clip(rng.poisson(mean, n), 0, n); lens[rng.integers(0, n, n // 20)] = 0
+        rowptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+        col = np.concatenate([np.sort(rng.choice(n, l, replace=False)) for l in lens] + [np.empty(0, int)]).astype(np.int32)
+        return rowptr, col, rng.uniform(-1, 1, rowptr[-1])
+    L = O.laplacian3d(24, 20, 16)
+    G = sc.graph_laplacian_2d(50, 41)
+    nw = 786432                                                          # x = 6 MiB, 8 uniformly random columns per row: a wide-scatter matrix
+    wide = (np.arange(0, 8 * nw + 1, 8, dtype=np.int32), rng.integers(0, nw, 8 * nw).astype(np.int32), rng.uniform(-1, 1, 8 * nw))
+    csr = {"graph": (G.indptr, G.indices, G.data), "varcoef7": (L.rowptr, L.col, rng.standard_normal(L.val.shape[0])),
+           "ragged8": ragged(6000, 7), "ragged12": ragged(6000, 12), "ragged32": ragged(6000, 32), "small": ragged(1000, 5),
+           "empty": (np.zeros(5001, np.int32), np.empty(0, np.int32), np.empty(0)), "wide": wide}
+    makers = {"lap3d": lambda: ks.Mat.laplacian3d(ctx, 24, 20, 16), "lap2d": lambda: ks.Mat.laplacian2d(ctx, 80, 60)}
+    makers.update({k: (lambda a=a: ks.Mat.from_csr(ctx, *a)) for k, a in csr.items()})
+    table = {}
+    for name, make in makers.items():
+        row = []
+        for fmt in (None,) + SPMV_OVERRIDES:
+            if fmt is None:
+                monkeypatch.delenv("KSGPU_SPMV", raising=False)
+            else:
+                monkeypatch.setenv("KSGPU_SPMV", fmt)
+            A = make()
+            row.append(A.layout())
+            A.destroy()
+        table[name] = tuple(row)
+    monkeypatch.delenv("KSGPU_SPMV", raising=False)
+    return table
+
+
+def test_spmv_layout_choice_table(ctx, monkeypatch):
+    """The layout chosen at assembly, automatically and under each KSGPU_SPMV override, for stencils from the generators and from CSR,
+    a graph Laplacian, ragged rows of three mean lengths, a small matrix, an empty one and a wide-scatter one."""
+    expected = {
+        #            auto      csr    csrvec csrregs  sell    dict     odict    binned    sliced
+        # binned / sliced on the generators: built since they share from_csr's chooser (before, the request was ignored: "sell")
+        "lap3d":    ("dict",  "csr", "csr", "csr",  "sell", "dict",  "odict", "binned", "sliced"),
+        "lap2d":    ("dict",  "csr", "csr", "csr",  "sell", "dict",  "odict", "binned", "sliced"),
+        "graph":    ("dict",  "csr", "csr", "csr",  "sell", "dict",  "odict", "sell",   "sell"),
+        "varcoef7": ("odict", "csr", "csr", "csr",  "sell", "odict", "odict", "binned", "sliced"),
+        "ragged8":  ("csr",   "csr", "csr", "csr",  "sell", "csr",   "csr",   "binned", "sliced"),
+        "ragged12": ("csr",   "csr", "csr", "csr",  "sell", "csr",   "csr",   "binned", "sliced"),
+        "ragged32": ("csr",   "csr", "csr", "csr",  "sell", "csr",   "csr",   "binned", "sliced"),
+        "small":    ("csr",   "csr", "csr", "csr",  "sell", "csr",   "csr",   "csr",    "csr"),
+        "empty":    ("csr",   "csr", "csr", "csr",  "csr",  "csr",   "csr",   "csr",    "csr"),
+        "wide":     ("binned", "csr", "csr", "csr", "sell", "sell",  "sell",  "binned", "sliced"),
+    }
+    assert _layout_choice_table(ctx, monkeypatch) == expected
+
+
+@pytest.mark.parametrize("fmt", ["csrblock", "nonsense"])
+def test_spmv_unknown_override(ctx, monkeypatch, fmt):
+    """A KSGPU_SPMV value that names no layout fails the creation (KS_ERR_ARG_WRONG) instead of being ignored."""
+    import slepc_amd as ks
+    monkeypatch.setenv("KSGPU_SPMV", fmt)
+    for make in (lambda: ks.Mat.from_csr(ctx, [0, 1, 2], [0, 1], [2.0, 3.0]), lambda: ks.Mat.laplacian2d(ctx, 10)):
+        with pytest.raises(ks.KsError) as e:
+            make()
+        assert e.value.rc == 62
+
+
 def test_spmv_rejects_bad_input(ctx):
     import slepc_amd as ks
     with pytest.raises(ks.KsError) as e:
