@@ -216,6 +216,12 @@ int ks_mat_mult(ks_mat A, const double *x_dev, double *y_dev);
 int ks_mat_mult_transpose(ks_mat A, const double *x_dev, double *y_dev);
 int ks_mat_shell_set_mult_transpose(ks_mat A, ks_shell_mult_fn mult_transpose);
 int ks_mat_mult_host(ks_mat A, const double *x_host, double *y_host);  /* convenience for tests (single rank) */
+/* MatMatMult / MatProductNumeric(AB) with a dense column-major block: Y(:,j) = A X(:,j), j < ncols (X(:,j) at X_dev + j*ldx, Y(:,j) at
+   Y_dev + j*ldy). Every column is bit for bit ks_mat_mult(A, X(:,j)): the dictionary, offset-dictionary, SELL-64 and CSR row-block layouts
+   apply A to up to 8 columns per pass (the matrix streamed once per pass); BINNED, SLICED, shell matrices, the CSR-vector form of small
+   matrices and row-sharded matrices with a halo run one ks_mat_mult per column. ncols == 0 does nothing; ldx, ldy >= max(1, n_local)
+   (KS_ERR_ARG_SIZ); X and Y must not overlap (KS_ERR_ARG_WRONG). Enqueued on the context's stream, no host wait. */
+int ks_mat_mult_multi(ks_mat A, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy);
 /* How MatMult moves the boundary entries of x between ranks. KS_HALO_PROVIDER: packed into a send buffer and handed to the
  * communicator's exchange (grouped ncclSend / ncclRecv with the RCCL provider; PETSc's VecScatter is the reference's). KS_HALO_PEER: the pack
  * kernel stores every boundary entry straight into the ghost mailbox of the rank that needs it (device memory of that rank mapped here:
@@ -283,6 +289,13 @@ int ks_bv_copy(ks_bv V, ks_bv W);                                               
 int ks_bv_copycolumn(ks_bv V, int j, int i);                                                     /* ops->copycolumn */
 int ks_bv_matmult(ks_bv V, ks_mat A, ks_bv W);                                                   /* ops->matmult (column loop, svec.c:213) */
 int ks_bv_matmultcolumn(ks_bv V, ks_mat A, int j);                                               /* BVMatMultColumn bvops.c:862 */
+/* BVSetMatMultMethod bvbasic.c:1020 (BVMatMultType slepcbv.h:106-108): how ks_bv_matmult (V's method), ks_bv_matproject and the B*X block
+   of ks_bv_dot with an inner-product matrix (X's method) apply a matrix to a block of columns. VECS: one ks_mat_mult per column; MAT:
+   one ks_mat_mult_multi (same bits). MAT_SAVE is stored as MAT (bvbasic.c:1053-1055); any other value is KS_ERR_ARG_OUTOFRANGE. The
+   default stays VECS (SLEPc's is MAT: INTEGRATION.md section 2); ks_bv_duplicate copies the method. */
+enum { KS_BV_MATMULT_VECS = 0, KS_BV_MATMULT_MAT = 1, KS_BV_MATMULT_MAT_SAVE = 2 };
+int ks_bv_set_matmult_method(ks_bv bv, int method);
+int ks_bv_get_matmult_method(ks_bv bv, int *method);                                             /* BVGetMatMultMethod bvbasic.c:1064 */
 
 /* ops->gramschmidt (bvimpl.h:53): ONE Gram-Schmidt pass, the function BVOrthogonalizeGS1 dispatches to (bvorthog.c:134) in place
    of BVOrthogonalizeCGS1 (:91-132) / BVOrthogonalizeMGS1 (:52-85), chosen by the BV's orthogonalization type. The caller

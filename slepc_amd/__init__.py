@@ -32,6 +32,8 @@ WHICH = {"largest_magnitude": 1, "smallest_magnitude": 2, "largest_real": 3, "sm
 BLOCK = {"gs": 0, "chol": 1, "tsqr": 2, "tsqrchol": 3, "svqb": 4}
 SHELL_MULT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
 ST_SHIFT, ST_SINVERT, ST_CAYLEY = 0, 1, 2
+BV_MATMULT_VECS, BV_MATMULT_MAT, BV_MATMULT_MAT_SAVE = 0, 1, 2
+MATMULT = {"vecs": BV_MATMULT_VECS, "mat": BV_MATMULT_MAT, "mat_save": BV_MATMULT_MAT_SAVE}
 EIG_COMPARE_FN = C.CFUNCTYPE(C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int), C.c_void_p)
 EPS_CONVERGED_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_void_p)
 EPS_STOPPING_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p)
@@ -48,6 +50,11 @@ def event_name(name):
 # kernel symbol behind each (class, variant) as rocprofv3 --kernel-trace names it (16-byte-load forms)
 def kernel_symbol(name, var):
     if name == "spmv_csr":
+        # 20-24: the block product of ks_mat_mult_multi (one launch per pass of up to 8 columns, KB = columns of the pass)
+        block = {20: "k_spmm_dict<W, KB>", 21: "k_spmm_odict<W, KB>", 22: "k_spmm_sell<KB>", 23: "k_spmm_csr<KB, false>",
+                 24: "k_spmm_pack<KB> + k_spmm_csr<KB, true>"}
+        if var in block:
+            return block[var]
         return ("k_spmv_dict<W>" if var == 16 else "k_spmv_odict<W>" if var == 17 else "k_binned_gather + k_binned_reduce" if var == 18
                 else "k_spmv_sell<4>" if var == 8 else "k_spmv_csr_wave_dma<8, 6, 8> | k_spmv_csr_wave<ROWSIDE, 8> | k_spmv_csr<G, 4, false, false>")
     if name == "bv_dot_sweep":
@@ -345,6 +352,21 @@ class Mat:
     def mult_dev(self, x_ptr, y_ptr):
         _lib.check(self.ctx.L.ks_mat_mult(self.h, C.c_void_p(x_ptr), C.c_void_p(y_ptr)))
 
+    def mult_multi_dev(self, X_ptr, ldx, Y_ptr, ldy, ncols):
+        """MatMatMult with a dense column-major block on device pointers: Y(:,j) = A X(:,j), j < ncols (ks_mat_mult_multi)."""
+        _lib.check(self.ctx.L.ks_mat_mult_multi(self.h, ncols, C.c_void_p(X_ptr), ldx, C.c_void_p(Y_ptr), ldy))
+
+    def mult_multi(self, X):
+        """Y = A X with a host block of shape (n, ncols) (test convenience, single rank)."""
+        X = np.asarray(X, dtype=np.float64)
+        ncols = X.shape[1]
+        if ncols == 0:
+            return np.zeros((self.n, 0))
+        XB, YB = BV(self.ctx, self.n, ncols), BV(self.ctx, self.n, ncols)
+        XB.set_dense(X)
+        self.mult_multi_dev(XB.column_ptr(0), XB.ld, YB.column_ptr(0), YB.ld, ncols)
+        return YB.dense()
+
     def spmv_bytes(self):
         """Algorithmic bytes of one MatMult: 12*nnz + 4*(n+1) + 16*n."""
         return 12.0 * self.nnz + 4.0 * (self.n + 1) + 16.0 * self.n
@@ -556,6 +578,13 @@ class BV:
 
     def MatMultColumn(self, A, j):
         _lib.check(self.ctx.L.ks_bv_matmultcolumn(self.h, A.h, j))
+
+    def SetMatMultMethod(self, method):
+        """BVSetMatMultMethod: "vecs" / "mat" / "mat_save" (or the BV_MATMULT_* number)."""
+        _lib.check(self.ctx.L.ks_bv_set_matmult_method(self.h, MATMULT.get(method, method)))
+
+    def GetMatMultMethod(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_bv_get_matmult_method(self.h, C.byref(v))); return v.value
 
     def OrthogonalizeColumn(self, j):
         nrm = C.c_double(); lin = C.c_int()

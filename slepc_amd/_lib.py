@@ -71,6 +71,7 @@ _SIG = {
     "ks_mat_get_sizes": [vp, ip, ip, llp],
     "ks_mat_mult": [vp, vp, vp],
     "ks_mat_mult_host": [vp, dp, dp],
+    "ks_mat_mult_multi": [vp, C.c_int, vp, C.c_int, vp, C.c_int],
     # bv
     "ks_bv_create": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
     "ks_bv_destroy": [vp],
@@ -112,6 +113,8 @@ _SIG = {
     "ks_bv_copycolumn": [vp, C.c_int, C.c_int],
     "ks_bv_matmult": [vp, vp, vp],
     "ks_bv_matmultcolumn": [vp, vp, C.c_int],
+    "ks_bv_set_matmult_method": [vp, C.c_int],
+    "ks_bv_get_matmult_method": [vp, ip],
     "ks_bv_gramschmidt_pass": [vp, C.c_int, vp, ip, dp, dp, dp, dp],
     "ks_bv_orthogonalizecolumn": [vp, C.c_int, dp, dp, ip],
     "ks_bv_orthonormalizecolumn": [vp, C.c_int, C.c_int, dp, ip],

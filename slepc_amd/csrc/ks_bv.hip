@@ -415,6 +415,7 @@ extern "C" int ks_bv_duplicate(ks_bv bv, ks_bv *out)
   KS_CHECK(bv && out, KS_ERR_ARG_NULL, "NULL argument");
   KS_CALL(ks_bv_create(bv->ctx, bv->n, bv->N, bv->m, bv->ld, out));
   (*out)->orthog_type = bv->orthog_type; (*out)->orthog_ref = bv->orthog_ref; (*out)->orthog_eta = bv->orthog_eta;
+  (*out)->matmult = bv->matmult;                                                       // bvbasic.c:1633
   (*out)->l = bv->l; (*out)->k = bv->k; (*out)->row_start = bv->row_start;
   return KS_SUCCESS;
 }
@@ -770,8 +771,7 @@ int ksb_dot_range(ks_bv X, int xs, int xe, ks_bv Y, int ys, int ye, double *M, i
     // bvglobal.c:103-107: cached = B*X(:,xs:xe), then M = Y^H cached
     ks_bv W = nullptr;
     KS_CALL(ks_bv_create(ctx, X->n, X->N, nx, 0, &W));
-    int rc = KS_SUCCESS;
-    for (int j = 0; j < nx && !rc; j++) rc = ks_mat_mult_internal(X->matrix, X->array + (size_t)(X->nc + xs + j) * X->ld, ks_bv_col(W, j));
+    int rc = ksb_matmult_block(X, X->matrix, ks_bv_col(X, xs), X->ld, ks_bv_col(W, 0), W->ld, nx);
     if (!rc) {
       std::vector<double> T((size_t)ldm * nx, 0.0);
       rc = ksb_dot_range(W, 0, nx, Y, ys, ye, T.data(), ldm);
@@ -1103,6 +1103,31 @@ extern "C" int ks_bv_matmult(ks_bv V, ks_mat A, ks_bv W)   // bvops.c BVMatMult,
   KS_CHECK(A->n == W->n && A->n == V->n, KS_ERR_ARG_INCOMP, "Mismatching local row dimension");
   KS_CHECK(V->k - V->l == W->k - W->l, KS_ERR_ARG_SIZ, "Y has %d active columns, should match %d active columns in V", W->k - W->l, V->k - V->l);
   KS_HIP(hipSetDevice(V->ctx->device));
-  for (int j = 0; j < V->k - V->l; j++) KS_CALL(ks_mat_mult_internal(A, ks_bv_col(V, V->l + j), ks_bv_col(W, W->l + j)));
+  return ksb_matmult_block(V, A, ks_bv_col(V, V->l), V->ld, ks_bv_col(W, W->l), W->ld, V->k - V->l);
+}
+
+// BVMatMult's product of A with a block of ncols contiguous columns (stride ld) under the method of method_bv: VECS the column loop of
+// svec.c:213-222, MAT the block product of svec.c:210-221 (MatProductNumeric) - the same bits either way
+int ksb_matmult_block(ks_bv method_bv, ks_mat A, const double *X, int ldx, double *Y, int ldy, int ncols)
+{
+  if (method_bv->matmult == KS_BV_MATMULT_MAT) return ks_mat_mult_multi_internal(A, ncols, X, ldx, Y, ldy);
+  for (int j = 0; j < ncols; j++) KS_CALL(ks_mat_mult_internal(A, X + (size_t)j * ldx, Y + (size_t)j * ldy));
+  return KS_SUCCESS;
+}
+
+extern "C" int ks_bv_set_matmult_method(ks_bv bv, int method)   // BVSetMatMultMethod bvbasic.c:1020-1060
+{
+  KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
+  switch (method) {
+  case KS_BV_MATMULT_VECS: bv->matmult = KS_BV_MATMULT_VECS; break;
+  case KS_BV_MATMULT_MAT: case KS_BV_MATMULT_MAT_SAVE: bv->matmult = KS_BV_MATMULT_MAT; break;      // MAT_SAVE is deprecated to MAT (bvbasic.c:1053-1055)
+  default: KS_FAIL(KS_ERR_ARG_OUTOFRANGE, "Unknown matmult method %d", method);
+  }
+  return KS_SUCCESS;
+}
+extern "C" int ks_bv_get_matmult_method(ks_bv bv, int *method)   // BVGetMatMultMethod bvbasic.c:1064
+{
+  KS_CHECK(bv && method, KS_ERR_ARG_NULL, "NULL argument");
+  *method = bv->matmult;
   return KS_SUCCESS;
 }

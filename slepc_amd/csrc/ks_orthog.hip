@@ -350,8 +350,7 @@ extern "C" int ks_bv_matproject(ks_bv X, ks_mat A, ks_bv Y, double *M, int ldm)
   const int nx = X->k - X->l;
   if (nx <= 0 || Y->k <= Y->l) return KS_SUCCESS;
   KS_CALL(ks_bv_create(X->ctx, X->n, X->N, nx, 0, &W));                  // BVDuplicateResize + BVMatMult (bvglobal.c:1127-1131)
-  int rc = KS_SUCCESS;
-  for (int j = 0; j < nx && !rc; j++) rc = ks_mat_mult_internal(A, ks_bv_col(X, X->l + j), ks_bv_col(W, j));
+  int rc = ksb_matmult_block(X, A, ks_bv_col(X, X->l), X->ld, ks_bv_col(W, 0), W->ld, nx);
   if (!rc) {
     std::vector<double> T((size_t)ldm * nx);
     rc = ksb_dot_range(W, 0, nx, Y, Y->l, Y->k, T.data(), ldm);

@@ -1,0 +1,403 @@
+// MatMatMult / MatProductNumeric(AB) with a dense column-major block: Y(:,j) = A X(:,j), j < ncols.
+//
+// The product behind BVMatMult's MAT method (bvbasic.c:1020-1060, svec.c:210-221): one pass applies the diagonal block to up to
+// MM_KB = 8 columns at once, so the matrix is streamed once per pass instead of once per column. Per column a pass moves
+// A_bytes / KB + 16 B per row (the x gather and the y store); the column loop moves A_bytes + 16 B per row.
+//
+// Bit contract: every lane owns one row and runs, for every column of the pass, the single-vector kernel's chain
+// acc = fma(a_e, x_e, acc) from 0.0 in entry order - padding entries included exactly where that kernel has them (the dictionary
+// forms and SELL-64 fma 0.0 * 0.0, the CSR row blocks skip them). So Y(:,j) is ks_mat_mult(A, X(:,j)) bit for bit, NaN, Inf and the
+// +0.0 of an empty row included. Layouts and forms without such a kernel (BINNED, SLICED, shell matrices, the CSR-vector form of small
+// matrices, anything with a halo) run the column loop over ks_mat_mult_internal: the same bits by construction.
+#include "ks_sweeps.cuh"
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+namespace {
+
+constexpr int MM_BLOCK = 256;
+constexpr int MM_KB = 8;                // columns per pass (KB accumulators per lane); every KB from 1 to 8 is compiled for the tail
+
+typedef int mm_i2v __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) void mm_lds_void;          // operands of __builtin_amdgcn_global_load_lds (LDS-DMA)
+typedef const __attribute__((address_space(1))) void mm_glb_void;
+
+// ---- dictionary ELL (k_spmv_dict's storage): a row's codes are decoded once, each entry gathers its KB x values ---------------------
+template <int W, int KB>
+__global__ __launch_bounds__(MM_BLOCK) void k_spmm_dict(int nrows, const uint4 *__restrict__ codes, const double *__restrict__ dval, int nval, const int *__restrict__ doff, int noff,
+                                                        const double *__restrict__ X, long long ldx, double *__restrict__ Y, long long ldy, int xcd_remap)
+{
+  __shared__ double sv[256];
+  __shared__ int so[256];
+  for (int i = threadIdx.x; i < nval; i += MM_BLOCK) sv[i] = dval[i];
+  for (int i = threadIdx.x; i < noff; i += MM_BLOCK) so[i] = doff[i];
+  __syncthreads();
+  constexpr int Q = W / 8;
+  const long long groups = ((long long)nrows + MM_BLOCK - 1) / MM_BLOCK;
+  long long g0 = 0, g1 = groups, lb = blockIdx.x, nb = gridDim.x;
+  if (xcd_remap) {                                          // each XCD one contiguous eighth of the row groups (k_spmv_dict)
+    const long long gper = (groups + 7) / 8;
+    g0 = (blockIdx.x % 8) * gper; g1 = g0 + gper < groups ? g0 + gper : groups;
+    lb = blockIdx.x / 8; nb = gridDim.x / 8;
+  }
+  for (long long g = g0 + lb; g < g1; g += nb) {
+    const long long r = g * MM_BLOCK + threadIdx.x;
+    if (r >= nrows) break;
+    double acc[KB];
+#pragma unroll
+    for (int k = 0; k < KB; k++) acc[k] = 0.0;
+#pragma unroll 1
+    for (int q = 0; q < Q; q++) {                           // eight entries at a time: 8 KB gathers in flight, not W KB
+      const uint4 c = ksk::ldstream4(codes + r * Q + q);
+      const unsigned wds[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        const unsigned code = (wds[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
+        const unsigned oc = code & 0xffu, vc = code >> 8;
+        const bool ok = vc != 255u;
+        const double a = ok ? sv[vc] : 0.0;
+        const long long xi = r + (ok ? so[oc] : 0);
+#pragma unroll
+        for (int k = 0; k < KB; k++) acc[k] = fma(a, ok ? X[k * ldx + xi] : 0.0, acc[k]);      // padding: fma(0.0, 0.0, acc) as in k_spmv_dict
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < KB; k++) __builtin_nontemporal_store(acc[k], Y + k * ldy + r);
+  }
+}
+
+// ---- offset-dictionary ELL (k_spmv_odict's storage) ------------------------------------------------------------------------------
+template <int W, int KB>
+__global__ __launch_bounds__(MM_BLOCK) void k_spmm_odict(int nrows, const unsigned char *__restrict__ codes, const double *__restrict__ vals, const int *__restrict__ doff, int noff,
+                                                         const double *__restrict__ X, long long ldx, double *__restrict__ Y, long long ldy, int xcd_remap)
+{
+  __shared__ int so[256];
+  for (int i = threadIdx.x; i < noff; i += MM_BLOCK) so[i] = doff[i];
+  __syncthreads();
+  const long long groups = ((long long)nrows + MM_BLOCK - 1) / MM_BLOCK;
+  long long g0 = 0, g1 = groups, lb = blockIdx.x, nb = gridDim.x;
+  if (xcd_remap) {
+    const long long gper = (groups + 7) / 8;
+    g0 = (blockIdx.x % 8) * gper; g1 = g0 + gper < groups ? g0 + gper : groups;
+    lb = blockIdx.x / 8; nb = gridDim.x / 8;
+  }
+  for (long long g = g0 + lb; g < g1; g += nb) {
+    const long long r = g * MM_BLOCK + threadIdx.x;
+    if (r >= nrows) break;
+    const double *vb = vals + ((r >> 6) * W) * 64 + (r & 63);
+    double acc[KB];
+#pragma unroll
+    for (int k = 0; k < KB; k++) acc[k] = 0.0;
+#pragma unroll 1
+    for (int e8 = 0; e8 < W; e8 += 8) {                     // eight entries at a time (their codes: one 8-byte load)
+      const uint2 cw = *reinterpret_cast<const uint2 *>(codes + r * W + e8);
+      const unsigned wds[2] = {cw.x, cw.y};
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        const unsigned oc = (wds[e >> 2] >> ((e & 3) * 8)) & 0xffu;
+        const bool ok = oc != 255u;
+        const double a = ok ? ksk::ldstream(vb + (long long)(e8 + e) * 64) : 0.0;
+        const long long xi = r + (ok ? so[oc] : 0);
+#pragma unroll
+        for (int k = 0; k < KB; k++) acc[k] = fma(a, ok ? X[k * ldx + xi] : 0.0, acc[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < KB; k++) __builtin_nontemporal_store(acc[k], Y + k * ldy + r);
+  }
+}
+
+// ---- SELL-64 (k_spmv_sell's entry pairs): batches of MM_UNR pairs, predicated as there, so the padding fmas fall where they fall in
+// k_spmv_sell<4> ------------------------------------------------------------------------------------------------------------------
+constexpr int MM_UNR = 4;
+template <int KB>
+__global__ __launch_bounds__(MM_BLOCK) void k_spmm_sell(int nrows, int nslices, const int *__restrict__ sp, const int *__restrict__ rlen,
+                                                        const int *__restrict__ col, const double *__restrict__ val,
+                                                        const double *__restrict__ X, long long ldx, double *__restrict__ Y, long long ldy, int xcd_remap)
+{
+  const int lane = threadIdx.x & 63;
+  const int wpb = MM_BLOCK / 64;
+  long long nblk = gridDim.x;
+  long long b = blockIdx.x;
+  if (xcd_remap) {
+    const long long per = nblk / 8;
+    if (b < per * 8) b = (b % 8) * per + b / 8;
+  }
+  const long long nsb = ((long long)nslices + wpb - 1) / wpb;
+  for (long long g = b; g < nsb; g += nblk) {
+    const long long s = g * wpb + (threadIdx.x >> 6);
+    if (s >= nslices) continue;
+    const long long r = s * 64 + lane;
+    const int w = sp[s + 1] - sp[s], wp = w >> 1;
+    const int len = (r < nrows) ? rlen[r] : 0;
+    const long long sb = (long long)sp[s] * 64;
+    double acc[KB];
+#pragma unroll
+    for (int k = 0; k < KB; k++) acc[k] = 0.0;
+    for (int q = 0; q < wp; q += MM_UNR) {
+      mm_i2v c[MM_UNR]; ksk::ks_d2v a[MM_UNR];
+#pragma unroll
+      for (int u = 0; u < MM_UNR; u++) {
+        const int j = 2 * (q + u);
+        const bool ok = q + u < wp && j < len;
+        const long long p = sb + (long long)(q + u) * 128 + lane * 2;
+        c[u] = ok ? __builtin_nontemporal_load(reinterpret_cast<const mm_i2v *>(col + p)) : mm_i2v{-1, -1};
+        a[u] = ok ? __builtin_nontemporal_load(reinterpret_cast<const ksk::ks_d2v *>(val + p)) : ksk::ks_d2v{0.0, 0.0};
+        if (j + 1 >= len) { c[u].y = -1; a[u].y = 0.0; }
+      }
+#pragma unroll
+      for (int u = 0; u < MM_UNR; u++) {
+#pragma unroll
+        for (int k = 0; k < KB; k++) {
+          const double x0 = c[u].x >= 0 ? X[k * ldx + c[u].x] : 0.0, x1 = c[u].y >= 0 ? X[k * ldx + c[u].y] : 0.0;
+          acc[k] = fma(a[u].x, x0, acc[k]); acc[k] = fma(a[u].y, x1, acc[k]);
+        }
+      }
+    }
+    if (w & 1) {
+      const bool ok = w - 1 < len;
+      const long long p = sb + (long long)wp * 128 + lane;
+      const int c = ok ? ksk::ldstream(col + p) : -1;
+      const double a = ok ? ksk::ldstream(val + p) : 0.0;
+#pragma unroll
+      for (int k = 0; k < KB; k++) acc[k] = fma(a, c >= 0 ? X[k * ldx + c] : 0.0, acc[k]);
+    }
+    if (r < nrows) {
+#pragma unroll
+      for (int k = 0; k < KB; k++) __builtin_nontemporal_store(acc[k], Y + k * ldy + r);
+    }
+  }
+}
+
+// ---- CSR row blocks: k_spmv_csr_wave_dma's staging (a wave owns 64 rows, their col / val run goes chunk by chunk straight into a
+// wave-private piece of LDS), lane = row, KB chains per lane -----------------------------------------------------------------------
+// IL: where an entry's KB x values come from. false (direct): the column-major block, KB separate gathers (KB cache lines for a
+// scattered column). true (interleaved): a row-major n x KB copy of the pass's columns (k_spmm_pack, owned by the matrix), so one
+// entry's KB values are one run of 8 KB bytes.
+struct MmRows { int p0, p1, E0, E1; long long r; bool has; };
+__device__ __forceinline__ MmRows mm_rows(int n, const int *__restrict__ rp, int g, int w, int lane)
+{
+  MmRows q; q.p0 = q.p1 = q.E0 = q.E1 = 0; q.has = false;
+  const long long r0 = (long long)g * 256 + (long long)w * 64;
+  q.r = r0 + lane;
+  if (r0 >= n) return q;
+  q.has = q.r < n;
+  if (q.has) { mm_i2v pp; __builtin_memcpy(&pp, rp + q.r, sizeof(pp)); q.p0 = pp.x; q.p1 = pp.y; }
+  q.E0 = rp[r0]; q.E1 = rp[r0 + 64 < n ? r0 + 64 : n];
+  return q;
+}
+template <int KB, bool IL>
+__device__ __forceinline__ void mm_gather(double (&xv)[KB], const double *__restrict__ X, long long ldx, int c, bool ok)
+{
+  if (IL && KB % 2 == 0) {
+#pragma unroll
+    for (int k = 0; k < KB; k += 2) {
+      const ksk::ks_d2v t = ok ? *reinterpret_cast<const ksk::ks_d2v *>(X + (long long)c * KB + k) : ksk::ks_d2v{0.0, 0.0};
+      xv[k] = t.x; xv[k + 1] = t.y;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < KB; k++) xv[k] = ok ? (IL ? X[(long long)c * KB + k] : X[k * ldx + c]) : 0.0;
+  }
+}
+constexpr int MM_CH = 512;           // entries per chunk (as k_spmv_csr_wave_dma<8, ...>): 6 KB of LDS per wave
+constexpr int MM_GU = 2;             // entries whose KB gathers are in flight per lane
+template <int KB, bool IL>
+__global__ __launch_bounds__(256, 4) void k_spmm_csr(int n, const int *__restrict__ rp, const int *__restrict__ col, const double *__restrict__ val,
+                                                     const double *__restrict__ X, long long ldx, double *__restrict__ Y, long long ldy, int xcd_remap)
+{
+  __shared__ __attribute__((aligned(16))) double sa_all[4][MM_CH];
+  __shared__ __attribute__((aligned(16))) int sc_all[4][MM_CH];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  double *sa = sa_all[w];
+  int *sc = sc_all[w];
+  const int NG = (n + 255) / 256;
+  int g, gend, gstep;
+  if (xcd_remap) {
+    const int xcd = blockIdx.x & 7, li = blockIdx.x >> 3, lc = gridDim.x >> 3;
+    g = (int)((long long)NG * xcd / 8) + li; gend = (int)((long long)NG * (xcd + 1) / 8); gstep = lc;
+  } else { g = blockIdx.x; gend = NG; gstep = gridDim.x; }
+  if (g >= gend) return;
+  MmRows cu = mm_rows(n, rp, g, w, lane);
+  MmRows nx = g + gstep < gend ? mm_rows(n, rp, g + gstep, w, lane) : MmRows{0, 0, 0, 0, 0, false};
+  for (;;) {
+    double acc[KB];
+#pragma unroll
+    for (int k = 0; k < KB; k++) acc[k] = 0.0;
+    for (int e0 = cu.E0 & ~3; e0 < cu.E1; e0 += MM_CH) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // the row lanes' reads of the previous chunk are done before this one may land
+#pragma unroll
+      for (int i = 0; i < MM_CH / 128; i++) {
+        const int e = e0 + 128 * i + 2 * lane;
+        if (e < cu.E1) __builtin_amdgcn_global_load_lds((mm_glb_void *)(val + e), (mm_lds_void *)(sa + 128 * i), 16, 0, 2);     // may take one entry past E1: CW_PAD
+      }
+#pragma unroll
+      for (int i = 0; i < MM_CH / 256; i++) {
+        const int e = e0 + 256 * i + 4 * lane;
+        if (e < cu.E1) __builtin_amdgcn_global_load_lds((mm_glb_void *)(col + e), (mm_lds_void *)(sc + 256 * i), 16, 0, 2);     // up to three past E1: CW_PAD
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // an LDS-DMA is a pending LDS write on the VM counter
+      const int lo = max(cu.p0, e0), hi = min(cu.p1, e0 + MM_CH);
+      for (int p = lo; __builtin_amdgcn_ballot_w64(p < hi) != 0; p += MM_GU) {
+        double av[MM_GU], xv[MM_GU][KB];
+#pragma unroll
+        for (int j = 0; j < MM_GU; j++) {
+          const bool ok = p + j < hi;
+          const int sl = ok ? p + j - e0 : 0;
+          av[j] = sa[sl];
+          mm_gather<KB, IL>(xv[j], X, ldx, ok ? sc[sl] : 0, ok);
+        }
+#pragma unroll
+        for (int j = 0; j < MM_GU; j++)
+          if (p + j < hi) {
+#pragma unroll
+            for (int k = 0; k < KB; k++) acc[k] = fma(av[j], xv[j][k], acc[k]);
+          }
+      }
+    }
+    if (cu.has) {
+#pragma unroll
+      for (int k = 0; k < KB; k++) __builtin_nontemporal_store(acc[k], Y + k * ldy + cu.r);
+    }
+    g += gstep;
+    if (g >= gend) break;
+    cu = nx;
+    nx = g + gstep < gend ? mm_rows(n, rp, g + gstep, w, lane) : MmRows{0, 0, 0, 0, 0, false};
+  }
+}
+
+// X(:, 0:KB) column-major -> Xi (n x KB, row-major): thread = row; the loads of a column and the stores of a row block are contiguous
+template <int KB>
+__global__ __launch_bounds__(256) void k_spmm_pack(int n, const double *__restrict__ X, long long ldx, double *__restrict__ Xi)
+{
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  double v[KB];
+#pragma unroll
+  for (int k = 0; k < KB; k++) v[k] = X[k * ldx + r];
+#pragma unroll
+  for (int k = 0; k < KB; k++) Xi[r * KB + k] = v[k];
+}
+
+#define MM_KB_SWITCH(kb, F) \
+  switch (kb) { case 1: F(1); break; case 2: F(2); break; case 3: F(3); break; case 4: F(4); break; case 5: F(5); break; case 6: F(6); break; case 7: F(7); break; default: F(8); break; }
+
+// The CSR gather form: interleaved where rows are long enough for the gathers to bind - more than 12 entries per row on average, the
+// threshold above which ks_mat_mult_internal gathers on the entry side (profiles/r05_spmm.txt times both forms on both sides of it).
+// KSGPU_SPMM=direct|interleaved forces one (A/B legs of scripts/spmm_probe.py; read at every pass).
+bool csr_interleaved(ks_mat A)
+{
+  const char *force = getenv("KSGPU_SPMM");
+  if (force && !strcmp(force, "direct")) return false;
+  if (force && !strcmp(force, "interleaved")) return true;
+  return A->nnz_d > 12LL * A->n;
+}
+
+// one pass over kb <= MM_KB columns; the caller has ruled out every layout and form the column loop takes
+int spmm_pass(ks_mat A, int kb, const double *X, long long ldx, double *Y, long long ldy)
+{
+  ks_ctx ctx = A->ctx;
+  const bool il = A->layout == KS_MAT_LAYOUT_CSR && csr_interleaved(A);
+  if (il && !A->mm_xi) {
+    const size_t bytes = sizeof(double) * (size_t)A->n * MM_KB;         // the widest pass: allocated once, freed by ks_mat_destroy
+    if (hipMalloc(&A->mm_xi, bytes) != hipSuccess) { A->mm_xi = nullptr; KS_FAIL(KS_ERR_MEM, "hipMalloc of the interleaved block (%zu bytes) failed", bytes); }
+  }
+  // variants 20: k_spmm_dict, 21: k_spmm_odict, 22: k_spmm_sell, 23: k_spmm_csr (direct), 24: k_spmm_pack + k_spmm_csr (interleaved);
+  // algorithmic bytes A_bytes + 16 n KB with the CSR stream as A_bytes (as ks_mat_mult_internal counts), the layout's own next to them
+  const double xy = 16.0 * A->n * kb;
+  const double alg = 12.0 * A->nnz_d + 4.0 * (A->n + 1) + xy;
+  int variant = 23; double own = alg;
+  switch (A->layout) {
+  case KS_MAT_LAYOUT_DICT: variant = 20; own = 2.0 * A->dict_w * A->n + xy; break;
+  case KS_MAT_LAYOUT_ODICT: variant = 21; own = 8.0 * A->nnz_d + (double)A->dict_w * A->n + xy; break;
+  case KS_MAT_LAYOUT_SELL: variant = 22; own = 12.0 * A->s_entries + 4.0 * A->n + xy; break;
+  default: if (il) { variant = 24; own = alg + xy; } break;              // the pack reads the pass's columns and writes them once more
+  }
+  KsProfScope ps(ctx, KS_K_SPMV, alg, variant, own);
+  switch (A->layout) {
+  case KS_MAT_LAYOUT_DICT:
+  case KS_MAT_LAYOUT_ODICT: {
+    const long long groups = ((long long)A->n + MM_BLOCK - 1) / MM_BLOCK;       // the grid of ks_mat_mult_internal's dictionary launch
+    long long nblk = std::max<long long>(1, std::min<long long>(groups, (long long)ctx->num_cu * 64));
+    const int remap = nblk >= 64 ? 1 : 0;
+    if (remap) nblk = std::min<long long>((nblk + 7) / 8, (groups + 7) / 8) * 8;
+    const dim3 gr((unsigned)nblk);
+#define MM_DICT(KB)                                                                                                                                                                   \
+  if (A->layout == KS_MAT_LAYOUT_DICT) {                                                                                                                                              \
+    if (A->dict_w == 8) hipLaunchKernelGGL((k_spmm_dict<8, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);     \
+    else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmm_dict<32, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap); \
+    else hipLaunchKernelGGL((k_spmm_dict<16, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);              \
+  } else if (A->dict_w == 8) hipLaunchKernelGGL((k_spmm_odict<8, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);                   \
+  else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmm_odict<32, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);                 \
+  else hipLaunchKernelGGL((k_spmm_odict<16, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap)
+    MM_KB_SWITCH(kb, MM_DICT);
+#undef MM_DICT
+    break;
+  }
+  case KS_MAT_LAYOUT_SELL: {
+    const long long groups = ((long long)A->nslices + 3) / 4;                    // the grid of ks_mat_mult_internal's SELL launch
+    const long long blocks = std::min<long long>(groups, (long long)ctx->num_cu * 4096);
+    const int remap = (blocks == groups && blocks >= 64) ? 1 : 0;
+    const dim3 gr((unsigned)std::max<long long>(blocks, 1));
+#define MM_SELL(KB) hipLaunchKernelGGL((k_spmm_sell<KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, A->nslices, A->s_ptr, A->s_len, A->s_col, A->s_val, X, ldx, Y, ldy, remap)
+    MM_KB_SWITCH(kb, MM_SELL);
+#undef MM_SELL
+    break;
+  }
+  default: {                                                                      // CSR row blocks (n >= 2048, not the CSR-vector form)
+    const long long NG = ((long long)A->n + 255) / 256;
+    long long nb = std::min<long long>(NG, (long long)ctx->num_cu * 4);          // four workgroups of four waves per CU (the launch bounds)
+    const int remap = nb >= 64 ? 1 : 0;
+    if (remap) nb = (nb / 8) * 8;
+    const dim3 gr((unsigned)nb);
+    const unsigned npk = (unsigned)((A->n + 255) / 256);
+#define MM_CSR(KB)                                                                                                                                                    \
+  if (il) {                                                                                                                                                           \
+    hipLaunchKernelGGL((k_spmm_pack<KB>), dim3(npk), dim3(256), 0, ctx->stream, A->n, X, ldx, A->mm_xi);                                                            \
+    hipLaunchKernelGGL((k_spmm_csr<KB, true>), gr, dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, (const double *)A->mm_xi, ldx, Y, ldy, remap); \
+  } else hipLaunchKernelGGL((k_spmm_csr<KB, false>), gr, dim3(256), 0, ctx->stream, A->n, A->d_rowptr, A->d_col, A->d_val, X, ldx, Y, ldy, remap)
+    MM_KB_SWITCH(kb, MM_CSR);
+#undef MM_CSR
+    break;
+  }
+  }
+  KS_HIP(hipGetLastError());
+  return KS_SUCCESS;
+}
+
+} // namespace
+
+// The one dispatch of the block product (a switch on A->layout, as in ks_mat_mult_internal): passes of up to MM_KB columns where a
+// block kernel exists, the column loop everywhere else
+int ks_mat_mult_multi_internal(ks_mat A, int ncols, const double *X, int ldx, double *Y, int ldy)
+{
+  if (ncols <= 0) return KS_SUCCESS;
+  ks_ctx ctx = A->ctx;
+  const bool halo = ctx->comm.size > 1 && (A->nsend > 0 || A->nghost > 0);       // several columns through the halo at once: not built
+  bool loop = ncols == 1 || A->shell_mult || halo || A->n_orows > 0;
+  switch (A->layout) {
+  case KS_MAT_LAYOUT_DICT: case KS_MAT_LAYOUT_ODICT: case KS_MAT_LAYOUT_SELL: break;
+  case KS_MAT_LAYOUT_CSR: if (A->n < 2048 || A->csr_form == ks_mat_s::CSR_VEC) loop = true; break;      // the CSR-vector kernel: its sums are not in entry order
+  default: loop = true; break;                                                                            // BINNED, SLICED
+  }
+  if (loop) {
+    for (int j = 0; j < ncols; j++) KS_CALL(ks_mat_mult_internal(A, X + (size_t)j * ldx, Y + (size_t)j * ldy));
+    return KS_SUCCESS;
+  }
+  for (int j0 = 0; j0 < ncols; j0 += MM_KB) KS_CALL(spmm_pass(A, std::min(MM_KB, ncols - j0), X + (size_t)j0 * ldx, ldx, Y + (size_t)j0 * ldy, ldy));
+  return KS_SUCCESS;
+}
+
+extern "C" int ks_mat_mult_multi(ks_mat A, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy)
+{
+  KS_CHECK(A && X_dev && Y_dev, KS_ERR_ARG_NULL, "NULL argument");
+  KS_CHECK(ncols >= 0, KS_ERR_ARG_OUTOFRANGE, "Number of columns %d must be non-negative", ncols);
+  KS_CHECK(ldx >= std::max(1, A->n) && ldy >= std::max(1, A->n), KS_ERR_ARG_SIZ, "Leading dimensions ldx %d, ldy %d must be at least %d (local rows)", ldx, ldy, std::max(1, A->n));
+  if (ncols == 0) return KS_SUCCESS;
+  const uintptr_t x0 = (uintptr_t)X_dev, x1 = x0 + sizeof(double) * ((size_t)(ncols - 1) * ldx + A->n);
+  const uintptr_t y0 = (uintptr_t)Y_dev, y1 = y0 + sizeof(double) * ((size_t)(ncols - 1) * ldy + A->n);
+  KS_CHECK(X_dev != Y_dev && (x1 <= y0 || y1 <= x0), KS_ERR_ARG_WRONG, "X and Y must be different blocks: they overlap");      // MatMult's x != y, for blocks
+  KS_HIP(hipSetDevice(A->ctx->device));
+  return ks_mat_mult_multi_internal(A, ncols, X_dev, ldx, Y_dev, ldy);
+}

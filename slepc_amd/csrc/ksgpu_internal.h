@@ -170,6 +170,7 @@ struct ks_mat_s {
   int nslice = 0, slice_cols = 0;
   int *sl_rowptr = nullptr; int *sl_col = nullptr; double *sl_val = nullptr; long long *sl_base = nullptr;   // [nslice][n+1], entries, device offsets [nslice+1]
   double *ypart = nullptr;                    // [8][n]
+  double *mm_xi = nullptr;                    // block product, CSR interleaved form: [n][8] row-major copy of a pass's columns (ks_spmm.hip), allocated on first use
   // MatGetDiagonal / the infinity norm, taken before the binned, sliced and dictionary layouts release the CSR arrays (non-null: released)
   double *diag_cache = nullptr; double norm_inf_cache = -1.0;
   // Binned ("propagation blocking") copy of the diagonal block for wide-scatter matrices, the successor of the XCD-sliced one: the product
@@ -275,6 +276,7 @@ struct ks_bv_s {
   int n = 0, N = 0, m = 0, l = 0, k = 0, nc = 0, ld = 0;
   int orthog_type = KS_BV_ORTHOG_CGS, orthog_ref = KS_BV_ORTHOG_REFINE_IFNEEDED, orthog_block = KS_BV_ORTHOG_BLOCK_GS;
   ks_mat matrix = nullptr;   // inner-product matrix B of BVSetMatrix (positive definite), borrowed; nullptr = standard
+  int matmult = KS_BV_MATMULT_VECS;   // BVSetMatMultMethod: how the products of a block of this BV's columns run (ksb_matmult_block)
   double *Bx = nullptr;      // B*x of the vector an inner product is being taken with (BV_IPMatMult bvimpl.h:147-158)
   bool fetch_pending = false; size_t fetch_coefs = 0;     // result copies of the last enqueued column are on their way (gs_enqueue_column with early copies)
   // ops->gramschmidt slot, pass chaining (ks_bv_set_state): the last pass on column `col` left the next pass's dots in `partials`; they are used
@@ -326,6 +328,8 @@ int ksk_copy(ks_ctx ctx, const double *src, double *dst, size_t n);
 
 int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *rowscale = nullptr);   // rowscale: y = rowscale .* (A x) where the layout can fold it into its last pass (else the caller scales)
 bool ks_mat_can_rowscale(ks_mat A);
+int ks_mat_mult_multi_internal(ks_mat A, int ncols, const double *X, int ldx, double *Y, int ldy);   // Y(:,j) = A X(:,j), j < ncols (ks_spmm.hip)
+int ksb_matmult_block(ks_bv method_bv, ks_mat A, const double *X, int ldx, double *Y, int ldy, int ncols);   // BVMatMult's block product under method_bv's method
 int ks_mat_mult_dot_fused(ks_mat A, ks_bv bv, const double *x, int jy, bool gate, bool *done);   // y = A x inside the dot sweep of column jy (ks_spmv.hip); *done = false: not applicable                                 // the product can take a row scaling in the same launches
 int ks_bv_orthonormalize_coefs(ks_bv bv, int j, double *H, double *norm, int *lindep);
 bool ks_bv_orthonormalize_can_split(ks_bv bv);
