@@ -101,8 +101,10 @@ int ks_ctx_destroy(ks_ctx ctx);
 int ks_ctx_synchronize(ks_ctx ctx);
 /* Test hooks (compiled with -DKSD_TEST_HOOKS, which the in-tree build sets): each makes a test run the path the fast one replaces, to compare bits,
  * or a multi-rank path on one rank. Set BEFORE the objects they affect are created: NO_FUSED_GS is read at ks_bv_create, FORCE_MULTI at
- * ks_comm_init_rccl / ks_comm_set_ops, ONESHOT_SEQ0 (first stamp of the one-shot allreduce) at ks_comm_set_allreduce; the others per call. */
-enum { KS_DEBUG_NO_FUSED_GS = 0, KS_DEBUG_NO_MFMA = 1, KS_DEBUG_NO_SPMV_DOT = 2, KS_DEBUG_FORCE_MULTI = 3, KS_DEBUG_HALO_OVERLAP = 4, KS_DEBUG_ONESHOT_SEQ0 = 5 };
+ * ks_comm_init_rccl / ks_comm_set_ops, ONESHOT_SEQ0 (first stamp of the one-shot allreduce) at ks_comm_set_allreduce, NO_DICT_PATTERNS (keep the
+ * dictionary layout's 2-byte codes per entry, never its row-pattern form) at matrix assembly; the others per call. */
+enum { KS_DEBUG_NO_FUSED_GS = 0, KS_DEBUG_NO_MFMA = 1, KS_DEBUG_NO_SPMV_DOT = 2, KS_DEBUG_FORCE_MULTI = 3, KS_DEBUG_HALO_OVERLAP = 4, KS_DEBUG_ONESHOT_SEQ0 = 5,
+       KS_DEBUG_NO_DICT_PATTERNS = 6 };
 int ks_ctx_set_debug(ks_ctx ctx, int key, long long value);
 int ks_ctx_sync_count(ks_ctx ctx, long long *count);   /* instrumentation: host waits on the context's stream made by the library so far */
 int ks_ctx_device_info(ks_ctx ctx, char *arch, int arch_len, int *num_cu, size_t *mem_total);
@@ -206,6 +208,11 @@ int ks_mat_get_sizes(ks_mat A, int *n_local, int *n_global, long long *nnz_local
    random access in LDS) for matrices whose columns scatter over a vector much larger than an L2; SLICED is round 1's layout for those */
 enum { KS_MAT_LAYOUT_CSR = 0, KS_MAT_LAYOUT_SELL = 1, KS_MAT_LAYOUT_SLICED = 2, KS_MAT_LAYOUT_SHELL = 3, KS_MAT_LAYOUT_DICT = 4, KS_MAT_LAYOUT_ODICT = 5, KS_MAT_LAYOUT_BINNED = 6 };
 int ks_mat_get_layout(ks_mat A, int *layout);
+/* The dictionary layout (KS_MAT_LAYOUT_DICT) stores a row as W 2-byte codes (W = 8, 16 or 32 entry slots). When the matrix has at most 256 distinct
+   rows of codes it keeps one byte per row instead, the index of the row's code word in a table of *npatterns words (the row-pattern form), and frees the
+   codes. *patterns = 1 in that form, 0 otherwise; *npatterns = 0 and *index_bytes = 2 W n with the codes, n (plus padding to 256 rows) with the
+   patterns: the device memory held per row of the diagonal block. Any other layout: all four 0. */
+int ks_mat_get_dict_info(ks_mat A, int *patterns, int *npatterns, int *w, long long *index_bytes);
 /* MatMult: y = A x on device pointers (x, y: n_local doubles owned by this rank).
    Multi-rank: performs the halo exchange of x (PETSc VecScatter inside MatMult_MPIAIJ).        */
 int ks_mat_mult(ks_mat A, const double *x_dev, double *y_dev);

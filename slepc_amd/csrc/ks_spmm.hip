@@ -23,17 +23,19 @@ typedef int mm_i2v __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void mm_lds_void;          // operands of __builtin_amdgcn_global_load_lds (LDS-DMA)
 typedef const __attribute__((address_space(1))) void mm_glb_void;
 
-// ---- dictionary ELL (k_spmv_dict's storage): a row's codes are decoded once, each entry gathers its KB x values ---------------------
+extern __shared__ __attribute__((aligned(16))) uint4 mm_pat_lds[];     // row-pattern form of the dictionary layout: npat code words of W / 8 uint4 each
+// ---- dictionary ELL (k_spmv_dict's storage, either form): a row's codes are decoded once, each entry gathers its KB x values ---------------------
 template <int W, int KB>
-__global__ __launch_bounds__(MM_BLOCK) void k_spmm_dict(int nrows, const uint4 *__restrict__ codes, const double *__restrict__ dval, int nval, const int *__restrict__ doff, int noff,
+__global__ __launch_bounds__(MM_BLOCK) void k_spmm_dict(int nrows, const uint4 *__restrict__ codes, const unsigned char *__restrict__ rowpat, const uint4 *__restrict__ pats, int npat, const double *__restrict__ dval, int nval, const int *__restrict__ doff, int noff,
                                                         const double *__restrict__ X, long long ldx, double *__restrict__ Y, long long ldy, int xcd_remap)
 {
   __shared__ double sv[256];
   __shared__ int so[256];
   for (int i = threadIdx.x; i < nval; i += MM_BLOCK) sv[i] = dval[i];
   for (int i = threadIdx.x; i < noff; i += MM_BLOCK) so[i] = doff[i];
-  __syncthreads();
   constexpr int Q = W / 8;
+  if (rowpat) for (int i = threadIdx.x; i < npat * Q; i += MM_BLOCK) mm_pat_lds[i] = pats[i];      // the row-pattern form: the table of code words
+  __syncthreads();
   const long long groups = ((long long)nrows + MM_BLOCK - 1) / MM_BLOCK;
   long long g0 = 0, g1 = groups, lb = blockIdx.x, nb = gridDim.x;
   if (xcd_remap) {                                          // each XCD one contiguous eighth of the row groups (k_spmv_dict)
@@ -47,9 +49,10 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spmm_dict(int nrows, const uint4 *
     double acc[KB];
 #pragma unroll
     for (int k = 0; k < KB; k++) acc[k] = 0.0;
+    const int p = rowpat ? rowpat[r] : 0;
 #pragma unroll 1
     for (int q = 0; q < Q; q++) {                           // eight entries at a time: 8 KB gathers in flight, not W KB
-      const uint4 c = ksk::ldstream4(codes + r * Q + q);
+      const uint4 c = rowpat ? mm_pat_lds[p * Q + q] : ksk::ldstream4(codes + r * Q + q);
       const unsigned wds[4] = {c.x, c.y, c.z, c.w};
 #pragma unroll
       for (int e = 0; e < 8; e++) {
@@ -309,7 +312,7 @@ int spmm_pass(ks_mat A, int kb, const double *X, long long ldx, double *Y, long 
   const double alg = 12.0 * A->nnz_d + 4.0 * (A->n + 1) + xy;
   int variant = 23; double own = alg;
   switch (A->layout) {
-  case KS_MAT_LAYOUT_DICT: variant = 20; own = 2.0 * A->dict_w * A->n + xy; break;
+  case KS_MAT_LAYOUT_DICT: variant = 20; own = (A->dc_rowpat ? 1.0 : 2.0 * A->dict_w) * A->n + xy; break;
   case KS_MAT_LAYOUT_ODICT: variant = 21; own = 8.0 * A->nnz_d + (double)A->dict_w * A->n + xy; break;
   case KS_MAT_LAYOUT_SELL: variant = 22; own = 12.0 * A->s_entries + 4.0 * A->n + xy; break;
   default: if (il) { variant = 24; own = alg + xy; } break;              // the pack reads the pass's columns and writes them once more
@@ -323,11 +326,12 @@ int spmm_pass(ks_mat A, int kb, const double *X, long long ldx, double *Y, long 
     const int remap = nblk >= 64 ? 1 : 0;
     if (remap) nblk = std::min<long long>((nblk + 7) / 8, (groups + 7) / 8) * 8;
     const dim3 gr((unsigned)nblk);
+    const size_t lds = A->layout == KS_MAT_LAYOUT_DICT && A->dc_rowpat ? (size_t)A->dict_npat * A->dict_w * 2 : 0;
 #define MM_DICT(KB)                                                                                                                                                                   \
   if (A->layout == KS_MAT_LAYOUT_DICT) {                                                                                                                                              \
-    if (A->dict_w == 8) hipLaunchKernelGGL((k_spmm_dict<8, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);     \
-    else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmm_dict<32, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap); \
-    else hipLaunchKernelGGL((k_spmm_dict<16, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);              \
+    if (A->dict_w == 8) hipLaunchKernelGGL((k_spmm_dict<8, KB>), gr, dim3(MM_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);     \
+    else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmm_dict<32, KB>), gr, dim3(MM_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap); \
+    else hipLaunchKernelGGL((k_spmm_dict<16, KB>), gr, dim3(MM_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);              \
   } else if (A->dict_w == 8) hipLaunchKernelGGL((k_spmm_odict<8, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);                   \
   else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmm_odict<32, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);                 \
   else hipLaunchKernelGGL((k_spmm_odict<16, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap)

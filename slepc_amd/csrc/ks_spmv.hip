@@ -350,72 +350,18 @@ __global__ __launch_bounds__(SPMV_BLOCK) void k_spmv_sell(int nrows, int nslices
 // marks padding): 16 or 32 bytes per row instead of 12 per entry, one 16-byte load per lane. The dictionaries sit in
 // LDS. Entries keep their CSR order and the products are accumulated in that order with fma, exactly as k_spmv_sell
 // does, so y is bit-identical to the SELL / CSR result.
+// Row-pattern form: a matrix with constant coefficients has very few distinct rows of codes (the 7-point Dirichlet Laplacian on a box: 27), so
+// when there are at most 256 the matrix keeps one byte per row, the index of the row's code word in a table that goes to LDS beside the two
+// dictionaries (rowpat != nullptr; codes is then null). A lane takes its row's word from LDS instead of from memory and decodes it as before: the
+// product reads n bytes of matrix instead of 2 W n.
+extern __shared__ __attribute__((aligned(16))) uint4 dict_pat_lds[];          // npat code words of W / 8 uint4 each
+// one row from its code word: decode, gather, fma chain from 0.0 in entry order, padding included - every kernel of the layout goes through here
 template <int W>
-__global__ __launch_bounds__(SPMV_BLOCK) void k_spmv_dict(int nrows, const uint4 *__restrict__ codes, const double *__restrict__ dval, int nval, const int *__restrict__ doff, int noff,
-                                                          const double *__restrict__ x, double *__restrict__ y, int xcd_remap)
+__device__ __forceinline__ double dict_word_row(const uint4 (&c)[W / 8], long long r, const double *sv, const int *so, const double *__restrict__ x)
 {
-  __shared__ double sv[256];
-  __shared__ int so[256];
-  for (int i = threadIdx.x; i < nval; i += SPMV_BLOCK) sv[i] = dval[i];
-  for (int i = threadIdx.x; i < noff; i += SPMV_BLOCK) so[i] = doff[i];
-  __syncthreads();
-  constexpr int Q = W / 8;                                  // uint4 (8 entries) per row
-  // Workgroups b, b+8, b+16, ... run on the same XCD (round-robin dispatch). With xcd_remap (grid a multiple of 8) each
-  // XCD walks ONE contiguous eighth of the row groups, so that the x entries its rows share (the +-nx, +-nx*ny
-  // neighbours of a stencil) are fetched into that XCD's L2 once instead of into all eight.
-  const long long groups = ((long long)nrows + SPMV_BLOCK - 1) / SPMV_BLOCK;
-  long long g0 = 0, g1 = groups, lb = blockIdx.x, nb = gridDim.x;
-  if (xcd_remap) {
-    const long long gper = (groups + 7) / 8;
-    g0 = (blockIdx.x % 8) * gper; g1 = g0 + gper < groups ? g0 + gper : groups;
-    lb = blockIdx.x / 8; nb = gridDim.x / 8;
-  }
-  for (long long g = g0 + lb; g < g1; g += nb) {
-    const long long r = g * SPMV_BLOCK + threadIdx.x;
-    if (r >= nrows) break;
-    uint4 c[Q];
-#pragma unroll
-    for (int q = 0; q < Q; q++) c[q] = ksk::ldstream4(codes + r * Q + q);
-    double a[W], xv[W];
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-      const unsigned wds[4] = {c[q].x, c[q].y, c[q].z, c[q].w};
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        const unsigned code = (wds[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
-        const unsigned oc = code & 0xffu, vc = code >> 8;
-        const bool ok = vc != 255u;
-        a[q * 8 + e] = ok ? sv[vc] : 0.0;
-        xv[q * 8 + e] = ok ? x[r + so[oc]] : 0.0;
-      }
-    }
-    double acc = 0.0;
-#pragma unroll
-    for (int e = 0; e < W; e++) acc = fma(a[e], xv[e], acc);
-    // Nontemporal, as in every product kernel below: a plain store leaves the 80 MB of y dirty in the L2s, and their write-back then mixes into the
-    // read streams of the dot sweep that follows (15 us of its 303 on the 216^3 workload: profiles/r02_ab_spmv_store_nt.txt)
-    __builtin_nontemporal_store(acc, y + r);
-  }
-}
-
-// ---- dictionary product fused into the dot sweep that follows it --------------------------------------------------------------------
-// A Krylov step is y = A x followed by the dot products of y with the basis columns (and itself). While the basis is resident in the
-// Infinity Cache (config 1 and 2: a step is five dependent launches of 5 - 30 us each) the product is worth a launch of its own no longer:
-// the dictionary layout is row-local (lane = row), so the dot sweep's tile loop computes its two rows of y itself - same entry order and fma
-// chain as k_spmv_dict, same bits -, stores them, and uses them from registers as the vector of the dots and as the last "column". One
-// launch, one kernel boundary and one read of y less per step. Not for bases that stream from HBM: the sweep's tiles are interleaved over
-// the XCDs, so the stencil's far neighbours (+-nx*ny) would miss the tile's L2 where k_spmv_dict, which gives every XCD one contiguous
-// range of rows, hits it (DESIGN section 11).
-template <int W>
-__device__ __forceinline__ double dict_row(const uint4 *__restrict__ codes, long long r, const double *sv, const int *so, const double *__restrict__ x)
-{
-  constexpr int Q = W / 8;
-  uint4 c[Q];
-#pragma unroll
-  for (int q = 0; q < Q; q++) c[q] = codes[r * Q + q];
   double a[W], xv[W];
 #pragma unroll
-  for (int q = 0; q < Q; q++) {
+  for (int q = 0; q < W / 8; q++) {
     const unsigned wds[4] = {c[q].x, c[q].y, c[q].z, c[q].w};
 #pragma unroll
     for (int e = 0; e < 8; e++) {
@@ -431,8 +377,74 @@ __device__ __forceinline__ double dict_row(const uint4 *__restrict__ codes, long
   for (int e = 0; e < W; e++) acc = fma(a[e], xv[e], acc);
   return acc;
 }
+// One row per lane and at most 64 workgroups per CU also in the pattern form: two rows per lane with 16-byte stores of y measured the same within
+// 2 %, four rows per lane, 16 workgroups per CU and one 256-row group per workgroup slower (profiles/r06_dict_patterns.txt)
+template <int W>
+__global__ __launch_bounds__(SPMV_BLOCK) void k_spmv_dict(int nrows, const uint4 *__restrict__ codes, const unsigned char *__restrict__ rowpat, const uint4 *__restrict__ pats, int npat,
+                                                          const double *__restrict__ dval, int nval, const int *__restrict__ doff, int noff,
+                                                          const double *__restrict__ x, double *__restrict__ y, int xcd_remap)
+{
+  __shared__ double sv[256];
+  __shared__ int so[256];
+  constexpr int Q = W / 8;                                  // uint4 (8 entries) per row
+  for (int i = threadIdx.x; i < nval; i += SPMV_BLOCK) sv[i] = dval[i];
+  for (int i = threadIdx.x; i < noff; i += SPMV_BLOCK) so[i] = doff[i];
+  if (rowpat) for (int i = threadIdx.x; i < npat * Q; i += SPMV_BLOCK) dict_pat_lds[i] = pats[i];
+  __syncthreads();
+  // Workgroups b, b+8, b+16, ... run on the same XCD (round-robin dispatch). With xcd_remap (grid a multiple of 8) each
+  // XCD walks ONE contiguous eighth of the row groups, so that the x entries its rows share (the +-nx, +-nx*ny
+  // neighbours of a stencil) are fetched into that XCD's L2 once instead of into all eight.
+  const long long groups = ((long long)nrows + SPMV_BLOCK - 1) / SPMV_BLOCK;
+  long long g0 = 0, g1 = groups, lb = blockIdx.x, nb = gridDim.x;
+  if (xcd_remap) {
+    const long long gper = (groups + 7) / 8;
+    g0 = (blockIdx.x % 8) * gper; g1 = g0 + gper < groups ? g0 + gper : groups;
+    lb = blockIdx.x / 8; nb = gridDim.x / 8;
+  }
+  for (long long g = g0 + lb; g < g1; g += nb) {
+    const long long r = g * SPMV_BLOCK + threadIdx.x;
+    if (r >= nrows) break;
+    uint4 c[Q];
+    if (rowpat) {
+      const int p = rowpat[r];
+#pragma unroll
+      for (int q = 0; q < Q; q++) c[q] = dict_pat_lds[p * Q + q];
+    } else {
+#pragma unroll
+      for (int q = 0; q < Q; q++) c[q] = ksk::ldstream4(codes + r * Q + q);
+    }
+    // Nontemporal, as in every product kernel below: a plain store leaves the 80 MB of y dirty in the L2s, and their write-back then mixes into the
+    // read streams of the dot sweep that follows (15 us of its 303 on the 216^3 workload: profiles/r02_ab_spmv_store_nt.txt)
+    __builtin_nontemporal_store(dict_word_row<W>(c, r, sv, so, x), y + r);
+  }
+}
+
+// ---- dictionary product fused into the dot sweep that follows it --------------------------------------------------------------------
+// A Krylov step is y = A x followed by the dot products of y with the basis columns (and itself). While the basis is resident in the
+// Infinity Cache (config 1 and 2: a step is five dependent launches of 5 - 30 us each) the product is worth a launch of its own no longer:
+// the dictionary layout is row-local (lane = row), so the dot sweep's tile loop computes its two rows of y itself - same entry order and fma
+// chain as k_spmv_dict, same bits -, stores them, and uses them from registers as the vector of the dots and as the last "column". One
+// launch, one kernel boundary and one read of y less per step. Not for bases that stream from HBM: the sweep's tiles are interleaved over
+// the XCDs, so the stencil's far neighbours (+-nx*ny) would miss the tile's L2 where k_spmv_dict, which gives every XCD one contiguous
+// range of rows, hits it (DESIGN section 11).
+template <int W>
+__device__ __forceinline__ double dict_row(const uint4 *__restrict__ codes, const unsigned char *__restrict__ rowpat, long long r, const double *sv, const int *so, const double *__restrict__ x)
+{
+  constexpr int Q = W / 8;
+  uint4 c[Q];
+  if (rowpat) {                                              // the row-pattern form: the code word comes from the table in LDS
+    const int p = rowpat[r];
+#pragma unroll
+    for (int q = 0; q < Q; q++) c[q] = dict_pat_lds[p * Q + q];
+  } else {
+#pragma unroll
+    for (int q = 0; q < Q; q++) c[q] = codes[r * Q + q];
+  }
+  return dict_word_row<W>(c, r, sv, so, x);
+}
 template <int KT, int W>
 __global__ __launch_bounds__(ksk::SW_BLOCK) void k_dot_spmv_dict(const double *__restrict__ Vb, long long ld, int n, int ncols, const uint4 *__restrict__ codes,
+                                                                 const unsigned char *__restrict__ rowpat, const uint4 *__restrict__ pats, int npat,
                                                                  const double *__restrict__ dval, int nval, const int *__restrict__ doff, int noff,
                                                                  const double *__restrict__ x, double *__restrict__ y, double *__restrict__ partials,
                                                                  const KsGsState *__restrict__ gate, int *__restrict__ pgrid, int rev)
@@ -443,6 +455,7 @@ __global__ __launch_bounds__(ksk::SW_BLOCK) void k_dot_spmv_dict(const double *_
   __shared__ int so[256];
   for (int i = threadIdx.x; i < nval; i += SW_BLOCK) sv[i] = dval[i];
   for (int i = threadIdx.x; i < noff; i += SW_BLOCK) so[i] = doff[i];
+  if (rowpat) for (int i = threadIdx.x; i < npat * (W / 8); i += SW_BLOCK) dict_pat_lds[i] = pats[i];
   __syncthreads();
   if (pgrid && blockIdx.x == 0 && threadIdx.x == 0) *pgrid = gridDim.x;
   double acc[KT];
@@ -458,7 +471,7 @@ __global__ __launch_bounds__(ksk::SW_BLOCK) void k_dot_spmv_dict(const double *_
 #pragma unroll
       for (int i = 0; i < KT; i++) { const int ii = i < nprev ? i : (nprev > 0 ? nprev - 1 : 0); if (nprev > 0) xv[i] = ldplain2(Vb + (long long)ii * ld + r); else xv[i] = double2{0.0, 0.0}; }
       double2 yv;
-      yv.x = dict_row<W>(codes, r, sv, so, x); yv.y = dict_row<W>(codes, r + 1, sv, so, x);
+      yv.x = dict_row<W>(codes, rowpat, r, sv, so, x); yv.y = dict_row<W>(codes, rowpat, r + 1, sv, so, x);
       *reinterpret_cast<double2 *>(y + r) = yv;
 #pragma unroll
       for (int i = 0; i < KT; i++) {
@@ -466,7 +479,7 @@ __global__ __launch_bounds__(ksk::SW_BLOCK) void k_dot_spmv_dict(const double *_
         acc[i] = fma(c.x, yv.x, acc[i]); acc[i] = fma(c.y, yv.y, acc[i]);
       }
     } else if (r < n) {
-      const double yv = dict_row<W>(codes, r, sv, so, x);
+      const double yv = dict_row<W>(codes, rowpat, r, sv, so, x);
       y[r] = yv;
 #pragma unroll
       for (int i = 0; i < KT; i++) {
@@ -566,6 +579,21 @@ __global__ void k_dict_encode(int n, int W, const int *__restrict__ rowptr, cons
     }
     codes[r * W + j] = code;
   }
+}
+// one thread per row: find the row's code word (wpr 32-bit words) in the sorted candidate table (binary search, words compared in order) and write its
+// index; rows that are not covered are counted and the code words of the first `cap` of them recorded so that the host can extend the table
+__global__ void k_dict_match(int n, int wpr, const unsigned *__restrict__ codes, const unsigned *__restrict__ pats, int npat, unsigned char *__restrict__ rowpat,
+                             int *miss, unsigned *__restrict__ miss_words, int cap)
+{
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const unsigned *c = codes + r * wpr;
+  auto cmp = [&](int m) { for (int i = 0; i < wpr; i++) { const unsigned a = pats[(long long)m * wpr + i], b = c[i]; if (a != b) return a < b ? -1 : 1; } return 0; };
+  int lo = 0, hi = npat;
+  while (lo < hi) { const int m = (lo + hi) >> 1; if (cmp(m) < 0) lo = m + 1; else hi = m; }
+  if (lo < npat && cmp(lo) == 0) { rowpat[r] = (unsigned char)lo; return; }
+  if (*(volatile int *)miss < cap) { const int idx = atomicAdd(miss, 1); if (idx < cap) for (int i = 0; i < wpr; i++) miss_words[(long long)idx * wpr + i] = c[i]; }
+  else atomicAdd(miss + 1, 1);
 }
 __global__ void k_max_rowlen(int n, const int *__restrict__ rowptr, int *out)
 {
@@ -1242,6 +1270,48 @@ int build_sliced(ks_mat A)
   return KS_SUCCESS;
 }
 
+// The row-pattern form of the dictionary layout (see k_spmv_dict): the distinct rows of codes are found the way build_dict finds its dictionaries -
+// match every row against the sorted table, extend the table by the rows that missed, repeat; every round with a miss adds at least one word, so the
+// loop ends with every row matched or with more than 256 words, and then the matrix keeps its codes as they are.
+int build_dict_patterns(ks_mat A)
+{
+  ks_ctx ctx = A->ctx;
+  const int n = A->n, wpr = A->dict_w / 2, cap = 4096;
+  const size_t nidx = ((size_t)n + 255) / 256 * 256;
+  using Word = std::vector<unsigned>;
+  std::vector<Word> table;                                                 // sorted
+  unsigned char *rowpat = nullptr; unsigned *d_pats = nullptr, *m_words = nullptr; int *d_miss = nullptr;
+  auto cleanup = [&]() { hipFree(rowpat); hipFree(d_pats); hipFree(m_words); hipFree(d_miss); };
+  KS_HIP(hipMalloc(&rowpat, nidx)); KS_HIP(hipMalloc(&d_pats, sizeof(unsigned) * 256 * wpr));
+  KS_HIP(hipMalloc(&m_words, sizeof(unsigned) * (size_t)cap * wpr)); KS_HIP(hipMalloc(&d_miss, sizeof(int) * 2));
+  KS_HIP(hipMemsetAsync(rowpat, 0, nidx, ctx->stream));
+  std::vector<unsigned> flat, got;
+  bool done = false;
+  while (!done) {
+    flat.clear();
+    for (const Word &w : table) flat.insert(flat.end(), w.begin(), w.end());
+    KS_HIP(hipMemsetAsync(d_miss, 0, sizeof(int) * 2, ctx->stream));
+    if (!flat.empty()) KS_HIP(hipMemcpyAsync(d_pats, flat.data(), sizeof(unsigned) * flat.size(), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_dict_match, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, wpr, (const unsigned *)A->dc_codes, d_pats, (int)table.size(),
+                       rowpat, d_miss, m_words, cap);
+    int miss[2] = {0, 0};
+    KS_HIP(hipMemcpyAsync(miss, d_miss, sizeof(int) * 2, hipMemcpyDeviceToHost, ctx->stream));
+    KS_HIP(ks_sync(ctx));
+    if (miss[0] == 0) { done = true; break; }
+    const int m = std::min(miss[0], cap);
+    got.resize((size_t)m * wpr);
+    KS_HIP(hipMemcpy(got.data(), m_words, sizeof(unsigned) * got.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < m; i++) table.emplace_back(got.begin() + (size_t)i * wpr, got.begin() + (size_t)(i + 1) * wpr);
+    std::sort(table.begin(), table.end()); table.erase(std::unique(table.begin(), table.end()), table.end());
+    if (table.size() > 256) break;                                         // too many distinct rows: the 2-byte codes stay
+  }
+  if (!done) { cleanup(); return KS_SUCCESS; }
+  A->dc_rowpat = rowpat; rowpat = nullptr; A->dc_pats = (unsigned short *)d_pats; d_pats = nullptr; A->dict_npat = (int)table.size();
+  hipFree(A->dc_codes); A->dc_codes = nullptr;
+  cleanup();
+  return KS_SUCCESS;
+}
+
 // Try the dictionary layout (see k_spmv_dict); offsets_only: the offset-dictionary form at once. Needs the CSR arrays of the diagonal block on the device.
 int build_dict(ks_mat A, bool offsets_only)
 {
@@ -1311,7 +1381,7 @@ int build_dict(ks_mat A, bool offsets_only)
   A->dc_codes = codes; codes = nullptr;
   A->layout = KS_MAT_LAYOUT_DICT; A->dict_w = W; A->dict_nval = (int)vals.size(); A->dict_noff = (int)offs.size();
   cleanup();
-  return KS_SUCCESS;
+  return ctx->dbg.no_dict_patterns ? KS_SUCCESS : build_dict_patterns(A);
 }
 
 // Build the SELL-64 copy of the diagonal block when its padding is small (<= 12.5 % extra entries) or it is forced.
@@ -1396,11 +1466,12 @@ int ks_mat_mult_dot_fused(ks_mat A, ks_bv bv, const double *x, int jy, bool gate
   const int rev = bv->sweep_dir; bv->sweep_dir ^= 1;
   bv->spec.valid = false; bv->last_grid = grid;
   const KsGsState *g = gate ? bv->gs : nullptr;
-  KsProfScope ps(ctx, KS_K_SPMVDOT, 8.0 * bv->n * ncols + 12.0 * A->nnz + 4.0 * (A->n + 1) + 16.0 * A->n, ks_kt_for(ncols), 8.0 * bv->n * ncols + (2.0 * A->dict_w + 8.0) * A->n);
+  KsProfScope ps(ctx, KS_K_SPMVDOT, 8.0 * bv->n * ncols + 12.0 * A->nnz + 4.0 * (A->n + 1) + 16.0 * A->n, ks_kt_for(ncols), 8.0 * bv->n * ncols + (A->dc_rowpat ? 9.0 : 2.0 * A->dict_w + 8.0) * A->n);
+  const size_t lds = A->dc_rowpat ? (size_t)A->dict_npat * A->dict_w * 2 : 0;          // the pattern table, in LDS beside the dictionaries
 #define LAUNCH_FD(KT)                                                                                                                                      \
   do {                                                                                                                                                     \
-    if (A->dict_w == 8) hipLaunchKernelGGL((k_dot_spmv_dict<KT, 8>), dim3(grid), dim3(ksk::SW_BLOCK), 0, ctx->stream, Vb, (long long)bv->ld, bv->n, ncols, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, bv->partials, g, &bv->gs->pgrid, rev); \
-    else if (A->dict_w == 16) hipLaunchKernelGGL((k_dot_spmv_dict<KT, 16>), dim3(grid), dim3(ksk::SW_BLOCK), 0, ctx->stream, Vb, (long long)bv->ld, bv->n, ncols, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, bv->partials, g, &bv->gs->pgrid, rev); \
+    if (A->dict_w == 8) hipLaunchKernelGGL((k_dot_spmv_dict<KT, 8>), dim3(grid), dim3(ksk::SW_BLOCK), lds, ctx->stream, Vb, (long long)bv->ld, bv->n, ncols, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, bv->partials, g, &bv->gs->pgrid, rev); \
+    else if (A->dict_w == 16) hipLaunchKernelGGL((k_dot_spmv_dict<KT, 16>), dim3(grid), dim3(ksk::SW_BLOCK), lds, ctx->stream, Vb, (long long)bv->ld, bv->n, ncols, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, bv->partials, g, &bv->gs->pgrid, rev); \
     else return KS_SUCCESS;                                                                                                                                \
   } while (0)
   if (A->dict_w != 8 && A->dict_w != 16) return KS_SUCCESS;
@@ -1564,7 +1635,7 @@ extern "C" int ks_mat_destroy(ks_mat A)
   ks_halo_release(A);                 // not collective: waits for the neighbours' last acknowledgements (ks_halo.hip); ks_mat_set_halo(A, KS_HALO_PROVIDER) first is the collective way
   hipFree(A->ghost); hipFree(A->send_idx); hipFree(A->send_buf);
   hipFree(A->s_ptr); hipFree(A->s_len); hipFree(A->s_col); hipFree(A->s_val);
-  hipFree(A->dc_codes); hipFree(A->dc_val); hipFree(A->dc_off); hipFree(A->dc_codes8); hipFree(A->dc_vals);
+  hipFree(A->dc_codes); hipFree(A->dc_rowpat); hipFree(A->dc_pats); hipFree(A->dc_val); hipFree(A->dc_off); hipFree(A->dc_codes8); hipFree(A->dc_vals);
   hipFree(A->sl_rowptr); hipFree(A->sl_col); hipFree(A->sl_val); hipFree(A->sl_base); hipFree(A->ypart); hipFree(A->diag_cache); hipFree(A->mm_xi);
   hipFree(A->bn_col16); hipFree(A->bn_row16); hipFree(A->bn_val); hipFree(A->bn_g); hipFree(A->bn_off1); hipFree(A->bn_off2t); hipFree(A->bn_wseg); hipFree(A->bn_sbase); hipFree(A->bn_off2); hipFree(A->bn_log2);
   delete A;
@@ -1584,6 +1655,16 @@ extern "C" int ks_mat_get_layout(ks_mat A, int *layout)     // storage of the di
 {
   KS_CHECK(A && layout, KS_ERR_ARG_NULL, "NULL argument");
   *layout = A->shell_mult ? KS_MAT_LAYOUT_SHELL : A->layout;
+  return KS_SUCCESS;
+}
+extern "C" int ks_mat_get_dict_info(ks_mat A, int *patterns, int *npatterns, int *w, long long *index_bytes)
+{
+  KS_CHECK(A && patterns && npatterns && w && index_bytes, KS_ERR_ARG_NULL, "NULL argument");
+  *patterns = *npatterns = *w = 0; *index_bytes = 0;
+  if (A->shell_mult || A->layout != KS_MAT_LAYOUT_DICT) return KS_SUCCESS;
+  *w = A->dict_w;
+  if (A->dc_rowpat) { *patterns = 1; *npatterns = A->dict_npat; *index_bytes = ((long long)A->n + 255) / 256 * 256; }
+  else *index_bytes = 2LL * A->dict_w * A->n;
   return KS_SUCCESS;
 }
 extern "C" int ks_mat_get_sizes(ks_mat A, int *n_local, int *n_global, long long *nnz_local)
@@ -1633,7 +1714,7 @@ int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *row
     int variant = 0; double own = -1.0;        // variant 18: k_binned_*, 16: k_spmv_dict, 17: k_spmv_odict, 8: k_spmv_sell<8>, 0: k_spmv_csr; the layout's own compulsory bytes
     switch (A->layout) {
     case KS_MAT_LAYOUT_BINNED: variant = 18; own = 28.0 * A->bn_entries + 16.0 * A->n + 12.0 * A->nnz_o; break;
-    case KS_MAT_LAYOUT_DICT: variant = 16; own = (2.0 * A->dict_w + 16.0) * A->n + 12.0 * A->nnz_o; break;
+    case KS_MAT_LAYOUT_DICT: variant = 16; own = (A->dc_rowpat ? 17.0 : 2.0 * A->dict_w + 16.0) * A->n + 12.0 * A->nnz_o; break;       // one byte per row in the row-pattern form
     case KS_MAT_LAYOUT_ODICT: variant = 17; own = 8.0 * A->nnz_d + (A->dict_w + 16.0) * A->n + 12.0 * A->nnz_o; break;
     case KS_MAT_LAYOUT_SELL: variant = 8; break;
     }
@@ -1659,9 +1740,13 @@ int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *row
       if (remap) nblk = std::min<long long>((nblk + 7) / 8, (groups + 7) / 8) * 8;
       const dim3 gr((unsigned)nblk);
       if (A->layout == KS_MAT_LAYOUT_DICT) {
-        if (A->dict_w == 8) hipLaunchKernelGGL((k_spmv_dict<8>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, remap);
-        else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmv_dict<32>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, remap);
-        else hipLaunchKernelGGL((k_spmv_dict<16>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, remap);
+        const size_t lds = A->dc_rowpat ? (size_t)A->dict_npat * A->dict_w * 2 : 0;          // the pattern table, in LDS beside the dictionaries
+#define SPMV_DICT(W) hipLaunchKernelGGL((k_spmv_dict<W>), gr, dim3(SPMV_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, \
+                                        A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, remap)
+        if (A->dict_w == 8) SPMV_DICT(8);
+        else if (A->dict_w == 32) SPMV_DICT(32);
+        else SPMV_DICT(16);
+#undef SPMV_DICT
       } else if (A->dict_w == 8) hipLaunchKernelGGL((k_spmv_odict<8>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, x, y, remap);
       else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmv_odict<32>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, x, y, remap);
       else hipLaunchKernelGGL((k_spmv_odict<16>), gr, dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, x, y, remap);

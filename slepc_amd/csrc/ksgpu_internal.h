@@ -70,7 +70,7 @@ struct ks_ctx_s {
   hipStream_t halo_stream = nullptr; hipEvent_t ev_x = nullptr, ev_halo = nullptr;
   bool halo_overlap = true;
   // test hooks (ks_ctx_set_debug; each makes a test run the path the fast one replaces, or a multi-rank path on one rank)
-  struct { bool no_fused_gs = false, no_mfma = false, no_spmv_dot = false, force_multi = false; unsigned oneshot_seq0 = 0; } dbg;
+  struct { bool no_fused_gs = false, no_mfma = false, no_spmv_dot = false, force_multi = false, no_dict_patterns = false; unsigned oneshot_seq0 = 0; } dbg;
   long long nsync = 0;              // host synchronisations of the context's stream made by the library (ks_ctx_sync_count)
   int num_cu = 256;
   char arch[64] = {0};
@@ -161,6 +161,9 @@ struct ks_mat_s {
   // dictionary ELL (few distinct values and few distinct column offsets, rows of at most 32 entries): 2 bytes per entry
   int dict_w = 0; int dict_nval = 0, dict_noff = 0;
   unsigned short *dc_codes = nullptr; double *dc_val = nullptr; int *dc_off = nullptr;
+  // row-pattern form of the same layout (at most 256 distinct rows): one byte per row, the index of its code word (dict_w 2-byte codes) in dc_pats;
+  // dc_codes is then null. dc_rowpat is padded with zeros to a multiple of 256 rows.
+  unsigned char *dc_rowpat = nullptr; unsigned short *dc_pats = nullptr; int dict_npat = 0;
   // offset-dictionary ELL: any values, few distinct column offsets: 1 byte per entry for the index, values in SELL order
   unsigned char *dc_codes8 = nullptr; double *dc_vals = nullptr;
   // XCD-sliced copy of the diagonal block for wide-scatter matrices (columns spread over a vector much larger than one
