@@ -1,0 +1,203 @@
+// The row walks of the stored layouts: how a kernel finds its rows, brings a row's entries in and decodes them, and the host-side grid of each walk.
+// The kernels of ks_spmv.hip (y = A x, and the product inside the dot sweep) and ks_spmm.hip (Y = A X, every column bit for bit the single-vector
+// product) take these pieces from here; what stays with a kernel is what is tuned per kernel: how many entries it keeps in flight, its fma chains and
+// its stores. ks_mat.hip builds the layouts and shares the storage rules (CW_PAD, sell_pos).
+// Pieces that load from memory inside a tuned loop are MACROS, not inline functions: as functions (by value, by reference, returning a struct) they made
+// the compiler schedule those loops differently (scripts/isa_diff.py against the kernels they were taken from); the macro is the same text in place.
+#pragma once
+#include "ks_sweeps.cuh"
+#include <algorithm>
+
+namespace ksr {
+
+typedef int ks_i2v __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) void ks_lds_void;          // operands of __builtin_amdgcn_global_load_lds (LDS-DMA)
+typedef const __attribute__((address_space(1))) void ks_glb_void;
+constexpr int ROW_BLOCK = 256;                             // lane = row kernels: rows of a workgroup
+constexpr int CW_PAD = 8;                                  // CSR col / val allocations are this much longer than nnz (what a chunk load may read past its end)
+
+template <int BLOCK, typename T>
+__device__ __forceinline__ void lds_fill(T *dst, const T *src, int n) { for (int i = threadIdx.x; i < n; i += BLOCK) dst[i] = src[i]; }
+
+// ---- which rows ----------------------------------------------------------------------------------------------------------------------
+// lane = row, groups of `block` rows. Workgroups b, b+8, b+16, ... run on the same XCD (round-robin dispatch). With xcd_remap (grid a multiple of 8)
+// each XCD walks ONE contiguous eighth of the row groups, so that the x entries its rows share (the +-nx, +-nx*ny neighbours of a stencil) are
+// fetched into that XCD's L2 once instead of into all eight: for (g = g0 + lb; g < g1; g += nb).
+struct RowGroups { long long g0, g1, lb, nb; };
+__device__ __forceinline__ RowGroups row_groups_xcd(int nrows, int block, int xcd_remap)
+{
+  const long long groups = ((long long)nrows + block - 1) / block;
+  RowGroups q = {0, groups, blockIdx.x, gridDim.x};
+  if (xcd_remap) {
+    const long long gper = (groups + 7) / 8;
+    q.g0 = (blockIdx.x % 8) * gper; q.g1 = q.g0 + gper < groups ? q.g0 + gper : groups;
+    q.lb = blockIdx.x / 8; q.nb = gridDim.x / 8;
+  }
+  return q;
+}
+// a wave per 64 rows, groups of 256 rows: one per workgroup and iteration; with xcd_remap each XCD takes one contiguous eighth of them
+// (k_spmv_csr_wave keeps the same lines in place: this function changes its register allocation)
+struct WaveGroups { int g, gend, gstep; };
+__device__ __forceinline__ WaveGroups wave_groups_xcd(int n, int xcd_remap)
+{
+  const int NG = (n + 255) / 256;
+  int g, gend, gstep;
+  if (xcd_remap) {
+    const int xcd = blockIdx.x & 7, li = blockIdx.x >> 3, lc = gridDim.x >> 3;
+    g = (int)((long long)NG * xcd / 8) + li; gend = (int)((long long)NG * (xcd + 1) / 8); gstep = lc;
+  } else { g = blockIdx.x; gend = NG; gstep = gridDim.x; }
+  return {g, gend, gstep};
+}
+
+// ---- CSR row blocks: the wave's 64 rows and their one contiguous run of entries ------------------------------------------------------------
+struct CwRows { int p0, p1, E0, E1; long long r; bool has; };
+__device__ __forceinline__ CwRows cw_rows(int n, const int *__restrict__ rp, int g, int w, int lane)
+{
+  CwRows q; q.p0 = q.p1 = q.E0 = q.E1 = 0; q.has = false;
+  const long long r0 = (long long)g * 256 + (long long)w * 64;
+  q.r = r0 + lane;
+  if (r0 >= n) return q;
+  q.has = q.r < n;
+  if (q.has) { ks_i2v pp; __builtin_memcpy(&pp, rp + q.r, sizeof(pp)); q.p0 = pp.x; q.p1 = pp.y; }       // rp[r], rp[r + 1]: one 8-byte load (4-byte aligned)
+  q.E0 = rp[r0]; q.E1 = rp[r0 + 64 < n ? r0 + 64 : n];                 // the wave's run of entries (uniform: scalar loads)
+  return q;
+}
+// One chunk of CH entries from e0 (a multiple of four: 16-byte aligned in both streams) straight into the wave's pieces of LDS: CH / 128 LDS-DMA
+// instructions for the values (lane l of instruction i brings entries 128 i + 2 l, + 1), CH / 256 for the columns (256 i + 4 l .. + 3), into a
+// lane-linear image (the DMA's destination is base + lane x 16). Returns with the chunk in LDS.
+template <int CH>
+__device__ __forceinline__ void cw_dma_chunk(double *sa, int *sc, const int *col, const double *val, int e0, int E1, int lane)
+{
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // the row lanes' reads of the previous chunk are done before this one may land
+#pragma unroll
+  for (int i = 0; i < CH / 128; i++) {
+    const int e = e0 + 128 * i + 2 * lane;
+    if (e < E1) __builtin_amdgcn_global_load_lds((ks_glb_void *)(val + e), (ks_lds_void *)(sa + 128 * i), 16, 0, 2);       // aux 2 = nt: the default policy cost 10 % (profiles/r04_csr_lds_dma.txt)      // may take one entry past E1: CW_PAD
+  }
+#pragma unroll
+  for (int i = 0; i < CH / 256; i++) {
+    const int e = e0 + 256 * i + 4 * lane;
+    if (e < E1) __builtin_amdgcn_global_load_lds((ks_glb_void *)(col + e), (ks_lds_void *)(sc + 256 * i), 16, 0, 2);      // up to three past E1: CW_PAD
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // an LDS-DMA is a pending LDS write on the VM counter
+}
+
+// ---- SELL-64: entries in pairs, a slice of odd width keeps its last entry as a column of singles behind its pairs ------------------------------
+__device__ __forceinline__ long long sell_pos(long long sbase, int w, int j, int lane)
+{
+  return (j | 1) < w ? sbase + (long long)(j >> 1) * 128 + lane * 2 + (j & 1) : sbase + (long long)(w >> 1) * 128 + lane;
+}
+// the workgroup's first group of four slices. Blocks b, b+8, ... share an XCD: with xcd_remap each XCD gets one contiguous range of slice groups
+__device__ __forceinline__ long long sell_first_group(long long nblk, int xcd_remap)       // nblk: the grid
+{
+  long long b = blockIdx.x;
+  if (xcd_remap) {
+    const long long per = nblk / 8;
+    if (b < per * 8) b = (b % 8) * per + b / 8;
+  }
+  return b;
+}
+// pairs q .. q + UNR - 1 of the lane's row into c[UNR] (ks_i2v), a[UNR] (ks_d2v); wp pairs in the slice, len entries in the row. Fully predicated: all
+// loads of a batch are independent
+#define KS_SELL_LOAD_PAIRS(UNR, c, a, col, val, sb, q, wp, len, lane)                                                             \
+  _Pragma("unroll") for (int u = 0; u < (UNR); u++) {                                                                              \
+    const int j = 2 * ((q) + u);                                                                                                   \
+    const bool ok = (q) + u < (wp) && j < (len);                                                                                   \
+    const long long p = (sb) + (long long)((q) + u) * 128 + (lane) * 2;                                                            \
+    c[u] = ok ? __builtin_nontemporal_load(reinterpret_cast<const ks_i2v *>((col) + p)) : ks_i2v{-1, -1};                          \
+    a[u] = ok ? __builtin_nontemporal_load(reinterpret_cast<const ksk::ks_d2v *>((val) + p)) : ksk::ks_d2v{0.0, 0.0};              \
+    if (j + 1 >= (len)) { c[u].y = -1; a[u].y = 0.0; }         /* the pair's second slot is padding: never gathered, never multiplied */ \
+  }
+struct SellEntry { int c; double a; };                     // c < 0: padding (a = 0.0, x is not gathered)
+__device__ __forceinline__ SellEntry sell_tail(const int *col, const double *val, long long sb, int w, int len, int lane)
+{
+  const bool ok = w - 1 < len;                              // the last entry slot of a slice of odd width w: singles
+  const long long p = sb + (long long)(w >> 1) * 128 + lane;
+  return {ok ? ksk::ldstream(col + p) : -1, ok ? ksk::ldstream(val + p) : 0.0};
+}
+
+// ---- dictionary ELL: W 2-byte codes per row (offset code, value code; value code 255 marks padding), or one byte per row into a table of such words --
+extern __shared__ __attribute__((aligned(16))) uint4 dict_pat_lds[];          // row-pattern form: npat code words of W / 8 uint4 each
+// the preamble of the layout's kernels (k_dot_spmv_dict keeps the same lines in place: through the macro its sweep loop is scheduled differently): values, offsets and (row-pattern form) the table of code words into LDS (sv, so: the kernel's __shared__ arrays)
+#define KS_DICT_LDS_FILL(BLOCK, W, sv, so, dval, nval, doff, noff, rowpat, pats, npat)                                            \
+  do {                                                                                                                             \
+    for (int i = threadIdx.x; i < (nval); i += (BLOCK)) sv[i] = dval[i];                                                           \
+    for (int i = threadIdx.x; i < (noff); i += (BLOCK)) so[i] = doff[i];                                                           \
+    if (rowpat) for (int i = threadIdx.x; i < (npat) * ((W) / 8); i += (BLOCK)) dict_pat_lds[i] = pats[i];                         \
+    __syncthreads();                                                                                                               \
+  } while (0)
+// entry e < 8 of the four words of a uint4 of codes: offset code, value code; ok = false: padding - its value and its x count as 0.0 and are not loaded,
+// the chain still runs fma(0.0, 0.0, acc) there, in every kernel of the layout
+struct DictCode { unsigned oc, vc; bool ok; };
+__device__ __forceinline__ DictCode dict_code(unsigned word, int e)          // word = wds[e >> 1]
+{
+  const unsigned code = (word >> ((e & 1) * 16)) & 0xffffu;
+  return {code & 0xffu, code >> 8, (code >> 8) != 255u};
+}
+// offset-dictionary ELL: entry e of the 1-byte codes packed in 32-bit words; word = wds[e >> 2]. Code 255 = padding, as above
+__device__ __forceinline__ DictCode odict_code(unsigned word, int e)
+{
+  const unsigned oc = (word >> ((e & 3) * 8)) & 0xffu;
+  return {oc, 0u, oc != 255u};
+}
+// one row from its code word: decode, gather, fma chain from 0.0 in entry order, padding included - the single-vector kernels of the layout (k_spmv_dict, k_dot_spmv_dict) go through here
+template <int W>
+__device__ __forceinline__ double dict_word_row(const uint4 (&c)[W / 8], long long r, const double *sv, const int *so, const double *x)
+{
+  double a[W], xv[W];
+#pragma unroll
+  for (int q = 0; q < W / 8; q++) {
+    const unsigned wds[4] = {c[q].x, c[q].y, c[q].z, c[q].w};
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      const DictCode d = dict_code(wds[e >> 1], e);
+      a[q * 8 + e] = d.ok ? sv[d.vc] : 0.0;
+      xv[q * 8 + e] = d.ok ? x[r + so[d.oc]] : 0.0;
+    }
+  }
+  double acc = 0.0;
+#pragma unroll
+  for (int e = 0; e < W; e++) acc = fma(a[e], xv[e], acc);
+  return acc;
+}
+
+// ---- host side: the grid of each walk, the LDS of the pattern table, the bytes a layout must move ----------------------------------------------------
+struct LaunchGrid { unsigned blocks; int remap; };
+static inline LaunchGrid dict_launch_grid(ks_mat A)               // dictionary forms: up to 64 workgroups per CU
+{
+  const long long groups = ((long long)A->n + ROW_BLOCK - 1) / ROW_BLOCK;
+  long long nblk = std::max<long long>(1, std::min<long long>(groups, (long long)A->ctx->num_cu * 64));
+  const int remap = nblk >= 64 ? 1 : 0;                   // small matrices: nothing to pin
+  if (remap) nblk = std::min<long long>((nblk + 7) / 8, (groups + 7) / 8) * 8;
+  return {(unsigned)nblk, remap};
+}
+static inline LaunchGrid sell_launch_grid(ks_mat A)
+{
+  const long long groups = ((long long)A->nslices + 3) / 4;
+  const long long blocks = std::min<long long>(groups, (long long)A->ctx->num_cu * 4096);     // one 256-row group per block measured fastest
+  // each XCD one contiguous range of slices (179 -> 172 us on the 216^3 Laplacian), only with one slice group per workgroup (a strided
+  // loop would interleave the ranges again)
+  return {(unsigned)std::max<long long>(blocks, 1), (blocks == groups && blocks >= 64) ? 1 : 0};
+}
+static inline LaunchGrid csr_wave_launch_grid(ks_mat A, int per_cu)     // per_cu workgroups of four waves per CU (the kernel's launch bounds); a multiple of 8 so that every XCD gets its eighth of the rows
+{
+  long long nb = std::min<long long>(((long long)A->n + 255) / 256, (long long)A->ctx->num_cu * per_cu);
+  const int remap = nb >= 64 ? 1 : 0;
+  if (remap) nb = (nb / 8) * 8;
+  return {(unsigned)nb, remap};
+}
+static inline size_t dict_pattern_lds_bytes(ks_mat A) { return A->layout == KS_MAT_LAYOUT_DICT && A->dc_rowpat ? (size_t)A->dict_npat * A->dict_w * 2 : 0; }   // dynamic LDS: the pattern table beside the dictionaries
+// compulsory bytes of the stored diagonal block per product (the matrix part of a KsProfScope byte model: callers add their x / y traffic)
+static inline double layout_own_bytes(ks_mat A)
+{
+  switch (A->layout) {
+  case KS_MAT_LAYOUT_BINNED: return 28.0 * A->bn_entries;
+  case KS_MAT_LAYOUT_DICT: return (A->dc_rowpat ? 1.0 : 2.0 * A->dict_w) * A->n;            // one byte per row in the row-pattern form
+  case KS_MAT_LAYOUT_ODICT: return 8.0 * A->nnz_d + (double)A->dict_w * A->n;
+  case KS_MAT_LAYOUT_SELL: return 12.0 * A->s_entries + 4.0 * A->n;
+  default: return 12.0 * A->nnz_d + 4.0 * (A->n + 1);                                        // the CSR stream
+  }
+}
+#define KS_DICT_W_SWITCH(w, F) do { if ((w) == 8) { F(8); } else if ((w) == 32) { F(32); } else { F(16); } } while (0)
+
+} // namespace ksr

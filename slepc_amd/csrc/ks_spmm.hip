@@ -9,21 +9,16 @@
 // forms and SELL-64 fma 0.0 * 0.0, the CSR row blocks skip them). So Y(:,j) is ks_mat_mult(A, X(:,j)) bit for bit, NaN, Inf and the
 // +0.0 of an empty row included. Layouts and forms without such a kernel (BINNED, SLICED, shell matrices, the CSR-vector form of small
 // matrices, anything with a halo) run the column loop over ks_mat_mult_internal: the same bits by construction.
-#include "ks_sweeps.cuh"
-#include <algorithm>
+#include "ks_rows.cuh"
 #include <cstdlib>
 #include <cstring>
 
 namespace {
+using namespace ksr;
 
-constexpr int MM_BLOCK = 256;
+constexpr int MM_BLOCK = ROW_BLOCK;
 constexpr int MM_KB = 8;                // columns per pass (KB accumulators per lane); every KB from 1 to 8 is compiled for the tail
 
-typedef int mm_i2v __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void mm_lds_void;          // operands of __builtin_amdgcn_global_load_lds (LDS-DMA)
-typedef const __attribute__((address_space(1))) void mm_glb_void;
-
-extern __shared__ __attribute__((aligned(16))) uint4 mm_pat_lds[];     // row-pattern form of the dictionary layout: npat code words of W / 8 uint4 each
 // ---- dictionary ELL (k_spmv_dict's storage, either form): a row's codes are decoded once, each entry gathers its KB x values ---------------------
 template <int W, int KB>
 __global__ __launch_bounds__(MM_BLOCK) void k_spmm_dict(int nrows, const uint4 *__restrict__ codes, const unsigned char *__restrict__ rowpat, const uint4 *__restrict__ pats, int npat, const double *__restrict__ dval, int nval, const int *__restrict__ doff, int noff,
@@ -31,19 +26,10 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spmm_dict(int nrows, const uint4 *
 {
   __shared__ double sv[256];
   __shared__ int so[256];
-  for (int i = threadIdx.x; i < nval; i += MM_BLOCK) sv[i] = dval[i];
-  for (int i = threadIdx.x; i < noff; i += MM_BLOCK) so[i] = doff[i];
+  KS_DICT_LDS_FILL(MM_BLOCK, W, sv, so, dval, nval, doff, noff, rowpat, pats, npat);
   constexpr int Q = W / 8;
-  if (rowpat) for (int i = threadIdx.x; i < npat * Q; i += MM_BLOCK) mm_pat_lds[i] = pats[i];      // the row-pattern form: the table of code words
-  __syncthreads();
-  const long long groups = ((long long)nrows + MM_BLOCK - 1) / MM_BLOCK;
-  long long g0 = 0, g1 = groups, lb = blockIdx.x, nb = gridDim.x;
-  if (xcd_remap) {                                          // each XCD one contiguous eighth of the row groups (k_spmv_dict)
-    const long long gper = (groups + 7) / 8;
-    g0 = (blockIdx.x % 8) * gper; g1 = g0 + gper < groups ? g0 + gper : groups;
-    lb = blockIdx.x / 8; nb = gridDim.x / 8;
-  }
-  for (long long g = g0 + lb; g < g1; g += nb) {
+  const RowGroups rg = row_groups_xcd(nrows, MM_BLOCK, xcd_remap);
+  for (long long g = rg.g0 + rg.lb; g < rg.g1; g += rg.nb) {
     const long long r = g * MM_BLOCK + threadIdx.x;
     if (r >= nrows) break;
     double acc[KB];
@@ -52,15 +38,14 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spmm_dict(int nrows, const uint4 *
     const int p = rowpat ? rowpat[r] : 0;
 #pragma unroll 1
     for (int q = 0; q < Q; q++) {                           // eight entries at a time: 8 KB gathers in flight, not W KB
-      const uint4 c = rowpat ? mm_pat_lds[p * Q + q] : ksk::ldstream4(codes + r * Q + q);
+      const uint4 c = rowpat ? dict_pat_lds[p * Q + q] : ksk::ldstream4(codes + r * Q + q);
       const unsigned wds[4] = {c.x, c.y, c.z, c.w};
 #pragma unroll
       for (int e = 0; e < 8; e++) {
-        const unsigned code = (wds[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
-        const unsigned oc = code & 0xffu, vc = code >> 8;
-        const bool ok = vc != 255u;
-        const double a = ok ? sv[vc] : 0.0;
-        const long long xi = r + (ok ? so[oc] : 0);
+        const DictCode d = dict_code(wds[e >> 1], e);
+        const bool ok = d.ok;
+        const double a = ok ? sv[d.vc] : 0.0;
+        const long long xi = r + (ok ? so[d.oc] : 0);
 #pragma unroll
         for (int k = 0; k < KB; k++) acc[k] = fma(a, ok ? X[k * ldx + xi] : 0.0, acc[k]);      // padding: fma(0.0, 0.0, acc) as in k_spmv_dict
       }
@@ -76,16 +61,10 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spmm_odict(int nrows, const unsign
                                                          const double *__restrict__ X, long long ldx, double *__restrict__ Y, long long ldy, int xcd_remap)
 {
   __shared__ int so[256];
-  for (int i = threadIdx.x; i < noff; i += MM_BLOCK) so[i] = doff[i];
+  lds_fill<MM_BLOCK>(so, doff, noff);
   __syncthreads();
-  const long long groups = ((long long)nrows + MM_BLOCK - 1) / MM_BLOCK;
-  long long g0 = 0, g1 = groups, lb = blockIdx.x, nb = gridDim.x;
-  if (xcd_remap) {
-    const long long gper = (groups + 7) / 8;
-    g0 = (blockIdx.x % 8) * gper; g1 = g0 + gper < groups ? g0 + gper : groups;
-    lb = blockIdx.x / 8; nb = gridDim.x / 8;
-  }
-  for (long long g = g0 + lb; g < g1; g += nb) {
+  const RowGroups rg = row_groups_xcd(nrows, MM_BLOCK, xcd_remap);
+  for (long long g = rg.g0 + rg.lb; g < rg.g1; g += rg.nb) {
     const long long r = g * MM_BLOCK + threadIdx.x;
     if (r >= nrows) break;
     const double *vb = vals + ((r >> 6) * W) * 64 + (r & 63);
@@ -98,10 +77,10 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spmm_odict(int nrows, const unsign
       const unsigned wds[2] = {cw.x, cw.y};
 #pragma unroll
       for (int e = 0; e < 8; e++) {
-        const unsigned oc = (wds[e >> 2] >> ((e & 3) * 8)) & 0xffu;
-        const bool ok = oc != 255u;
+        const DictCode d = odict_code(wds[e >> 2], e);
+        const bool ok = d.ok;
         const double a = ok ? ksk::ldstream(vb + (long long)(e8 + e) * 64) : 0.0;
-        const long long xi = r + (ok ? so[oc] : 0);
+        const long long xi = r + (ok ? so[d.oc] : 0);
 #pragma unroll
         for (int k = 0; k < KB; k++) acc[k] = fma(a, ok ? X[k * ldx + xi] : 0.0, acc[k]);
       }
@@ -121,14 +100,9 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spmm_sell(int nrows, int nslices, 
 {
   const int lane = threadIdx.x & 63;
   const int wpb = MM_BLOCK / 64;
-  long long nblk = gridDim.x;
-  long long b = blockIdx.x;
-  if (xcd_remap) {
-    const long long per = nblk / 8;
-    if (b < per * 8) b = (b % 8) * per + b / 8;
-  }
-  const long long nsb = ((long long)nslices + wpb - 1) / wpb;
-  for (long long g = b; g < nsb; g += nblk) {
+  const long long nsb = ((long long)nslices + wpb - 1) / wpb;     // slice groups
+  const long long nblk = gridDim.x;
+  for (long long g = sell_first_group(nblk, xcd_remap); g < nsb; g += nblk) {
     const long long s = g * wpb + (threadIdx.x >> 6);
     if (s >= nslices) continue;
     const long long r = s * 64 + lane;
@@ -139,16 +113,8 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spmm_sell(int nrows, int nslices, 
 #pragma unroll
     for (int k = 0; k < KB; k++) acc[k] = 0.0;
     for (int q = 0; q < wp; q += MM_UNR) {
-      mm_i2v c[MM_UNR]; ksk::ks_d2v a[MM_UNR];
-#pragma unroll
-      for (int u = 0; u < MM_UNR; u++) {
-        const int j = 2 * (q + u);
-        const bool ok = q + u < wp && j < len;
-        const long long p = sb + (long long)(q + u) * 128 + lane * 2;
-        c[u] = ok ? __builtin_nontemporal_load(reinterpret_cast<const mm_i2v *>(col + p)) : mm_i2v{-1, -1};
-        a[u] = ok ? __builtin_nontemporal_load(reinterpret_cast<const ksk::ks_d2v *>(val + p)) : ksk::ks_d2v{0.0, 0.0};
-        if (j + 1 >= len) { c[u].y = -1; a[u].y = 0.0; }
-      }
+      ks_i2v c[MM_UNR]; ksk::ks_d2v a[MM_UNR];
+      KS_SELL_LOAD_PAIRS(MM_UNR, c, a, col, val, sb, q, wp, len, lane)
 #pragma unroll
       for (int u = 0; u < MM_UNR; u++) {
 #pragma unroll
@@ -159,12 +125,9 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spmm_sell(int nrows, int nslices, 
       }
     }
     if (w & 1) {
-      const bool ok = w - 1 < len;
-      const long long p = sb + (long long)wp * 128 + lane;
-      const int c = ok ? ksk::ldstream(col + p) : -1;
-      const double a = ok ? ksk::ldstream(val + p) : 0.0;
+      const SellEntry t = sell_tail(col, val, sb, w, len, lane);
 #pragma unroll
-      for (int k = 0; k < KB; k++) acc[k] = fma(a, c >= 0 ? X[k * ldx + c] : 0.0, acc[k]);
+      for (int k = 0; k < KB; k++) acc[k] = fma(t.a, t.c >= 0 ? X[k * ldx + t.c] : 0.0, acc[k]);
     }
     if (r < nrows) {
 #pragma unroll
@@ -178,18 +141,6 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spmm_sell(int nrows, int nslices, 
 // IL: where an entry's KB x values come from. false (direct): the column-major block, KB separate gathers (KB cache lines for a
 // scattered column). true (interleaved): a row-major n x KB copy of the pass's columns (k_spmm_pack, owned by the matrix), so one
 // entry's KB values are one run of 8 KB bytes.
-struct MmRows { int p0, p1, E0, E1; long long r; bool has; };
-__device__ __forceinline__ MmRows mm_rows(int n, const int *__restrict__ rp, int g, int w, int lane)
-{
-  MmRows q; q.p0 = q.p1 = q.E0 = q.E1 = 0; q.has = false;
-  const long long r0 = (long long)g * 256 + (long long)w * 64;
-  q.r = r0 + lane;
-  if (r0 >= n) return q;
-  q.has = q.r < n;
-  if (q.has) { mm_i2v pp; __builtin_memcpy(&pp, rp + q.r, sizeof(pp)); q.p0 = pp.x; q.p1 = pp.y; }
-  q.E0 = rp[r0]; q.E1 = rp[r0 + 64 < n ? r0 + 64 : n];
-  return q;
-}
 template <int KB, bool IL>
 __device__ __forceinline__ void mm_gather(double (&xv)[KB], const double *__restrict__ X, long long ldx, int c, bool ok)
 {
@@ -215,32 +166,18 @@ __global__ __launch_bounds__(256, 4) void k_spmm_csr(int n, const int *__restric
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   double *sa = sa_all[w];
   int *sc = sc_all[w];
-  const int NG = (n + 255) / 256;
-  int g, gend, gstep;
-  if (xcd_remap) {
-    const int xcd = blockIdx.x & 7, li = blockIdx.x >> 3, lc = gridDim.x >> 3;
-    g = (int)((long long)NG * xcd / 8) + li; gend = (int)((long long)NG * (xcd + 1) / 8); gstep = lc;
-  } else { g = blockIdx.x; gend = NG; gstep = gridDim.x; }
+  const WaveGroups wg = wave_groups_xcd(n, xcd_remap);
+  int g = wg.g;
+  const int gend = wg.gend, gstep = wg.gstep;
   if (g >= gend) return;
-  MmRows cu = mm_rows(n, rp, g, w, lane);
-  MmRows nx = g + gstep < gend ? mm_rows(n, rp, g + gstep, w, lane) : MmRows{0, 0, 0, 0, 0, false};
+  CwRows cu = cw_rows(n, rp, g, w, lane);
+  CwRows nx = g + gstep < gend ? cw_rows(n, rp, g + gstep, w, lane) : CwRows{0, 0, 0, 0, 0, false};
   for (;;) {
     double acc[KB];
 #pragma unroll
     for (int k = 0; k < KB; k++) acc[k] = 0.0;
     for (int e0 = cu.E0 & ~3; e0 < cu.E1; e0 += MM_CH) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // the row lanes' reads of the previous chunk are done before this one may land
-#pragma unroll
-      for (int i = 0; i < MM_CH / 128; i++) {
-        const int e = e0 + 128 * i + 2 * lane;
-        if (e < cu.E1) __builtin_amdgcn_global_load_lds((mm_glb_void *)(val + e), (mm_lds_void *)(sa + 128 * i), 16, 0, 2);     // may take one entry past E1: CW_PAD
-      }
-#pragma unroll
-      for (int i = 0; i < MM_CH / 256; i++) {
-        const int e = e0 + 256 * i + 4 * lane;
-        if (e < cu.E1) __builtin_amdgcn_global_load_lds((mm_glb_void *)(col + e), (mm_lds_void *)(sc + 256 * i), 16, 0, 2);     // up to three past E1: CW_PAD
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // an LDS-DMA is a pending LDS write on the VM counter
+      cw_dma_chunk<MM_CH>(sa, sc, col, val, e0, cu.E1, lane);
       const int lo = max(cu.p0, e0), hi = min(cu.p1, e0 + MM_CH);
       for (int p = lo; __builtin_amdgcn_ballot_w64(p < hi) != 0; p += MM_GU) {
         double av[MM_GU], xv[MM_GU][KB];
@@ -266,7 +203,7 @@ __global__ __launch_bounds__(256, 4) void k_spmm_csr(int n, const int *__restric
     g += gstep;
     if (g >= gend) break;
     cu = nx;
-    nx = g + gstep < gend ? mm_rows(n, rp, g + gstep, w, lane) : MmRows{0, 0, 0, 0, 0, false};
+    nx = g + gstep < gend ? cw_rows(n, rp, g + gstep, w, lane) : CwRows{0, 0, 0, 0, 0, false};
   }
 }
 
@@ -306,55 +243,41 @@ int spmm_pass(ks_mat A, int kb, const double *X, long long ldx, double *Y, long 
     const size_t bytes = sizeof(double) * (size_t)A->n * MM_KB;         // the widest pass: allocated once, freed by ks_mat_destroy
     if (hipMalloc(&A->mm_xi, bytes) != hipSuccess) { A->mm_xi = nullptr; KS_FAIL(KS_ERR_MEM, "hipMalloc of the interleaved block (%zu bytes) failed", bytes); }
   }
-  // variants 20: k_spmm_dict, 21: k_spmm_odict, 22: k_spmm_sell, 23: k_spmm_csr (direct), 24: k_spmm_pack + k_spmm_csr (interleaved);
   // algorithmic bytes A_bytes + 16 n KB with the CSR stream as A_bytes (as ks_mat_mult_internal counts), the layout's own next to them
   const double xy = 16.0 * A->n * kb;
   const double alg = 12.0 * A->nnz_d + 4.0 * (A->n + 1) + xy;
-  int variant = 23; double own = alg;
+  int variant = il ? KS_SPMM_CSR_IL : KS_SPMM_CSR;
   switch (A->layout) {
-  case KS_MAT_LAYOUT_DICT: variant = 20; own = (A->dc_rowpat ? 1.0 : 2.0 * A->dict_w) * A->n + xy; break;
-  case KS_MAT_LAYOUT_ODICT: variant = 21; own = 8.0 * A->nnz_d + (double)A->dict_w * A->n + xy; break;
-  case KS_MAT_LAYOUT_SELL: variant = 22; own = 12.0 * A->s_entries + 4.0 * A->n + xy; break;
-  default: if (il) { variant = 24; own = alg + xy; } break;              // the pack reads the pass's columns and writes them once more
+  case KS_MAT_LAYOUT_DICT: variant = KS_SPMM_DICT; break;
+  case KS_MAT_LAYOUT_ODICT: variant = KS_SPMM_ODICT; break;
+  case KS_MAT_LAYOUT_SELL: variant = KS_SPMM_SELL; break;
   }
-  KsProfScope ps(ctx, KS_K_SPMV, alg, variant, own);
+  KsProfScope ps(ctx, KS_K_SPMV, alg, variant, layout_own_bytes(A) + (il ? 2.0 : 1.0) * xy);      // interleaved: the pack reads the pass's columns and writes them once more
   switch (A->layout) {
   case KS_MAT_LAYOUT_DICT:
   case KS_MAT_LAYOUT_ODICT: {
-    const long long groups = ((long long)A->n + MM_BLOCK - 1) / MM_BLOCK;       // the grid of ks_mat_mult_internal's dictionary launch
-    long long nblk = std::max<long long>(1, std::min<long long>(groups, (long long)ctx->num_cu * 64));
-    const int remap = nblk >= 64 ? 1 : 0;
-    if (remap) nblk = std::min<long long>((nblk + 7) / 8, (groups + 7) / 8) * 8;
-    const dim3 gr((unsigned)nblk);
-    const size_t lds = A->layout == KS_MAT_LAYOUT_DICT && A->dc_rowpat ? (size_t)A->dict_npat * A->dict_w * 2 : 0;
-#define MM_DICT(KB)                                                                                                                                                                   \
-  if (A->layout == KS_MAT_LAYOUT_DICT) {                                                                                                                                              \
-    if (A->dict_w == 8) hipLaunchKernelGGL((k_spmm_dict<8, KB>), gr, dim3(MM_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);     \
-    else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmm_dict<32, KB>), gr, dim3(MM_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap); \
-    else hipLaunchKernelGGL((k_spmm_dict<16, KB>), gr, dim3(MM_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);              \
-  } else if (A->dict_w == 8) hipLaunchKernelGGL((k_spmm_odict<8, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);                   \
-  else if (A->dict_w == 32) hipLaunchKernelGGL((k_spmm_odict<32, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap);                 \
-  else hipLaunchKernelGGL((k_spmm_odict<16, KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, X, ldx, Y, ldy, remap)
+    const LaunchGrid lg = dict_launch_grid(A);
+    const size_t lds = dict_pattern_lds_bytes(A);
+#define MM_DICT_W(W) hipLaunchKernelGGL((k_spmm_dict<W, MM_DICT_KB>), dim3(lg.blocks), dim3(MM_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, X, ldx, Y, ldy, lg.remap)
+#define MM_ODICT_W(W) hipLaunchKernelGGL((k_spmm_odict<W, MM_DICT_KB>), dim3(lg.blocks), dim3(MM_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, X, ldx, Y, ldy, lg.remap)
+#define MM_DICT(KB) { constexpr int MM_DICT_KB = KB; if (A->layout == KS_MAT_LAYOUT_DICT) KS_DICT_W_SWITCH(A->dict_w, MM_DICT_W); else KS_DICT_W_SWITCH(A->dict_w, MM_ODICT_W); }
     MM_KB_SWITCH(kb, MM_DICT);
 #undef MM_DICT
+#undef MM_DICT_W
+#undef MM_ODICT_W
     break;
   }
   case KS_MAT_LAYOUT_SELL: {
-    const long long groups = ((long long)A->nslices + 3) / 4;                    // the grid of ks_mat_mult_internal's SELL launch
-    const long long blocks = std::min<long long>(groups, (long long)ctx->num_cu * 4096);
-    const int remap = (blocks == groups && blocks >= 64) ? 1 : 0;
-    const dim3 gr((unsigned)std::max<long long>(blocks, 1));
-#define MM_SELL(KB) hipLaunchKernelGGL((k_spmm_sell<KB>), gr, dim3(MM_BLOCK), 0, ctx->stream, A->n, A->nslices, A->s_ptr, A->s_len, A->s_col, A->s_val, X, ldx, Y, ldy, remap)
+    const LaunchGrid lg = sell_launch_grid(A);
+#define MM_SELL(KB) hipLaunchKernelGGL((k_spmm_sell<KB>), dim3(lg.blocks), dim3(MM_BLOCK), 0, ctx->stream, A->n, A->nslices, A->s_ptr, A->s_len, A->s_col, A->s_val, X, ldx, Y, ldy, lg.remap)
     MM_KB_SWITCH(kb, MM_SELL);
 #undef MM_SELL
     break;
   }
   default: {                                                                      // CSR row blocks (n >= 2048, not the CSR-vector form)
-    const long long NG = ((long long)A->n + 255) / 256;
-    long long nb = std::min<long long>(NG, (long long)ctx->num_cu * 4);          // four workgroups of four waves per CU (the launch bounds)
-    const int remap = nb >= 64 ? 1 : 0;
-    if (remap) nb = (nb / 8) * 8;
-    const dim3 gr((unsigned)nb);
+    const LaunchGrid lg = csr_wave_launch_grid(A, 4);
+    const dim3 gr(lg.blocks);
+    const int remap = lg.remap;
     const unsigned npk = (unsigned)((A->n + 255) / 256);
 #define MM_CSR(KB)                                                                                                                                                    \
   if (il) {                                                                                                                                                           \

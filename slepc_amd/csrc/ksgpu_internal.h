@@ -152,7 +152,7 @@ struct ks_mat_s {
   // diagonal block (columns owned by this rank, LOCAL column indices)
   int *d_rowptr = nullptr; int *d_col = nullptr; double *d_val = nullptr; long long nnz_d = 0;
   int lanes_per_row = 8;
-  // device layout of the diagonal block, chosen at assembly (choose_layout, ks_spmv.hip): a KS_MAT_LAYOUT_* value (SHELL is shell_mult's)
+  // device layout of the diagonal block, chosen at assembly (choose_layout, ks_mat.hip): a KS_MAT_LAYOUT_* value (SHELL is shell_mult's)
   int layout = KS_MAT_LAYOUT_CSR;
   enum CsrForm : unsigned char { CSR_AUTO, CSR_VEC, CSR_REGS } csr_form = CSR_AUTO;   // the CSR kernel KSGPU_SPMV=csrvec / csrregs forces
   // sliced-ELL copy of the diagonal block (slice = 64 rows = one wavefront), chosen at assembly when the
@@ -211,6 +211,18 @@ struct ks_mat_s {
   bool shell_nosync = false;                  // the callback only enqueues work on the context's stream: a Krylov run may be enqueued ahead through it
   void *shell_user = nullptr;
 };
+// Binned layout: constants and the dynamic LDS of its two kernels, shared by the build (ks_mat.hip: fit test) and the product (ks_spmv.hip: kernels, launch)
+constexpr int BN_MAXSEG = 12;            // segments a 1024-entry window may touch on the fast path
+constexpr int BN_CS_MAX = 9984;          // columns of a slice: 78 KB of LDS next to the two offset rows
+constexpr int BN_SEG_PAD = 8;            // a (slice, wave-bin) segment holds a multiple of 8 entries (padding: value 0 into the spare accumulator): every segment then
+                                         // starts on a 64-byte boundary of G / the values in both orders. Against padding to pairs only, same box: gather 385 -> 343-357 us,
+                                         // reduce 511 -> 493 us with 2.5 % more entries (profiles/r03_ab_binned.txt); 4: 370-377 / 508, 16: 346-362 / 497
+static inline size_t ks_binned_lds1(int cs, int wb) { return (size_t)cs * 8 + (size_t)(2 * wb + 1) * 4 + 16 + 16 * 2048; }   // gather: x piece, off1 row, off2t row (+ 2 KB of column codes per wave)
+static inline size_t ks_binned_lds2(int wr) { return (size_t)4 * (wr + 1) * 8; }                                             // reduce: 4 x (wr + 1) accumulators
+int ks_binned_prepare(size_t lds1, size_t lds2);            // lets the two kernels have that much dynamic LDS (they live in ks_spmv.hip)
+// `variant` of a KS_K_SPMV profile record: which product kernel ran (bench.py and the profiles key on the values)
+enum KsSpmvVariant { KS_SPMV_CSR = 0, KS_SPMV_SELL = 8, KS_SPMV_DICT = 16, KS_SPMV_ODICT = 17, KS_SPMV_BINNED = 18,      // k_spmv_csr*, k_spmv_sell<4>, k_spmv_dict, k_spmv_odict, k_binned_*
+                     KS_SPMM_DICT = 20, KS_SPMM_ODICT = 21, KS_SPMM_SELL = 22, KS_SPMM_CSR = 23, KS_SPMM_CSR_IL = 24 };    // k_spmm_*; 24: k_spmm_pack + k_spmm_csr (interleaved)
 int ks_mat_get_diagonal_internal(ks_mat A, double *d_dev);
 int ks_mat_mult_transpose_internal(ks_mat A, const double *x, double *y);
 int ks_st_apply_transpose_internal(ks_st st, const double *x, double *y);
