@@ -2,7 +2,7 @@
 
 A GPU box admits at most 6 processes on its card, so the eight ranks are eight THREADS of one process, each with its own
 libksgpu context (own streams) and a communicator provider that meets the others at a threading.Barrier (allreduce in
-fixed rank order, host allgather, neighbour exchange through a mailbox). That runs what an 8-GPU node runs per rank - halo
+fixed rank order, host allgather, neighbour exchange through a mailbox: tests/thread_comm.py). That runs what an 8-GPU node runs per rank - halo
 plans of the two edge ranks and the six interior ranks, the halo stream under the diagonal-block product, the split
 reduce | allreduce | bookkeeping Gram-Schmidt, replicated control flow with the synchronised projected solve - against the
 single-rank CPU oracle. RCCL itself (and xGMI) is not involved: that is the driver's 8-GPU run."""
@@ -14,53 +14,10 @@ import threading
 import numpy as np
 import pytest
 
+from thread_comm import ThreadComm
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-class ThreadComm:
-    def __init__(self, size):
-        self.size = size
-        self.bar = threading.Barrier(size, timeout=240)
-        self.slots = [None] * size
-        self.mail = {}
-
-    def install(self, ctx, rank):
-        size, bar, slots, mail = self.size, self.bar, self.slots, self.mail
-
-        def allreduce_sum(ptr, count, stream):
-            h = np.empty(count)
-            ctx.memcpy_d2h(h, ptr, stream)
-            slots[rank] = h
-            bar.wait()
-            tot = slots[0].copy()
-            for r in range(1, size):
-                tot += slots[r]                      # fixed rank order: identical bits on every rank
-            bar.wait()
-            ctx.memcpy_h2d(ptr, tot, stream)
-            return 0
-
-        def allgather_host(send, nbytes, recv):
-            slots[rank] = ctypes.string_at(send, nbytes)
-            bar.wait()
-            ctypes.memmove(recv, b"".join(slots[r] for r in range(size)), nbytes * size)
-            bar.wait()
-            return 0
-
-        def exchange(peers, dsend, soff, scnt, drecv, roff, rcnt, eb, stream):
-            for i, p in enumerate(peers):
-                if scnt[i]:
-                    h = np.empty(scnt[i] * eb, dtype=np.uint8)
-                    ctx.memcpy_d2h(h, dsend + soff[i] * eb, stream)
-                    mail[(rank, p)] = h
-            bar.wait()
-            for i, p in enumerate(peers):
-                if rcnt[i]:
-                    ctx.memcpy_h2d(drecv + roff[i] * eb, mail[(p, rank)], stream)
-            bar.wait()
-            return 0
-
-        ctx.set_comm_ops(rank, size, allreduce_sum, allgather_host, exchange)
 
 
 def _rank(rank, world, comm, geom, x, m, out):
