@@ -615,7 +615,7 @@ int build_dict(ks_mat A, bool offsets_only)
   const size_t nslot = (size_t)((n + 63) / 64) * 64 * W;
   std::vector<long long> vals; std::vector<int> offs;                   // sorted candidate dictionaries
   bool done = false;
-  for (int round = 0; round < 8 && !done; round++) {
+  while (!done) {                                                          // every round with a miss adds a value or an offset: ends coded, or with a dictionary full
     KS_HIP(hipMemsetAsync(d_int, 0, sizeof(int) * 2, ctx->stream));
     if (!vals.empty()) KS_HIP(hipMemcpyAsync(d_bits, vals.data(), sizeof(long long) * vals.size(), hipMemcpyHostToDevice, ctx->stream));
     if (!offs.empty()) KS_HIP(hipMemcpyAsync(d_offs, offs.data(), sizeof(int) * offs.size(), hipMemcpyHostToDevice, ctx->stream));
