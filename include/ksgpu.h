@@ -203,11 +203,22 @@ int ks_mat_get_diagonal(ks_mat A, double *d_dev);                      /* MatGet
 int ks_mat_shell_set_enqueue_only(ks_mat A, int flag);   /* the callback only enqueues work on the context's stream: Krylov runs are then enqueued ahead through it */
 int ks_mat_destroy(ks_mat A);
 int ks_mat_get_sizes(ks_mat A, int *n_local, int *n_global, long long *nnz_local);
-/* device layout chosen at assembly for the local diagonal block (KSGPU_SPMV=csr|csrvec|csrregs|sell|dict|odict|binned|sliced overrides the choice, any other value fails the creation): dictionary forms for
+/* device layout chosen at assembly for the local diagonal block (KSGPU_SPMV=csr|csrvec|csrregs|sell|dict|odict|binned|sliced|window overrides the choice, any other value fails the creation): dictionary forms for
    stencil-like matrices with few distinct values / offsets, SELL-64 for short regular rows, CSR row blocks for ragged ones, BINNED (two streaming phases, every
-   random access in LDS) for matrices whose columns scatter over a vector much larger than an L2; SLICED is round 1's layout for those */
-enum { KS_MAT_LAYOUT_CSR = 0, KS_MAT_LAYOUT_SELL = 1, KS_MAT_LAYOUT_SLICED = 2, KS_MAT_LAYOUT_SHELL = 3, KS_MAT_LAYOUT_DICT = 4, KS_MAT_LAYOUT_ODICT = 5, KS_MAT_LAYOUT_BINNED = 6 };
+   random access in LDS) for matrices whose columns scatter over a vector much larger than an L2; SLICED is round 1's layout for those.
+   WINDOW is CSR for ragged rows of more than 16 entries whose columns are stripe-local (mesh orderings with several unknowns per node): rows are cut
+   into blocks, a block whose entries reference at most max_segments 64-double segments of x keeps a 16-bit code per entry (10 bytes per nonzero
+   instead of 12) and the product stages those segments in LDS and gathers from there; a block that references more keeps its 32-bit columns and
+   gathers from memory. Values, row pointers, entry order and the bits of y are those of CSR. Built only when asked for: KSGPU_SPMV=window
+   builds it for any matrix with rows and entries; no automatic rule picks it yet. */
+enum { KS_MAT_LAYOUT_CSR = 0, KS_MAT_LAYOUT_SELL = 1, KS_MAT_LAYOUT_SLICED = 2, KS_MAT_LAYOUT_SHELL = 3, KS_MAT_LAYOUT_DICT = 4, KS_MAT_LAYOUT_ODICT = 5, KS_MAT_LAYOUT_BINNED = 6,
+       KS_MAT_LAYOUT_WINDOW = 7 };
 int ks_mat_get_layout(ks_mat A, int *layout);
+/* The windowed CSR layout (KS_MAT_LAYOUT_WINDOW). *block_rows (rows of a block) and *max_segments (segments of x a window holds) are the library's two
+   constants and are returned for any matrix. For a matrix in this layout: *blocks, *direct_blocks (blocks that reference more segments than a window
+   holds), *window_entries (entries of the other blocks) and *index_bytes, the column information a product reads: 2 bytes per window entry, 4 per
+   direct entry, 4 per listed segment. Any other layout: these four 0. */
+int ks_mat_get_window_info(ks_mat A, int *block_rows, int *max_segments, long long *blocks, long long *direct_blocks, long long *window_entries, long long *index_bytes);
 /* The dictionary layout (KS_MAT_LAYOUT_DICT) stores a row as W 2-byte codes (W = 8, 16 or 32 entry slots). When the matrix has at most 256 distinct
    rows of codes it keeps one byte per row instead, the index of the row's code word in a table of *npatterns words (the row-pattern form), and frees the
    codes. *patterns = 1 in that form, 0 otherwise; *npatterns = 0 and *index_bytes = 2 W n with the codes, n (plus padding to 256 rows) with the
@@ -225,7 +236,7 @@ int ks_mat_shell_set_mult_transpose(ks_mat A, ks_shell_mult_fn mult_transpose);
 int ks_mat_mult_host(ks_mat A, const double *x_host, double *y_host);  /* convenience for tests (single rank) */
 /* MatMatMult / MatProductNumeric(AB) with a dense column-major block: Y(:,j) = A X(:,j), j < ncols (X(:,j) at X_dev + j*ldx, Y(:,j) at
    Y_dev + j*ldy). Every column is bit for bit ks_mat_mult(A, X(:,j)): the dictionary, offset-dictionary, SELL-64 and CSR row-block layouts
-   apply A to up to 8 columns per pass (the matrix streamed once per pass); BINNED, SLICED, shell matrices, the CSR-vector form of small
+   apply A to up to 8 columns per pass (the matrix streamed once per pass); BINNED, SLICED, WINDOW, shell matrices, the CSR-vector form of small
    matrices and row-sharded matrices with a halo run one ks_mat_mult per column. ncols == 0 does nothing; ldx, ldy >= max(1, n_local)
    (KS_ERR_ARG_SIZ); X and Y must not overlap (KS_ERR_ARG_WRONG). Enqueued on the context's stream, no host wait. */
 int ks_mat_mult_multi(ks_mat A, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy);

@@ -320,7 +320,14 @@ class Mat:
 
     def layout(self):
         v = C.c_int(); _lib.check(self.ctx.L.ks_mat_get_layout(self.h, C.byref(v)))
-        return ["csr", "sell", "sliced", "shell", "dict", "odict", "binned"][v.value]
+        return ["csr", "sell", "sliced", "shell", "dict", "odict", "binned", "window"][v.value]
+
+    def window_info(self):
+        """The windowed CSR layout (ks_mat_get_window_info): the two constants for any matrix, the counts 0 unless layout() is "window"."""
+        r, s = C.c_int(), C.c_int()
+        b, d, e, ib = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
+        _lib.check(self.ctx.L.ks_mat_get_window_info(self.h, C.byref(r), C.byref(s), C.byref(b), C.byref(d), C.byref(e), C.byref(ib)))
+        return {"block_rows": r.value, "max_segments": s.value, "blocks": b.value, "direct_blocks": d.value, "window_entries": e.value, "index_bytes": ib.value}
 
     def dict_info(self):
         """Storage form of the dictionary layout (ks_mat_get_dict_info): the row-pattern form keeps one byte per row."""

@@ -84,6 +84,42 @@ void csr_transpose(int nrows, int ncols, const int *rp, const int *col, const do
   for (int r = 0; r < nrows; r++)
     for (int p = rp[r]; p < rp[r + 1]; p++) { const int q = cur[col[p]]++; colt[q] = r; valt[q] = val[p]; }
 }
+void csr_window_plan(int n, const int *rp, const int *col, int block_rows, int max_segments, int pad, WindowPlan &out)
+{
+  out = WindowPlan();
+  const long long nnz = n > 0 ? rp[n] : 0;
+  const long long blocks = ((long long)n + block_rows - 1) / block_rows;
+  const int nsegs = (n + 63) / 64;
+  out.blocks = blocks;
+  out.nseg.assign((size_t)blocks, 0); out.segptr.assign((size_t)blocks + 1, 0); out.dbase.assign((size_t)blocks, WIN_NOT_DIRECT);
+  out.codes.assign((size_t)nnz + pad, 0);
+  std::vector<long long> stamp((size_t)nsegs, -1);        // the last block that referenced the segment
+  std::vector<int> slot((size_t)nsegs, 0), list;
+  long long drun = 0;
+  for (long long b = 0; b < blocks; b++) {
+    const int r0 = (int)(b * block_rows), r1 = (int)std::min<long long>((long long)n, (b + 1) * block_rows);
+    const int e0 = rp[r0], e1 = rp[r1];
+    list.clear();
+    for (int e = e0; e < e1; e++) { const int s = col[e] >> 6; if (stamp[s] != b) { stamp[s] = b; list.push_back(s); } }
+    out.nseg[b] = (int)list.size();
+    if ((int)list.size() <= max_segments) {
+      std::sort(list.begin(), list.end());
+      for (size_t i = 0; i < list.size(); i++) slot[list[i]] = (int)i;
+      out.seg.insert(out.seg.end(), list.begin(), list.end());
+      out.window_entries += e1 - e0;
+      for (int e = e0; e < e1; e++) out.codes[e] = (unsigned short)(slot[col[e] >> 6] * 64 + (col[e] & 63));
+    } else {
+      const long long start = (drun + 3) / 4 * 4 + (e0 & 3);      // start = e0 (mod 4)
+      out.dbase[b] = (int)(start - e0);
+      drun = start + (e1 - e0);
+      out.direct_blocks++; out.direct_entries += e1 - e0;
+      out.dcol.resize((size_t)drun, 0); std::copy(col + e0, col + e1, out.dcol.begin() + start);
+    }
+    out.segptr[b + 1] = (int)out.seg.size();
+  }
+  out.total_segments = (long long)out.seg.size();
+  out.dcol.resize((size_t)drun + pad, 0);
+}
 } // namespace ksc
 
 #ifdef KSD_TEST_HOOKS
@@ -104,6 +140,21 @@ long long ksc_csr_axpy(int n, int row_start, const int *rpa, const int *ca, cons
   std::copy(r.begin(), r.end(), rp);
   if (col && val && (long long)c.size() <= cap) { std::copy(c.begin(), c.end(), col); std::copy(v.begin(), v.end(), val); }
   return (long long)c.size();
+}
+// test hook: the plan of the windowed layout. nseg, dbase: one per block; codes: one per entry; totals: blocks, direct blocks, window entries,
+// direct entries, segments listed, length of the direct column array without its padding. seg (the concatenated lists) may be NULL or has room
+// for seg_cap segments. Returns the number of segments listed.
+long long ksc_window_plan(int n, const int *rp, const int *col, int block_rows, int max_segments, int *nseg, int *dbase, unsigned short *codes,
+                          int *seg, long long seg_cap, long long *totals)
+{
+  ksc::WindowPlan p;
+  ksc::csr_window_plan(n, rp, col, block_rows, max_segments, 8, p);
+  std::copy(p.nseg.begin(), p.nseg.end(), nseg); std::copy(p.dbase.begin(), p.dbase.end(), dbase);
+  std::copy(p.codes.begin(), p.codes.end() - 8, codes);
+  if (seg && (long long)p.seg.size() <= seg_cap) std::copy(p.seg.begin(), p.seg.end(), seg);
+  totals[0] = p.blocks; totals[1] = p.direct_blocks; totals[2] = p.window_entries; totals[3] = p.direct_entries; totals[4] = p.total_segments;
+  totals[5] = (long long)p.dcol.size() - 8;
+  return p.total_segments;
 }
 }
 #endif

@@ -374,7 +374,7 @@ int wide_scatter(ks_mat A, bool *wide)
 
 // The binned, XCD-sliced and dictionary layouts are the only copy of the diagonal block kept: its diagonal and infinity norm are taken from
 // the CSR arrays before those are released (local rows only: no collective inside the per-rank layout choice).
-int release_csr(ks_mat A)
+int release_csr(ks_mat A, bool keep_val = false)            // keep_val: the windowed layout walks d_val as it is
 {
   double *d = nullptr, nrm = 0.0;
   KS_HIP(hipMalloc(&d, sizeof(double) * A->n));
@@ -382,7 +382,45 @@ int release_csr(ks_mat A)
   if (!rc) rc = ks_mat_norm_inf_local(A, &nrm);            // waits for the stream: the diagonal is complete too
   if (rc) { hipFree(d); return rc; }
   A->diag_cache = d; A->norm_inf_cache = nrm;
-  hipFree(A->d_col); hipFree(A->d_val); A->d_col = nullptr; A->d_val = nullptr;
+  hipFree(A->d_col); A->d_col = nullptr;
+  if (!keep_val) { hipFree(A->d_val); A->d_val = nullptr; }
+  return KS_SUCCESS;
+}
+
+// The windowed CSR layout: the plan is made on the host (ks_csr.cpp) from the row pointers and columns of the diagonal block, copied back once;
+// the values stay where they are. Out of host or device memory: the matrix stays CSR.
+int build_window(ks_mat A)
+{
+  ks_ctx ctx = A->ctx;
+  const int n = A->n;
+  const long long nnz = A->nnz_d;
+  auto drop = [&]() {
+    hipFree(A->wn_codes); hipFree(A->wn_dcol); hipFree(A->wn_segptr); hipFree(A->wn_seg); hipFree(A->wn_dbase);
+    A->wn_codes = nullptr; A->wn_dcol = A->wn_segptr = A->wn_seg = A->wn_dbase = nullptr;
+    (void)hipGetLastError();
+    return KS_SUCCESS;
+  };
+  try {
+  std::vector<int> rp(n + 1), col(nnz);
+  KS_HIP(hipMemcpyAsync(rp.data(), A->d_rowptr, sizeof(int) * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
+  KS_HIP(hipMemcpyAsync(col.data(), A->d_col, sizeof(int) * nnz, hipMemcpyDeviceToHost, ctx->stream));
+  KS_HIP(ks_sync(ctx));
+  ksc::WindowPlan p;
+  ksc::csr_window_plan(n, rp.data(), col.data(), WIN_ROWS, WIN_SMAX, CW_PAD, p);
+  if (p.dcol.size() >= 2147483647u) return KS_SUCCESS;   // positions in the direct column array are 32-bit
+  bool ok = true;
+  auto up = [&](auto **dev, const auto &host) {
+    using T = typename std::remove_reference<decltype(host)>::type::value_type;
+    if (!ok) return;
+    ok = hipMalloc((void **)dev, sizeof(T) * std::max<size_t>(host.size(), 1)) == hipSuccess &&
+         hipMemcpy(*dev, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice) == hipSuccess;
+  };
+  up(&A->wn_codes, p.codes); up(&A->wn_dcol, p.dcol); up(&A->wn_segptr, p.segptr); up(&A->wn_seg, p.seg); up(&A->wn_dbase, p.dbase);
+  if (!ok) return drop();
+  KS_CALL(release_csr(A, true));
+  A->layout = KS_MAT_LAYOUT_WINDOW;
+  A->wn_blocks = p.blocks; A->wn_direct_blocks = p.direct_blocks; A->wn_entries = p.window_entries; A->wn_direct_entries = p.direct_entries; A->wn_segments = p.total_segments;
+  } catch (const std::exception &) { return drop(); }
   return KS_SUCCESS;
 }
 
@@ -692,17 +730,19 @@ int build_sell(ks_mat A, bool forced)
 
 // The device layout of the diagonal block, chosen at assembly by every creation path: wide-scatter matrices get the binned layout, or the
 // XCD-sliced one where the binned build declines; the others a dictionary form, SELL-64 when its padding is small, or CSR. KSGPU_SPMV=<name>
-// forces one (tests and A/B legs); a forced layout that cannot be built falls through to SELL-64 under the padding rule, or CSR.
+// forces one (tests and A/B legs); a forced layout that cannot be built falls through to SELL-64 under the padding rule, or CSR. window (the windowed
+// CSR layout) is built only when forced: for any matrix with rows and entries, without the dictionary and SELL attempts (all its blocks may be
+// direct). No automatic rule picks it: the product has not been timed against the CSR kernel it would replace.
 int choose_layout(ks_mat A)
 {
-  enum { AUTO, CSR, CSRVEC, CSRREGS, SELL, DICT, ODICT, BINNED, SLICED };
-  static const char *const names[] = {"", "csr", "csrvec", "csrregs", "sell", "dict", "odict", "binned", "sliced"};
+  enum { AUTO, CSR, CSRVEC, CSRREGS, SELL, DICT, ODICT, BINNED, SLICED, WINDOW };
+  static const char *const names[] = {"", "csr", "csrvec", "csrregs", "sell", "dict", "odict", "binned", "sliced", "window"};
   const char *force = getenv("KSGPU_SPMV");
   int want = AUTO;
   if (force) {
     want = -1;
-    for (int i = CSR; i <= SLICED; i++) if (!strcmp(force, names[i])) want = i;
-    KS_CHECK(want >= 0, KS_ERR_ARG_WRONG, "KSGPU_SPMV=%s: not one of csr, csrvec, csrregs, sell, dict, odict, binned, sliced", force);
+    for (int i = CSR; i <= WINDOW; i++) if (!strcmp(force, names[i])) want = i;
+    KS_CHECK(want >= 0, KS_ERR_ARG_WRONG, "KSGPU_SPMV=%s: not one of csr, csrvec, csrregs, sell, dict, odict, binned, sliced, window", force);
   }
   bool wide = false;
   if (want == AUTO) KS_CALL(wide_scatter(A, &wide));
@@ -715,6 +755,7 @@ int choose_layout(ks_mat A)
     return KS_SUCCESS;
   }
   if (A->n == 0 || A->nnz_d == 0) return KS_SUCCESS;
+  if (want == WINDOW) return build_window(A);
   if (want == AUTO || want == DICT || want == ODICT) {
     KS_CALL(build_dict(A, want == ODICT));
     if (A->layout != KS_MAT_LAYOUT_CSR) return release_csr(A);
@@ -880,6 +921,7 @@ extern "C" int ks_mat_destroy(ks_mat A)
   hipFree(A->dc_codes); hipFree(A->dc_rowpat); hipFree(A->dc_pats); hipFree(A->dc_val); hipFree(A->dc_off); hipFree(A->dc_codes8); hipFree(A->dc_vals);
   hipFree(A->sl_rowptr); hipFree(A->sl_col); hipFree(A->sl_val); hipFree(A->sl_base); hipFree(A->ypart); hipFree(A->diag_cache); hipFree(A->mm_xi);
   hipFree(A->bn_col16); hipFree(A->bn_row16); hipFree(A->bn_val); hipFree(A->bn_g); hipFree(A->bn_off1); hipFree(A->bn_off2t); hipFree(A->bn_wseg); hipFree(A->bn_sbase); hipFree(A->bn_off2); hipFree(A->bn_log2);
+  hipFree(A->wn_codes); hipFree(A->wn_dcol); hipFree(A->wn_segptr); hipFree(A->wn_seg); hipFree(A->wn_dbase);
   delete A;
   return KS_SUCCESS;
 }
@@ -907,6 +949,16 @@ extern "C" int ks_mat_get_dict_info(ks_mat A, int *patterns, int *npatterns, int
   *w = A->dict_w;
   if (A->dc_rowpat) { *patterns = 1; *npatterns = A->dict_npat; *index_bytes = ((long long)A->n + 255) / 256 * 256; }
   else *index_bytes = 2LL * A->dict_w * A->n;
+  return KS_SUCCESS;
+}
+extern "C" int ks_mat_get_window_info(ks_mat A, int *block_rows, int *max_segments, long long *blocks, long long *direct_blocks, long long *window_entries, long long *index_bytes)
+{
+  KS_CHECK(A && block_rows && max_segments && blocks && direct_blocks && window_entries && index_bytes, KS_ERR_ARG_NULL, "NULL argument");
+  *block_rows = WIN_ROWS; *max_segments = WIN_SMAX;
+  *blocks = *direct_blocks = *window_entries = *index_bytes = 0;
+  if (A->shell_mult || A->layout != KS_MAT_LAYOUT_WINDOW) return KS_SUCCESS;
+  *blocks = A->wn_blocks; *direct_blocks = A->wn_direct_blocks; *window_entries = A->wn_entries;
+  *index_bytes = 2 * A->wn_entries + 4 * A->wn_direct_entries + 4 * A->wn_segments;
   return KS_SUCCESS;
 }
 extern "C" int ks_mat_get_sizes(ks_mat A, int *n_local, int *n_global, long long *nnz_local)

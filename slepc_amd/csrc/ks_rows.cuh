@@ -186,6 +186,12 @@ static inline LaunchGrid csr_wave_launch_grid(ks_mat A, int per_cu)     // per_c
   if (remap) nb = (nb / 8) * 8;
   return {(unsigned)nb, remap};
 }
+static inline LaunchGrid window_launch_grid(ks_mat A)              // windowed CSR: a workgroup per block of WIN_ROWS rows (one barrier per block and none between blocks); eight or more blocks per XCD: every XCD one contiguous eighth
+{
+  const long long nb = std::max<long long>(1, A->wn_blocks);
+  const int remap = nb >= 64 ? 1 : 0;
+  return {(unsigned)(remap ? (nb + 7) / 8 * 8 : nb), remap};
+}
 static inline size_t dict_pattern_lds_bytes(ks_mat A) { return A->layout == KS_MAT_LAYOUT_DICT && A->dc_rowpat ? (size_t)A->dict_npat * A->dict_w * 2 : 0; }   // dynamic LDS: the pattern table beside the dictionaries
 // compulsory bytes of the stored diagonal block per product (the matrix part of a KsProfScope byte model: callers add their x / y traffic)
 static inline double layout_own_bytes(ks_mat A)
@@ -195,6 +201,8 @@ static inline double layout_own_bytes(ks_mat A)
   case KS_MAT_LAYOUT_DICT: return (A->dc_rowpat ? 1.0 : 2.0 * A->dict_w) * A->n;            // one byte per row in the row-pattern form
   case KS_MAT_LAYOUT_ODICT: return 8.0 * A->nnz_d + (double)A->dict_w * A->n;
   case KS_MAT_LAYOUT_SELL: return 12.0 * A->s_entries + 4.0 * A->n;
+  case KS_MAT_LAYOUT_WINDOW:                                                                   // values + codes or columns, row pointers, every window filled once, the segment lists and the two per-block tables
+    return 10.0 * A->wn_entries + 12.0 * A->wn_direct_entries + 4.0 * (A->n + 1) + 512.0 * A->wn_segments + 4.0 * A->wn_segments + 8.0 * A->wn_blocks;
   default: return 12.0 * A->nnz_d + 4.0 * (A->n + 1);                                        // the CSR stream
   }
 }

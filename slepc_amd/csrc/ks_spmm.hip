@@ -296,7 +296,8 @@ int spmm_pass(ks_mat A, int kb, const double *X, long long ldx, double *Y, long 
 } // namespace
 
 // The one dispatch of the block product (a switch on A->layout, as in ks_mat_mult_internal): passes of up to MM_KB columns where a
-// block kernel exists, the column loop everywhere else
+// block kernel exists, the column loop everywhere else - BINNED, SLICED and WINDOW, whose column indices no longer exist as d_col (spmm_pass must
+// never see them: its default branch is the CSR block kernel)
 int ks_mat_mult_multi_internal(ks_mat A, int ncols, const double *X, int ldx, double *Y, int ldy)
 {
   if (ncols <= 0) return KS_SUCCESS;
@@ -306,6 +307,7 @@ int ks_mat_mult_multi_internal(ks_mat A, int ncols, const double *X, int ldx, do
   switch (A->layout) {
   case KS_MAT_LAYOUT_DICT: case KS_MAT_LAYOUT_ODICT: case KS_MAT_LAYOUT_SELL: break;
   case KS_MAT_LAYOUT_CSR: if (A->n < 2048 || A->csr_form == ks_mat_s::CSR_VEC) loop = true; break;      // the CSR-vector kernel: its sums are not in entry order
+  case KS_MAT_LAYOUT_WINDOW: loop = true; break;                                                          // no block kernel: spmm_pass's default is the CSR block kernel, which would read the released d_col
   default: loop = true; break;                                                                            // BINNED, SLICED
   }
   if (loop) {

@@ -244,6 +244,121 @@ __global__ __launch_bounds__(256, WPS) void k_spmv_csr_wave_dma(int n, const int
   }
 }
 
+// ---- windowed CSR (KS_MAT_LAYOUT_WINDOW; the plan: ks_csr.h) -------------------------------------------------------------------------------
+// For ragged rows of more than 16 entries whose columns are stripe-local (a mesh ordering with several unknowns per node): the entry-side form above
+// pulls a 128-byte line of x through L2 and L1 for every 8 bytes it gathers. Here a block of WIN_ROWS rows brings the 64-double segments of x its
+// entries reference - at most WIN_SMAX, listed ascending by the builder - into LDS once, by LDS-DMA at 16 bytes per lane (one wave instruction moves two
+// segments: lanes 0-31 the even slot, lanes 32-63 the odd one; the image is lane-linear, slot s at win + 64 s), and the entry lanes gather from
+// there by ds_read_b64 through a 16-bit code per entry, slot * 64 + (col & 63): 10 bytes per nonzero instead of 12 and no line traffic per entry.
+// A segment that reaches past n brings only its lanes below n (x may end where the allocation ends), the last odd element by a plain load; the
+// words left unwritten are never referenced, for a code only names a column of the matrix. An x that is not 16-byte aligned fills by plain loads.
+// The walk is k_spmv_csr_wave's entry side: a wave per 64 rows streams their one run of entries in chunks of 64 CW_STEPS - values one per lane,
+// codes FOUR per lane in one 8-byte load (entries 256 i + 4 l .. + 3 of the chunk; a chunk starts on a multiple of four entries), both
+// nontemporal - parks (value, x) in its own piece of LDS and then lane = row sums fma(a, x, acc) from 0.0 in entry order: the bits of every other
+// layout. Entries in front of the wave's run that the aligned start takes along are neither gathered nor summed. One workgroup barrier per block,
+// between the fill and the first gather, and none per chunk; the grid is a workgroup per block (the second barrier, in front of a refill, is only
+// reached by a grid that was capped), XCD by XCD one contiguous eighth of the blocks as in wave_groups_xcd.
+// A DIRECT block (more segments than a window holds) is a workgroup-uniform branch into the same walk: four 32-bit columns per lane in one 16-byte
+// load from the side array, x gathered from memory; no fill and no barrier.
+typedef int ks_i4v __attribute__((ext_vector_type(4)));
+typedef unsigned ks_u2v __attribute__((ext_vector_type(2)));
+template <int CW_STEPS> struct WinRegs { double a[CW_STEPS]; ks_i4v c[CW_STEPS / 4]; };     // window block: c[i].x, .y hold the four codes
+template <int CW_STEPS>
+__device__ __forceinline__ void win_load(WinRegs<CW_STEPS> &r, bool direct, const unsigned short *__restrict__ codes, const int *__restrict__ dc,
+                                         const double *__restrict__ val, int e0, int E1, int lane)
+{
+#pragma unroll
+  for (int i = 0; i < CW_STEPS / 4; i++) {
+    const int e = e0 + 256 * i + 4 * lane;                     // up to three past E1: CW_PAD
+    if (direct) r.c[i] = e < E1 ? __builtin_nontemporal_load(reinterpret_cast<const ks_i4v *>(dc + e)) : ks_i4v{0, 0, 0, 0};
+    else { const ks_u2v t = e < E1 ? __builtin_nontemporal_load(reinterpret_cast<const ks_u2v *>(codes + e)) : ks_u2v{0u, 0u}; r.c[i] = ks_i4v{(int)t.x, (int)t.y, 0, 0}; }
+  }
+#pragma unroll
+  for (int u = 0; u < CW_STEPS; u++) {
+    const int e = e0 + u * 64 + lane;
+    r.a[u] = e < E1 ? ksk::ldstream(val + e) : 0.0;
+  }
+}
+template <int CW_STEPS>
+__global__ __launch_bounds__(WIN_ROWS, 2) void k_spmv_window(int n, const int *__restrict__ rp, const unsigned short *__restrict__ codes, const int *__restrict__ dcol,
+                                                             const double *__restrict__ val, const int *__restrict__ segptr, const int *__restrict__ seg,
+                                                             const int *__restrict__ dbase, const double *__restrict__ x, double *__restrict__ y, int xcd_remap)
+{
+  constexpr int CH = 64 * CW_STEPS, WAVES = WIN_ROWS / 64, NQ = CW_STEPS / 4;
+  static_assert(CW_STEPS % 4 == 0, "codes come four per lane: chunks of 256 entries");
+  __shared__ __attribute__((aligned(16))) double win[WIN_SMAX * 64];
+  __shared__ double sa_all[WAVES][CH + CH / 32];
+  __shared__ double sx_all[WAVES][CH + CH / 32];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  double *sa = sa_all[w], *sx = sx_all[w];
+  const int NG = (n + WIN_ROWS - 1) / WIN_ROWS;              // blocks: as wave_groups_xcd (ks_rows.cuh), with the layout's block in place of 256 rows
+  int g, gend, gstep;
+  if (xcd_remap) {
+    const int xcd = blockIdx.x & 7, li = blockIdx.x >> 3, lc = gridDim.x >> 3;
+    g = (int)((long long)NG * xcd / 8) + li; gend = (int)((long long)NG * (xcd + 1) / 8); gstep = lc;
+  } else { g = blockIdx.x; gend = NG; gstep = gridDim.x; }
+  const bool x16 = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  for (; g < gend; g += gstep) {
+    const int db = dbase[g];
+    const bool direct = db != ksc::WIN_NOT_DIRECT;          // the same for the whole workgroup
+    const int *dc = dcol + (direct ? db : 0);
+    const CwRows cu = WIN_ROWS == 256 ? cw_rows(n, rp, g, w, lane) : cw_rows(n, rp, g >> 2, g & 3, lane);
+    int e0 = cu.E0 & ~3;
+    WinRegs<CW_STEPS> cur, nxt;
+    if (e0 < cu.E1) win_load(cur, direct, codes, dc, val, e0, cu.E1, lane);      // the first chunk is on its way while the window fills
+    if (!direct) {
+      const int s0 = segptr[g], ns = segptr[g + 1] - s0;
+      for (int i = w; 2 * i < ns; i += WAVES) {
+        const int sl = 2 * i + (lane >> 5);
+        if (sl < ns) {
+          const long long c = (long long)seg[s0 + sl] * 64 + (lane & 31) * 2;
+          if (x16 && c + 1 < n) __builtin_amdgcn_global_load_lds((ks_glb_void *)(x + c), (ks_lds_void *)(win + 128 * i), 16, 0, 0);
+          else {
+            if (c < n) win[64 * sl + (lane & 31) * 2] = x[c];
+            if (c + 1 < n) win[64 * sl + (lane & 31) * 2 + 1] = x[c + 1];
+          }
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // an LDS-DMA is a pending LDS write on the VM counter; the barrier then orders the other waves' reads behind it
+      __syncthreads();
+    }
+    double acc = 0.0;
+    while (e0 < cu.E1) {
+#pragma unroll
+      for (int u = 0; u < CW_STEPS; u++) sa[cw_slot(u * 64 + lane)] = cur.a[u];
+      double xg[4 * NQ];
+#pragma unroll
+      for (int i = 0; i < NQ; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const int e = e0 + 256 * i + 4 * lane + j;
+          const bool ok = e >= cu.E0 && e < cu.E1;
+          if (direct) xg[4 * i + j] = ok ? x[cur.c[i][j]] : 0.0;
+          else xg[4 * i + j] = ok ? win[((unsigned)cur.c[i][j >> 1] >> (16 * (j & 1))) & 0xffffu] : 0.0;
+        }
+#pragma unroll
+      for (int i = 0; i < NQ; i++) {
+        const int sl = cw_slot(256 * i + 4 * lane);            // 4 l .. 4 l + 3 never straddle a skew step
+#pragma unroll
+        for (int j = 0; j < 4; j++) sx[sl + j] = xg[4 * i + j];
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const int en = e0 + CH;
+      if (en < cu.E1) win_load(nxt, direct, codes, dc, val, en, cu.E1, lane);
+      const int lo = max(cu.p0, e0), hi = min(cu.p1, en);
+      for (int p = lo; p < hi; p++) { const int sl = cw_slot(p - e0); acc = fma(sa[sl], sx[sl], acc); }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      if (en < cu.E1) cur = nxt;
+      e0 = en;
+    }
+    if (cu.has) __builtin_nontemporal_store(acc, y + cu.r);
+    if (g + gstep < gend) __syncthreads();                    // a capped grid: the next block's fill waits for this block's last gather
+  }
+}
+#ifndef KS_WIN_STEPS
+#define KS_WIN_STEPS 4      // chunks of 256 entries: 49.6 KB of LDS per workgroup, three workgroups per CU (8: 66.5 KB, two)
+#endif
+
 // ---- sliced ELL (SELL-64) ---------------------------------------------------------------------------
 // lane <-> row: every val/col load of a wavefront is one contiguous run, the x gather of a
 // stencil matrix is contiguous too (consecutive rows -> consecutive columns), y is stored 512 B per wave,
@@ -648,6 +763,7 @@ int ks_mat_mult_dot_fused(ks_mat A, ks_bv bv, const double *x, int jy, bool gate
   const int ncols = bv->nc + jy + 1;
   const double *Vb = ks_bv_col(bv, -bv->nc);
   double *y = ks_bv_col(bv, jy);
+  // (the other row-local layouts, the windowed CSR among them, keep their own launch: only the dictionary rows are cheap enough to ride in the sweep)
   if (A->layout != KS_MAT_LAYOUT_DICT || A->shell_mult || ks_is_multi(ctx) || A->n_orows > 0 || bv->matrix || A->n != bv->n) return KS_SUCCESS;
   if (ncols < 1 || ncols > KS_MAX_COLS || bv->ld % 2 || (((uintptr_t)Vb) & 15) || (((uintptr_t)y) & 15)) return KS_SUCCESS;
   if (!ksk::ks_basis_is_cache_resident((size_t)(bv->nc + bv->m), (size_t)bv->ld)) return KS_SUCCESS;
@@ -711,6 +827,7 @@ int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *row
     case KS_MAT_LAYOUT_DICT: variant = KS_SPMV_DICT; break;
     case KS_MAT_LAYOUT_ODICT: variant = KS_SPMV_ODICT; break;
     case KS_MAT_LAYOUT_SELL: variant = KS_SPMV_SELL; own = csr_bytes; break;                            // filed under the CSR stream's bytes (its padding is at most 12.5 %)
+    case KS_MAT_LAYOUT_WINDOW: variant = KS_SPMV_WINDOW; break;
     }
     KsProfScope ps(ctx, KS_K_SPMV, csr_bytes, variant, own);
     switch (A->layout) {
@@ -741,6 +858,12 @@ int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *row
     case KS_MAT_LAYOUT_SELL: {
       const LaunchGrid lg = sell_launch_grid(A);
       hipLaunchKernelGGL((k_spmv_sell<4>), dim3(lg.blocks), dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->nslices, A->s_ptr, A->s_len, A->s_col, A->s_val, x, y, lg.remap);
+      break;
+    }
+    case KS_MAT_LAYOUT_WINDOW: {
+      const LaunchGrid lg = window_launch_grid(A);
+      hipLaunchKernelGGL((k_spmv_window<KS_WIN_STEPS>), dim3(lg.blocks), dim3(WIN_ROWS), 0, ctx->stream, A->n, A->d_rowptr, A->wn_codes, A->wn_dcol, A->d_val,
+                         A->wn_segptr, A->wn_seg, A->wn_dbase, x, y, lg.remap);
       break;
     }
     default:                                   // CSR

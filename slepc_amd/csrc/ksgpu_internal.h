@@ -192,6 +192,13 @@ struct ks_mat_s {
   long long *bn_sbase = nullptr;              // [ns + 1]     start of slice s in bn_col16
   int *bn_off2 = nullptr;                     // [wb][ns]     physical start of segment (wb, s): bin-major order GROUPED by phase-2 workgroup, [wb / 4][ns][wb % 4]
   int *bn_log2 = nullptr;                     // [wb][ns + 1] logical start of that segment inside its wave-bin (piece after piece); [ns] = entries of the wave-bin
+  // Windowed CSR (KS_MAT_LAYOUT_WINDOW, the plan: ks_csr.h): d_rowptr and d_val stay as they are, d_col is replaced by a 16-bit code per entry of a
+  // window block (slot * 64 + (col & 63) against the block's ascending list of 64-double segments of x, which the kernel stages in LDS) and by
+  // the 32-bit columns of the direct blocks (more than WIN_SMAX segments) in wn_dcol, entry e at wn_dcol[wn_dbase[block] + e]
+  unsigned short *wn_codes = nullptr;         // [nnz_d + CW_PAD]
+  int *wn_dcol = nullptr;                     // [direct entries + gaps + CW_PAD]
+  int *wn_segptr = nullptr, *wn_seg = nullptr, *wn_dbase = nullptr;      // [blocks + 1], [wn_segments], [blocks] (ksc::WIN_NOT_DIRECT: a window block)
+  long long wn_blocks = 0, wn_direct_blocks = 0, wn_entries = 0, wn_direct_entries = 0, wn_segments = 0;
   // off-diagonal block (columns owned by other ranks), compressed to ghost indices [0,nghost)
   int *o_rowptr = nullptr; int *o_col = nullptr; double *o_val = nullptr; long long nnz_o = 0;
   int nghost = 0;
@@ -219,9 +226,20 @@ constexpr int BN_SEG_PAD = 8;            // a (slice, wave-bin) segment holds a 
                                          // reduce 511 -> 493 us with 2.5 % more entries (profiles/r03_ab_binned.txt); 4: 370-377 / 508, 16: 346-362 / 497
 static inline size_t ks_binned_lds1(int cs, int wb) { return (size_t)cs * 8 + (size_t)(2 * wb + 1) * 4 + 16 + 16 * 2048; }   // gather: x piece, off1 row, off2t row (+ 2 KB of column codes per wave)
 static inline size_t ks_binned_lds2(int wr) { return (size_t)4 * (wr + 1) * 8; }                                             // reduce: 4 x (wr + 1) accumulators
+// Windowed CSR: rows of a block (one workgroup: a wave per 64 rows) and the segments of x its window holds (WIN_SMAX * 512 bytes of LDS next to the
+// 17 KB the four waves stage their chunks in: three workgroups per CU). The choice: DESIGN section 16, profiles/r07_window_layout.txt.
+#ifndef KS_WIN_ROWS
+#define KS_WIN_ROWS 256
+#endif
+#ifndef KS_WIN_SMAX
+#define KS_WIN_SMAX 64
+#endif
+constexpr int WIN_ROWS = KS_WIN_ROWS, WIN_SMAX = KS_WIN_SMAX;
+static_assert(WIN_ROWS == 256 || WIN_ROWS == 64, "a block is one workgroup of four waves or one wave");
+static_assert(WIN_SMAX >= 1 && WIN_SMAX * 64 <= 65536, "a code is slot * 64 + (col & 63) in 16 bits");
 int ks_binned_prepare(size_t lds1, size_t lds2);            // lets the two kernels have that much dynamic LDS (they live in ks_spmv.hip)
 // `variant` of a KS_K_SPMV profile record: which product kernel ran (bench.py and the profiles key on the values)
-enum KsSpmvVariant { KS_SPMV_CSR = 0, KS_SPMV_SELL = 8, KS_SPMV_DICT = 16, KS_SPMV_ODICT = 17, KS_SPMV_BINNED = 18,      // k_spmv_csr*, k_spmv_sell<4>, k_spmv_dict, k_spmv_odict, k_binned_*
+enum KsSpmvVariant { KS_SPMV_CSR = 0, KS_SPMV_SELL = 8, KS_SPMV_DICT = 16, KS_SPMV_ODICT = 17, KS_SPMV_BINNED = 18, KS_SPMV_WINDOW = 19,      // k_spmv_csr*, k_spmv_sell<4>, k_spmv_dict, k_spmv_odict, k_binned_*, k_spmv_window
                      KS_SPMM_DICT = 20, KS_SPMM_ODICT = 21, KS_SPMM_SELL = 22, KS_SPMM_CSR = 23, KS_SPMM_CSR_IL = 24 };    // k_spmm_*; 24: k_spmm_pack + k_spmm_csr (interleaved)
 int ks_mat_get_diagonal_internal(ks_mat A, double *d_dev);
 int ks_mat_mult_transpose_internal(ks_mat A, const double *x, double *y);
