@@ -465,9 +465,16 @@ int ks_st_set_gmres_cgs_refinement(ks_st st, int refine);
    KS_PC_BJACOBI - PCBJACOBI (the reference's choice with a split preconditioner, stsles.c:46-48; -st_pc_type bjacobi in ex46.c:113,
    test34.c:113) with blocks of block_size consecutive local rows (-pc_bjacobi_local_blocks n_local/block_size) solved exactly
    (-sub_pc_type lu): the dense diagonal blocks of P = A - sigma B are inverted on the host at STSetUp and applied by one kernel.
-   2 <= block_size <= 32; the matrices must hold their CSR arrays (KS_MAT_KEEP_CSR); a singular block is KS_ERR_MAT_LU_ZRPVT. */
+   2 <= block_size <= 32; the matrices must hold their CSR arrays (KS_MAT_KEEP_CSR); a singular block is KS_ERR_MAT_LU_ZRPVT.
+   KS_PC_BJACOBI_ILU - PCBJACOBI with -sub_pc_type ilu at zero fill, PETSc's parallel default for AIJ matrices (PCSetUp_BJacobi; the sub-solver is
+   MatILUFactor with levels 0 in natural ordering): blocks of block_size consecutive local rows, the last one of a rank as short as one row,
+   columns outside the block dropped; each block is factored on its own pattern on the host at STSetUp (IKJ order, no pivoting, no fill) and
+   applied by two level-scheduled sparse triangular solves, one workgroup per block with the block's vector in LDS.
+   64 <= block_size <= 8192 (KS_ERR_ARG_OUTOFRANGE otherwise); the matrices must hold their CSR arrays (KS_ERR_ORDER at set-up); a row of a block
+   without a stored diagonal entry is KS_ERR_ARG_WRONGSTATE ("Matrix is missing diagonal entry"), a zero pivot KS_ERR_MAT_LU_ZRPVT. */
 #define KS_PC_JACOBI  0
 #define KS_PC_BJACOBI 1
+#define KS_PC_BJACOBI_ILU 2
 int ks_st_set_pc(ks_st st, int type, int block_size);
 int ks_st_set_ksp(ks_st st, double rtol, int max_it, int restart);        /* KSPSetTolerances / KSPGMRESSetRestart on STGetKSP; 0 keeps */
 int ks_st_setup(ks_st st);                                                /* STSetUp */
@@ -475,6 +482,10 @@ int ks_st_apply(ks_st st, const double *x_dev, double *y_dev);            /* STA
 /* STApplyHermitianTranspose (stsolve.c:153-162) for the transformations without a solve: shift with one matrix, y = (A - sigma I)^T x
    (MatMultTranspose of A); the ones with a solve would need it with the transposed matrix: KS_ERR_SUP */
 int ks_st_apply_transpose(ks_st st, const double *x_dev, double *y_dev);
+/* PCApply on KSPGetPC(STGetKSP) (the KSP of stsles.c:51-58; PCApply itself is PETSc's, external to the reference): y = M^-1 x with the
+   preconditioner of the inner solves, whichever of the three types is set. Runs STSetUp if needed; x == y is KS_ERR_ARG_IDN; a transformation
+   without a linear solve (STSHIFT with one matrix) has no preconditioner: KS_ERR_ORDER. Enqueued on the context's stream, no host wait. */
+int ks_st_pc_apply(ks_st st, const double *x_dev, double *y_dev);
 int ks_st_backtransform(ks_st st, int n, double *eigr, double *eigi);     /* STBackTransform stsolve.c:563 */
 int ks_st_get_ksp_stats(ks_st st, long long *solves, long long *iterations, double *last_rnorm);
 

@@ -758,8 +758,9 @@ class ST:
         _lib.check(self.ctx.L.ks_st_set_gmres_cgs_refinement(self.h, {"ifneeded": 0, "never": 1, "always": 2}.get(t, t)))
 
     def SetPC(self, t, block_size=0):
-        """PCSetType on the ST's KSP: "jacobi" (default) or "bjacobi" with blocks of block_size consecutive local rows, solved exactly."""
-        _lib.check(self.ctx.L.ks_st_set_pc(self.h, {"jacobi": 0, "bjacobi": 1}.get(t, t), block_size))
+        """PCSetType on the ST's KSP: "jacobi" (default), "bjacobi" with blocks of block_size (2..32) consecutive local rows, solved exactly, or
+        "bjacobi-ilu" with blocks of block_size (64..8192) rows, each factored by ILU(0)."""
+        _lib.check(self.ctx.L.ks_st_set_pc(self.h, {"jacobi": 0, "bjacobi": 1, "bjacobi-ilu": 2}.get(t, t), block_size))
 
     def SetMatMode(self, mode):
         """STSetMatMode: "shell" (default here) or "copy" (P = A - sigma B assembled; the matrices need keep_csr)."""
@@ -781,6 +782,18 @@ class ST:
         W = BV(self.ctx, len(x), 2)
         W.set_column(0, x)
         _lib.check(self.ctx.L.ks_st_apply(self.h, C.c_void_p(W.column_ptr(0)), C.c_void_p(W.column_ptr(1))))
+        return W.column(1)
+
+    def PCApplyDev(self, xp, yp):
+        """y = M^-1 x with the preconditioner of the inner solves (PCApply on the ST's KSP), device pointers; enqueued, no host wait."""
+        _lib.check(self.ctx.L.ks_st_pc_apply(self.h, C.c_void_p(xp), C.c_void_p(yp)))
+
+    def PCApply(self, x):
+        """y = M^-1 x with host vectors (this rank's rows)."""
+        x = _f64(x)
+        W = BV(self.ctx, len(x), 2)
+        W.set_column(0, x)
+        self.PCApplyDev(W.column_ptr(0), W.column_ptr(1))
         return W.column(1)
 
     def ApplyTranspose(self, x):

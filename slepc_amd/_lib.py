@@ -212,6 +212,7 @@ _SIG = {
     "ks_st_get_matmode": [vp, C.POINTER(C.c_int)],
     "ks_st_setup": [vp],
     "ks_st_apply": [vp, vp, vp],
+    "ks_st_pc_apply": [vp, vp, vp],
     "ks_st_backtransform": [vp, C.c_int, dp, dp],
     "ks_st_get_ksp_stats": [vp, llp, llp, dp],
     # profiling

@@ -120,6 +120,112 @@ void csr_window_plan(int n, const int *rp, const int *col, int block_rows, int m
   out.total_segments = (long long)out.seg.size();
   out.dcol.resize((size_t)drun + pad, 0);
 }
+void csr_ilu0_blocks(int n, int row_start, int bs, const int *rp, const int *col, const double *val, bool keep_factors, IluPlan &out)
+{
+  out = IluPlan();
+  const int nblk = (int)(((long long)n + bs - 1) / bs);
+  out.blk.resize((size_t)nblk); out.rows.assign((size_t)2 * n, 0); out.dinv.assign((size_t)n, 0.0);
+  if (keep_factors) out.frp.assign(1, 0);
+  std::vector<int> brp, bcol, diag, pos, level, count, start, order, where, perm;
+  std::vector<double> bval;
+  for (int b = 0; b < nblk; b++) {
+    const int b0 = b * bs, bl = std::min(bs, n - b0);
+    const long long c0 = (long long)row_start + b0;
+    // the block on its sorted pattern
+    brp.assign((size_t)bl + 1, 0); bcol.clear(); bval.clear(); diag.assign((size_t)bl, -1);
+    for (int r = 0; r < bl; r++) {
+      perm.clear();
+      for (int p = rp[b0 + r]; p < rp[b0 + r + 1]; p++) { const long long c = (long long)col[p] - c0; if (c >= 0 && c < bl) perm.push_back(p); }
+      std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return col[x] < col[y]; });
+      for (size_t i = 0; i < perm.size(); i++) {
+        const int c = (int)((long long)col[perm[i]] - c0);
+        if (i > 0 && col[perm[i]] == col[perm[i - 1]]) { bval.back() = bval.back() + val[perm[i]]; continue; }
+        if (c == r) diag[r] = (int)bcol.size();
+        bcol.push_back(c); bval.push_back(val[perm[i]]);
+      }
+      brp[r + 1] = (int)bcol.size();
+      out.longest_row = std::max(out.longest_row, brp[r + 1] - brp[r]);
+      if (diag[r] < 0) { out.status = ILU_NO_DIAGONAL; out.bad_block = b; out.bad_row = b0 + r; return; }
+    }
+    // ILU(0), IKJ
+    pos.assign((size_t)bl, -1);
+    for (int i = 0; i < bl; i++) {
+      for (int p = brp[i]; p < brp[i + 1]; p++) pos[bcol[p]] = p;
+      for (int p = brp[i]; p < diag[i]; p++) {
+        const int k = bcol[p];
+        const double l = bval[p] / bval[diag[k]];
+        bval[p] = l;
+        for (int q = diag[k] + 1; q < brp[k + 1]; q++) { const int t = pos[bcol[q]]; if (t >= 0) { const double m = l * bval[q]; bval[t] = bval[t] - m; } }
+      }
+      for (int p = brp[i]; p < brp[i + 1]; p++) pos[bcol[p]] = -1;
+      if (bval[diag[i]] == 0.0) { out.status = ILU_ZERO_PIVOT; out.bad_block = b; out.bad_row = b0 + i; return; }
+    }
+    if (keep_factors) {
+      out.fcol.insert(out.fcol.end(), bcol.begin(), bcol.end()); out.fval.insert(out.fval.end(), bval.begin(), bval.end());
+      for (int r = 0; r < bl; r++) out.frp.push_back(out.frp.back() + brp[r + 1] - brp[r]);
+    }
+    // level sets and the ELL image of each level: pass 0 = L, pass 1 = U
+    out.blk[b].ell = (long long)out.val.size(); out.blk[b].lev = (int)(out.lev.size() / 2); out.blk[b].pad = 0;
+    level.assign((size_t)bl, 0); order.resize((size_t)bl);
+    for (int pass = 0; pass < 2; pass++) {
+      int nlev = 0;
+      for (int s = 0; s < bl; s++) {
+        const int i = pass == 0 ? s : bl - 1 - s;
+        const int e0 = pass == 0 ? brp[i] : diag[i] + 1, e1 = pass == 0 ? diag[i] : brp[i + 1];
+        int lv = 0;
+        for (int p = e0; p < e1; p++) lv = std::max(lv, level[bcol[p]] + 1);
+        level[i] = lv; nlev = std::max(nlev, lv + 1);
+      }
+      count.assign((size_t)nlev, 0); start.assign((size_t)nlev + 1, 0); where.assign((size_t)nlev, 0);
+      for (int i = 0; i < bl; i++) count[level[i]]++;
+      for (int l = 0; l < nlev; l++) { start[l + 1] = start[l] + count[l]; where[l] = start[l]; }
+      for (int i = 0; i < bl; i++) order[where[level[i]]++] = i;
+      unsigned short *rows = out.rows.data() + (size_t)2 * b0 + (size_t)pass * bl;
+      for (int l = 0; l < nlev; l++) {
+        const int nl = count[l];
+        int w = 0;
+        for (int p = start[l]; p < start[l + 1]; p++) { const int i = order[p]; w = std::max(w, pass == 0 ? diag[i] - brp[i] : brp[i + 1] - diag[i] - 1); }
+        const size_t base = out.val.size();
+        out.val.resize(base + (size_t)nl * w, 0.0); out.code.resize(base + (size_t)nl * w, 0);
+        for (int p = 0; p < nl; p++) {
+          const int i = order[start[l] + p];
+          rows[start[l] + p] = (unsigned short)i;
+          if (pass == 1) out.dinv[(size_t)b0 + start[l] + p] = 1.0 / bval[diag[i]];
+          const int e0 = pass == 0 ? brp[i] : diag[i] + 1, e1 = pass == 0 ? diag[i] : brp[i + 1];
+          for (int s = 0; s < w; s++) {
+            const size_t at = base + (size_t)s * nl + p;
+            if (e0 + s < e1) { out.val[at] = bval[e0 + s]; out.code[at] = (unsigned short)bcol[e0 + s]; }
+            else out.code[at] = (unsigned short)i;
+          }
+        }
+        out.lev.push_back(nl); out.lev.push_back(w);
+      }
+      (pass == 0 ? out.blk[b].nL : out.blk[b].nU) = nlev;
+    }
+  }
+}
+void ilu0_apply_host(const IluPlan &p, int n, int bs, const double *in, double *out)
+{
+  std::vector<double> x;
+  for (size_t b = 0; b < p.blk.size(); b++) {
+    const int b0 = (int)b * bs, bl = std::min(bs, n - b0);
+    x.assign(in + b0, in + b0 + bl);
+    const double *v = p.val.data() + p.blk[b].ell; const unsigned short *c = p.code.data() + p.blk[b].ell;
+    const unsigned short *rows = p.rows.data() + (size_t)2 * b0; const double *dinv = p.dinv.data() + b0;
+    for (int l = 0; l < p.blk[b].nL + p.blk[b].nU; l++) {
+      const int nl = p.lev[(size_t)2 * (p.blk[b].lev + l)], w = p.lev[(size_t)2 * (p.blk[b].lev + l) + 1];
+      const bool upper = l >= p.blk[b].nL;
+      for (int i = 0; i < nl; i++) {
+        const int r = rows[i];
+        double acc = 0.0;
+        for (int s = 0; s < w; s++) acc = __builtin_fma(v[(size_t)s * nl + i], x[c[(size_t)s * nl + i]], acc);
+        x[r] = upper ? (x[r] - acc) * dinv[i] : x[r] - acc;
+      }
+      v += (size_t)nl * w; c += (size_t)nl * w; rows += nl; if (upper) dinv += nl;
+    }
+    std::copy(x.begin(), x.end(), out + b0);
+  }
+}
 } // namespace ksc
 
 #ifdef KSD_TEST_HOOKS
@@ -155,6 +261,22 @@ long long ksc_window_plan(int n, const int *rp, const int *col, int block_rows, 
   totals[0] = p.blocks; totals[1] = p.direct_blocks; totals[2] = p.window_entries; totals[3] = p.direct_entries; totals[4] = p.total_segments;
   totals[5] = (long long)p.dcol.size() - 8;
   return p.total_segments;
+}
+// test hook: ILU(0) of the diagonal blocks (block size bs) and the solve the kernel runs, on the host. frp (n + 1), fcol, fval (cap entries, may be
+// NULL): the factors on the blocks' sorted patterns, block-local columns. in / out (may be NULL): out = (LU)^-1 in through the level layout.
+// info: status (0, 1 = a row without a diagonal entry, 2 = zero pivot), block, local row, longest row, levels, ELL entries. Returns the number of
+// entries of the factors, -1 on a status other than 0.
+long long ksc_ilu0_blocks(int n, int row_start, int bs, const int *rp, const int *col, const double *val, int *frp, int *fcol, double *fval, long long cap,
+                          const double *in, double *out, long long *info)
+{
+  ksc::IluPlan p;
+  ksc::csr_ilu0_blocks(n, row_start, bs, rp, col, val, true, p);
+  info[0] = p.status; info[1] = p.bad_block; info[2] = p.bad_row; info[3] = p.longest_row; info[4] = (long long)p.lev.size() / 2; info[5] = (long long)p.val.size();
+  if (p.status) return -1;
+  if (frp) std::copy(p.frp.begin(), p.frp.end(), frp);
+  if (fcol && fval && (long long)p.fcol.size() <= cap) { std::copy(p.fcol.begin(), p.fcol.end(), fcol); std::copy(p.fval.begin(), p.fval.end(), fval); }
+  if (in && out) ksc::ilu0_apply_host(p, n, bs, in, out);
+  return (long long)p.fcol.size();
 }
 }
 #endif

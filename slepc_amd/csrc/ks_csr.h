@@ -32,4 +32,32 @@ struct WindowPlan {
 };
 // pad: what the code and column arrays are longer than their last entry (CW_PAD)
 void csr_window_plan(int n, const int *rp, const int *col, int block_rows, int max_segments, int pad, WindowPlan &out);
+
+// ILU(0) of the diagonal blocks of a CSR row block, laid out for k_bjacobi_ilu_apply (ks_pc.hip): PCBJACOBI with -sub_pc_type ilu at zero fill
+// (PETSc's MatILUFactorSymbolic/Numeric on each block, natural ordering). Block b is local rows b*bs .. min(n, (b+1)*bs) - 1 and the columns
+// row_start + the same range; everything else in those rows (other blocks, ghost columns) is dropped. A block's rows are sorted by column and
+// repeated entries summed in the order they are stored; the sorted pattern (explicit zeros included) is factored in place in IKJ order, no
+// pivoting, no fill: l_ik = a_ik / u_kk, a_ij -= l_ik u_kj for the j > k of row k that row i stores. L is unit lower triangular.
+// The solves run level by level: a row's level is one more than the largest level among the rows it reads (L: the columns left of the diagonal,
+// levels ascending from row 0; U: the columns right of it, ascending from the last row). Per block the rows are listed by level (ascending row
+// inside a level), first the L levels, then the U levels, and a level's off-diagonal entries are stored slot-major across its rows - ELL per
+// level, padded to the level's longest row: entry s of the row at position p of a level of nl rows is at (level's start) + s * nl + p. A code
+// is the entry's block-local column; padding is a zero value with the row's own index as its code (an entry that reads nothing new).
+struct IluBlock { long long ell; int lev, nL, nU, pad; };      // where the block's entries and level descriptors start; its numbers of L and U levels
+struct IluPlan {
+  int status = 0, bad_block = -1, bad_row = -1;   // 0, or ILU_NO_DIAGONAL / ILU_ZERO_PIVOT with the block and the local row
+  int longest_row = 0;                            // most entries in one row of a block, diagonal included
+  std::vector<IluBlock> blk;                      // [blocks]
+  std::vector<int> lev;                           // two per level: rows, slots (a block's L levels, then its U levels)
+  std::vector<double> val;                        // ELL values of every level
+  std::vector<unsigned short> code;               // their block-local columns
+  std::vector<unsigned short> rows;               // [2 n]: block b's rows in L level order at 2 * b * bs, in U level order behind them
+  std::vector<double> dinv;                       // [n]: 1 / u_rr in the block's U level order (position p of the U list at b * bs + p)
+  std::vector<int> frp, fcol; std::vector<double> fval;   // the factors on the blocks' sorted patterns (block-local columns), kept only on request
+};
+constexpr int ILU_NO_DIAGONAL = 1, ILU_ZERO_PIVOT = 2;
+constexpr int ILU_BS_MAX = 8192;                  // 64 KB of LDS for the block's vector; codes fit 16 bits
+void csr_ilu0_blocks(int n, int row_start, int bs, const int *rp, const int *col, const double *val, bool keep_factors, IluPlan &out);
+// what the kernel computes, on the host, in the same order: out = (LU)^-1 in block by block
+void ilu0_apply_host(const IluPlan &p, int n, int bs, const double *in, double *out);
 }

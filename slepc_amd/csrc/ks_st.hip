@@ -99,19 +99,25 @@ int bjacobi_apply(ks_st st, const double *in, double *out)
   KS_HIP(hipGetLastError());
   return KS_SUCCESS;
 }
+// out = M^-1 in for the block preconditioners: the dense inverses, or the ILU(0) factors (k_bjacobi_ilu_apply, ks_pc.hip)
+int blocks_apply(ks_st st, const double *in, double *out)
+{
+  if (st->pc_type == KS_PC_BJACOBI_ILU) return ks_pc_ilu_apply(st->ctx, st->ilu, in, out);
+  return bjacobi_apply(st, in, out);
+}
 // out = M^-1 (a u + b v) with the left preconditioner M of the KSP: diag(P) (one fused kernel) or the diagonal blocks of P
 int pc_lincomb(ks_st st, double a, const double *u, double b, const double *v, double *out)
 {
   if (st->pc_type == KS_PC_JACOBI) return lincomb(st->ctx, st->n, st->dinv, a, u, b, v, out);
   KS_CALL(lincomb(st->ctx, st->n, nullptr, a, u, b, v, st->pcwork));
-  return bjacobi_apply(st, st->pcwork, out);
+  return blocks_apply(st, st->pcwork, out);
 }
 // out = M^-1 P x
 int apply_MP(ks_st st, const double *x, double *out, double *tmp)
 {
   if (st->pc_type == KS_PC_JACOBI) return apply_P(st, st->dinv, x, out, tmp);
   KS_CALL(apply_P(st, nullptr, x, st->pcwork, tmp));
-  return bjacobi_apply(st, st->pcwork, out);
+  return blocks_apply(st, st->pcwork, out);
 }
 
 // Left-preconditioned restarted GMRES for P y = rhs (KSPGMRES defaults: restart 30, classical Gram-Schmidt)
@@ -261,26 +267,36 @@ int st_bilinear_mult(void *user, const double *x, double *y)
 
 } // namespace
 
-// Block Jacobi set-up (PCSetUp_BJacobi with LU sub-solves, PETSc): the dense diagonal blocks of P - pc_bs consecutive local rows each - from the
-// CSR arrays the matrices keep (entry by entry a_ij + (-sigma b_ij), ks_csr.cpp, as the assembled P of ST_MATMODE_COPY has them), inverted on
-// the host by Gauss-Jordan elimination with partial pivoting, uploaded row by row.
-static int bjacobi_setup(ks_st st)
+// The CSR arrays of P the block preconditioners take their blocks from: entry by entry a_ij + (-sigma b_ij) of the arrays the matrices keep
+// (ks_csr.cpp, as the assembled P of ST_MATMODE_COPY has them) for sinvert and cayley, B's own for a shift with two matrices. Global columns;
+// the same arrays in both matrix modes. rp / col / val hold the sum where one is formed.
+static int pc_block_source(ks_st st, std::vector<int> &rp, std::vector<int> &col, std::vector<double> &val, const int **prp, const int **pcol, const double **pval)
 {
-  ks_ctx ctx = st->ctx; ks_mat A = st->A, B = st->B;
-  const int n = st->n, bs = st->pc_bs;
+  ks_mat A = st->A, B = st->B;
   const bool p_is_b = (st->type == KS_ST_SHIFT);                   // shift, nmat = 2: P = B
   ks_mat M0 = p_is_b ? B : A;
   KS_CHECK(M0 && M0->keep_csr && (p_is_b || !B || B->keep_csr), KS_ERR_ORDER, "the block-Jacobi preconditioner takes its blocks from the CSR arrays of the matrices: create them with KS_MAT_KEEP_CSR");
-  std::vector<int> rp, col; std::vector<double> val;
-  const int *prp; const int *pcol; const double *pval;
-  if (p_is_b) { prp = B->k_rowptr.data(); pcol = B->k_col.data(); pval = B->k_val.data(); }
+  if (p_is_b) { *prp = B->k_rowptr.data(); *pcol = B->k_col.data(); *pval = B->k_val.data(); }
   else {
     bool fits = false;
-    try { fits = ksc::csr_axpy(n, A->row_start, A->k_rowptr.data(), A->k_col.data(), A->k_val.data(), -st->sigma, B ? B->k_rowptr.data() : nullptr, B ? B->k_col.data() : nullptr, B ? B->k_val.data() : nullptr, rp, col, val); }
+    try { fits = ksc::csr_axpy(st->n, A->row_start, A->k_rowptr.data(), A->k_col.data(), A->k_val.data(), -st->sigma, B ? B->k_rowptr.data() : nullptr, B ? B->k_col.data() : nullptr, B ? B->k_val.data() : nullptr, rp, col, val); }
     catch (const std::exception &e) { KS_FAIL(KS_ERR_MEM, "block Jacobi set-up: %s", e.what()); }
     KS_CHECK(fits, KS_ERR_ARG_OUTOFRANGE, "A - sigma B exceeds 32-bit PetscInt indices");
-    prp = rp.data(); pcol = col.data(); pval = val.data();
+    *prp = rp.data(); *pcol = col.data(); *pval = val.data();
   }
+  return KS_SUCCESS;
+}
+
+// Block Jacobi set-up (PCSetUp_BJacobi with LU sub-solves, PETSc): the dense diagonal blocks of P - pc_bs consecutive local rows each - from the
+// CSR arrays the matrices keep, inverted on the host by Gauss-Jordan elimination with partial pivoting, uploaded row by row.
+static int bjacobi_setup(ks_st st)
+{
+  ks_ctx ctx = st->ctx;
+  const int n = st->n, bs = st->pc_bs;
+  ks_mat M0 = (st->type == KS_ST_SHIFT) ? st->B : st->A;
+  std::vector<int> rp, col; std::vector<double> val;
+  const int *prp; const int *pcol; const double *pval;
+  KS_CALL(pc_block_source(st, rp, col, val, &prp, &pcol, &pval));
   std::vector<double> inv;
   try { inv.assign((size_t)n * bs, 0.0); } catch (const std::exception &e) { KS_FAIL(KS_ERR_MEM, "block Jacobi set-up: %s", e.what()); }
   std::vector<double> Mb((size_t)bs * 2 * bs);
@@ -312,6 +328,20 @@ static int bjacobi_setup(ks_st st)
   return KS_SUCCESS;
 }
 
+// Block Jacobi with ILU(0) blocks (PCSetUp_BJacobi with -sub_pc_type ilu): the same blocks, factored on their own pattern and laid out by levels
+// on the host (ksc::csr_ilu0_blocks), uploaded once per set-up (ks_pc.hip)
+static int bjacobi_ilu_setup(ks_st st)
+{
+  ks_mat M0 = (st->type == KS_ST_SHIFT) ? st->B : st->A;
+  std::vector<int> rp, col; std::vector<double> val;
+  const int *prp; const int *pcol; const double *pval;
+  KS_CALL(pc_block_source(st, rp, col, val, &prp, &pcol, &pval));
+  KS_CALL(ks_pc_ilu_build(st->ctx, st->n, M0->row_start, st->pc_bs, prp, pcol, pval, &st->ilu));
+  if (st->pcwork) { hipFree(st->pcwork); st->pcwork = nullptr; }
+  KS_HIP(hipMalloc(&st->pcwork, sizeof(double) * std::max(st->n, 1)));
+  return KS_SUCCESS;
+}
+
 bool ks_st_is_plain(ks_st st) { return !st || (st->type == KS_ST_SHIFT && st->sigma == 0.0 && !st->B); }
 
 int ks_st_setup_internal(ks_st st)
@@ -328,6 +358,7 @@ int ks_st_setup_internal(ks_st st)
     KS_CHECK(st->nu != -st->sigma, KS_ERR_USER_INPUT, "It is not allowed to set the antishift equal to minus the shift (the target)");
   }
   if (st->Pmat) { ks_mat_destroy(st->Pmat); st->Pmat = nullptr; }           // the assembled P of an earlier shift / type / mode
+  if (st->ilu) { ks_pc_ilu_free(st->ilu); st->ilu = nullptr; }              // and its ILU(0) blocks
   const bool need_solve = (st->type == KS_ST_SINVERT) || (st->type == KS_ST_CAYLEY) || (st->type == KS_ST_SHIFT && B);
   if (st->W) { int wn = 0; ks_bv_get_sizes(st->W, &wn, nullptr, nullptr, nullptr); if (wn != A->n) { ks_bv_destroy(st->W); ks_bv_destroy(st->K); ks_bv_destroy(st->Kb); st->W = st->K = st->Kb = nullptr; if (st->dinv) hipFree(st->dinv); st->dinv = nullptr; } }
   if (!st->W) KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 3, 0, &st->W));
@@ -356,6 +387,7 @@ int ks_st_setup_internal(ks_st st)
     }
     KS_HIP(hipGetLastError());
     if (st->pc_type == KS_PC_BJACOBI) KS_CALL(bjacobi_setup(st));
+    if (st->pc_type == KS_PC_BJACOBI_ILU) KS_CALL(bjacobi_ilu_setup(st));
   }
   if (!st->op) KS_CALL(ks_mat_create_shell(ctx, A->n, A->row_start, A->n_global, st_shell_mult, st, &st->op));
   st->op->n = A->n; st->op->row_start = A->row_start; st->op->n_global = A->n_global;
@@ -423,6 +455,7 @@ extern "C" int ks_st_destroy(ks_st st)
   if (st->Pmat) ks_mat_destroy(st->Pmat);
   if (st->binv) hipFree(st->binv);
   if (st->pcwork) hipFree(st->pcwork);
+  ks_pc_ilu_free(st->ilu);
   delete st;
   return KS_SUCCESS;
 }
@@ -479,11 +512,12 @@ extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType
   if (st->ksp_type != type) { st->ksp_type = type; st->ready = false; }
   return KS_SUCCESS;
 }
-extern "C" int ks_st_set_pc(ks_st st, int type, int block_size)       // PCSetType (+ PCBJacobiSetLocalBlocks, -sub_pc_type lu) on the KSP's PC
+extern "C" int ks_st_set_pc(ks_st st, int type, int block_size)       // PCSetType (+ PCBJacobiSetLocalBlocks, -sub_pc_type lu | ilu) on the KSP's PC
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  KS_CHECK(type == KS_PC_JACOBI || type == KS_PC_BJACOBI, KS_ERR_SUP, "only PCJACOBI and PCBJACOBI are built");
-  KS_CHECK(type == KS_PC_JACOBI || (block_size >= 2 && block_size <= 32), KS_ERR_ARG_OUTOFRANGE, "block size %d (2..32)", block_size);
+  KS_CHECK(type == KS_PC_JACOBI || type == KS_PC_BJACOBI || type == KS_PC_BJACOBI_ILU, KS_ERR_SUP, "only PCJACOBI and PCBJACOBI (sub-solves: LU on dense blocks, or ILU(0)) are built");
+  KS_CHECK(type != KS_PC_BJACOBI || (block_size >= 2 && block_size <= 32), KS_ERR_ARG_OUTOFRANGE, "block size %d (2..32)", block_size);
+  KS_CHECK(type != KS_PC_BJACOBI_ILU || (block_size >= 64 && block_size <= ksc::ILU_BS_MAX), KS_ERR_ARG_OUTOFRANGE, "block size %d (64..%d)", block_size, ksc::ILU_BS_MAX);
   if (type == KS_PC_JACOBI) block_size = 0;
   if (st->pc_type != type || st->pc_bs != block_size) { st->pc_type = type; st->pc_bs = block_size; st->ready = false; }
   return KS_SUCCESS;
@@ -503,6 +537,17 @@ extern "C" int ks_st_apply(ks_st st, const double *x_dev, double *y_dev)        
   KS_CHECK(st->A, KS_ERR_ORDER, "STSetMatrices must be called first");
   KS_HIP(hipSetDevice(st->ctx->device));
   return ks_st_apply_internal(st, x_dev, y_dev);
+}
+extern "C" int ks_st_pc_apply(ks_st st, const double *x_dev, double *y_dev)     // PCApply on KSPGetPC(STGetKSP)
+{
+  KS_CHECK(st && x_dev && y_dev, KS_ERR_ARG_NULL, "NULL argument");
+  KS_CHECK(x_dev != y_dev, KS_ERR_ARG_IDN, "x and y must be different vectors");
+  KS_CHECK(st->A, KS_ERR_ORDER, "STSetMatrices must be called first");
+  KS_HIP(hipSetDevice(st->ctx->device));
+  if (!st->ready) KS_CALL(ks_st_setup_internal(st));
+  KS_CHECK(st->type != KS_ST_SHIFT || st->B, KS_ERR_ORDER, "this transformation has no linear solve, so no preconditioner (STSHIFT with one matrix)");
+  if (st->pc_type == KS_PC_JACOBI) return lincomb(st->ctx, st->n, st->dinv, 1.0, x_dev, 0.0, nullptr, y_dev);
+  return blocks_apply(st, x_dev, y_dev);
 }
 // STApplyHermitianTranspose_Generic (stsolve.c:153-162), real scalars: only the branch without a solve (st->M alone: shift with one matrix)
 int ks_st_apply_transpose_internal(ks_st st, const double *x, double *y)

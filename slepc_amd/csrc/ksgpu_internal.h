@@ -249,6 +249,12 @@ int ks_halo_peer_exchange(ks_mat A, const double *x, hipStream_t hs);     // pac
 
 int ks_mat_norm_inf_local(ks_mat A, double *val);           // max row sum of |a_ij| over this rank's rows
 
+// ---- block Jacobi with ILU(0) blocks (ks_pc.hip): factors and level schedule from CSR arrays with global columns, y = U^-1 L^-1 x ----
+struct KsIlu;
+int ks_pc_ilu_build(ks_ctx ctx, int n, int row_start, int bs, const int *rp, const int *col, const double *val, KsIlu **out);
+int ks_pc_ilu_apply(ks_ctx ctx, const KsIlu *p, const double *in, double *out);      // enqueued; in != out
+void ks_pc_ilu_free(KsIlu *p);
+
 // ---- ST: spectral transformation (ks_st.hip) ----------------------------------------------------
 struct ks_st_s {
   ks_ctx ctx = nullptr;
@@ -263,9 +269,10 @@ struct ks_st_s {
   ks_bv Kb = nullptr;                         // BiCGStab work vectors (7 columns)
   ks_bv K = nullptr, W = nullptr;             // GMRES basis (restart+1 columns), work vectors (3 columns)
   double *dinv = nullptr;                     // Jacobi: 1/diag(P)
-  int pc_type = KS_PC_JACOBI, pc_bs = 0;      // PCSetType on the KSP's PC: point Jacobi, or block Jacobi with blocks of pc_bs consecutive local rows
+  int pc_type = KS_PC_JACOBI, pc_bs = 0;      // PCSetType on the KSP's PC: point Jacobi, or block Jacobi (dense inverses or ILU(0) factors) with blocks of pc_bs consecutive local rows
   double *binv = nullptr;                     // block Jacobi: row i holds the pc_bs coefficients of row i of its block's inverse (n x pc_bs, zero beyond a short last block)
   double *pcwork = nullptr;                   // block Jacobi: the vector the blocks are applied to (n)
+  KsIlu *ilu = nullptr;                       // KS_PC_BJACOBI_ILU: the blocks' factors on the device (owned)
   int matmode = KS_ST_MATMODE_SHELL;          // STSetMatMode: how P = A - sigma B exists (shell: applied term by term; copy: assembled, stsolve.c:603-631)
   ks_mat Pmat = nullptr;                      // ST_MATMODE_COPY: the assembled P (owned)
   ks_mat op = nullptr;                        // shell matrix whose MatMult is STApply
