@@ -1,6 +1,7 @@
-// Host side of the path: the Krylov-Schur restart driver and the dense projected problem (DS HEP).
+// Host side of the path: the Krylov-Schur restart driver. The dense projected problem it solves at every restart
+// (DS HEP / NHEP), the eigenvalue comparisons and the ST's eigenvalue map are host-only code in ks_ds.cpp.
 //
-// Restates, in plain C++ on host scalars (no device code here):
+// Restates, in plain C++ on host scalars:
 //   EPSSetUp_KrylovSchur            src/eps/impls/krylov/krylovschur/krylovschur.c:93-194
 //   EPSSetDimensions_Default        src/eps/interface/epssetup.c:654-678
 //   EPSSolve_KrylovSchur_Default    krylovschur.c:227-337
@@ -9,348 +10,13 @@
 //   EPSGetStartVector               src/eps/interface/epssolve.c:841-873
 //   EPSSolve epilogue + SlepcSortEigenvalues  epssolve.c:119-208, src/sys/slepcsc.c:89-140
 //   EPSComputeError / EPSComputeResidualNorm_Private  epssolve.c:666-718,742-815
-//   DS HEP (compact, extra row):    src/sys/classes/ds/impls/hep/dshep.c:137-175 (vectors), :221-262
-//       (DSArrowTridiag), :267-321 (intermediate), :323-347 (sort), :349-381 (extra row), :383-426
-//       (solve), :643-671 (truncate); sort kernels src/sys/classes/ds/interface/dspriv.c:224-270
-// The reference calls LAPACK steqr / lartg / BLAS rot for the m x m (m <= 64) problem; LAPACK is not
-// part of this image's C toolchain, so the tridiagonal eigenproblem is solved by the implicit QL/QR
-// iteration written out below (same algorithm family as steqr; eigenvalues returned ascending as steqr
-// does, so that the insertion sort of DSSort sees the same input order).
 #include "ksgpu_internal.h"
-#include "ks_dense.h"
+#include "ks_ds.h"
 #include <algorithm>
 #include <limits>
 
-namespace {
+using ksd::KsCompare;
 
-// ---- small dense kernels ---------------------------------------------------------------------------
-// Givens rotation with LAPACK-3.10 dlartg conventions: c >= 0, r = sign(f)*hypot(f,g)
-void lartg(double f, double g, double *c, double *s, double *r)
-{
-  if (g == 0.0) { *c = 1.0; *s = 0.0; *r = f; }
-  else if (f == 0.0) { *c = 0.0; *s = (g < 0.0) ? -1.0 : 1.0; *r = fabs(g); }
-  else { const double d = hypot(f, g); *c = fabs(f) / d; *r = copysign(d, f); *s = g / *r; }
-}
-
-// BLAS drot on the first n entries of two columns
-void rot(int n, double *x, double *y, double c, double s)
-{
-  for (int i = 0; i < n; i++) { const double t = c * x[i] + s * y[i]; y[i] = c * y[i] - s * x[i]; x[i] = t; }
-}
-
-// Symmetric tridiagonal eigenproblem by implicit QL with Wilkinson shifts, accumulating the rotations
-// into the columns of Z (Z <- Z * eigvecs), eigenvalues sorted ascending on exit (steqr 'V' contract).
-// d[0..n), e[0..n-1) ; Z is ldz x n column-major with n rows used (nz rows updated).
-int tridiag_ql(int n, double *d, double *e, double *Z, int ldz, int nz)
-{
-  if (n <= 1) return 0;
-  std::vector<double> ee(n, 0.0);
-  for (int i = 0; i < n - 1; i++) ee[i] = e[i];
-  const double eps = std::numeric_limits<double>::epsilon();
-  for (int l = 0; l < n; l++) {
-    int iter = 0, mm;
-    do {
-      for (mm = l; mm < n - 1; mm++) {
-        const double dd = fabs(d[mm]) + fabs(d[mm + 1]);
-        if (fabs(ee[mm]) <= eps * dd) break;
-      }
-      if (mm != l) {
-        if (iter++ == 60 * 4) return l + 1;
-        double g = (d[l + 1] - d[l]) / (2.0 * ee[l]);
-        double r = hypot(g, 1.0);
-        g = d[mm] - d[l] + ee[l] / (g + copysign(r, g));
-        double s = 1.0, c = 1.0, p = 0.0;
-        int i;
-        for (i = mm - 1; i >= l; i--) {
-          double f = s * ee[i];
-          const double b = c * ee[i];
-          r = hypot(f, g);
-          ee[i + 1] = r;
-          if (r == 0.0) { d[i + 1] -= p; ee[mm] = 0.0; break; }
-          s = f / r; c = g / r;
-          g = d[i + 1] - p;
-          r = (d[i] - g) * s + 2.0 * c * b;
-          p = s * r;
-          d[i + 1] = g + p;
-          g = c * r - b;
-          for (int k = 0; k < nz; k++) {
-            double *zk = Z + k;
-            f = zk[(size_t)(i + 1) * ldz];
-            zk[(size_t)(i + 1) * ldz] = s * zk[(size_t)i * ldz] + c * f;
-            zk[(size_t)i * ldz] = c * zk[(size_t)i * ldz] - s * f;
-          }
-        }
-        if (r == 0.0 && i >= l) continue;
-        d[l] -= p; ee[l] = g; ee[mm] = 0.0;
-      }
-    } while (mm != l);
-  }
-  // selection sort, ascending, swapping eigenvector columns (dsteqr epilogue)
-  for (int ii = 1; ii < n; ii++) {
-    const int i = ii - 1; int k = i; double p = d[i];
-    for (int j = ii; j < n; j++) if (d[j] < p) { k = j; p = d[j]; }
-    if (k != i) { d[k] = d[i]; d[i] = p; for (int r = 0; r < nz; r++) std::swap(Z[r + (size_t)i * ldz], Z[r + (size_t)k * ldz]); }
-  }
-  for (int i = 0; i < n - 1; i++) e[i] = 0.0;
-  return 0;
-}
-
-// SlepcCompare* (src/sys/slepcsc.c:152-300), real scalars; EPS_WHICH_USER calls the function installed with
-// ks_eps_set_eigenvalue_comparison (EPSSetEigenvalueComparison epsopts.c:563)
-struct KsCompare {
-  int which = 0;                      // 0 = not set: resolved at set-up (EPSSetWhichEigenpairs_Default epsdefault.c:209-219)
-  double target = 0.0;
-  ks_eig_compare_fn fn = nullptr; void *fn_ctx = nullptr;
-  ks_st map = nullptr;                // SlepcMap_ST: compare the back-transformed values (SlepcSCCompare slepcsc.c:41-62)
-};
-int compare_eig(const KsCompare &cmp, double ar, double ai, double br, double bi)
-{
-  double a, b;
-  if (cmp.map) { ks_st_backtransform_internal(cmp.map, 1, &ar, &ai); ks_st_backtransform_internal(cmp.map, 1, &br, &bi); }
-  switch (cmp.which) {
-    case KS_EPS_LARGEST_MAGNITUDE:  a = hypot(ar, ai); b = hypot(br, bi); return a < b ? 1 : (a > b ? -1 : 0);
-    case KS_EPS_SMALLEST_MAGNITUDE: a = hypot(ar, ai); b = hypot(br, bi); return a > b ? 1 : (a < b ? -1 : 0);
-    case KS_EPS_LARGEST_REAL:       return ar < br ? 1 : (ar > br ? -1 : 0);
-    case KS_EPS_SMALLEST_REAL:      return ar > br ? 1 : (ar < br ? -1 : 0);
-    case KS_EPS_LARGEST_IMAGINARY:  a = fabs(ai); b = fabs(bi); return a < b ? 1 : (a > b ? -1 : 0);
-    case KS_EPS_SMALLEST_IMAGINARY: a = fabs(ai); b = fabs(bi); return a > b ? 1 : (a < b ? -1 : 0);
-    case KS_EPS_TARGET_MAGNITUDE:   a = hypot(ar - cmp.target, ai); b = hypot(br - cmp.target, bi); return a > b ? 1 : (a < b ? -1 : 0);
-    case KS_EPS_TARGET_REAL:        a = fabs(ar - cmp.target); b = fabs(br - cmp.target); return a > b ? 1 : (a < b ? -1 : 0);
-    case KS_EPS_WHICH_USER: { int r = 0; cmp.fn(ar, ai, br, bi, &r, cmp.fn_ctx); return r; }
-  }
-  return 0;
-}
-
-enum { DS_RAW = 0, DS_INTERMEDIATE = 1, DS_CONDENSED = 2, DS_TRUNCATED = 3 };
-
-// DS type HEP, compact storage with extra row (krylovschur.c:160-168)
-struct DsHep {
-  int ld = 0, n = 0, l = 0, k = 0, t = 0, state = DS_RAW; KsCompare which;
-  std::vector<double> T, Q; std::vector<int> perm;
-  void allocate(int ld_) { ld = ld_; T.assign((size_t)3 * ld, 0.0); Q.assign((size_t)ld * ld, 0.0); perm.assign(ld, 0); }
-  double *d() { return T.data(); }
-  double *e() { return T.data() + ld; }
-  void set_dimensions(int n_, int l_, int k_) { n = n_; t = n_; l = l_; k = k_; }           // dsops.c:130-165
-
-  void arrow_tridiag(int nn, double *dd, double *ee, double *QQ)                             // dshep.c:221-262
-  {
-    if (nn <= 2) return;
-    for (int j = 0; j < nn - 2; j++) {
-      double c, s, temp = ee[j + 1];
-      lartg(temp, ee[j], &c, &s, &ee[j + 1]);
-      s = -s;
-      temp = dd[j + 1];
-      ee[j] = c * s * (temp - dd[j]);
-      dd[j + 1] = s * s * dd[j] + c * c * temp;
-      dd[j] = c * c * dd[j] + s * s * temp;
-      const int j2 = j + 2;
-      rot(j2, QQ + (size_t)j * ld, QQ + (size_t)(j + 1) * ld, c, s);
-      for (int i = j - 1; i >= 0; i--) {
-        const double off = -s * ee[i];
-        ee[i] = c * ee[i];
-        temp = ee[i + 1];
-        lartg(temp, off, &c, &s, &ee[i + 1]);
-        s = -s;
-        temp = (dd[i] - dd[i + 1]) * s - 2.0 * c * ee[i];
-        const double p = s * temp;
-        dd[i + 1] += p;
-        dd[i] -= p;
-        ee[i] = -ee[i] - c * temp;
-        rot(j2, QQ + (size_t)i * ld, QQ + (size_t)(i + 1) * ld, c, s);
-      }
-    }
-  }
-
-  int solve(double *wr)                                                                     // dsops.c:723, dshep.c:383-426
-  {
-    if (state >= DS_CONDENSED) return 0;
-    const int n1 = n - l; const size_t off = (size_t)l + (size_t)l * ld;
-    std::fill(Q.begin(), Q.end(), 0.0);
-    for (int i = 0; i < ld; i++) Q[(size_t)i + (size_t)i * ld] = 1.0;                       // DSSetIdentity
-    if (state < DS_INTERMEDIATE) arrow_tridiag(std::max(0, k - l + 1), d() + l, e() + l, Q.data() + off);   // DSIntermediate_HEP
-    for (int i = 0; i < l; i++) wr[i] = d()[i];
-    int info = tridiag_ql(n1, d() + l, e() + l, Q.data() + off, ld, n1);
-    if (info) return info;
-    for (int i = l; i < n; i++) wr[i] = d()[i];
-    for (int i = 0; i < n - 1; i++) e()[i] = 0.0;                                           // compact: zero e(0:n-2), keep e(n-1)
-    state = DS_CONDENSED;
-    return 0;
-  }
-
-  // rr/ri: auxiliary values of an arbitrary selection (DSSort with rr: the order comes from them, dshep.c:335-336)
-  void sort(double *wr, const double *rr = nullptr, const double *ri = nullptr)             // dsops.c:329-345, dshep.c:323-347
-  {
-    for (int i = 0; i < n; i++) perm[i] = i;
-    double *dd = d();
-    const double *key = rr ? rr : dd;
-    auto im = [&](int i) { return ri ? ri[i] : 0.0; };
-    // DSSortEigenvaluesReal_Private dspriv.c:224-243 / DSSortEigenvalues_Private :172-222: insertion sort of the first t values from l
-    for (int i = l + 1; i < t; i++) {
-      const double re = key[perm[i]], rim = im(perm[i]);
-      int j = i - 1;
-      int result = compare_eig(which, re, rim, key[perm[j]], im(perm[j]));
-      while (result < 0 && j >= l) {
-        std::swap(perm[j], perm[j + 1]); j--;
-        if (j >= l) result = compare_eig(which, re, rim, key[perm[j]], im(perm[j]));
-      }
-    }
-    for (int i = l; i < n; i++) wr[i] = dd[perm[i]];
-    // DSPermuteColumns_Private dspriv.c:248-270
-    for (int i = l; i < n; i++) {
-      const int p = perm[i];
-      if (p != i) {
-        int j = i + 1;
-        while (perm[j] != i) j++;
-        perm[j] = p; perm[i] = i;
-        for (int r = 0; r < n; r++) std::swap(Q[(size_t)r + (size_t)p * ld], Q[(size_t)r + (size_t)i * ld]);
-      }
-    }
-    for (int i = l; i < n; i++) dd[i] = wr[i];
-  }
-
-  void update_extra_row()                                                                   // dshep.c:349-381 (compact)
-  {
-    const double beta = e()[n - 1];
-    for (int i = 0; i < n; i++) e()[i] = beta * Q[(size_t)(n - 1) + (size_t)i * ld];
-    k = n;
-  }
-  double vectors_resnorm(int j) { return fabs(Q[(size_t)(n - 1) + (size_t)j * ld]); }       // dshep.c:152
-
-  void truncate(int nn, bool trim)                                                          // dsops.c DSTruncate + dshep.c:643-671
-  {
-    if (trim) { l = 0; k = 0; n = nn; t = nn; state = DS_RAW; }
-    else { k = nn; t = n; n = nn; state = DS_TRUNCATED; }
-  }
-};
-
-// DS type NHEP with extra row (krylovschur.c:153-159): A is ld x ld column-major, row n holds the extra row.
-// Restates DSSolve_NHEP_Private / DSSort_NHEP_Total (src/sys/classes/ds/impls/dsutil.c:21-175),
-// DSVectors_NHEP_Eigen_Some (nhep/dsnhep.c:101-167), DSUpdateExtraRow_NHEP (:318-341), DSTruncate_NHEP (:385-415),
-// DSGetTruncateSize_Default (interface/dsops.c:329-345) on top of the host kernels of ks_dense.cpp.
-struct DsNhep {
-  int ld = 0, n = 0, l = 0, k = 0, t = 0, state = DS_RAW; KsCompare which;
-  std::vector<double> A, Q, X;
-  void allocate(int ld_) { ld = ld_; A.assign((size_t)ld * ld, 0.0); Q.assign((size_t)ld * ld, 0.0); X.assign((size_t)ld * ld, 0.0); }
-  double &a(int i, int j) { return A[(size_t)i + (size_t)j * ld]; }
-  double &q(int i, int j) { return Q[(size_t)i + (size_t)j * ld]; }
-  void set_dimensions(int n_, int l_, int k_) { n = n_; t = n_; l = l_; k = k_; }
-
-  // DSTranslateHarmonic_NHEP dsnhep.c:466-537. g (ld entries) lives in the caller between the two calls. Forward:
-  // g = (A - tau I)^{-T} (beta e_n) and A(:,n-1) += beta g. Recover (after solve and sort, with l = converged and
-  // k = kept): the rank-one term is removed from the kept block and g is projected out of the kept Schur vectors.
-  int translate_harmonic(double tau, double beta, bool recover, double *g, double *gamma_out)
-  {
-    if (!recover) {
-      std::vector<double> W((size_t)n * n);
-      for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) W[i + (size_t)j * n] = a(i, j) - (i == j ? tau : 0.0);
-      std::fill(g, g + ld, 0.0); g[n - 1] = beta;
-      if (ksd::lu_solve_trans(n, W.data(), n, g)) return 1;                                  // getrf + getrs 'C'
-      for (int i = 0; i < n; i++) a(i, n - 1) += g[i] * beta;
-    } else {
-      const int ncol = l + k;
-      std::vector<double> ghat(ncol);
-      for (int j = 0; j < ncol; j++) { double s2 = 0.0; for (int i = 0; i < n; i++) s2 += q(i, j) * g[i]; ghat[j] = -s2; }   // gemv 'C', alpha = -1
-      for (int i = 0; i < ncol; i++) for (int j = l; j < ncol; j++) a(i, j) += ghat[i] * q(n - 1, j) * beta;
-      for (int j = 0; j < ncol; j++) { const double t2 = ghat[j]; if (t2 != 0.0) for (int i = 0; i < n; i++) g[i] += t2 * q(i, j); }   // gemv 'N'
-    }
-    double scale = 0.0, ssq = 1.0;                                                           // dnrm2
-    for (int i = 0; i < n; i++) if (g[i] != 0.0) { const double ax = fabs(g[i]); if (scale < ax) { ssq = 1.0 + ssq * (scale / ax) * (scale / ax); scale = ax; } else ssq += (ax / scale) * (ax / scale); }
-    const double gamma = hypot(1.0, scale * sqrt(ssq));                                      // SlepcAbs(1.0, nrm2)
-    if (gamma_out) *gamma_out = gamma;
-    if (recover) for (int j = l; j < l + k; j++) a(n, j) *= gamma;                           // extra row
-    return 0;
-  }
-
-  void eig_from_T(double *wr, double *wi, int j0, int j1)                                    // dsutil.c:65-79,160-170
-  {
-    for (int j = j0; j < j1; j++) {
-      if (j == n - 1 || a(j + 1, j) == 0.0) { wr[j] = a(j, j); wi[j] = 0.0; }
-      else {
-        wr[j] = a(j, j); wr[j + 1] = a(j, j);
-        wi[j] = sqrt(fabs(a(j + 1, j))) * sqrt(fabs(a(j, j + 1))); wi[j + 1] = -wi[j];
-        j++;
-      }
-    }
-  }
-
-  int solve(double *wr, double *wi)                                                          // dsutil.c:21-91
-  {
-    if (state >= DS_CONDENSED) return 0;
-    std::fill(Q.begin(), Q.end(), 0.0);
-    for (int i = 0; i < n; i++) q(i, i) = 1.0;
-    if (n == 1) { wr[0] = a(0, 0); wi[0] = 0.0; state = DS_CONDENSED; return 0; }
-    if (state < DS_INTERMEDIATE) ksd::hess_reduce(n, l, A.data(), ld, Q.data());             // gehrd + orghr
-    const int info = ksd::real_schur(n, l, A.data(), ld, wr, wi, Q.data());                  // hseqr 'S','V'
-    if (info) return info;
-    eig_from_T(wr, wi, 0, l);
-    state = DS_CONDENSED;
-    return 0;
-  }
-
-  int sort(double *wr, double *wi)                                                           // dsutil.c:93-175
-  {
-    for (int i = l; i < n - 1; i++) {
-      double re = wr[i], im = wi[i];
-      int pos = 0;
-      for (int j = (im != 0.0) ? i + 2 : i + 1; j < n; j++) {
-        if (compare_eig(which, re, im, wr[j], wi[j]) > 0) { re = wr[j]; im = wi[j]; pos = j; }
-        if (wi[j] != 0.0) j++;
-      }
-      if (pos) {
-        if (ksd::trexc_up(n, A.data(), ld, Q.data(), pos, i)) return 1;                      // trexc 'V', ifst=pos+1, ilst=i+1
-        eig_from_T(wr, wi, i, n);
-      }
-      if (wi[i] != 0.0) i++;
-    }
-    return 0;
-  }
-
-  void update_extra_row()                                                                    // dsnhep.c:318-341
-  {
-    std::vector<double> x(n);
-    for (int j = 0; j < n; j++) x[j] = a(n, j);
-    for (int j = 0; j < n; j++) { double s = 0.0; for (int i = 0; i < n; i++) s += q(i, j) * x[i]; a(n, j) = s; }
-    k = n;
-  }
-
-  // k-th eigenvector of A back-transformed with Q (or not), normalised, into X(:,k[,k+1]); returns the index of the
-  // last column written; rnorm = |last component| (dsnhep.c:101-167)
-  int vectors(int kk, bool back, double *rnorm)
-  {
-    std::vector<double> xr_(n + 1), xi_(n + 1), zr_(n + 1), zi_(n + 1);
-    double *xr = xr_.data(), *xi = xi_.data(), *zr = zr_.data(), *zi = zi_.data();
-    const bool cplx = ksd::trevc_one(n, A.data(), ld, kk, xr, xi) != 0;
-    for (int i = 0; i < n; i++) {
-      if (back) { double sr = 0.0, si = 0.0; for (int j = 0; j < n; j++) { sr += q(i, j) * xr[j]; si += q(i, j) * xi[j]; } zr[i] = sr; zi[i] = si; }
-      else { zr[i] = xr[i]; zi[i] = xi[i]; }
-    }
-    double nr = 0.0, ni = 0.0;
-    for (int i = 0; i < n; i++) { nr = hypot(nr, zr[i]); ni = hypot(ni, zi[i]); }
-    const double norm = cplx ? hypot(nr, ni) : nr;
-    for (int i = 0; i < n; i++) { X[(size_t)i + (size_t)kk * ld] = zr[i] / norm; if (cplx) X[(size_t)i + (size_t)(kk + 1) * ld] = zi[i] / norm; }
-    if (rnorm) *rnorm = cplx ? hypot(zr[n - 1] / norm, zi[n - 1] / norm) : fabs(zr[n - 1] / norm);
-    return cplx ? kk + 1 : kk;
-  }
-
-  int get_truncate_size(int ll, int nn, int kk)                                              // dsops.c:329-345
-  {
-    if (a(ll + kk, ll + kk - 1) != 0.0) kk = (ll + kk < nn - 1) ? kk + 1 : kk - 1;
-    return kk;
-  }
-
-  void truncate(int nn, bool trim)                                                           // dsnhep.c:385-415
-  {
-    if (trim) {
-      for (int j = l; j < n; j++) a(n, j) = 0.0;
-      l = 0; k = 0; n = nn; t = nn; state = DS_RAW;
-    } else {
-      if (k == n) { for (int j = l; j < nn; j++) a(nn, j) = a(n, j); for (int j = l; j < n; j++) a(n, j) = 0.0; }
-      k = nn; t = n; n = nn; state = DS_TRUNCATED;
-    }
-  }
-};
-
-} // namespace
 
 struct ks_eps_s {
   ks_ctx ctx = nullptr;
@@ -388,8 +54,7 @@ struct ks_eps_s {
   bool trueres = false;                                          // EPSSetTrueResidual
   int extraction = KS_EPS_RITZ;                                  // EPSSetExtraction: Ritz or harmonic (krylovschur.c:120)
   int conv = KS_EPS_CONV_REL; double nrma = 0.0, nrmb = 0.0;   // EPSSetConvergenceTest; ||A||_inf, ||B||_inf for CONV_NORM / ERROR_BACKWARD
-  DsHep ds;
-  DsNhep dsn;
+  ksd::DsHep dsh; ksd::DsNhep dsn;                                     // the projected problem of the last solve: the symmetric or the general variant
 };
 
 extern "C" int ks_eps_create(ks_ctx ctx, ks_eps *out)
@@ -867,7 +532,7 @@ static int start_vector(ks_eps eps, int i, bool *breakdown)
 static int compute_vectors(ks_eps eps)
 {
   if (eps->vectors_done) return KS_SUCCESS;
-  ks_bv V = eps->V; DsNhep &ds = eps->dsn;
+  ks_bv V = eps->V; ksd::DsNhep &ds = eps->dsn;
   const int nc = eps->nconv;
   KS_CALL(ks_bv_set_active_columns(V, 0, nc));
   if (nc) {
@@ -882,150 +547,13 @@ static int compute_vectors(ks_eps eps)
   return KS_SUCCESS;
 }
 
-// Non-Hermitian branch of EPSSolve_KrylovSchur_Default (krylovschur.c:227-337 with BVMatArnoldi), the conjugate-pair
-// handling of EPSKrylovConvergence (epskrylov.c:262-287), EPSComputeVectors_Schur (epsdefault.c:105-169) and the
-// pair-aware SlepcSortEigenvalues (slepcsc.c:89-140).
-static int solve_nhep(ks_eps eps, long long passes0)
-{
-  ks_mat A = eps->op; ks_bv V = eps->V;
-  const int nev = eps->nev, ncv = eps->ncv, mpd = eps->mpd;
-  ks_st map = eps->cmp_ds.map;
-  const bool isshift = !map || map->type == KS_ST_SHIFT;
-  DsNhep &ds = eps->dsn;
-  ds.allocate(ncv + 1); ds.which = eps->cmp_ds; ds.state = DS_RAW;
-  const bool harmonic = eps->extraction == KS_EPS_HARMONIC;
-  std::vector<double> g(harmonic ? ncv + 1 : 0);
-  KS_CALL(start_vector(eps, 0, nullptr));
-  int l = 0;
-  while (eps->reason == KS_EPS_CONVERGED_ITERATING) {
-    eps->its++;
-    int nv = std::min(eps->nconv + mpd, ncv);
-    if (eps->max_steps && eps->steps + (nv - (eps->nconv + l)) > eps->max_steps) nv = eps->nconv + l + (int)(eps->max_steps - eps->steps);
-    ds.set_dimensions(nv, eps->nconv, eps->nconv + l);
-    double beta = 0.0; int breakdown = 0;
-    const int k0 = eps->nconv + l;
-    KS_CALL(ks_bv_matarnoldi(V, A, ds.A.data(), ds.ld, k0, &nv, &beta, &breakdown));
-    eps->steps += nv - k0;
-    ds.set_dimensions(nv, eps->nconv, eps->nconv + l);
-    ds.state = l ? DS_RAW : DS_INTERMEDIATE;
-    KS_CALL(ks_bv_set_active_columns(V, eps->nconv, nv));
-
-    // translation of the Krylov decomposition for harmonic extraction (krylovschur.c:270-271)
-    double gamma = 1.0;
-    if (harmonic) KS_CHECK(!ds.translate_harmonic(eps->which.target, beta, false, g.data(), &gamma), KS_ERR_LIB, "harmonic extraction: H - target*I is singular");
-
-    int info = ds.solve(eps->eigr.data(), eps->eigi.data());
-    KS_CHECK(info == 0, KS_ERR_LIB, "Hessenberg QR iteration failed to converge (info=%d)", info);
-    info = ds.sort(eps->eigr.data(), eps->eigi.data());
-    KS_CHECK(info == 0, KS_ERR_LIB, "reordering of the Schur form failed: blocks too close to swap");
-    ds.update_extra_row();
-    KS_CALL(ds_synchronize(eps, &ds.A, &ds.Q, &beta, &nv, &breakdown));      // krylovschur.c:281
-
-    // EPSKrylovConvergence(eps,FALSE,nconv,nv-nconv,beta,0.0,1.0,&k)
-    int marker = -1, k;
-    for (k = eps->nconv; k < nv; k++) {
-      double re = eps->eigr[k], im = eps->eigi[k];
-      if ((isshift || eps->conv == KS_EPS_CONV_NORM) && map) ks_st_backtransform_internal(map, 1, &re, &im);          // epskrylov.c:253
-      double resnorm = 0.0;
-      const int newk = ds.vectors(k, true, &resnorm);
-      if (eps->trueres) {                                      // epskrylov.c:256-264
-        if (!((isshift || eps->conv == KS_EPS_CONV_NORM) && map) && map) ks_st_backtransform_internal(map, 1, &re, &im);
-        KS_CALL(true_residual(eps, nv, re, im, ds.X.data() + (size_t)k * ds.ld, newk == k + 1 ? ds.X.data() + (size_t)newk * ds.ld : nullptr, &resnorm));
-      } else
-      resnorm *= beta * gamma;                                 // corrf: only in harmonic KS (epskrylov.c:265)
-      eps->errest[k] = converged_estimate(eps, re, im, resnorm);
-      if (marker == -1 && eps->errest[k] >= eps->tol) marker = k;
-      if (newk == k + 1) { eps->errest[k + 1] = eps->errest[k]; k++; }
-      if (marker != -1 && !eps->trackall) break;               // getall: estimates for every Ritz pair (epskrylov.c:240,280)
-    }
-    k = (marker != -1) ? marker : nv;
-    KS_CHECK(!eps->cb_err, eps->cb_err, "the user's convergence test returned %d", eps->cb_err);
-    KS_CALL(stopping_test(eps, k));
-    const int nconv_mon = k;
-
-    if (eps->reason != KS_EPS_CONVERGED_ITERATING || breakdown || k == nv) l = 0;
-    else {
-      l = std::max(1, (int)((nv - k) * eps->keep));
-      l = ds.get_truncate_size(k, nv, l);                      // do not split a 2x2 block (krylovschur.c:300)
-    }
-    if (!eps->lock && l > 0) { l += k; k = 0; }                // non-locking variant (krylovschur.c:294)
-    if (eps->reason == KS_EPS_CONVERGED_ITERATING) {
-      if (breakdown || k == nv) {
-        if (k < nev) {
-          bool brk = false;
-          KS_CALL(start_vector(eps, k, &brk));
-          if (brk) eps->reason = KS_EPS_DIVERGED_BREAKDOWN;
-        }
-      } else {
-        if (harmonic) {                                        // undo the translation (krylovschur.c:310-320): gamma u^ = u - U g~
-          ds.set_dimensions(nv, k, l);
-          ds.translate_harmonic(0.0, beta, true, g.data(), &gamma);
-          KS_CALL(ks_bv_set_active_columns(V, 0, nv));
-          KS_CALL(ks_bv_multcolumn(V, -1.0, 1.0, nv, g.data()));
-          KS_CALL(ks_bv_scalecolumn(V, nv, 1.0 / gamma));
-          KS_CALL(ks_bv_set_active_columns(V, eps->nconv, nv));
-          ds.set_dimensions(nv, k, nv);
-        }
-        ds.truncate(k + l, false);
-      }
-    }
-    KS_CALL(ks_bv_multinplace(V, ds.Q.data(), ds.ld, eps->nconv, k + l));
-    if (eps->reason == KS_EPS_CONVERGED_ITERATING && !breakdown) KS_CALL(ks_bv_copycolumn(V, nv, k + l));
-    eps->nconv = k;
-    KS_CALL(monitor(eps, nconv_mon, nv));
-    eps->restarts++;
-  }
-  ds.truncate(eps->nconv, true);
-
-  // the eigenvectors are formed on first use (compute_vectors); V(:,0:nconv) stays the Schur basis until then
-  const int nc = eps->nconv;
-  KS_CALL(ks_bv_set_active_columns(V, 0, nc));
-  eps->vectors_done = false;
-  // EPSComputeValues (epssolve.c:27-41), then conjugate pairs with the positive imaginary part first (:160-175):
-  // the inversion of sinvert flips the sign
-  if (map) ks_st_backtransform_internal(map, nc, eps->eigr.data(), eps->eigi.data());
-  for (int i = 0; i < nc - 1; i++) {
-    if (eps->eigi[i] != 0.0) {
-      if (eps->eigi[i] < 0.0) {                                 // "the next correction only works with eigenvectors" (epssolve.c:166-169)
-        eps->eigi[i] = -eps->eigi[i]; eps->eigi[i + 1] = -eps->eigi[i + 1];
-        KS_CALL(compute_vectors(eps));
-        KS_CALL(ks_bv_scalecolumn(V, i + 1, -1.0));
-      }
-      i++;
-    }
-  }
-  // SlepcSortEigenvalues keeping conjugate pairs together
-  std::vector<int> &perm = eps->perm;
-  const double *eigr = eps->eigr.data(), *eigi = eps->eigi.data();
-  for (int i = 0; i <= ncv; i++) perm[i] = i;
-  for (int i = nc - 1; i >= 0; i--) {
-    const double re = eigr[perm[i]]; double im = eigi[perm[i]];
-    int j = i + 1;
-    if (im != 0.0) { i--; im = eigi[perm[i]]; }                // complex eigenvalue: positive imaginary part first
-    while (j < nc) {
-      if (compare_eig(eps->cmp_final, re, im, eigr[perm[j]], eigi[perm[j]]) <= 0) break;
-      if (im == 0.0) {
-        if (eigi[perm[j]] == 0.0) { std::swap(perm[j - 1], perm[j]); j++; }
-        else { const int tmp = perm[j - 1]; perm[j - 1] = perm[j]; perm[j] = perm[j + 1]; perm[j + 1] = tmp; j += 2; }
-      } else {
-        if (eigi[perm[j]] == 0.0) { const int tmp = perm[j - 2]; perm[j - 2] = perm[j]; perm[j] = perm[j - 1]; perm[j - 1] = tmp; j++; }
-        else { std::swap(perm[j - 2], perm[j]); std::swap(perm[j - 1], perm[j + 1]); j += 2; }
-      }
-    }
-  }
-  long long passes1 = 0; ks_bv_gs_passes(V, &passes1, nullptr);
-  eps->passes = passes1 - passes0;
-  KS_CALL(ks_bv_set_num_constraints(V, 0));                            // remove the deflation space (epssolve.c:201-205)
-  eps->solved = true;
-  return KS_SUCCESS;
-}
-
-extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119 -> EPSSolve_KrylovSchur_Default krylovschur.c:227
+// ---- EPSSetUp (epssetup.c:286-420): problem type, ST, sort criteria, dimensions, basis, constraints, balancing. passes0: the basis'
+// Gram-Schmidt pass count before the solve's own work ----
+static int set_up(ks_eps eps, long long *passes0)
 {
   KS_CHECK(eps && eps->A, KS_ERR_ORDER, "EPSSetOperators must be called first");
   ks_mat A = eps->A;
   const int n = A->n_global;
-  // ---- EPSSetUp (epssetup.c:286-420) ----
   KS_CHECK(eps->which.which != KS_EPS_WHICH_USER || eps->which.fn, KS_ERR_ORDER, "Must call EPSSetEigenvalueComparison() first");   // epssetup.c:311
   int ptype = eps->problem_type;
   if (!ptype) ptype = eps->B ? KS_EPS_GNHEP : KS_EPS_NHEP;             // default problem type (epssetup.c:318-322)
@@ -1048,7 +576,7 @@ extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119 -> EPSSolve
     if (!st) { KS_CALL(ks_eps_get_st(eps, &st)); }
     KS_CALL(ks_st_set_matrices(st, A, eps->B)); st->ready = false;
     KS_CALL(ks_st_setup_internal(st));
-    eps->op = st->op; eps->cmp_ds.map = st;
+    eps->op = st->op; eps->cmp_ds.map = ksd::StMap{st->type, st->sigma, st->nu};   // after the set-up, which resolves nu
   } else eps->op = A;
   int nev = eps->nev, ncv = eps->ncv_user, mpd = eps->mpd_user;
   if (ncv) { KS_CHECK(ncv >= nev + 1 || (ncv == nev && ncv == n), KS_ERR_USER_INPUT, "The value of ncv must be at least nev+1"); }
@@ -1065,16 +593,14 @@ extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119 -> EPSSolve
   if (!eps->W) { KS_CALL(ks_bv_create(eps->ctx, A->n, A->n_global, 5, 0, &eps->W)); }     // work vectors: u, B*xr, B*xi, Ritz vector x, y
   eps->eigr.assign(ncv + 1, 0.0); eps->eigi.assign(ncv + 1, 0.0); eps->errest.assign(ncv + 1, 0.0);
   eps->perm.resize(ncv + 1); for (int i = 0; i <= ncv; i++) eps->perm[i] = i;
-  DsHep &ds = eps->ds;
-  ds.allocate(ncv + 1); ds.which = eps->cmp_ds; ds.state = DS_RAW;
   eps->cb_err = 0;
   eps->nconv = 0; eps->its = 0; eps->reason = KS_EPS_CONVERGED_ITERATING; eps->steps = 0; eps->restarts = 0; eps->solved = false;
-  long long passes0 = 0; ks_bv_gs_passes(eps->V, &passes0, nullptr);
+  ks_bv_gs_passes(eps->V, passes0, nullptr);
   ks_bv V = eps->V;
   KS_CALL(ks_bv_set_active_columns(V, 0, ncv + 1));
   KS_CALL(ks_bv_set_matrix(V, ghep ? (cayley ? st->bil : eps->B) : nullptr));   // EPS_SetInnerProduct epsimpl.h:280-292: STGetBilinearForm = B, or A + nu B for STCAYLEY (cayley.c:70-77)
   eps->ghep = ghep;
-  eps->problem_type_resolved_hermitian = (ptype == KS_EPS_HEP || ghep) && eps->extraction != KS_EPS_HARMONIC;
+  eps->problem_type_resolved_hermitian = (ptype == KS_EPS_HEP || ghep) && eps->extraction != KS_EPS_HARMONIC;   // else variant EPS_KS_DEFAULT on the general DS (krylovschur.c:133-151)
   eps->vectors_done = true;
   if (eps->nds) {                                                      // process the deflation space (epssetup.c:397-404)
     KS_CHECK(eps->defl && eps->defl->n == A->n, KS_ERR_ARG_INCOMP, "the deflation space was set for an operator of another size");
@@ -1099,10 +625,19 @@ extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119 -> EPSSolve
   }
   KS_CHECK(eps->extraction == KS_EPS_RITZ || !ghep, KS_ERR_SUP, "harmonic extraction with a B-inner product is not built");
   KS_CHECK(!eps->arb_fn || ((ptype == KS_EPS_HEP || ghep) && eps->extraction == KS_EPS_RITZ), KS_ERR_SUP, "arbitrary selection is built for the symmetric (Lanczos) variant only");
-  if ((ptype != KS_EPS_HEP && !ghep) || eps->extraction == KS_EPS_HARMONIC) return solve_nhep(eps, passes0);   // variant EPS_KS_DEFAULT (krylovschur.c:133-151)
-  const bool isshift = !st || st->type == KS_ST_SHIFT;
+  return KS_SUCCESS;
+}
 
-  // ---- EPSSolve_KrylovSchur_Default ----
+// EPSSolve_KrylovSchur_Default (krylovschur.c:227-337) over the DS interface, with EPSKrylovConvergence (epskrylov.c:207-295) and its
+// conjugate pairs. Symmetric variant: BVMatLanczos into T, arbitrary selection. General variant: BVMatArnoldi into A, harmonic extraction.
+static int restart_loop(ks_eps eps, ksd::Ds &ds)
+{
+  ks_bv V = eps->V;
+  const int nev = eps->nev, ncv = eps->ncv, mpd = eps->mpd;
+  const bool hermitian = eps->problem_type_resolved_hermitian, harmonic = eps->extraction == KS_EPS_HARMONIC;   // harmonic: on eps->dsn
+  const ksd::StMap &map = eps->cmp_ds.map;
+  const bool early = map && (map.type == KS_ST_SHIFT || eps->conv == KS_EPS_CONV_NORM);    // epskrylov.c:253: back-transform before the estimate
+  std::vector<double> g(harmonic ? ncv + 1 : 0);
   KS_CALL(start_vector(eps, 0, nullptr));
   int l = 0;
   while (eps->reason == KS_EPS_CONVERGED_ITERATING) {
@@ -1112,54 +647,66 @@ extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119 -> EPSSolve
     ds.set_dimensions(nv, eps->nconv, eps->nconv + l);
     double beta = 0.0; int breakdown = 0;
     const int k0 = eps->nconv + l;
-    KS_CALL(ks_bv_matlanczos(V, eps->op, ds.T.data(), ds.ld, k0, &nv, &beta, &breakdown));
+    KS_CALL(hermitian ? ks_bv_matlanczos(V, eps->op, ds.M().data(), ds.ld, k0, &nv, &beta, &breakdown)
+                      : ks_bv_matarnoldi(V, eps->op, ds.M().data(), ds.ld, k0, &nv, &beta, &breakdown));
     eps->steps += nv - k0;
     ds.set_dimensions(nv, eps->nconv, eps->nconv + l);
-    ds.state = l ? DS_RAW : DS_INTERMEDIATE;
+    ds.state = l ? ksd::DS_RAW : ksd::DS_INTERMEDIATE;
     KS_CALL(ks_bv_set_active_columns(V, eps->nconv, nv));
 
+    // translation of the Krylov decomposition for harmonic extraction (krylovschur.c:270-271)
+    double gamma = 1.0;
+    if (harmonic) KS_CHECK(!eps->dsn.translate_harmonic(eps->which.target, beta, false, g.data(), &gamma), KS_ERR_LIB, "harmonic extraction: H - target*I is singular");
+
     // solve projected problem
-    int info = ds.solve(eps->eigr.data());
-    KS_CHECK(info == 0, KS_ERR_LIB, "tridiagonal QL iteration failed to converge (info=%d)", info);
+    int info = ds.solve(eps->eigr.data(), eps->eigi.data());
+    KS_CHECK(info == 0, KS_ERR_LIB, hermitian ? "tridiagonal QL iteration failed to converge (info=%d)" : "Hessenberg QR iteration failed to converge (info=%d)", info);
+    std::vector<double> rr, ri;
     if (eps->arb_fn) {                                         // EPSGetArbitraryValues krylovschur.c:30-58, then DSSort on rr/ri
-      std::vector<double> rr(ncv + 1, 0.0), ri(ncv + 1, 0.0);
+      rr.assign(ncv + 1, 0.0); ri.assign(ncv + 1, 0.0);
       for (int i = ds.l; i < ds.n; i++) {
         double re = eps->eigr[i], im0 = 0.0;
-        if (eps->cmp_ds.map) ks_st_backtransform_internal(eps->cmp_ds.map, 1, &re, &im0);
+        map.backtransform(1, &re, &im0);
         KS_CALL(ritz_vector(eps, nv, ds.Q.data() + (size_t)i * ds.ld, nullptr));       // DSVectors(X,i) = Q(:,i) for DSHEP
         KS_HIP(ks_sync(eps->ctx));
         const int rc = eps->arb_fn(re, im0, ks_bv_col(eps->W, 3), ks_bv_col(eps->W, 4), &rr[i], &ri[i], eps->arb_ctx);
         KS_CHECK(!rc, rc, "the user's arbitrary selection function returned %d", rc);
       }
-      ds.sort(eps->eigr.data(), rr.data(), ri.data());
-    } else ds.sort(eps->eigr.data());
+    }
+    info = ds.sort(eps->eigr.data(), eps->eigi.data(), eps->arb_fn ? rr.data() : nullptr, eps->arb_fn ? ri.data() : nullptr);
+    KS_CHECK(info == 0, KS_ERR_LIB, "reordering of the Schur form failed: blocks too close to swap");
     ds.update_extra_row();
-    KS_CALL(ds_synchronize(eps, &ds.T, &ds.Q, &beta, &nv, &breakdown));      // krylovschur.c:281
+    KS_CALL(ds_synchronize(eps, &ds.M(), &ds.Q, &beta, &nv, &breakdown));      // krylovschur.c:281
 
     // EPSKrylovConvergence(eps,FALSE,nconv,nv-nconv,beta,0.0,1.0,&k)
     int marker = -1, k;
     for (k = eps->nconv; k < nv; k++) {
-      double re = eps->eigr[k], im0 = 0.0;
-      if ((isshift || eps->conv == KS_EPS_CONV_NORM) && eps->cmp_ds.map) ks_st_backtransform_internal(eps->cmp_ds.map, 1, &re, &im0);   // epskrylov.c:253 (identity for sigma = 0)
-      double resnorm = ds.vectors_resnorm(k) * beta * 1.0;
-      if (eps->trueres) {                                      // epskrylov.c:256-264: X(:,k) = Q(:,k) for DSHEP (dshep.c:140-155)
-        if (!((isshift || eps->conv == KS_EPS_CONV_NORM) && eps->cmp_ds.map) && eps->cmp_ds.map) ks_st_backtransform_internal(eps->cmp_ds.map, 1, &re, &im0);
-        KS_CALL(true_residual(eps, nv, re, 0.0, ds.Q.data() + (size_t)k * ds.ld, nullptr, &resnorm));
-      }
-      eps->errest[k] = converged_estimate(eps, re, 0.0, resnorm);
+      double re = eps->eigr[k], im = eps->eigi[k];
+      if (early) map.backtransform(1, &re, &im);
+      double resnorm = 0.0; const double *Zr = nullptr, *Zi = nullptr;
+      const int newk = ds.ritz(k, &resnorm, &Zr, &Zi);
+      if (eps->trueres) {                                      // epskrylov.c:256-264
+        if (!early) map.backtransform(1, &re, &im);
+        KS_CALL(true_residual(eps, nv, re, im, Zr, Zi, &resnorm));
+      } else
+      resnorm *= beta * gamma;                                 // corrf: only in harmonic KS (epskrylov.c:265)
+      eps->errest[k] = converged_estimate(eps, re, im, resnorm);
       if (marker == -1 && eps->errest[k] >= eps->tol) marker = k;
+      if (newk == k + 1) { eps->errest[k + 1] = eps->errest[k]; k++; }
       if (marker != -1 && !eps->trackall) break;               // getall: estimates for every Ritz pair (epskrylov.c:240,280)
     }
-    if (marker != -1) k = marker;
-    // EPSStoppingBasic
+    k = (marker != -1) ? marker : nv;
     KS_CHECK(!eps->cb_err, eps->cb_err, "the user's convergence test returned %d", eps->cb_err);
-    KS_CALL(stopping_test(eps, k));
+    KS_CALL(stopping_test(eps, k));                            // EPSStoppingBasic
     const int nconv_mon = k;
 
     // update l
     if (eps->reason != KS_EPS_CONVERGED_ITERATING || breakdown || k == nv) l = 0;
-    else l = std::max(1, (int)((nv - k) * eps->keep));
-    if (!eps->lock && l > 0) { l += k; k = 0; }      // non-locking variant: reset no. of converged pairs (krylovschur.c:294)
+    else {
+      l = std::max(1, (int)((nv - k) * eps->keep));
+      l = ds.truncate_size(k, nv, l);                          // do not split a 2x2 block (krylovschur.c:300)
+    }
+    if (!eps->lock && l > 0) { l += k; k = 0; }                // non-locking variant: reset no. of converged pairs (krylovschur.c:294)
     if (eps->reason == KS_EPS_CONVERGED_ITERATING) {
       if (breakdown || k == nv) {
         if (k < nev) {
@@ -1167,7 +714,18 @@ extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119 -> EPSSolve
           KS_CALL(start_vector(eps, k, &brk));
           if (brk) eps->reason = KS_EPS_DIVERGED_BREAKDOWN;
         }
-      } else ds.truncate(k + l, false);
+      } else {
+        if (harmonic) {                                        // undo the translation (krylovschur.c:310-320): gamma u^ = u - U g~
+          ds.set_dimensions(nv, k, l);
+          eps->dsn.translate_harmonic(0.0, beta, true, g.data(), &gamma);
+          KS_CALL(ks_bv_set_active_columns(V, 0, nv));
+          KS_CALL(ks_bv_multcolumn(V, -1.0, 1.0, nv, g.data()));
+          KS_CALL(ks_bv_scalecolumn(V, nv, 1.0 / gamma));
+          KS_CALL(ks_bv_set_active_columns(V, eps->nconv, nv));
+          ds.set_dimensions(nv, k, nv);
+        }
+        ds.truncate(k + l, false);
+      }
     }
     // V(:,nconv:k+l) = V(:,nconv:nv) * Q(nconv:nv, nconv:k+l)      krylovschur.c:324-327
     KS_CALL(ks_bv_multinplace(V, ds.Q.data(), ds.ld, eps->nconv, k + l));
@@ -1177,20 +735,21 @@ extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119 -> EPSSolve
     eps->restarts++;
   }
   ds.truncate(eps->nconv, true);
+  return KS_SUCCESS;
+}
 
-  // ---- EPSSolve epilogue ----
-  KS_CALL(ks_bv_set_active_columns(V, 0, eps->nconv));
-  // EPSComputeValues (epssolve.c:27-41): map the eigenvalues back through the ST
-  const int nc = eps->nconv;
-  if (eps->cmp_ds.map) ks_st_backtransform_internal(eps->cmp_ds.map, nc, eps->eigr.data(), eps->eigi.data());
-  if (ghep && eps->purify) {
-    // EPSComputeVectors_Hermitian epsdefault.c:27-49: purification x <- OP x (EPS_Purify epsimpl.h:297-312), then B-normalise
-    for (int i = 0; i < nc; i++) {
+// EPSComputeVectors_Hermitian epsdefault.c:27-49 for a GHEP: the basis already holds the Ritz vectors
+static int epilogue_hermitian(ks_eps eps)
+{
+  ks_bv V = eps->V; ks_st st = eps->st;
+  if (eps->ghep && eps->purify) {
+    // purification x <- OP x (EPS_Purify epsimpl.h:297-312), then B-normalise
+    for (int i = 0; i < eps->nconv; i++) {
       KS_CALL(ksk_copy(eps->ctx, ks_bv_col(V, i), ks_bv_col(eps->W, 0), V->n));
       KS_CALL(ks_mat_mult_internal(eps->op, ks_bv_col(eps->W, 0), ks_bv_col(V, i)));
     }
     KS_CALL(ks_bv_normalize(V, nullptr));
-  } else if (ghep && cayley) {
+  } else if (eps->ghep && st && st->type == KS_ST_CAYLEY) {
     // without purification the Lanczos vectors are the eigenvectors; under the Cayley transformation they are orthonormal in
     // the A + nu B inner product and still have to be B-normalised (epsdefault.c:38-47)
     KS_CALL(ks_bv_set_matrix(V, eps->B));
@@ -1198,19 +757,67 @@ extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119 -> EPSSolve
     KS_CALL(ks_bv_set_matrix(V, st->bil));
     if (rc) return rc;
   }
-  // SlepcSortEigenvalues slepcsc.c:89-140 (all eigenvalues real here)
-  for (int i = 0; i <= ncv; i++) eps->perm[i] = i;
-  for (int i = nc - 1; i >= 0; i--) {
-    const double re = eps->eigr[eps->perm[i]];
-    int j = i + 1;
-    while (j < nc) {
-      if (compare_eig(eps->cmp_final, re, 0.0, eps->eigr[eps->perm[j]], 0.0) <= 0) break;
-      std::swap(eps->perm[j - 1], eps->perm[j]); j++;
+  return KS_SUCCESS;
+}
+
+// The eigenvectors of the general variant are formed on first use (compute_vectors); V(:,0:nconv) stays the Schur basis until then.
+// Conjugate pairs come with the positive imaginary part first (epssolve.c:160-175): the inversion of sinvert flips the sign
+static int epilogue_schur(ks_eps eps)
+{
+  eps->vectors_done = false;
+  for (int i = 0; i < eps->nconv - 1; i++) {
+    if (eps->eigi[i] != 0.0) {
+      if (eps->eigi[i] < 0.0) {                                 // "the next correction only works with eigenvectors" (epssolve.c:166-169)
+        eps->eigi[i] = -eps->eigi[i]; eps->eigi[i + 1] = -eps->eigi[i + 1];
+        KS_CALL(compute_vectors(eps));
+        KS_CALL(ks_bv_scalecolumn(eps->V, i + 1, -1.0));
+      }
+      i++;
     }
   }
-  long long passes1 = 0; ks_bv_gs_passes(V, &passes1, nullptr);
+  return KS_SUCCESS;
+}
+
+// SlepcSortEigenvalues slepcsc.c:89-140 into eps->perm, keeping conjugate pairs together
+static void sort_eigenvalues(ks_eps eps)
+{
+  std::vector<int> &perm = eps->perm;
+  const double *eigr = eps->eigr.data(), *eigi = eps->eigi.data();
+  const int nc = eps->nconv;
+  for (int i = 0; i <= eps->ncv; i++) perm[i] = i;
+  for (int i = nc - 1; i >= 0; i--) {
+    const double re = eigr[perm[i]]; double im = eigi[perm[i]];
+    int j = i + 1;
+    if (im != 0.0) { i--; im = eigi[perm[i]]; }                // complex eigenvalue: positive imaginary part first
+    while (j < nc) {
+      if (ksd::compare_eig(eps->cmp_final, re, im, eigr[perm[j]], eigi[perm[j]]) <= 0) break;
+      if (im == 0.0) {
+        if (eigi[perm[j]] == 0.0) { std::swap(perm[j - 1], perm[j]); j++; }
+        else { const int tmp = perm[j - 1]; perm[j - 1] = perm[j]; perm[j] = perm[j + 1]; perm[j + 1] = tmp; j += 2; }
+      } else {
+        if (eigi[perm[j]] == 0.0) { const int tmp = perm[j - 2]; perm[j - 2] = perm[j]; perm[j] = perm[j - 1]; perm[j - 1] = tmp; j++; }
+        else { std::swap(perm[j - 2], perm[j]); std::swap(perm[j - 1], perm[j + 1]); j += 2; }
+      }
+    }
+  }
+}
+
+extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119 -> EPSSolve_KrylovSchur_Default krylovschur.c:227
+{
+  long long passes0 = 0;
+  KS_CALL(set_up(eps, &passes0));
+  const bool hermitian = eps->problem_type_resolved_hermitian;
+  ksd::Ds &ds = hermitian ? static_cast<ksd::Ds &>(eps->dsh) : eps->dsn;
+  ds.allocate(eps->ncv + 1); ds.which = eps->cmp_ds; ds.state = ksd::DS_RAW;
+  KS_CALL(restart_loop(eps, ds));
+  // ---- EPSSolve epilogue ----
+  KS_CALL(ks_bv_set_active_columns(eps->V, 0, eps->nconv));
+  eps->cmp_ds.map.backtransform(eps->nconv, eps->eigr.data(), eps->eigi.data());   // EPSComputeValues (epssolve.c:27-41): map the eigenvalues back through the ST
+  KS_CALL(hermitian ? epilogue_hermitian(eps) : epilogue_schur(eps));
+  sort_eigenvalues(eps);
+  long long passes1 = 0; ks_bv_gs_passes(eps->V, &passes1, nullptr);
   eps->passes = passes1 - passes0;
-  KS_CALL(ks_bv_set_num_constraints(V, 0));                            // remove the deflation space (epssolve.c:201-205)
+  KS_CALL(ks_bv_set_num_constraints(eps->V, 0));                       // remove the deflation space (epssolve.c:201-205)
   eps->solved = true;
   return KS_SUCCESS;
 }

@@ -14,6 +14,7 @@
 // ks_gs.hip, the update x += K y is BVMultVec.
 #include "ksgpu_internal.h"
 #include "ks_csr.h"
+#include "ks_ds.h"
 #include <algorithm>
 
 namespace {
@@ -418,26 +419,7 @@ int ks_st_apply_internal(ks_st st, const double *x, double *y)     // STApply_Ge
   return linop_apply(st, 1.0, st->A, -st->sigma, nullptr, st->sigma != 0.0, nullptr, x, y, t1);
 }
 
-void ks_st_backtransform_internal(ks_st st, int n, double *eigr, double *eigi)
-{
-  if (!st) return;
-  for (int j = 0; j < n; j++) {
-    if (st->type == KS_ST_SHIFT) eigr[j] += st->sigma;                                  // shift.c:49-56
-    else if (st->type == KS_ST_CAYLEY) {                                                 // cayley.c:79-107
-      if (eigi[j] == 0.0) eigr[j] = (st->nu + eigr[j] * st->sigma) / (eigr[j] - 1.0);
-      else {
-        // lambda = (nu + theta sigma) / (theta - 1) for theta = a + b i. Stated deviation: cayley.c:93-99 forms the denominator
-        // |theta - 1|^2 = b^2 + a (a - 2) + 1 AFTER it has overwritten a and b with the numerator; here it is taken from theta.
-        const double a = eigr[j], b = eigi[j];
-        const double t = b * b + a * (a - 2.0) + 1.0;
-        eigr[j] = (st->sigma * (a * a + b * b - a) + st->nu * (a - 1.0)) / t;
-        eigi[j] = (-st->sigma * b - st->nu * b) / t;
-      }
-    }
-    else if (eigi[j] == 0.0) eigr[j] = 1.0 / eigr[j] + st->sigma;                        // sinvert.c:16-40
-    else { const double t = eigr[j] * eigr[j] + eigi[j] * eigi[j]; eigr[j] = eigr[j] / t + st->sigma; eigi[j] = -eigi[j] / t; }
-  }
-}
+void ks_st_backtransform_internal(ks_st st, int n, double *eigr, double *eigi) { if (st) ksd::StMap{st->type, st->sigma, st->nu}.backtransform(n, eigr, eigi); }
 
 extern "C" int ks_st_create(ks_ctx ctx, ks_st *out)
 {
