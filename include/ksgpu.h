@@ -233,6 +233,13 @@ int ks_mat_mult(ks_mat A, const double *x_dev, double *y_dev);
    Used by the two-sided balancing (EPSBuildBalance_Krylov epsdefault.c:402-411). */
 int ks_mat_mult_transpose(ks_mat A, const double *x_dev, double *y_dev);
 int ks_mat_shell_set_mult_transpose(ks_mat A, ks_shell_mult_fn mult_transpose);
+/* MatCreateTranspose: *At is a matrix whose ks_mat_mult is ks_mat_mult_transpose(A) and whose transposed product is ks_mat_mult(A); what the
+   two-sided solver expands its left basis with. Assembled A: the view is the transposed matrix A builds once for ks_mat_mult_transpose (same
+   conditions: KS_MAT_KEEP_CSR or KS_ERR_ORDER, one rank or KS_ERR_SUP), an assembled matrix in its own device layout - Krylov runs are enqueued
+   ahead through it and ks_mat_mult on it is bit for bit ks_mat_mult_transpose(A). Shell A: a shell over the transposed callback (KS_ERR_SUP
+   without one) with the same enqueue-only flag. The view does not own A and A does not wait for it: destroy the view (ks_mat_destroy) before
+   A; destroying A first and using or destroying the view afterwards is the caller's error. */
+int ks_mat_create_transpose(ks_mat A, ks_mat *At);
 int ks_mat_mult_host(ks_mat A, const double *x_host, double *y_host);  /* convenience for tests (single rank) */
 /* MatMatMult / MatProductNumeric(AB) with a dense column-major block: Y(:,j) = A X(:,j), j < ncols (X(:,j) at X_dev + j*ldx, Y(:,j) at
    Y_dev + j*ldy). Every column is bit for bit ks_mat_mult(A, X(:,j)): the dictionary, offset-dictionary, SELL-64 and CSR row-block layouts
@@ -432,7 +439,33 @@ int ks_eps_get_true_residual(ks_eps eps, int *trueres);
 int ks_eps_get_operators(ks_eps eps, ks_mat *A, ks_mat *B);
 int ks_eps_get_problem_type(ks_eps eps, int *type, int *generalized, int *hermitian, int *positive);
 int ks_eps_get_bv(ks_eps eps, ks_bv *V);
+/* arnoldi_steps and gs_passes of a two-sided solve count the steps and passes of both runs (Op on the right basis, Op^T on the left) */
 int ks_eps_get_stats(ks_eps eps, long long *arnoldi_steps, long long *gs_passes, int *restarts);
+/* EPSSetTwoSided (epsopts.c) with EPSGetLeftEigenvector (epssolve.c:567): two-sided Krylov-Schur (ks-twosided.c; Zwaan and Hochstenbach 2017) for
+   non-symmetric problems. Every restart runs two Arnoldi expansions through ks_bv_matarnoldi, one with Op and one with Op^T (ks_mat_create_transpose
+   of the solver's operator: A must have a transposed product, KS_MAT_KEEP_CSR or a shell with ks_mat_shell_set_mult_transpose; checked at set-up),
+   and solves the two projected problems together (DS NHEPTS). Convergence is the larger of the right and the left estimate, ks_eps_compute_error
+   the larger of the right residual and the left one, ||A^T y - conj(k) y||. Left eigenvectors satisfy y^H A = k y^H: for a conjugate pair (yr, yi)
+   of the first member and (yr, -yi) of the second, each normalised to unit 2-norm as a complex vector.
+   ks_eps_solve returns KS_ERR_SUP with the flag set when
+     - the problem type is KS_EPS_HEP or KS_EPS_GHEP (the reference's own check, epssetup.c:309)
+     - a B matrix is set
+     - the ST is not STSHIFT (sinvert and Cayley need solves with the transposed matrix)
+     - balancing is on
+     - the extraction is harmonic
+     - the true residual is asked for
+     - a deflation space is set
+     - the context has more than one rank
+   Without the flag ks_eps_get_left_eigenvector returns the right eigenvector for KS_EPS_HEP / KS_EPS_GHEP (the left one of a symmetric problem)
+   and KS_ERR_ARG_WRONGSTATE for a non-symmetric one. */
+int ks_eps_set_two_sided(ks_eps eps, int twosided);
+int ks_eps_get_two_sided(ks_eps eps, int *twosided);
+int ks_eps_set_left_initial_space(ks_eps eps, int n, const double *const *w_dev);   /* EPSSetLeftInitialSpace: device vectors; the first starts the left recurrence */
+int ks_eps_get_left_eigenvector(ks_eps eps, int i, double *yr_dev, double *yi_dev);  /* device vectors of n_local doubles; either may be NULL */
+int ks_eps_get_left_eigenvector_host(ks_eps eps, int i, double *yr_host, double *yi_host);
+/* instrumentation: restarts of the last two-sided solve whose two projected halves came out of the sort in different orders (eigenvalues that tie
+   under the criterion) and had the second half permuted to match the first (DSSort_NHEPTS dsnhepts.c:216-231) */
+int ks_eps_get_two_sided_stats(ks_eps eps, long long *ds_permutations);
 
 /* ---- ST: spectral transformation (slepcst.h) ---------------------------------------------------
    STSHIFT and STSINVERT in matrix mode "shell" (A - sigma*B is applied, never assembled); the linear solves are

@@ -296,6 +296,17 @@ class Mat:
         self._cb_t = SHELL_MULT_FN(tramp)
         _lib.check(self.ctx.L.ks_mat_shell_set_mult_transpose(self.h, C.cast(self._cb_t, C.c_void_p)))
 
+    def transpose_view(self):
+        """MatCreateTranspose: a matrix whose product is this one's transposed product (ks_mat_create_transpose). The view keeps this
+        matrix alive; it must not be used after this matrix was destroyed explicitly."""
+        if getattr(self, "_viewed", None) is not None:
+            return self._viewed             # the transpose of a view is the matrix itself
+        h = C.c_void_p()
+        _lib.check(self.ctx.L.ks_mat_create_transpose(self.h, C.byref(h)))
+        v = Mat(self.ctx, h)
+        v._viewed = self
+        return v
+
     def mult_transpose_dev(self, x_ptr, y_ptr):
         """MatMultTranspose on device pointers."""
         _lib.check(self.ctx.L.ks_mat_mult_transpose(self.h, C.c_void_p(x_ptr), C.c_void_p(y_ptr)))
@@ -345,6 +356,9 @@ class Mat:
         return V.column(0)
 
     def destroy(self):
+        viewed = getattr(self, "_viewed", None)
+        if viewed is not None and viewed.h is None:
+            self.h = None                  # a view whose matrix was destroyed first: the matrix took the transposed copy with it
         if self.h and self.ctx.h:      # a closed context already released the device; never touch it again
             self.ctx.L.ks_mat_destroy(self.h)
         self.h = None
@@ -1004,6 +1018,35 @@ class EPS:
         tmp.set_dense(Vmat)
         ptrs = (C.c_void_p * Vmat.shape[1])(*[tmp.column_ptr(j) for j in range(Vmat.shape[1])])
         _lib.check(self.ctx.L.ks_eps_set_initial_space(self.h, Vmat.shape[1], ptrs))
+
+    def SetTwoSided(self, flag=True):
+        """EPSSetTwoSided: also compute left eigenvectors (two-sided Krylov-Schur, non-symmetric standard problems)."""
+        _lib.check(self.ctx.L.ks_eps_set_two_sided(self.h, int(bool(flag))))
+
+    def GetTwoSided(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_get_two_sided(self.h, C.byref(v))); return bool(v.value)
+
+    def GetTwoSidedStats(self):
+        """{"ds_permutations": restarts of the last two-sided solve that had to reorder the left half of the projected problem}"""
+        v = C.c_longlong(); _lib.check(self.ctx.L.ks_eps_get_two_sided_stats(self.h, C.byref(v)))
+        return {"ds_permutations": v.value}
+
+    def SetLeftInitialSpace(self, Wmat):
+        """EPSSetLeftInitialSpace with the vectors as the columns of a host matrix; the first one starts the left recurrence."""
+        Wmat = np.asarray(Wmat, dtype=np.float64)
+        tmp = BV(self.ctx, Wmat.shape[0], max(Wmat.shape[1], 1))
+        tmp.set_dense(Wmat)
+        ptrs = (C.c_void_p * Wmat.shape[1])(*[tmp.column_ptr(j) for j in range(Wmat.shape[1])])
+        _lib.check(self.ctx.L.ks_eps_set_left_initial_space(self.h, Wmat.shape[1], ptrs))
+
+    def GetLeftEigenvector(self, i):
+        """EPSGetLeftEigenvector: (yr, yi) with y^H A = k y^H; the right eigenvector for a symmetric problem."""
+        yr = np.empty(self._A.n); yi = np.empty(self._A.n)
+        _lib.check(self.ctx.L.ks_eps_get_left_eigenvector_host(self.h, i, _p(yr), _p(yi)))
+        return yr, yi
+
+    def GetLeftEigenvectorDev(self, i, yr_ptr, yi_ptr=None):
+        _lib.check(self.ctx.L.ks_eps_get_left_eigenvector(self.h, i, C.c_void_p(yr_ptr) if yr_ptr else None, C.c_void_p(yi_ptr) if yi_ptr else None))
 
     def SetDeflationSpace(self, Cmat):
         """EPSSetDeflationSpace with the vectors given as the columns of a host matrix (local rows of this rank)."""

@@ -57,6 +57,7 @@ _SIG = {
     "ks_mat_set_halo": [vp, C.c_int, ip],
     "ks_mat_mult_transpose": [vp, vp, vp],
     "ks_mat_shell_set_mult_transpose": [vp, vp],
+    "ks_mat_create_transpose": [vp, C.POINTER(vp)],
     "ks_st_apply_transpose": [vp, vp, vp],
     "ks_mat_get_halo": [vp, ip],
     "ks_mat_create_laplacian3d": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)],
@@ -196,6 +197,12 @@ _SIG = {
     "ks_eps_get_true_residual": [vp, C.POINTER(C.c_int)],
     "ks_eps_get_operators": [vp, C.POINTER(vp), C.POINTER(vp)],
     "ks_eps_get_problem_type": [vp, ip, ip, ip, ip],
+    "ks_eps_set_two_sided": [vp, C.c_int],
+    "ks_eps_get_two_sided": [vp, ip],
+    "ks_eps_get_two_sided_stats": [vp, llp],
+    "ks_eps_set_left_initial_space": [vp, C.c_int, C.POINTER(C.c_void_p)],
+    "ks_eps_get_left_eigenvector": [vp, C.c_int, vp, vp],
+    "ks_eps_get_left_eigenvector_host": [vp, C.c_int, dp, dp],
     "ks_st_create": [vp, C.POINTER(vp)],
     "ks_st_destroy": [vp],
     "ks_st_set_type": [vp, C.c_int],

@@ -550,10 +550,9 @@ void tsqr_combine(int n, double *R1, int ld1, double *R2, int ld2)
     }
 }
 
-// P A = L U with row interchanges (unblocked right-looking dgetf2), then A^T x = b as U^T y = b, L^T z = y, x = P^T z
-int lu_solve_trans(int n, double *A, int ld, double *b)
+// P A = L U with row interchanges (unblocked right-looking dgetf2); piv[j] = the row exchanged with row j
+int lu_factor(int n, double *A, int ld, int *piv)
 {
-  std::vector<int> piv(n);
   int info = 0;
   for (int j = 0; j < n; j++) {
     int p = j; double mx = fabs(A[j + (size_t)j * ld]);
@@ -568,7 +567,26 @@ int lu_solve_trans(int n, double *A, int ld, double *b)
       if (u != 0.0) for (int i = j + 1; i < n; i++) A[i + (size_t)c * ld] -= A[i + (size_t)j * ld] * u;
     }
   }
-  if (info) return info;
+  return info;
+}
+
+// dgetrs on those factors. 'N': x = U^-1 L^-1 P b. 'T': U^T y = b, L^T z = y, x = P^T z
+void lu_solve(int n, const double *A, int ld, const int *piv, double *b, bool trans)
+{
+  if (!trans) {
+    for (int j = 0; j < n; j++) if (piv[j] != j) std::swap(b[j], b[piv[j]]);          // P b
+    for (int i = 0; i < n; i++) {                     // L z = P b: unit lower triangle, forward
+      double s = b[i];
+      for (int r = 0; r < i; r++) s -= A[i + (size_t)r * ld] * b[r];
+      b[i] = s;
+    }
+    for (int i = n - 1; i >= 0; i--) {                // U x = z, backward
+      double s = b[i];
+      for (int r = i + 1; r < n; r++) s -= A[i + (size_t)r * ld] * b[r];
+      b[i] = s / A[i + (size_t)i * ld];
+    }
+    return;
+  }
   for (int i = 0; i < n; i++) {                       // U^T y = b: forward substitution over the columns of U
     double s = b[i];
     for (int r = 0; r < i; r++) s -= A[r + (size_t)i * ld] * b[r];
@@ -580,6 +598,14 @@ int lu_solve_trans(int n, double *A, int ld, double *b)
     b[i] = s;
   }
   for (int j = n - 1; j >= 0; j--) if (piv[j] != j) std::swap(b[j], b[piv[j]]);   // x = P^T z
+}
+
+int lu_solve_trans(int n, double *A, int ld, double *b)
+{
+  std::vector<int> piv(n);
+  const int info = lu_factor(n, A, ld, piv.data());
+  if (info) return info;
+  lu_solve(n, A, ld, piv.data(), b, true);
   return 0;
 }
 
@@ -598,5 +624,7 @@ int ksd_sym_eig(int n, double *A, int ld, double *w) { return ksd::sym_eig(n, A,
 void ksd_tsqr_combine(int n, double *R1, int ld1, double *R2, int ld2) { ksd::tsqr_combine(n, R1, ld1, R2, ld2); }
 void ksd_qr_explicit(int M, int n, double *A, int ld, double *R, int ldr, double *Q, int ldq) { ksd::qr_explicit(M, n, A, ld, R, ldr, Q, ldq); }
 int ksd_lu_solve_trans(int n, double *A, int ld, double *b) { return ksd::lu_solve_trans(n, A, ld, b); }
+int ksd_lu_factor(int n, double *A, int ld, int *piv) { return ksd::lu_factor(n, A, ld, piv); }
+void ksd_lu_solve(int n, const double *A, int ld, const int *piv, double *b, int trans) { ksd::lu_solve(n, A, ld, piv, b, trans != 0); }
 }
 #endif

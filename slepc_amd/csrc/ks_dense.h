@@ -41,6 +41,11 @@ void tsqr_combine(int n, double *R1, int ld1, double *R2, int ld2);
 // Solve A^T x = b for a general n x n matrix by LU with partial pivoting (dgetrf + dgetrs 'T'): A is overwritten by its
 // factors, b by x. Returns 0, or the 1-based index of an exactly zero pivot.
 int lu_solve_trans(int n, double *A, int ld, double *b);
+// The same factorisation kept for several right-hand sides (dgetrf, then dgetrs 'N' or 'T' per solve): lu_factor overwrites A with L and U and
+// fills piv (n entries, piv[j] = the row exchanged with row j), returns 0 or the 1-based index of an exactly zero pivot; lu_solve overwrites b
+// with A^-1 b (trans false) or A^-T b (trans true).
+int lu_factor(int n, double *A, int ld, int *piv);
+void lu_solve(int n, const double *A, int ld, const int *piv, double *b, bool trans);
 
 // Householder QR of the M x n matrix A (column-major, ld; M >= n) with the orthogonal factor formed explicitly (dgeqr2 + dorg2r):
 // R (n x n, upper triangular, ldr) and Q (M x n, ldq) with A = Q R. The combine step of the tall-skinny QR: A is the stack of the

@@ -294,6 +294,66 @@ void DsNhep::truncate(int nn, bool trim)
   }
 }
 
+// ---- DS NHEPTS: two NHEP halves ----------------------------------------------------------------------
+int DsNhepTs::solve(double *wr, double *wi)
+{
+  dims_to_b();                                                                             // with the state the first half starts from
+  const int info = DsNhep::solve(wr, wi);
+  if (info) return info;
+  return hb.solve(wr2.data(), wi2.data());
+}
+
+int DsNhepTs::sort_with_permutation(int *perm)
+{
+  double *T = hb.A.data(), *Z = hb.Q.data();
+  auto t = [&](int i, int j) -> double & { return T[(size_t)i + (size_t)j * ld]; };
+  for (int i = l; i < n - 1; i++) {
+    const int pos = perm[i];
+    const int inc = (pos < n - 1 && t(pos + 1, pos) != 0.0) ? 2 : 1;
+    if (pos != i) {
+      if (pos < i) return 2;                                                               // blocks only move upward
+      if (!((t(pos, pos - 1) == 0.0 || perm[i + 1] == pos - 1) && (pos == n - 1 || t(pos + 1, pos) == 0.0 || perm[i + 1] == pos + 1))) return 2;   // "Invalid permutation due to a 2x2 block"
+                                                                                           // (stated deviation: dsutil.c:202 also reads T(n,n-1) for pos = n-1, which is the extra row)
+      if (trexc_up(n, T, ld, Z, pos, i)) return 1;                                         // trexc 'V', ifst = pos+1, ilst = i+1
+      for (int j = i + 1; j < n; j++) if (perm[j] >= i && perm[j] < pos) perm[j] += inc;
+      perm[i] = i;
+      if (inc == 2) perm[i + 1] = i + 1;
+    }
+    if (inc == 2) i++;
+  }
+  hb.n = n; hb.eig_from_T(wr2.data(), wi2.data(), l, n);
+  return 0;
+}
+
+int DsNhepTs::sort(double *wr, double *wi, const double *, const double *)
+{
+  int info = DsNhep::sort(wr, wi);
+  if (info) return info;
+  dims_to_b();
+  info = hb.sort(wr2.data(), wi2.data());
+  if (info) return info;
+  // check correct eigenvalue correspondence
+  const double sqeps = sqrt(std::numeric_limits<double>::epsilon());
+  std::vector<int> idx(n), idx2(n), p(n, -1);
+  int cont = 0;
+  for (int i = 0; i < n; i++) if (hypot(wr2[i] - wr[i], wi2[i] - wi[i]) > sqeps) { idx2[cont] = i; idx[cont++] = i; }
+  if (!cont) return 0;
+  int id = 0;
+  for (int i = 0; i < cont; i++) {
+    double tmin = std::numeric_limits<double>::max();
+    for (int j = 0; j < cont; j++) {
+      if (idx2[j] == -1) continue;
+      const double s = hypot(wr2[idx[j]] - wr[idx[i]], wi2[idx[j]] - wi[idx[i]]);
+      if (s < tmin) { id = j; tmin = s; }
+    }
+    p[idx[i]] = idx[id];
+    idx2[id] = -1;
+  }
+  for (int i = 0; i < n; i++) if (p[i] == -1) p[i] = i;
+  permuted++;
+  return sort_with_permutation(p.data());
+}
+
 } // namespace ksd
 
 #ifdef KSD_TEST_HOOKS
@@ -342,6 +402,23 @@ int ksd_nhep(int op, int ld, int *dims, double *A, double *Q, double *X, double 
   else if (op == 7) rc = ds.translate_harmonic(x0, x1, a0 != 0, g, &out[0]);
   else rc = ksd_step(ds, ds.X.data(), op, wr, wi, nullptr, nullptr, a0, a1, a2, out);
   ksd_store(ds, dims, A, Q); std::copy(ds.X.begin(), ds.X.end(), X);
+  return rc;
+}
+// the two-sided DS on caller-owned arrays (B, Z, Y, wr2, wi2: the second half). Steps 0-4 as above; 6 vectors(a0, back = a1, left = a2; out[0] = rnorm);
+// out[1] = 1 when a sort had to permute the second half
+int ksd_nhepts(int op, int ld, int *dims, double *A, double *Q, double *X, double *B, double *Z, double *Y, double *wr, double *wi, double *wr2, double *wi2,
+               const ksd_cmp *c, int a0, int a1, int a2, double *out)
+{
+  ksd::DsNhepTs ds; ksd_load(ds, ld, dims, c, A, Q); std::copy(X, X + ds.X.size(), ds.X.begin());
+  std::copy(B, B + ds.hb.A.size(), ds.hb.A.begin()); std::copy(Z, Z + ds.hb.Q.size(), ds.hb.Q.begin()); std::copy(Y, Y + ds.hb.X.size(), ds.hb.X.begin());
+  std::copy(wr2, wr2 + ld, ds.wr2.begin()); std::copy(wi2, wi2 + ld, ds.wi2.begin());
+  int rc;
+  if (op == 6) rc = ds.vectors_side(a0, a2 != 0, a1 != 0, &out[0]);
+  else rc = ksd_step(ds, ds.X.data(), op, wr, wi, nullptr, nullptr, a0, a1, a2, out);
+  if (op == 1) out[1] = (double)ds.permuted;
+  ksd_store(ds, dims, A, Q); std::copy(ds.X.begin(), ds.X.end(), X);
+  std::copy(ds.hb.A.begin(), ds.hb.A.end(), B); std::copy(ds.hb.Q.begin(), ds.hb.Q.end(), Z); std::copy(ds.hb.X.begin(), ds.hb.X.end(), Y);
+  std::copy(ds.wr2.begin(), ds.wr2.end(), wr2); std::copy(ds.wi2.begin(), ds.wi2.end(), wi2);
   return rc;
 }
 void ksd_backtransform(int st_type, double sigma, double nu, int n, double *eigr, double *eigi) { ksd::StMap{st_type, sigma, nu}.backtransform(n, eigr, eigi); }

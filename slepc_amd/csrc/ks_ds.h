@@ -107,4 +107,26 @@ struct DsNhep : Ds {
   }
 };
 
+// DS type NHEPTS (dsnhepts.c), the projected problem of the two-sided solver: two NHEP halves that are solved, sorted, updated and truncated
+// together. This object is the first half (A, Q, X: the Arnoldi relation of Op); `hb` is the second (its A, Q, X are DS_MAT_B, DS_MAT_Z,
+// DS_MAT_Y: the relation of Op^T) with its own eigenvalues wr2 / wi2. Dimensions and state live here and are copied to hb before every step.
+struct DsNhepTs : DsNhep {
+  DsNhep hb;
+  std::vector<double> wr2, wi2;
+  long long permuted = 0;                                                                   // sorts that had to reorder the second half to match the first
+  void allocate(int ld_) override { DsNhep::allocate(ld_); hb.allocate(ld_); wr2.assign(ld_, 0.0); wi2.assign(ld_, 0.0); }
+  void dims_to_b() { hb.n = n; hb.l = l; hb.k = k; hb.t = t; hb.state = state; hb.which = which; }
+  int solve(double *wr, double *wi) override;                                               // dsnhepts.c:275-286
+  // both halves with the same comparison, then the correspondence check and, where the orders differ, the greedy nearest-value permutation
+  // applied to the second half (dsnhepts.c:193-242). Returns 0, 1 (a swap was rejected) or 2 (the permutation would split a 2x2 block)
+  int sort(double *wr, double *wi, const double *rr = nullptr, const double *ri = nullptr) override;
+  int sort_with_permutation(int *perm);                                                     // DSSortWithPermutation_NHEP_Private dsutil.c:177-237 on the second half
+  void update_extra_row() override { dims_to_b(); DsNhep::update_extra_row(); hb.update_extra_row(); }   // dsnhepts.c:244-273
+  int truncate_size(int ll, int nn, int kk) override                                        // a 2x2 block of either half (dsnhepts.c:353-371)
+  { if (a(ll + kk, ll + kk - 1) != 0.0 || hb.a(ll + kk, ll + kk - 1) != 0.0) kk = (ll + kk < nn - 1) ? kk + 1 : kk - 1; return kk; }
+  void truncate(int nn, bool trim) override { dims_to_b(); DsNhep::truncate(nn, trim); hb.truncate(nn, trim); }   // dsnhepts.c:373-406
+  // DSVectors(DS_MAT_X or DS_MAT_Y, kk): left = the eigenvector of the second half back-transformed with Z, into hb.X (dsnhepts.c:54-119)
+  int vectors_side(int kk, bool left, bool back, double *rnorm) { if (!left) return vectors(kk, back, rnorm); dims_to_b(); return hb.vectors(kk, back, rnorm); }
+};
+
 } // namespace ksd

@@ -10,8 +10,11 @@
 //   EPSGetStartVector               src/eps/interface/epssolve.c:841-873
 //   EPSSolve epilogue + SlepcSortEigenvalues  epssolve.c:119-208, src/sys/slepcsc.c:89-140
 //   EPSComputeError / EPSComputeResidualNorm_Private  epssolve.c:666-718,742-815
+//   EPSSolve_KrylovSchur_TwoSided   krylovschur/ks-twosided.c:27-241 (with EPSGetLeftStartVector epssolve.c:879-900 and the left
+//                                   branches of EPSKrylovConvergence, EPSComputeVectors_Schur, EPSGetLeftEigenvector, EPSComputeError)
 #include "ksgpu_internal.h"
 #include "ks_ds.h"
+#include "ks_dense.h"
 #include <algorithm>
 #include <limits>
 
@@ -55,6 +58,12 @@ struct ks_eps_s {
   int extraction = KS_EPS_RITZ;                                  // EPSSetExtraction: Ritz or harmonic (krylovschur.c:120)
   int conv = KS_EPS_CONV_REL; double nrma = 0.0, nrmb = 0.0;   // EPSSetConvergenceTest; ||A||_inf, ||B||_inf for CONV_NORM / ERROR_BACKWARD
   ksd::DsHep dsh; ksd::DsNhep dsn;                                     // the projected problem of the last solve: the symmetric or the general variant
+  // EPSSetTwoSided: the left basis (a duplicate of V), Op^T as a matrix (a view: ks_mat_create_transpose), the left start vector, DS NHEPTS
+  bool twosided = false, twosided_solved = false;                      // the flag; the last solve ran the two-sided variant
+  ks_bv VL = nullptr; ks_mat opT = nullptr; bool opT_owned = false;   // a shell view is this solver's to destroy; the view of an assembled matrix belongs to that matrix
+  bool left_trivial = false;                                           // symmetric problem type: the left eigenvectors are the right ones (epssolve.c:585)
+  std::vector<double> w0; bool have_w0 = false;
+  ksd::DsNhepTs dst;
 };
 
 extern "C" int ks_eps_create(ks_ctx ctx, ks_eps *out)
@@ -67,7 +76,8 @@ extern "C" int ks_eps_create(ks_ctx ctx, ks_eps *out)
 extern "C" int ks_eps_destroy(ks_eps eps)
 {
   if (!eps) return KS_SUCCESS;
-  ks_bv_destroy(eps->V); ks_bv_destroy(eps->W); ks_bv_destroy(eps->defl);
+  ks_bv_destroy(eps->V); ks_bv_destroy(eps->W); ks_bv_destroy(eps->defl); ks_bv_destroy(eps->VL);
+  if (eps->opT_owned) ks_mat_destroy(eps->opT);
   ks_st_destroy(eps->st);
   if (eps->D) hipFree(eps->D); if (eps->wb) hipFree(eps->wb); if (eps->bal_op) ks_mat_destroy(eps->bal_op);
   delete eps;
@@ -79,7 +89,8 @@ extern "C" int ks_eps_set_operators(ks_eps eps, ks_mat A, ks_mat B)   // epssetu
   KS_CHECK(eps && A, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(!B || (B->n == A->n && B->n_global == A->n_global), KS_ERR_ARG_INCOMP, "Mismatching dimensions of A (%d) and B (%d)", A->n, B ? B->n : 0);
   if (eps->A && eps->A->n != A->n) {                                   // EPSReset (epsbasic.c): everything sized by the old operator goes
-    ks_bv_destroy(eps->V); ks_bv_destroy(eps->W); eps->V = eps->W = nullptr;
+    ks_bv_destroy(eps->V); ks_bv_destroy(eps->W); ks_bv_destroy(eps->VL); eps->V = eps->W = eps->VL = nullptr;
+    eps->have_w0 = false; eps->w0.clear();
     ks_bv_destroy(eps->defl); eps->defl = nullptr; eps->nds = 0;
     eps->have_v0 = false; eps->v0.clear();
     if (eps->D) { hipFree(eps->D); eps->D = nullptr; } if (eps->wb) { hipFree(eps->wb); eps->wb = nullptr; } eps->D_n = 0;
@@ -263,6 +274,32 @@ extern "C" int ks_eps_set_initial_space(ks_eps eps, int n, const double *const *
   eps->have_v0 = true; eps->solved = false;
   return KS_SUCCESS;
 }
+// EPSSetTwoSided epsopts.c: also compute left eigenvectors (two-sided Krylov-Schur, non-symmetric problems)
+extern "C" int ks_eps_set_two_sided(ks_eps eps, int twosided)
+{
+  KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
+  eps->twosided = twosided != 0; eps->solved = false; return KS_SUCCESS;
+}
+extern "C" int ks_eps_get_two_sided(ks_eps eps, int *twosided) { KS_CHECK(eps && twosided, KS_ERR_ARG_NULL, "NULL argument"); *twosided = eps->twosided ? 1 : 0; return KS_SUCCESS; }
+extern "C" int ks_eps_get_two_sided_stats(ks_eps eps, long long *ds_permutations)
+{
+  KS_CHECK(eps && ds_permutations, KS_ERR_ARG_NULL, "NULL argument");
+  *ds_permutations = eps->twosided_solved ? eps->dst.permuted : 0; return KS_SUCCESS;
+}
+// EPSSetLeftInitialSpace epssetup.c with device vectors: as for the right one, the first vector starts the left recurrence
+extern "C" int ks_eps_set_left_initial_space(ks_eps eps, int n, const double *const *w_dev)
+{
+  KS_CHECK(eps && eps->A, KS_ERR_ORDER, "set the operators first");
+  KS_CHECK(n >= 0, KS_ERR_ARG_OUTOFRANGE, "Argument n cannot be negative");
+  if (!n) { eps->have_w0 = false; return KS_SUCCESS; }
+  KS_CHECK(w_dev && w_dev[0], KS_ERR_ARG_NULL, "NULL argument");
+  eps->w0.resize(std::max(eps->A->n, 1));
+  KS_HIP(hipSetDevice(eps->ctx->device));
+  KS_HIP(hipMemcpyAsync(eps->w0.data(), w_dev[0], sizeof(double) * eps->A->n, hipMemcpyDeviceToHost, eps->ctx->stream));
+  KS_HIP(ks_sync(eps->ctx));
+  eps->have_w0 = true; eps->solved = false;
+  return KS_SUCCESS;
+}
 extern "C" int ks_eps_set_ds_parallel(ks_eps eps, int pmode)
 {
   KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
@@ -434,14 +471,17 @@ static int build_balance(ks_eps eps)
 // EPSComputeResidualNorm_Private epssolve.c:666-718 (STGetMatrix 0/1 = the user's A and B): || A x - k B x ||_2 for a
 // real eigenvalue, hypot of the two real-arithmetic residuals for a pair (xi_sign * xi is the imaginary part).
 // Work vectors: W columns 0..2.
-static int residual_norm(ks_eps eps, double kr, double ki, const double *xr, const double *xi, double xi_sign, double *out)
+// trans (the left residual of the two-sided variant, one matrix): the transposed product and the conjugate eigenvalue, ||A^T y - conj(k) y|| (:676,692,705,711)
+static int residual_norm(ks_eps eps, double kr, double ki, const double *xr, const double *xi, double xi_sign, double *out, bool trans = false)
 {
   ks_bv W = eps->W; ks_ctx ctx = eps->ctx; ks_mat A = eps->A, B = eps->B;
   const long long n = W->n;
   double *u = ks_bv_col(W, 0);
   double nrm = 0.0;
+  auto mult = [&](const double *x, double *y) { return trans ? ks_mat_mult_transpose_internal(A, x, y) : ks_mat_mult_internal(A, x, y); };
+  if (trans) ki = -ki;
   if (ki == 0.0 || fabs(ki) < fabs(kr * std::numeric_limits<double>::epsilon())) {
-    KS_CALL(ks_mat_mult_internal(A, xr, u));                                        // u = A*x
+    KS_CALL(mult(xr, u));                                                            // u = A*x
     if (fabs(kr) > std::numeric_limits<double>::epsilon()) {
       const double *w = xr;
       if (B) { KS_CALL(ks_mat_mult_internal(B, xr, ks_bv_col(W, 2))); w = ks_bv_col(W, 2); }   // w = B*x
@@ -453,11 +493,11 @@ static int residual_norm(ks_eps eps, double kr, double ki, const double *xr, con
     const double *v = xr, *w = xi;                                                   // v = B*xr, w = B*xi (before the sign)
     if (B) { KS_CALL(ks_mat_mult_internal(B, xr, ks_bv_col(W, 1))); KS_CALL(ks_mat_mult_internal(B, xi, ks_bv_col(W, 2))); v = ks_bv_col(W, 1); w = ks_bv_col(W, 2); }
     double nr = 0.0, ni = 0.0;
-    KS_CALL(ks_mat_mult_internal(A, xr, u));                                        // u = A*xr - kr*B*xr + ki*B*xi
+    KS_CALL(mult(xr, u));                                                            // u = A*xr - kr*B*xr + ki*B*xi
     KS_CALL(ksk_lincomb(ctx, n, nullptr, 1.0, u, -kr, v, u));
     KS_CALL(ksk_lincomb(ctx, n, nullptr, 1.0, u, ki * sg, w, u));
     KS_CALL(ks_bv_normcolumn(W, 0, KS_NORM_2, &nr));
-    KS_CALL(ks_mat_mult_internal(A, xi, u));                                        // u = A*xi - kr*B*xi - ki*B*xr
+    KS_CALL(mult(xi, u));                                                            // u = A*xi - kr*B*xi - ki*B*xr
     KS_CALL(ksk_lincomb(ctx, n, nullptr, sg, u, -kr * sg, w, u));
     KS_CALL(ksk_lincomb(ctx, n, nullptr, 1.0, u, -ki, v, u));
     KS_CALL(ks_bv_normcolumn(W, 0, KS_NORM_2, &ni));
@@ -526,13 +566,29 @@ static int start_vector(ks_eps eps, int i, bool *breakdown)
   return KS_SUCCESS;
 }
 
+// EPSGetLeftStartVector epssolve.c:879-900: the first left initial vector, else a random one (its own stream of numbers), orthonormalised in the left basis
+static int left_start_vector(ks_eps eps, int i, bool *breakdown)
+{
+  if (i == 0 && eps->have_w0) KS_CALL(ks_bv_set_column_host(eps->VL, 0, eps->w0.data()));
+  else KS_CALL(ks_bv_set_random_column(eps->VL, i, eps->seed ^ 0x9E3779B97F4A7C15ULL));
+  double norm = 0.0; int lindep = 0;
+  KS_CALL(ks_bv_orthogonalizecolumn(eps->VL, i, nullptr, &norm, &lindep));
+  if (breakdown) *breakdown = lindep != 0;
+  else if (lindep || norm == 0.0) {
+    if (i == 0) KS_FAIL(KS_ERR_PLIB, "Left initial vector is zero");
+    KS_FAIL(KS_ERR_CONV_FAILED, "Unable to generate more left start vectors");
+  }
+  KS_CALL(ks_bv_scalecolumn(eps->VL, i, 1.0 / norm));
+  return KS_SUCCESS;
+}
+
 // EPSComputeVectors_Schur epsdefault.c:105-169, run on first use (EPSComputeVectors epssolve.c:... state EPS_STATE_EIGENVECTORS):
 // X = V*Z with Z the normalised eigenvectors of the trimmed quasi-triangular T. Until then V(:,0:nconv) is the orthonormal
 // Schur basis that EPSGetInvariantSubspace hands out.
 static int compute_vectors(ks_eps eps)
 {
   if (eps->vectors_done) return KS_SUCCESS;
-  ks_bv V = eps->V; ksd::DsNhep &ds = eps->dsn;
+  ks_bv V = eps->V; ksd::DsNhep &ds = eps->twosided_solved ? static_cast<ksd::DsNhep &>(eps->dst) : eps->dsn;
   const int nc = eps->nconv;
   KS_CALL(ks_bv_set_active_columns(V, 0, nc));
   if (nc) {
@@ -541,6 +597,14 @@ static int compute_vectors(ks_eps eps)
     if (eps->balanced) {                                    // epsdefault.c:130-139: x <- D \ x, then normalise (pairs together)
       for (int i = 0; i < nc; i++) KS_CALL(pointwise(eps, ks_bv_col(V, i), eps->D, ks_bv_col(V, i), false));
       KS_CALL(ks_bv_normalize(V, eps->eigi.data()));
+    }
+    if (eps->twosided_solved) {                             // left eigenvectors (epsdefault.c:141-167): W <- W Y, normalise, then y = wr - i wi for a pair
+      ks_bv W = eps->VL;
+      KS_CALL(ks_bv_set_active_columns(W, 0, nc));
+      for (int k = 0; k < nc; k++) k = eps->dst.vectors_side(k, true, false, nullptr);
+      KS_CALL(ks_bv_multinplace(W, eps->dst.hb.X.data(), ds.ld, 0, nc));
+      KS_CALL(ks_bv_normalize(W, eps->eigi.data()));
+      for (int i = 0; i < nc - 1; i++) if (eps->eigi[i] != 0.0) { if (eps->eigi[i] > 0.0) KS_CALL(ks_bv_scalecolumn(W, i + 1, -1.0)); i++; }
     }
   }
   eps->vectors_done = true;
@@ -561,6 +625,17 @@ static int set_up(ks_eps eps, long long *passes0)
   if (!eps->B && ptype == KS_EPS_GHEP) ptype = KS_EPS_HEP;
   KS_CHECK(!eps->B || ptype == KS_EPS_GNHEP || ptype == KS_EPS_GHEP, KS_ERR_ARG_INCOMP, "Inconsistent EPS state: the problem type does not match the number of matrices");
   const bool ghep = ptype == KS_EPS_GHEP;
+  eps->twosided_solved = false; eps->left_trivial = ptype == KS_EPS_HEP || ghep;
+  if (eps->twosided) {                                                 // what the two-sided variant is built for: each case is listed in ksgpu.h
+    KS_CHECK(ptype != KS_EPS_HEP && !ghep, KS_ERR_SUP, "Two-sided methods are not intended for Hermitian problems");   // epssetup.c:309
+    KS_CHECK(!eps->B, KS_ERR_SUP, "two-sided Krylov-Schur is built for standard problems (no B matrix)");
+    KS_CHECK(!eps->st || eps->st->type == KS_ST_SHIFT, KS_ERR_SUP, "two-sided Krylov-Schur is built for STSHIFT (the others need solves with the transposed matrix)");
+    KS_CHECK(eps->balance == KS_EPS_BALANCE_NONE, KS_ERR_SUP, "two-sided Krylov-Schur with balancing is not built");
+    KS_CHECK(eps->extraction == KS_EPS_RITZ, KS_ERR_SUP, "two-sided Krylov-Schur with harmonic extraction is not built");
+    KS_CHECK(!eps->trueres, KS_ERR_SUP, "two-sided Krylov-Schur with the true residual is not built");
+    KS_CHECK(!eps->nds, KS_ERR_SUP, "two-sided Krylov-Schur with a deflation space is not built");
+    KS_CHECK(eps->ctx->comm.size == 1, KS_ERR_SUP, "two-sided Krylov-Schur runs on one rank (the transpose of a row-sharded matrix is a redistribution)");
+  }
   if (eps->conv == KS_EPS_CONV_NORM) KS_CALL(matrix_norms(eps));
   ks_st st = eps->st;
   const bool cayley = st && st->type == KS_ST_CAYLEY;
@@ -622,6 +697,19 @@ static int set_up(ks_eps eps, long long *passes0)
     eps->bal_op->n = A->n; eps->bal_op->row_start = A->row_start; eps->bal_op->n_global = A->n_global;
     eps->bal_op->shell_nosync = !eps->op_inner->shell_mult;         // D A D^-1 on an assembled matrix is three kernel launches: keep the enqueued-ahead run
     eps->op = eps->bal_op; eps->balanced = true;
+  }
+  if (eps->twosided) {
+    // the left basis (EPSAllocateSolution: BVDuplicate, epssetup.c:733) and Op^T as a matrix (MatCreateHermitianTranspose of STGetOperator, ks-twosided.c:141-142)
+    if (eps->VL) { int vm = 0; ks_bv_get_sizes(eps->VL, nullptr, nullptr, &vm, nullptr); if (vm != ncv + 1) { ks_bv_destroy(eps->VL); eps->VL = nullptr; } }
+    if (!eps->VL) { KS_CALL(ks_bv_duplicate(V, &eps->VL)); eps->VL->row_start = A->row_start; }
+    KS_CALL(ks_bv_set_active_columns(eps->VL, 0, ncv + 1));
+    if (eps->opT_owned) ks_mat_destroy(eps->opT);
+    eps->opT = nullptr; eps->opT_owned = false;
+    KS_CALL(ks_mat_create_transpose(eps->op, &eps->opT));
+    eps->opT_owned = eps->op->shell_mult != nullptr;
+    // one transposed product now, so that an operator without one fails here and not inside the first restart
+    KS_HIP(hipMemsetAsync(ks_bv_col(eps->W, 3), 0, sizeof(double) * std::max(A->n, 1), eps->ctx->stream));
+    KS_CALL(ks_mat_mult_internal(eps->opT, ks_bv_col(eps->W, 3), ks_bv_col(eps->W, 4)));
   }
   KS_CHECK(eps->extraction == KS_EPS_RITZ || !ghep, KS_ERR_SUP, "harmonic extraction with a B-inner product is not built");
   KS_CHECK(!eps->arb_fn || ((ptype == KS_EPS_HEP || ghep) && eps->extraction == KS_EPS_RITZ), KS_ERR_SUP, "arbitrary selection is built for the symmetric (Lanczos) variant only");
@@ -738,6 +826,167 @@ static int restart_loop(ks_eps eps, ksd::Ds &ds)
   return KS_SUCCESS;
 }
 
+
+// ---- two-sided variant (ks-twosided.c) ----
+// BVMatProject(V,NULL,W,M) is L-shaped (BVMatProject_Dot bvglobal.c:1013-1049): with the active columns [k0, nv) of both bases it computes
+// W0^T V1 and W1^T [V0 V1], everything but the leading k0 x k0 block, which the caller carries over from the previous restart
+static int matproject_lshape(ks_bv V, ks_bv W, int k0, int nv, double *M, int ldm)
+{
+  KS_CALL(ksb_dot_range(V, k0, nv, W, 0, k0, M, ldm));
+  return ksb_dot_range(V, 0, nv, W, k0, nv, M, ldm);
+}
+// EPSTwoSidedRQUpdate1 ks-twosided.c:27-73: the residual vectors are made orthogonal to the other side's basis, u <- u - V (W^T V)^-1 W^T u and
+// its mirror image, and the last columns of the two Rayleigh quotients take the coefficients. One LU of M = W^T V, used as it is and transposed.
+static int rq_update1(ks_eps eps, const std::vector<double> &M, int nv, double beta, double betat)
+{
+  ks_bv V = eps->V, W = eps->VL; ksd::DsNhepTs &ds = eps->dst;
+  int l = 0, nnv = 0;
+  KS_CALL(ks_bv_get_active_columns(V, &l, &nnv));
+  KS_CALL(ks_bv_set_active_columns(V, 0, nv)); KS_CALL(ks_bv_set_active_columns(W, 0, nv));
+  std::vector<double> w(nv), LU((size_t)nv * nv); std::vector<int> piv(nv);
+  for (int j = 0; j < nv; j++) std::copy(M.begin() + (size_t)j * ds.ld, M.begin() + (size_t)j * ds.ld + nv, LU.begin() + (size_t)j * nv);
+  KS_CALL(ks_bv_dotvec(W, ks_bv_col(V, nv), w.data()));
+  const int info = ksd::lu_factor(nv, LU.data(), nv, piv.data());
+  KS_CHECK(info == 0, KS_ERR_LIB, "two-sided Krylov-Schur: W^T V is singular (zero pivot %d of %d): serious breakdown of the two-sided recurrence", info, nv);
+  ksd::lu_solve(nv, LU.data(), nv, piv.data(), w.data(), false);
+  KS_CALL(ks_bv_multcolumn(V, -1.0, 1.0, nv, w.data()));
+  for (int i = 0; i < nv; i++) ds.a(i, nv - 1) += beta * w[i];
+  KS_CALL(ks_bv_dotvec(V, ks_bv_col(W, nv), w.data()));
+  ksd::lu_solve(nv, LU.data(), nv, piv.data(), w.data(), true);
+  KS_CALL(ks_bv_multcolumn(W, -1.0, 1.0, nv, w.data()));
+  for (int i = 0; i < nv; i++) ds.hb.a(i, nv - 1) += betat * w[i];
+  KS_CALL(ks_bv_set_active_columns(V, l, nnv)); KS_CALL(ks_bv_set_active_columns(W, l, nnv));
+  return KS_SUCCESS;
+}
+// EPSTwoSidedRQUpdate2 ks-twosided.c:75-124: column kk of each basis (the residual vector, or a new start vector) is orthonormalised against its own
+// basis again and the kept block of the Rayleigh quotient follows, H <- H + (V^T u) b^T from the old nconv on; then M <- Z^T M Q with the full nv x nv Q and Z
+static int rq_update2(ks_eps eps, std::vector<double> &M, int kk)
+{
+  ks_bv V = eps->V, W = eps->VL; ksd::DsNhepTs &ds = eps->dst;
+  const int ld = ds.ld;
+  int l = 0, nv = 0;
+  KS_CALL(ks_bv_get_active_columns(V, &l, &nv));
+  KS_CALL(ks_bv_set_active_columns(V, 0, nv)); KS_CALL(ks_bv_set_active_columns(W, 0, nv));
+  std::vector<double> c(ld + 1, 0.0);
+  for (int side = 0; side < 2; side++) {
+    ksd::DsNhep &h = side ? eps->dst.hb : static_cast<ksd::DsNhep &>(eps->dst);
+    double norm = 0.0;
+    KS_CALL(ks_bv_orthogonalizecolumn(side ? W : V, kk, c.data(), &norm, nullptr));
+    KS_CALL(ks_bv_scalecolumn(side ? W : V, kk, 1.0 / norm));
+    for (int j = l; j < kk; j++) {
+      for (int i = 0; i < kk; i++) h.a(i, j) += c[i] * h.a(kk, j);
+      h.a(kk, j) *= norm;
+    }
+  }
+  std::vector<double> T((size_t)nv * nv);
+  for (int j = 0; j < nv; j++) for (int i = 0; i < nv; i++) { double s = 0.0; for (int p = 0; p < nv; p++) s += M[(size_t)i + (size_t)p * ld] * ds.q(p, j); T[(size_t)i + (size_t)j * nv] = s; }
+  for (int j = 0; j < nv; j++) for (int i = 0; i < nv; i++) { double s = 0.0; for (int p = 0; p < nv; p++) s += ds.hb.q(p, i) * T[(size_t)p + (size_t)j * nv]; M[(size_t)i + (size_t)j * ld] = s; }
+  KS_CALL(ks_bv_set_active_columns(V, l, nv)); KS_CALL(ks_bv_set_active_columns(W, l, nv));
+  return KS_SUCCESS;
+}
+
+// EPSSolve_KrylovSchur_TwoSided ks-twosided.c:126-241: per restart one Arnoldi expansion with Op and one with Op^T, both through ks_bv_matarnoldi
+static int restart_loop_twosided(ks_eps eps)
+{
+  ks_bv V = eps->V, W = eps->VL; ksd::DsNhepTs &ds = eps->dst;
+  const int nev = eps->nev, ncv = eps->ncv, mpd = eps->mpd, ld = ds.ld;
+  const ksd::StMap &map = eps->cmp_ds.map;
+  const bool early = map && (map.type == KS_ST_SHIFT || eps->conv == KS_EPS_CONV_NORM);
+  std::vector<double> M((size_t)ld * ld, 0.0);                     // W^T V (the reference's ncv x ncv M)
+  KS_CALL(start_vector(eps, 0, nullptr));
+  KS_CALL(left_start_vector(eps, 0, nullptr));
+  int l = 0;
+  while (eps->reason == KS_EPS_CONVERGED_ITERATING) {
+    eps->its++;
+    const int k0 = eps->nconv + l;
+    int nv = std::min(eps->nconv + mpd, ncv);
+    if (eps->max_steps && eps->steps + 2 * (nv - k0) > eps->max_steps) nv = k0 + std::max(1, (int)((eps->max_steps - eps->steps) / 2));   // (a step of each run per column)
+    ds.set_dimensions(nv, eps->nconv, k0);
+    double beta = 0.0, betat = 0.0; int breakdown = 0, breakdownt = 0;
+    KS_CALL(ks_bv_matarnoldi(V, eps->op, ds.A.data(), ld, k0, &nv, &beta, &breakdown));
+    int nvt = nv;
+    KS_CALL(ks_bv_matarnoldi(W, eps->opT, ds.hb.A.data(), ld, k0, &nvt, &betat, &breakdownt));
+    eps->steps += (nv - k0) + (nvt - k0);
+    nv = std::min(nv, nvt);                                    // make sure both factorizations have the same length
+    ds.set_dimensions(nv, eps->nconv, k0);
+    ds.state = l ? ksd::DS_RAW : ksd::DS_INTERMEDIATE;
+    breakdown = breakdown || breakdownt;
+
+    // update M, modify the Rayleigh quotients
+    KS_CALL(ks_bv_set_active_columns(V, k0, nv)); KS_CALL(ks_bv_set_active_columns(W, k0, nv));
+    KS_CALL(matproject_lshape(V, W, k0, nv, M.data(), ld));
+    KS_CALL(rq_update1(eps, M, nv, beta, betat));
+
+    // solve projected problem
+    int info = ds.solve(eps->eigr.data(), eps->eigi.data());
+    KS_CHECK(info == 0, KS_ERR_LIB, "Hessenberg QR iteration failed to converge (info=%d)", info);
+    info = ds.sort(eps->eigr.data(), eps->eigi.data());
+    KS_CHECK(info != 2, KS_ERR_LIB, "two-sided projected problem: invalid permutation due to a 2x2 block (the two halves do not hold the same eigenvalues)");
+    KS_CHECK(info == 0, KS_ERR_LIB, "reordering of the Schur form failed: blocks too close to swap");
+    KS_CALL(ds_synchronize(eps, &ds.A, &ds.Q, &beta, &nv, &breakdown));
+    KS_CALL(ds_synchronize(eps, &ds.hb.A, &ds.hb.Q, &betat, &nv, &breakdown));
+    ds.update_extra_row();
+
+    // check convergence: RQUpdate1 changed the two residual vectors, so their norms belong in the estimates (epskrylov.c:269-276)
+    double norm = 0.0, norm2 = 0.0;
+    KS_CALL(ks_bv_normcolumn(V, nv, KS_NORM_2, &norm));
+    KS_CALL(ks_bv_normcolumn(W, nv, KS_NORM_2, &norm2));
+    int marker = -1, k;
+    for (k = eps->nconv; k < nv; k++) {
+      double re = eps->eigr[k], im = eps->eigi[k];
+      if (early) map.backtransform(1, &re, &im);
+      double resnorm = 0.0, lresnorm = 0.0; const double *Zr = nullptr, *Zi = nullptr;
+      const int newk = ds.ritz(k, &resnorm, &Zr, &Zi);
+      eps->errest[k] = converged_estimate(eps, re, im, resnorm * beta * norm);
+      if (marker == -1 && eps->errest[k] >= eps->tol) marker = k;
+      ds.vectors_side(k, true, true, &lresnorm);
+      const double lerrest = converged_estimate(eps, re, im, lresnorm * betat * norm2);
+      eps->errest[k] = std::max(eps->errest[k], lerrest);
+      if (marker == -1 && lerrest >= eps->tol) marker = k;
+      if (newk == k + 1) { eps->errest[k + 1] = eps->errest[k]; k++; }
+      if (marker != -1 && !eps->trackall) break;
+    }
+    k = (marker != -1) ? marker : nv;
+    KS_CHECK(!eps->cb_err, eps->cb_err, "the user's convergence test returned %d", eps->cb_err);
+    KS_CALL(stopping_test(eps, k));
+    const int nconv_mon = k;
+
+    // update l
+    if (eps->reason != KS_EPS_CONVERGED_ITERATING || breakdown || k == nv) l = 0;
+    else {
+      l = std::max(1, (int)((nv - k) * eps->keep));
+      l = ds.truncate_size(k, nv, l);
+    }
+    if (!eps->lock && l > 0) { l += k; k = 0; }                // non-locking variant: reset no. of converged pairs
+
+    // update the corresponding vectors V(:,idx) = V*Q(:,idx), W(:,idx) = W*Z(:,idx)
+    KS_CALL(ks_bv_set_active_columns(V, eps->nconv, nv)); KS_CALL(ks_bv_set_active_columns(W, eps->nconv, nv));
+    KS_CALL(ks_bv_multinplace(V, ds.Q.data(), ld, eps->nconv, k + l));
+    KS_CALL(ks_bv_multinplace(W, ds.hb.Q.data(), ld, eps->nconv, k + l));
+    if (eps->reason == KS_EPS_CONVERGED_ITERATING && !breakdown) { KS_CALL(ks_bv_copycolumn(V, nv, k + l)); KS_CALL(ks_bv_copycolumn(W, nv, k + l)); }
+
+    if (eps->reason == KS_EPS_CONVERGED_ITERATING) {
+      if (breakdown || k == nv) {                              // start a new Arnoldi factorization
+        if (k < nev) {
+          bool brk = false, brkl = false;
+          KS_CALL(start_vector(eps, k, &brk));
+          KS_CALL(left_start_vector(eps, k, &brkl));
+          if (brk || brkl) eps->reason = KS_EPS_DIVERGED_BREAKDOWN;
+        }
+      } else {
+        ds.set_dimensions(ds.n, k, ds.k);
+        ds.truncate(k + l, false);
+      }
+      KS_CALL(rq_update2(eps, M, k + l));
+    }
+    eps->nconv = k;
+    KS_CALL(monitor(eps, nconv_mon, nv));
+    eps->restarts++;
+  }
+  ds.truncate(eps->nconv, true);
+  return KS_SUCCESS;
+}
+
 // EPSComputeVectors_Hermitian epsdefault.c:27-49 for a GHEP: the basis already holds the Ritz vectors
 static int epilogue_hermitian(ks_eps eps)
 {
@@ -807,16 +1056,21 @@ extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119 -> EPSSolve
   long long passes0 = 0;
   KS_CALL(set_up(eps, &passes0));
   const bool hermitian = eps->problem_type_resolved_hermitian;
-  ksd::Ds &ds = hermitian ? static_cast<ksd::Ds &>(eps->dsh) : eps->dsn;
+  ksd::Ds &ds = hermitian ? static_cast<ksd::Ds &>(eps->dsh) : eps->twosided ? static_cast<ksd::Ds &>(eps->dst) : eps->dsn;
   ds.allocate(eps->ncv + 1); ds.which = eps->cmp_ds; ds.state = ksd::DS_RAW;
+  long long passesl0 = 0;
+  if (eps->twosided) { eps->dst.permuted = 0; ks_bv_gs_passes(eps->VL, &passesl0, nullptr); KS_CALL(restart_loop_twosided(eps)); eps->twosided_solved = true; }
+  else
   KS_CALL(restart_loop(eps, ds));
   // ---- EPSSolve epilogue ----
   KS_CALL(ks_bv_set_active_columns(eps->V, 0, eps->nconv));
+  if (eps->twosided) KS_CALL(ks_bv_set_active_columns(eps->VL, 0, eps->nconv));
   eps->cmp_ds.map.backtransform(eps->nconv, eps->eigr.data(), eps->eigi.data());   // EPSComputeValues (epssolve.c:27-41): map the eigenvalues back through the ST
   KS_CALL(hermitian ? epilogue_hermitian(eps) : epilogue_schur(eps));
   sort_eigenvalues(eps);
   long long passes1 = 0; ks_bv_gs_passes(eps->V, &passes1, nullptr);
   eps->passes = passes1 - passes0;
+  if (eps->twosided) { long long pl = 0; ks_bv_gs_passes(eps->VL, &pl, nullptr); eps->passes += pl - passesl0; }
   KS_CALL(ks_bv_set_num_constraints(eps->V, 0));                       // remove the deflation space (epssolve.c:201-205)
   eps->solved = true;
   return KS_SUCCESS;
@@ -891,6 +1145,50 @@ extern "C" int ks_eps_get_eigenpair(ks_eps eps, int i, double *eigr, double *eig
   KS_HIP(ks_sync(ctx));
   return KS_SUCCESS;
 }
+// EPSGetLeftEigenvector epssolve.c:567-613: column i of the left basis through the same pair rules; for a symmetric problem the right eigenvector
+// (the "trivial" branch); a non-symmetric solve without EPSSetTwoSided has none
+static int left_basis(ks_eps eps, int i, ks_bv *bv)
+{
+  KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
+  KS_CHECK(eps->solved, KS_ERR_ARG_WRONGSTATE, "Must call EPSSolve() first");
+  KS_CHECK(i >= 0 && i < eps->nconv, KS_ERR_ARG_OUTOFRANGE, "The index can be nconv-1 at most, see EPSGetConverged()");
+  const bool trivial = eps->left_trivial;
+  KS_CHECK(trivial || eps->twosided_solved, KS_ERR_ARG_WRONGSTATE, "Must request left vectors with EPSSetTwoSided");
+  KS_CALL(compute_vectors(eps));
+  *bv = trivial ? eps->V : eps->VL;
+  return KS_SUCCESS;
+}
+extern "C" int ks_eps_get_left_eigenvector(ks_eps eps, int i, double *yr_dev, double *yi_dev)
+{
+  ks_bv W = nullptr;
+  KS_CALL(left_basis(eps, i, &W));
+  const int k = eps->perm[i]; const size_t nloc = W->n;
+  const double im = eps->eigi[k];
+  ks_ctx ctx = eps->ctx;
+  KS_HIP(hipSetDevice(ctx->device));
+  const int kr = im < 0.0 ? k - 1 : k;
+  if (yr_dev) KS_CALL(ksk_copy(ctx, ks_bv_col(W, kr), yr_dev, nloc));
+  if (yi_dev) {
+    if (im == 0.0) KS_HIP(hipMemsetAsync(yi_dev, 0, nloc * sizeof(double), ctx->stream));
+    else { KS_CALL(ksk_copy(ctx, ks_bv_col(W, kr + 1), yi_dev, nloc)); if (im < 0.0) KS_CALL(ksk_scale(ctx, yi_dev, nloc, -1.0)); }
+  }
+  KS_HIP(ks_sync(ctx));
+  return KS_SUCCESS;
+}
+extern "C" int ks_eps_get_left_eigenvector_host(ks_eps eps, int i, double *yr, double *yi)
+{
+  ks_bv W = nullptr;
+  KS_CALL(left_basis(eps, i, &W));
+  const int k = eps->perm[i], nloc = W->n;
+  const double im = eps->eigi[k];
+  const int kr = im < 0.0 ? k - 1 : k;
+  if (yr) KS_CALL(ks_bv_get_column_host(W, kr, yr));
+  if (yi) {
+    if (im == 0.0) for (int r = 0; r < nloc; r++) yi[r] = 0.0;
+    else { KS_CALL(ks_bv_get_column_host(W, kr + 1, yi)); if (im < 0.0) for (int r = 0; r < nloc; r++) yi[r] = -yi[r]; }
+  }
+  return KS_SUCCESS;
+}
 extern "C" int ks_eps_get_error_estimate(ks_eps eps, int i, double *errest)
 {
   KS_CHECK(eps && errest, KS_ERR_ARG_NULL, "NULL argument");
@@ -915,6 +1213,12 @@ extern "C" int ks_eps_compute_error(ks_eps eps, int i, int type, double *error) 
     // complex pair in real arithmetic: xr = V(:,jr), xi = sg*V(:,jr+1) (BV_GetEigenvector bvimpl.h:423-446)
     const int jr = ki > 0.0 ? j : j - 1;
     KS_CALL(residual_norm(eps, kr, ki, ks_bv_col(V, jr), ks_bv_col(V, jr + 1), ki > 0.0 ? 1.0 : -1.0, &nrm));
+  }
+  if (eps->twosided_solved) {                                         // two-sided: the maximum with the left residual (epssolve.c:778-783)
+    ks_bv W = eps->VL; double nrml = 0.0;
+    if (ki == 0.0) KS_CALL(residual_norm(eps, kr, ki, ks_bv_col(W, j), nullptr, 1.0, &nrml, true));
+    else { const int jr = ki > 0.0 ? j : j - 1; KS_CALL(residual_norm(eps, kr, ki, ks_bv_col(W, jr), ks_bv_col(W, jr + 1), ki > 0.0 ? 1.0 : -1.0, &nrml, true)); }
+    nrm = std::max(nrm, nrml);
   }
   double vecnorm = 1.0;
   if (eps->ghep) { ks_mat Bsave = V->matrix; V->matrix = nullptr; int rc = ks_bv_normcolumn(V, j, KS_NORM_2, &vecnorm); V->matrix = Bsave; if (rc) return rc; }   // epssolve.c:774: 2-norm of the eigenvector

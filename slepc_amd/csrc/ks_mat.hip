@@ -909,7 +909,8 @@ extern "C" int ks_mat_create_laplacian2d(ks_ctx ctx, int n, int m, ks_mat *out)
 extern "C" int ks_mat_destroy(ks_mat A)
 {
   if (!A) return KS_SUCCESS;
-  if (A->At) { ks_mat_destroy(A->At); A->At = nullptr; }
+  if (A->transpose_of) return KS_SUCCESS;     // a transposed view (ks_mat_create_transpose) of an assembled matrix: freed with the matrix it views
+  if (A->At) { A->At->transpose_of = nullptr; ks_mat_destroy(A->At); A->At = nullptr; }
   hipSetDevice(A->ctx->device);
   ks_sync(A->ctx);
   hipFree(A->d_rowptr); hipFree(A->d_col); hipFree(A->d_val);

@@ -906,6 +906,18 @@ extern "C" int ks_mat_mult(ks_mat A, const double *x_dev, double *y_dev)
 }
 
 // MatMultTranspose: through the transposed matrix, built once (MatTranspose on the host, ks_csr.cpp) and multiplied like any other
+static int build_transpose(ks_mat A)
+{
+  if (A->At) return KS_SUCCESS;
+  KS_CHECK(A->ctx->comm.size == 1 && A->n == A->n_global, KS_ERR_SUP, "MatMultTranspose of a row-sharded matrix is not built (the transpose is a redistribution)");
+  KS_CHECK(A->keep_csr, KS_ERR_ORDER, "MatMultTranspose builds the transpose from the CSR arrays of the matrix: create it with KS_MAT_KEEP_CSR");
+  std::vector<int> rp, col; std::vector<double> val;
+  try { ksc::csr_transpose(A->n, A->n_global, A->k_rowptr.data(), A->k_col.data(), A->k_val.data(), rp, col, val); }
+  catch (const std::exception &e) { KS_FAIL(KS_ERR_MEM, "MatTranspose on the host: %s", e.what()); }
+  KS_CALL(ks_mat_create_csr_flags(A->ctx, A->n, 0, A->n_global, rp.data(), col.data(), val.data(), 0u, &A->At));
+  A->At->transpose_of = A;
+  return KS_SUCCESS;
+}
 int ks_mat_mult_transpose_internal(ks_mat A, const double *x, double *y)
 {
   if (A->shell_mult) {
@@ -914,15 +926,27 @@ int ks_mat_mult_transpose_internal(ks_mat A, const double *x, double *y)
     KS_CHECK(rc == 0, rc > 0 ? rc : KS_ERR_LIB, "the shell matrix's transposed product returned %d", rc);
     return KS_SUCCESS;
   }
-  if (!A->At) {
-    KS_CHECK(A->ctx->comm.size == 1 && A->n == A->n_global, KS_ERR_SUP, "MatMultTranspose of a row-sharded matrix is not built (the transpose is a redistribution)");
-    KS_CHECK(A->keep_csr, KS_ERR_ORDER, "MatMultTranspose builds the transpose from the CSR arrays of the matrix: create it with KS_MAT_KEEP_CSR");
-    std::vector<int> rp, col; std::vector<double> val;
-    try { ksc::csr_transpose(A->n, A->n_global, A->k_rowptr.data(), A->k_col.data(), A->k_val.data(), rp, col, val); }
-    catch (const std::exception &e) { KS_FAIL(KS_ERR_MEM, "MatTranspose on the host: %s", e.what()); }
-    KS_CALL(ks_mat_create_csr_flags(A->ctx, A->n, 0, A->n_global, rp.data(), col.data(), val.data(), 0u, &A->At));
-  }
+  if (A->transpose_of) return ks_mat_mult_internal(A->transpose_of, x, y);      // a transposed view: its transposed product is the matrix it views
+  KS_CALL(build_transpose(A));
   return ks_mat_mult_internal(A->At, x, y);
+}
+// MatCreateTranspose. Assembled A: the view IS the transposed matrix A keeps for MatMultTranspose (built here if this is its first use), so every
+// consumer - ks_mat_mult, the Krylov runs and their product fused into the dot sweep - treats it as the assembled matrix it is. Shell A: a shell
+// over the two callbacks swapped.
+extern "C" int ks_mat_create_transpose(ks_mat A, ks_mat *At)
+{
+  KS_CHECK(A && At, KS_ERR_ARG_NULL, "NULL argument");
+  KS_HIP(hipSetDevice(A->ctx->device));
+  if (A->shell_mult) {
+    KS_CHECK(A->shell_mult_t, KS_ERR_SUP, "the shell matrix has no MATOP_MULT_TRANSPOSE (ks_mat_shell_set_mult_transpose)");
+    KS_CALL(ks_mat_create_shell(A->ctx, A->n, A->row_start, A->n_global, A->shell_mult_t, A->shell_user, At));
+    (*At)->shell_mult_t = A->shell_mult; (*At)->shell_nosync = A->shell_nosync;
+    return KS_SUCCESS;
+  }
+  if (A->transpose_of) { *At = A->transpose_of; return KS_SUCCESS; }                 // the transpose of a view is the matrix itself
+  KS_CALL(build_transpose(A));
+  *At = A->At;
+  return KS_SUCCESS;
 }
 extern "C" int ks_mat_mult_transpose(ks_mat A, const double *x_dev, double *y_dev)
 {

@@ -149,6 +149,7 @@ struct ks_mat_s {
   // the CSR arrays the matrix was created from (global columns), kept on the host for KS_MAT_KEEP_CSR: what MatDuplicate / MatAXPY need (ks_mat_create_axpy)
   bool keep_csr = false; std::vector<int> k_rowptr, k_col; std::vector<double> k_val;
   ks_mat At = nullptr;                        // MatMultTranspose: the transpose, built on first use from the kept arrays (owned)
+  ks_mat transpose_of = nullptr;              // set on such an At: the matrix that owns it. ks_mat_create_transpose hands the At out as a view; only its owner frees it
   // diagonal block (columns owned by this rank, LOCAL column indices)
   int *d_rowptr = nullptr; int *d_col = nullptr; double *d_val = nullptr; long long nnz_d = 0;
   int lanes_per_row = 8;
