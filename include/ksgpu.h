@@ -445,12 +445,14 @@ int ks_eps_get_stats(ks_eps eps, long long *arnoldi_steps, long long *gs_passes,
    non-symmetric problems. Every restart runs two Arnoldi expansions through ks_bv_matarnoldi, one with Op and one with Op^T (ks_mat_create_transpose
    of the solver's operator: A must have a transposed product, KS_MAT_KEEP_CSR or a shell with ks_mat_shell_set_mult_transpose; checked at set-up),
    and solves the two projected problems together (DS NHEPTS). Convergence is the larger of the right and the left estimate, ks_eps_compute_error
-   the larger of the right residual and the left one, ||A^T y - conj(k) y||. Left eigenvectors satisfy y^H A = k y^H: for a conjugate pair (yr, yi)
-   of the first member and (yr, -yi) of the second, each normalised to unit 2-norm as a complex vector.
+   the larger of the right residual and the left one, ||A^T y - conj(k) B^T y|| (epssolve.c:692-711). Left eigenvectors satisfy y^H A = k y^H B: for
+   a conjugate pair (yr, yi) of the first member and (yr, -yi) of the second, each normalised to unit 2-norm as a complex vector. With a B matrix
+   (KS_EPS_GNHEP; the inner product stays the standard one) the converged left vectors go through P^-T before they are normalised
+   (EPSComputeVectors_Twosided epsdefault.c:79-95, ks_st_matsolve_transpose).
    ks_eps_solve returns KS_ERR_SUP with the flag set when
      - the problem type is KS_EPS_HEP or KS_EPS_GHEP (the reference's own check, epssetup.c:309)
-     - a B matrix is set
-     - the ST is not STSHIFT (sinvert and Cayley need solves with the transposed matrix)
+     - a B matrix is set and the EPS's ST has no transposed solves (ks_st_set_transpose_solves)
+     - the ST is not STSHIFT and has no transposed solves (sinvert and Cayley need solves with the transposed matrix)
      - balancing is on
      - the extraction is harmonic
      - the true residual is asked for
@@ -512,9 +514,32 @@ int ks_st_set_pc(ks_st st, int type, int block_size);
 int ks_st_set_ksp(ks_st st, double rtol, int max_it, int restart);        /* KSPSetTolerances / KSPGMRESSetRestart on STGetKSP; 0 keeps */
 int ks_st_setup(ks_st st);                                                /* STSetUp */
 int ks_st_apply(ks_st st, const double *x_dev, double *y_dev);            /* STApply stsolve.c:44 */
-/* STApplyHermitianTranspose (stsolve.c:153-162) for the transformations without a solve: shift with one matrix, y = (A - sigma I)^T x
-   (MatMultTranspose of A); the ones with a solve would need it with the transposed matrix: KS_ERR_SUP */
+/* STApplyTranspose / STApplyHermitianTranspose (stsolve.c:107-116, :153-162; real scalars). Shift with one matrix: y = (A - sigma I)^T x
+   (MatMultTranspose of A), always. The transformations with a solve need it with the transposed matrix: KS_ERR_SUP unless the ST has transposed
+   solves (ks_st_set_transpose_solves), then by STApplyTranspose_Generic
+       sinvert, 1 matrix    y = P^-T x                  sinvert, 2 matrices  w = P^-T x, y = B^T w
+       cayley               w = P^-T x, y = (A + nu B)^T w   (B = I with one matrix)
+       shift, 2 matrices    w = B^-T x, y = (A - sigma B)^T w */
 int ks_st_apply_transpose(ks_st st, const double *x_dev, double *y_dev);
+/* Solves with the transposed matrix (STMatSolveTranspose stsolve.c, on PETSc's KSPSolveTranspose and PCApplyTranspose), prepared ON REQUEST:
+   enable = 0 is the default, and with it every code path, error code and device allocation of the ST is what it was before this switch existed.
+   With enable != 0 STSetUp also prepares the transposed side: the transposed matrices of A and B (ks_mat_create_transpose; shell mode) or of the
+   assembled P, which then keeps its CSR arrays (copy mode), and for KS_PC_BJACOBI_ILU a second level plan of the same factors - the device bytes
+   of the factors double. That cost is why this is a switch; the default may flip in a later change. Set-up errors with the switch on: KS_ERR_ORDER
+   when A or B did not keep its CSR arrays (KS_MAT_KEEP_CSR), KS_ERR_SUP on more than one rank (the transpose of a row-sharded matrix is a
+   redistribution). Changing the switch clears the set-up. With it on, ks_st_apply_transpose works for every transformation, two-sided
+   Krylov-Schur accepts sinvert, Cayley and a B matrix, and two-sided balancing works behind a solve. */
+int ks_st_set_transpose_solves(ks_st st, int enable);
+int ks_st_get_transpose_solves(ks_st st, int *enable);
+/* STMatSolveTranspose (stsolve.c): P^T y = b with the KSP of the ST on its transposed side (KSPSolveTranspose: the same left-preconditioned
+   iteration on M^-T P^T y = M^-T b, PCApplyBAorABTranspose with PC_LEFT); P = A - sigma B for sinvert and Cayley, P = B for a shift with two
+   matrices. ks_st_get_ksp_stats counts these solves with the others. KS_ERR_SUP without ks_st_set_transpose_solves; KS_ERR_ORDER for STSHIFT with
+   one matrix (no linear solve); b == y is KS_ERR_ARG_IDN. */
+int ks_st_matsolve_transpose(ks_st st, const double *b_dev, double *y_dev);
+/* PCApplyTranspose on KSPGetPC(STGetKSP) (PETSc's, as PCApply): y = M^-T x. Point Jacobi is its own transpose; the dense blocks are applied by
+   columns of the same inverses; the ILU(0) blocks use the SAME factors, y = L^-T U^-T x (not an ILU(0) of P^T), from their transposed level plan.
+   Same errors as ks_st_matsolve_transpose. Enqueued on the context's stream, no host wait. */
+int ks_st_pc_apply_transpose(ks_st st, const double *x_dev, double *y_dev);
 /* PCApply on KSPGetPC(STGetKSP) (the KSP of stsles.c:51-58; PCApply itself is PETSc's, external to the reference): y = M^-1 x with the
    preconditioner of the inner solves, whichever of the three types is set. Runs STSetUp if needed; x == y is KS_ERR_ARG_IDN; a transformation
    without a linear solve (STSHIFT with one matrix) has no preconditioner: KS_ERR_ORDER. Enqueued on the context's stream, no host wait. */

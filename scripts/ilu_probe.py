@@ -1,7 +1,9 @@
 """Probe of the ILU(0) block-Jacobi preconditioner (not a test): point Jacobi against bjacobi-ilu at a few block sizes on config 5's pencil and on a
 3-D Laplacian, shift-and-invert. Per case and preconditioner: levels per block (what an application waits for), inner iterations per solve, time per
-application of the preconditioner (mean of 200 back-to-back PCApply launches between two host waits), Arnoldi steps/s of a step-capped eigensolve.
-Usage: ilu_probe.py [output file] ; ILU_PROBE_SMALL=1 runs reduced sizes."""
+application of the preconditioner (mean of 200 back-to-back PCApply launches between two host waits) and of its transpose (PCApplyTranspose, a
+second ST with transposed solves on), Arnoldi steps/s of a step-capped eigensolve.
+Usage: ilu_probe.py [output file] ; ILU_PROBE_SMALL=1 runs reduced sizes, ILU_PROBE_PC_ONLY=1 leaves the solves out (set-up and the two
+applications only: a run whose length does not depend on how the inner solves converge)."""
 import os
 import sys
 import time
@@ -13,6 +15,7 @@ import slepc_amd as ks
 from slepc_amd.workloads import config5_pencil_arrays
 
 small = bool(os.environ.get("ILU_PROBE_SMALL"))
+pc_only = bool(os.environ.get("ILU_PROBE_PC_ONLY"))
 ctx = ks.Context(0)
 out = open(sys.argv[1], "a") if len(sys.argv) > 1 else sys.stdout
 
@@ -71,6 +74,21 @@ def run(name, arr, barr, sigma, nev, ncv, cap, problem, pcs):
             for _ in range(200):
                 st.PCApplyDev(W.column_ptr(0), W.column_ptr(1))
             ctx.synchronize(); tpc = (time.time() - t) / 200
+            # the transposed side: same factors, a second level plan (ks_st_set_transpose_solves)
+            stt = ks.ST(ctx); stt.SetType("sinvert"); stt.SetShift(sigma); stt.SetMatrices(A, B); stt.SetPC(pc, bs); stt.SetTransposeSolves(True)
+            t = time.time(); stt.SetUp(); ctx.synchronize(); tsett = time.time() - t
+            for _ in range(3):
+                stt.PCApplyTransposeDev(W.column_ptr(0), W.column_ptr(1))
+            ctx.synchronize(); t = time.time()
+            for _ in range(200):
+                stt.PCApplyTransposeDev(W.column_ptr(0), W.column_ptr(1))
+            ctx.synchronize(); tpct = (time.time() - t) / 200
+            del stt
+            lev = ("  levels/block %s" % levels_per_block(arr, barr, sigma, bs)) if bs else ""
+            if pc_only:
+                log("  %-18s set-up %6.2f s (%6.2f s with the transposed side)  PCApply %8.1f us  PCApplyTranspose %8.1f us%s" % (label, tset, tsett, 1e6 * tpc, 1e6 * tpct, lev))
+                del st, W
+                continue
             for _ in range(2):
                 st.Apply(x)
             s = st.GetKSPStats()
@@ -79,9 +97,8 @@ def run(name, arr, barr, sigma, nev, ncv, cap, problem, pcs):
             eps.SetMaxSteps(cap)
             t = time.time(); eps.Solve(); dt = time.time() - t
             es = eps.GetStats(); k2 = s2.GetKSPStats()
-            lev = ("  levels/block %s" % levels_per_block(arr, barr, sigma, bs)) if bs else ""
-            log("  %-18s set-up %6.2f s  PCApply %8.1f us  inner its/solve %7.1f (Apply) %7.1f (eigensolve)  %7.1f steps/s over %d steps%s"
-                % (label, tset, 1e6 * tpc, s["iterations"] / max(1, s["solves"]), k2["iterations"] / max(1, k2["solves"]), es["arnoldi_steps"] / dt, es["arnoldi_steps"], lev))
+            log("  %-18s set-up %6.2f s  PCApply %8.1f us  PCApplyTranspose %8.1f us  inner its/solve %7.1f (Apply) %7.1f (eigensolve)  %7.1f steps/s over %d steps%s"
+                % (label, tset, 1e6 * tpc, 1e6 * tpct, s["iterations"] / max(1, s["solves"]), k2["iterations"] / max(1, k2["solves"]), es["arnoldi_steps"] / dt, es["arnoldi_steps"], lev))
             del eps, st, W
         except ks.KsError as e:
             log("  %-18s failed: %s" % (label, e))

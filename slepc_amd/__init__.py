@@ -818,6 +818,33 @@ class ST:
         _lib.check(self.ctx.L.ks_st_apply_transpose(self.h, C.c_void_p(W.column_ptr(0)), C.c_void_p(W.column_ptr(1))))
         return W.column(1)
 
+    def SetTransposeSolves(self, flag=True):
+        """Prepare solves with the transposed matrix at set-up (STMatSolveTranspose / KSPSolveTranspose / PCApplyTranspose); off by default."""
+        _lib.check(self.ctx.L.ks_st_set_transpose_solves(self.h, 1 if flag else 0))
+
+    def GetTransposeSolves(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_st_get_transpose_solves(self.h, C.byref(v))); return bool(v.value)
+
+    def MatSolveTranspose(self, b):
+        """y with P^T y = b, host vectors (STMatSolveTranspose; single rank)."""
+        b = _f64(b)
+        W = BV(self.ctx, len(b), 2)
+        W.set_column(0, b)
+        _lib.check(self.ctx.L.ks_st_matsolve_transpose(self.h, C.c_void_p(W.column_ptr(0)), C.c_void_p(W.column_ptr(1))))
+        return W.column(1)
+
+    def PCApplyTransposeDev(self, xp, yp):
+        """y = M^-T x (PCApplyTranspose on the ST's KSP), device pointers; enqueued, no host wait."""
+        _lib.check(self.ctx.L.ks_st_pc_apply_transpose(self.h, C.c_void_p(xp), C.c_void_p(yp)))
+
+    def PCApplyTranspose(self, x):
+        """y = M^-T x with host vectors (this rank's rows)."""
+        x = _f64(x)
+        W = BV(self.ctx, len(x), 2)
+        W.set_column(0, x)
+        self.PCApplyTransposeDev(W.column_ptr(0), W.column_ptr(1))
+        return W.column(1)
+
     def BackTransform(self, eigr, eigi):
         r = _f64(np.atleast_1d(eigr)).copy(); i = _f64(np.atleast_1d(eigi)).copy()
         _lib.check(self.ctx.L.ks_st_backtransform(self.h, len(r), _p(r), _p(i)))

@@ -220,6 +220,10 @@ _SIG = {
     "ks_st_setup": [vp],
     "ks_st_apply": [vp, vp, vp],
     "ks_st_pc_apply": [vp, vp, vp],
+    "ks_st_set_transpose_solves": [vp, C.c_int],
+    "ks_st_get_transpose_solves": [vp, ip],
+    "ks_st_matsolve_transpose": [vp, vp, vp],
+    "ks_st_pc_apply_transpose": [vp, vp, vp],
     "ks_st_backtransform": [vp, C.c_int, dp, dp],
     "ks_st_get_ksp_stats": [vp, llp, llp, dp],
     # profiling

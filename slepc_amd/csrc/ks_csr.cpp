@@ -120,14 +120,64 @@ void csr_window_plan(int n, const int *rp, const int *col, int block_rows, int m
   out.total_segments = (long long)out.seg.size();
   out.dcol.resize((size_t)drun + pad, 0);
 }
-void csr_ilu0_blocks(int n, int row_start, int bs, const int *rp, const int *col, const double *val, bool keep_factors, IluPlan &out)
+namespace {
+struct IluLevelScratch { std::vector<int> level, count, start, order, where; };
+// Level sets and the ELL image of each level for the two triangular solves of one block, appended to `out`: pass 0 = the entries left of the
+// diagonal (levels ascending from row 0), pass 1 = the entries right of it (ascending from the last row). scale_pass: the pass whose rows are
+// multiplied by the reciprocal of their diagonal entry (1: the forward solve, U; 0: the transposed solve, U^T); dinv is in that pass's level order.
+void ilu_block_levels(int b, int b0, int bl, const std::vector<int> &brp, const std::vector<int> &bcol, const std::vector<double> &bval, const std::vector<int> &diag,
+                      int scale_pass, IluPlan &out, IluLevelScratch &sc)
+{
+  std::vector<int> &level = sc.level, &count = sc.count, &start = sc.start, &order = sc.order, &where = sc.where;
+  out.blk[b].ell = (long long)out.val.size(); out.blk[b].lev = (int)(out.lev.size() / 2); out.blk[b].pad = 0;
+  level.assign((size_t)bl, 0); order.resize((size_t)bl);
+  for (int pass = 0; pass < 2; pass++) {
+    int nlev = 0;
+    for (int s = 0; s < bl; s++) {
+      const int i = pass == 0 ? s : bl - 1 - s;
+      const int e0 = pass == 0 ? brp[i] : diag[i] + 1, e1 = pass == 0 ? diag[i] : brp[i + 1];
+      int lv = 0;
+      for (int p = e0; p < e1; p++) lv = std::max(lv, level[bcol[p]] + 1);
+      level[i] = lv; nlev = std::max(nlev, lv + 1);
+    }
+    count.assign((size_t)nlev, 0); start.assign((size_t)nlev + 1, 0); where.assign((size_t)nlev, 0);
+    for (int i = 0; i < bl; i++) count[level[i]]++;
+    for (int l = 0; l < nlev; l++) { start[l + 1] = start[l] + count[l]; where[l] = start[l]; }
+    for (int i = 0; i < bl; i++) order[where[level[i]]++] = i;
+    unsigned short *rows = out.rows.data() + (size_t)2 * b0 + (size_t)pass * bl;
+    for (int l = 0; l < nlev; l++) {
+      const int nl = count[l];
+      int w = 0;
+      for (int p = start[l]; p < start[l + 1]; p++) { const int i = order[p]; w = std::max(w, pass == 0 ? diag[i] - brp[i] : brp[i + 1] - diag[i] - 1); }
+      const size_t base = out.val.size();
+      out.val.resize(base + (size_t)nl * w, 0.0); out.code.resize(base + (size_t)nl * w, 0);
+      for (int p = 0; p < nl; p++) {
+        const int i = order[start[l] + p];
+        rows[start[l] + p] = (unsigned short)i;
+        if (pass == scale_pass) out.dinv[(size_t)b0 + start[l] + p] = 1.0 / bval[diag[i]];
+        const int e0 = pass == 0 ? brp[i] : diag[i] + 1, e1 = pass == 0 ? diag[i] : brp[i + 1];
+        for (int s = 0; s < w; s++) {
+          const size_t at = base + (size_t)s * nl + p;
+          if (e0 + s < e1) { out.val[at] = bval[e0 + s]; out.code[at] = (unsigned short)bcol[e0 + s]; }
+          else out.code[at] = (unsigned short)i;
+        }
+      }
+      out.lev.push_back(nl); out.lev.push_back(w);
+    }
+    (pass == 0 ? out.blk[b].nL : out.blk[b].nU) = nlev;
+  }
+}
+} // namespace
+void csr_ilu0_blocks(int n, int row_start, int bs, const int *rp, const int *col, const double *val, bool keep_factors, IluPlan &out, IluPlan *tr)
 {
   out = IluPlan();
   const int nblk = (int)(((long long)n + bs - 1) / bs);
   out.blk.resize((size_t)nblk); out.rows.assign((size_t)2 * n, 0); out.dinv.assign((size_t)n, 0.0);
   if (keep_factors) out.frp.assign(1, 0);
-  std::vector<int> brp, bcol, diag, pos, level, count, start, order, where, perm;
-  std::vector<double> bval;
+  if (tr) { *tr = IluPlan(); tr->blk.resize((size_t)nblk); tr->rows.assign((size_t)2 * n, 0); tr->dinv.assign((size_t)n, 0.0); }
+  std::vector<int> brp, bcol, diag, pos, perm, trp, tcol, tdiag;
+  std::vector<double> bval, tval;
+  IluLevelScratch sc;
   for (int b = 0; b < nblk; b++) {
     const int b0 = b * bs, bl = std::min(bs, n - b0);
     const long long c0 = (long long)row_start + b0;
@@ -164,47 +214,24 @@ void csr_ilu0_blocks(int n, int row_start, int bs, const int *rp, const int *col
       out.fcol.insert(out.fcol.end(), bcol.begin(), bcol.end()); out.fval.insert(out.fval.end(), bval.begin(), bval.end());
       for (int r = 0; r < bl; r++) out.frp.push_back(out.frp.back() + brp[r + 1] - brp[r]);
     }
-    // level sets and the ELL image of each level: pass 0 = L, pass 1 = U
-    out.blk[b].ell = (long long)out.val.size(); out.blk[b].lev = (int)(out.lev.size() / 2); out.blk[b].pad = 0;
-    level.assign((size_t)bl, 0); order.resize((size_t)bl);
-    for (int pass = 0; pass < 2; pass++) {
-      int nlev = 0;
-      for (int s = 0; s < bl; s++) {
-        const int i = pass == 0 ? s : bl - 1 - s;
-        const int e0 = pass == 0 ? brp[i] : diag[i] + 1, e1 = pass == 0 ? diag[i] : brp[i + 1];
-        int lv = 0;
-        for (int p = e0; p < e1; p++) lv = std::max(lv, level[bcol[p]] + 1);
-        level[i] = lv; nlev = std::max(nlev, lv + 1);
+    ilu_block_levels(b, b0, bl, brp, bcol, bval, diag, 1, out, sc);
+    if (tr) {
+      // the transposed triangles from the same factors: row r of the transposed block lists column r of the factors in ascending original row
+      // (the counting sort of csr_transpose) - u_cr for c < r, the pivot u_rr, then l_cr for c > r. U^T (lower, with the pivots) is solved
+      // first and carries the scaling, L^T (unit upper) second; the levels are those of the transposed triangles
+      csr_transpose(bl, bl, brp.data(), bcol.data(), bval.data(), trp, tcol, tval);
+      tdiag.assign((size_t)bl, -1);
+      for (int r = 0; r < bl; r++) {
+        for (int p = trp[r]; p < trp[r + 1]; p++) if (tcol[p] == r) { tdiag[r] = p; break; }
+        tr->longest_row = std::max(tr->longest_row, trp[r + 1] - trp[r]);
       }
-      count.assign((size_t)nlev, 0); start.assign((size_t)nlev + 1, 0); where.assign((size_t)nlev, 0);
-      for (int i = 0; i < bl; i++) count[level[i]]++;
-      for (int l = 0; l < nlev; l++) { start[l + 1] = start[l] + count[l]; where[l] = start[l]; }
-      for (int i = 0; i < bl; i++) order[where[level[i]]++] = i;
-      unsigned short *rows = out.rows.data() + (size_t)2 * b0 + (size_t)pass * bl;
-      for (int l = 0; l < nlev; l++) {
-        const int nl = count[l];
-        int w = 0;
-        for (int p = start[l]; p < start[l + 1]; p++) { const int i = order[p]; w = std::max(w, pass == 0 ? diag[i] - brp[i] : brp[i + 1] - diag[i] - 1); }
-        const size_t base = out.val.size();
-        out.val.resize(base + (size_t)nl * w, 0.0); out.code.resize(base + (size_t)nl * w, 0);
-        for (int p = 0; p < nl; p++) {
-          const int i = order[start[l] + p];
-          rows[start[l] + p] = (unsigned short)i;
-          if (pass == 1) out.dinv[(size_t)b0 + start[l] + p] = 1.0 / bval[diag[i]];
-          const int e0 = pass == 0 ? brp[i] : diag[i] + 1, e1 = pass == 0 ? diag[i] : brp[i + 1];
-          for (int s = 0; s < w; s++) {
-            const size_t at = base + (size_t)s * nl + p;
-            if (e0 + s < e1) { out.val[at] = bval[e0 + s]; out.code[at] = (unsigned short)bcol[e0 + s]; }
-            else out.code[at] = (unsigned short)i;
-          }
-        }
-        out.lev.push_back(nl); out.lev.push_back(w);
-      }
-      (pass == 0 ? out.blk[b].nL : out.blk[b].nU) = nlev;
+      ilu_block_levels(b, b0, bl, trp, tcol, tval, tdiag, 0, *tr, sc);
     }
   }
 }
-void ilu0_apply_host(const IluPlan &p, int n, int bs, const double *in, double *out)
+namespace {
+// the level walk of both kernels: `first_scaled` says which of the block's two runs of levels multiplies by dinv (the second: forward, the first: transposed)
+void ilu0_walk_host(const IluPlan &p, int n, int bs, bool first_scaled, const double *in, double *out)
 {
   std::vector<double> x;
   for (size_t b = 0; b < p.blk.size(); b++) {
@@ -214,7 +241,7 @@ void ilu0_apply_host(const IluPlan &p, int n, int bs, const double *in, double *
     const unsigned short *rows = p.rows.data() + (size_t)2 * b0; const double *dinv = p.dinv.data() + b0;
     for (int l = 0; l < p.blk[b].nL + p.blk[b].nU; l++) {
       const int nl = p.lev[(size_t)2 * (p.blk[b].lev + l)], w = p.lev[(size_t)2 * (p.blk[b].lev + l) + 1];
-      const bool upper = l >= p.blk[b].nL;
+      const bool upper = first_scaled ? l < p.blk[b].nL : l >= p.blk[b].nL;        // the run of levels with the pivots
       for (int i = 0; i < nl; i++) {
         const int r = rows[i];
         double acc = 0.0;
@@ -226,6 +253,9 @@ void ilu0_apply_host(const IluPlan &p, int n, int bs, const double *in, double *
     std::copy(x.begin(), x.end(), out + b0);
   }
 }
+} // namespace
+void ilu0_apply_host(const IluPlan &p, int n, int bs, const double *in, double *out) { ilu0_walk_host(p, n, bs, false, in, out); }
+void ilu0_apply_transpose_host(const IluPlan &t, int n, int bs, const double *in, double *out) { ilu0_walk_host(t, n, bs, true, in, out); }
 } // namespace ksc
 
 #ifdef KSD_TEST_HOOKS
@@ -277,6 +307,34 @@ long long ksc_ilu0_blocks(int n, int row_start, int bs, const int *rp, const int
   if (fcol && fval && (long long)p.fcol.size() <= cap) { std::copy(p.fcol.begin(), p.fcol.end(), fcol); std::copy(p.fval.begin(), p.fval.end(), fval); }
   if (in && out) ksc::ilu0_apply_host(p, n, bs, in, out);
   return (long long)p.fcol.size();
+}
+// test hook: the transposed level layout of the same factors and the solve k_bjacobi_ilu_apply_t runs, on the host: out_t = (LU)^-T in, out_f = (LU)^-1 in
+// (either may be NULL). per_block (six per block): L and U levels of the forward plan, first-phase (U^T) and second-phase (L^T) levels of the
+// transposed one, the largest code of the transposed plan, the block's length. info: status, block, local row, longest column, levels and ELL
+// entries of the transposed plan, and info[6] = 1 when the forward plan built together with the transposed one equals, array by array, the forward
+// plan built alone. Returns the ELL entries of the transposed plan, -1 on a status other than 0.
+long long ksc_ilu0_blocks_transpose(int n, int row_start, int bs, const int *rp, const int *col, const double *val, const double *in, double *out_t, double *out_f,
+                                    int *per_block, long long *info)
+{
+  ksc::IluPlan alone, p, t;
+  ksc::csr_ilu0_blocks(n, row_start, bs, rp, col, val, false, alone);
+  ksc::csr_ilu0_blocks(n, row_start, bs, rp, col, val, false, p, &t);
+  info[0] = p.status; info[1] = p.bad_block; info[2] = p.bad_row; info[3] = t.longest_row; info[4] = (long long)t.lev.size() / 2; info[5] = (long long)t.val.size();
+  if (p.status) return -1;
+  bool same = alone.lev == p.lev && alone.val == p.val && alone.code == p.code && alone.rows == p.rows && alone.dinv == p.dinv && alone.blk.size() == p.blk.size() && alone.longest_row == p.longest_row;
+  for (size_t b = 0; same && b < p.blk.size(); b++) same = alone.blk[b].ell == p.blk[b].ell && alone.blk[b].lev == p.blk[b].lev && alone.blk[b].nL == p.blk[b].nL && alone.blk[b].nU == p.blk[b].nU;
+  info[6] = same ? 1 : 0;
+  for (size_t b = 0; b < t.blk.size(); b++) {
+    const size_t e0 = (size_t)t.blk[b].ell, e1 = b + 1 < t.blk.size() ? (size_t)t.blk[b + 1].ell : t.code.size();
+    int top = 0;
+    for (size_t e = e0; e < e1; e++) top = std::max(top, (int)t.code[e]);
+    for (int i = 0; i < 2 * std::min(bs, n - (int)b * bs); i++) top = std::max(top, (int)t.rows[(size_t)2 * b * bs + i]);
+    int *o = per_block + 6 * b;
+    o[0] = p.blk[b].nL; o[1] = p.blk[b].nU; o[2] = t.blk[b].nL; o[3] = t.blk[b].nU; o[4] = top; o[5] = std::min(bs, n - (int)b * bs);
+  }
+  if (in && out_t) ksc::ilu0_apply_transpose_host(t, n, bs, in, out_t);
+  if (in && out_f) ksc::ilu0_apply_host(p, n, bs, in, out_f);
+  return (long long)t.val.size();
 }
 }
 #endif

@@ -57,7 +57,13 @@ struct IluPlan {
 };
 constexpr int ILU_NO_DIAGONAL = 1, ILU_ZERO_PIVOT = 2;
 constexpr int ILU_BS_MAX = 8192;                  // 64 KB of LDS for the block's vector; codes fit 16 bits
-void csr_ilu0_blocks(int n, int row_start, int bs, const int *rp, const int *col, const double *val, bool keep_factors, IluPlan &out);
-// what the kernel computes, on the host, in the same order: out = (LU)^-1 in block by block
+// tr (optional): a second plan of the same factors for the transposed solve y = (LU)^-T x = L^-T U^-T x (PCApplyTranspose; k_bjacobi_ilu_apply_t). It is
+// NOT an ILU(0) of the transposed block. Block by block the factors are transposed by a counting sort, so row r of U^T lists column r of U in
+// ascending original row, and the level sets are recomputed for the transposed triangles (as many levels as the forward solve, other members).
+// The layout is the same; what differs: the FIRST run of levels (nL of the block record) is U^T - lower triangular, with the pivots - and the
+// second (nU) is L^T, unit upper; dinv is 1 / u_rr in the first run's level order; longest_row is the longest column of a block.
+void csr_ilu0_blocks(int n, int row_start, int bs, const int *rp, const int *col, const double *val, bool keep_factors, IluPlan &out, IluPlan *tr = nullptr);
+// what the kernels compute, on the host, in the same order: out = (LU)^-1 in block by block from the forward plan, out = (LU)^-T in from the transposed one
 void ilu0_apply_host(const IluPlan &p, int n, int bs, const double *in, double *out);
+void ilu0_apply_transpose_host(const IluPlan &t, int n, int bs, const double *in, double *out);
 }

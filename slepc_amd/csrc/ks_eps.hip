@@ -471,7 +471,7 @@ static int build_balance(ks_eps eps)
 // EPSComputeResidualNorm_Private epssolve.c:666-718 (STGetMatrix 0/1 = the user's A and B): || A x - k B x ||_2 for a
 // real eigenvalue, hypot of the two real-arithmetic residuals for a pair (xi_sign * xi is the imaginary part).
 // Work vectors: W columns 0..2.
-// trans (the left residual of the two-sided variant, one matrix): the transposed product and the conjugate eigenvalue, ||A^T y - conj(k) y|| (:676,692,705,711)
+// trans (the left residual of the two-sided variant): the transposed products and the conjugate eigenvalue, ||A^T y - conj(k) B^T y|| (:676,692,705,711)
 static int residual_norm(ks_eps eps, double kr, double ki, const double *xr, const double *xi, double xi_sign, double *out, bool trans = false)
 {
   ks_bv W = eps->W; ks_ctx ctx = eps->ctx; ks_mat A = eps->A, B = eps->B;
@@ -479,19 +479,20 @@ static int residual_norm(ks_eps eps, double kr, double ki, const double *xr, con
   double *u = ks_bv_col(W, 0);
   double nrm = 0.0;
   auto mult = [&](const double *x, double *y) { return trans ? ks_mat_mult_transpose_internal(A, x, y) : ks_mat_mult_internal(A, x, y); };
+  auto multb = [&](const double *x, double *y) { return trans ? ks_mat_mult_transpose_internal(B, x, y) : ks_mat_mult_internal(B, x, y); };   // two matrices: || A^T y - conj(k) B^T y ||
   if (trans) ki = -ki;
   if (ki == 0.0 || fabs(ki) < fabs(kr * std::numeric_limits<double>::epsilon())) {
     KS_CALL(mult(xr, u));                                                            // u = A*x
     if (fabs(kr) > std::numeric_limits<double>::epsilon()) {
       const double *w = xr;
-      if (B) { KS_CALL(ks_mat_mult_internal(B, xr, ks_bv_col(W, 2))); w = ks_bv_col(W, 2); }   // w = B*x
+      if (B) { KS_CALL(multb(xr, ks_bv_col(W, 2))); w = ks_bv_col(W, 2); }   // w = B*x
       KS_CALL(ksk_lincomb(ctx, n, nullptr, 1.0, u, -kr, w, u));                      // u = A*x - k*B*x
     }
     KS_CALL(ks_bv_normcolumn(W, 0, KS_NORM_2, &nrm));
   } else {
     const double sg = xi_sign;
     const double *v = xr, *w = xi;                                                   // v = B*xr, w = B*xi (before the sign)
-    if (B) { KS_CALL(ks_mat_mult_internal(B, xr, ks_bv_col(W, 1))); KS_CALL(ks_mat_mult_internal(B, xi, ks_bv_col(W, 2))); v = ks_bv_col(W, 1); w = ks_bv_col(W, 2); }
+    if (B) { KS_CALL(multb(xr, ks_bv_col(W, 1))); KS_CALL(multb(xi, ks_bv_col(W, 2))); v = ks_bv_col(W, 1); w = ks_bv_col(W, 2); }
     double nr = 0.0, ni = 0.0;
     KS_CALL(mult(xr, u));                                                            // u = A*xr - kr*B*xr + ki*B*xi
     KS_CALL(ksk_lincomb(ctx, n, nullptr, 1.0, u, -kr, v, u));
@@ -603,6 +604,12 @@ static int compute_vectors(ks_eps eps)
       KS_CALL(ks_bv_set_active_columns(W, 0, nc));
       for (int k = 0; k < nc; k++) k = eps->dst.vectors_side(k, true, false, nullptr);
       KS_CALL(ks_bv_multinplace(W, eps->dst.hb.X.data(), ds.ld, 0, nc));
+      if (eps->B) {                                         // EPSComputeVectors_Twosided epsdefault.c:79-95: generalized problems, y <- P^-T y (shift: P = B)
+        for (int i = 0; i < nc; i++) {
+          KS_CALL(ksk_copy(eps->ctx, ks_bv_col(W, i), ks_bv_col(eps->W, 3), W->n));
+          KS_CALL(ks_st_matsolve_transpose(eps->st, ks_bv_col(eps->W, 3), ks_bv_col(W, i)));
+        }
+      }
       KS_CALL(ks_bv_normalize(W, eps->eigi.data()));
       for (int i = 0; i < nc - 1; i++) if (eps->eigi[i] != 0.0) { if (eps->eigi[i] > 0.0) KS_CALL(ks_bv_scalecolumn(W, i + 1, -1.0)); i++; }
     }
@@ -628,8 +635,9 @@ static int set_up(ks_eps eps, long long *passes0)
   eps->twosided_solved = false; eps->left_trivial = ptype == KS_EPS_HEP || ghep;
   if (eps->twosided) {                                                 // what the two-sided variant is built for: each case is listed in ksgpu.h
     KS_CHECK(ptype != KS_EPS_HEP && !ghep, KS_ERR_SUP, "Two-sided methods are not intended for Hermitian problems");   // epssetup.c:309
-    KS_CHECK(!eps->B, KS_ERR_SUP, "two-sided Krylov-Schur is built for standard problems (no B matrix)");
-    KS_CHECK(!eps->st || eps->st->type == KS_ST_SHIFT, KS_ERR_SUP, "two-sided Krylov-Schur is built for STSHIFT (the others need solves with the transposed matrix)");
+    const bool tsolves = eps->st && eps->st->tsolves;                  // the ST prepares solves with the transposed matrix (ks_st_set_transpose_solves)
+    KS_CHECK(!eps->B || tsolves, KS_ERR_SUP, "two-sided Krylov-Schur is built for standard problems (no B matrix) unless the ST has transposed solves (ks_st_set_transpose_solves)");
+    KS_CHECK(!eps->st || eps->st->type == KS_ST_SHIFT || tsolves, KS_ERR_SUP, "two-sided Krylov-Schur is built for STSHIFT (the others need solves with the transposed matrix: ks_st_set_transpose_solves)");
     KS_CHECK(eps->balance == KS_EPS_BALANCE_NONE, KS_ERR_SUP, "two-sided Krylov-Schur with balancing is not built");
     KS_CHECK(eps->extraction == KS_EPS_RITZ, KS_ERR_SUP, "two-sided Krylov-Schur with harmonic extraction is not built");
     KS_CHECK(!eps->trueres, KS_ERR_SUP, "two-sided Krylov-Schur with the true residual is not built");

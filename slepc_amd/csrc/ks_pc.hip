@@ -1,6 +1,7 @@
 // Block Jacobi with ILU(0) blocks (KS_PC_BJACOBI_ILU): PCBJACOBI with -sub_pc_type ilu, PETSc's parallel default for AIJ matrices, as the left
 // preconditioner of the ST's KSP (ks_st.hip). The factors and their level schedule are made on the host (ksc::csr_ilu0_blocks, ks_csr.cpp: the
-// layout is described there); this file uploads them and applies them: y = U^-1 L^-1 x block by block.
+// layout is described there); this file uploads them and applies them: y = U^-1 L^-1 x block by block, and - on request, from a second plan of the
+// same factors - the transposed preconditioner y = L^-T U^-T x (PCApplyTranspose).
 #include "ksgpu_internal.h"
 #include "ks_csr.h"
 #include <algorithm>
@@ -11,6 +12,7 @@ struct KsIlu {
   ksc::IluBlock *blk = nullptr; int2 *lev = nullptr;
   double *val = nullptr, *dinv = nullptr;
   unsigned short *code = nullptr, *rows = nullptr;
+  KsIlu *t = nullptr;          // the plan of the transposed triangles (ks_pc_ilu_build with transpose): same factors, owned
 };
 
 namespace {
@@ -29,10 +31,13 @@ constexpr int ILU_THREADS = 256;
 // each half of the wave); lanes p, p + 1 of a level in a stencil block read columns a constant stride apart, conflict-free when that stride
 // is odd - the diagonal wavefronts of a grid line of even length - and two-way when it is 2 mod 4. x[r] of the row lists is written in
 // ascending row order, near-consecutive words.
-__global__ void __launch_bounds__(ILU_THREADS) k_bjacobi_ilu_apply(int n, int bs, const ksc::IluBlock *__restrict__ blk, const int2 *__restrict__ lev,
-                                                                   const double *__restrict__ val, const unsigned short *__restrict__ code,
-                                                                   const unsigned short *__restrict__ rows, const double *__restrict__ dinv,
-                                                                   const double *__restrict__ in, double *__restrict__ out)
+// TRANS: the plan of the transposed triangles (ks_csr.h). The walk is the same; the run of levels that carries the pivots is the first one (U^T, lower
+// triangular: x[r] = (x[r] - sum_{c<r} u_cr x[c]) / u_rr), the unit triangle (L^T, upper) comes second, and dinv is in the first run's level order.
+template <bool TRANS>
+__device__ __forceinline__ void ilu_level_walk(int n, int bs, const ksc::IluBlock *__restrict__ blk, const int2 *__restrict__ lev,
+                                               const double *__restrict__ val, const unsigned short *__restrict__ code,
+                                               const unsigned short *__restrict__ rows, const double *__restrict__ dinv,
+                                               const double *__restrict__ in, double *__restrict__ out)
 {
   extern __shared__ double xs[];
   const int tid = threadIdx.x;
@@ -49,7 +54,7 @@ __global__ void __launch_bounds__(ILU_THREADS) k_bjacobi_ilu_apply(int n, int bs
   for (int l = 0; l < nlev; l++) {
     const int2 next = (l + 1 < nlev) ? lv[l + 1] : make_int2(0, 0);
     const int nl = d.x, w = d.y;
-    const bool upper = l >= B.nL;
+    const bool upper = TRANS ? l < B.nL : l >= B.nL;            // the run of levels with the pivots
     for (int i = tid; i < nl; i += ILU_THREADS) {
       const int r = rw[i];
       double acc = 0.0;
@@ -63,6 +68,21 @@ __global__ void __launch_bounds__(ILU_THREADS) k_bjacobi_ilu_apply(int n, int bs
   }
   for (int i = tid; i < bl; i += ILU_THREADS) out[b0 + i] = xs[i];
 }
+__global__ void __launch_bounds__(ILU_THREADS) k_bjacobi_ilu_apply(int n, int bs, const ksc::IluBlock *__restrict__ blk, const int2 *__restrict__ lev,
+                                                                   const double *__restrict__ val, const unsigned short *__restrict__ code,
+                                                                   const unsigned short *__restrict__ rows, const double *__restrict__ dinv,
+                                                                   const double *__restrict__ in, double *__restrict__ out)
+{
+  ilu_level_walk<false>(n, bs, blk, lev, val, code, rows, dinv, in, out);
+}
+// y = L^-T U^-T x from the transposed plan
+__global__ void __launch_bounds__(ILU_THREADS) k_bjacobi_ilu_apply_t(int n, int bs, const ksc::IluBlock *__restrict__ blk, const int2 *__restrict__ lev,
+                                                                     const double *__restrict__ val, const unsigned short *__restrict__ code,
+                                                                     const unsigned short *__restrict__ rows, const double *__restrict__ dinv,
+                                                                     const double *__restrict__ in, double *__restrict__ out)
+{
+  ilu_level_walk<true>(n, bs, blk, lev, val, code, rows, dinv, in, out);
+}
 
 template <class T> int upload(ks_ctx ctx, T **dst, const void *src, size_t count)
 {
@@ -75,20 +95,15 @@ template <class T> int upload(ks_ctx ctx, T **dst, const void *src, size_t count
 void ks_pc_ilu_free(KsIlu *p)
 {
   if (!p) return;
+  ks_pc_ilu_free(p->t);
   hipFree(p->blk); hipFree(p->lev); hipFree(p->val); hipFree(p->dinv); hipFree(p->code); hipFree(p->rows);
   delete p;
 }
 
-int ks_pc_ilu_build(ks_ctx ctx, int n, int row_start, int bs, const int *rp, const int *col, const double *val, KsIlu **out)
+namespace {
+// one plan on the device; the kernel that walks it may have 64 KB of dynamic LDS (the largest block)
+int upload_plan(ks_ctx ctx, int n, int bs, const ksc::IluPlan &plan, const void *kernel, const char *kname, KsIlu **out)
 {
-  static_assert(sizeof(ksc::IluBlock) == 24, "the kernel reads the host's block records as they are");
-  KS_CHECK(bs >= 64 && bs <= ksc::ILU_BS_MAX, KS_ERR_ARG_OUTOFRANGE, "block size %d (64..%d)", bs, ksc::ILU_BS_MAX);
-  ksc::IluPlan plan;
-  try { ksc::csr_ilu0_blocks(n, row_start, bs, rp, col, val, false, plan); }
-  catch (const std::exception &e) { KS_FAIL(KS_ERR_MEM, "ILU(0) block set-up: %s", e.what()); }
-  KS_CHECK(plan.status != ksc::ILU_NO_DIAGONAL, KS_ERR_ARG_WRONGSTATE, "Matrix is missing diagonal entry in local row %d (block %d of the block-Jacobi preconditioner)", plan.bad_row, plan.bad_block);
-  KS_CHECK(plan.status != ksc::ILU_ZERO_PIVOT, KS_ERR_MAT_LU_ZRPVT, "Zero pivot in the ILU(0) factorisation of block %d (local rows %d..%d), row %d", plan.bad_block,
-           plan.bad_block * bs, std::min(n, (plan.bad_block + 1) * bs) - 1, plan.bad_row);
   KsIlu *p = new KsIlu();
   p->n = n; p->bs = bs; p->nblk = (int)plan.blk.size(); p->longest_row = plan.longest_row; p->levels = (long long)plan.lev.size() / 2; p->entries = (long long)plan.val.size();
   int rc = upload(ctx, &p->blk, plan.blk.data(), plan.blk.size());
@@ -98,10 +113,27 @@ int ks_pc_ilu_build(ks_ctx ctx, int n, int row_start, int bs, const int *rp, con
   if (!rc) rc = upload(ctx, &p->rows, plan.rows.data(), plan.rows.size());
   if (!rc) rc = upload(ctx, &p->dinv, plan.dinv.data(), plan.dinv.size());
   if (!rc) { hipError_t e = ks_sync(ctx); if (e != hipSuccess) { ks_set_error("ILU(0) block set-up: %s", hipGetErrorString(e)); rc = KS_ERR_LIB; } }      // the plan's vectors go out of scope
-  // the largest block takes 64 KB of dynamic LDS
-  if (!rc) { hipError_t e = hipFuncSetAttribute((const void *)k_bjacobi_ilu_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(double) * ksc::ILU_BS_MAX);
-             if (e != hipSuccess) { ks_set_error("hipFuncSetAttribute(k_bjacobi_ilu_apply) failed: %s", hipGetErrorString(e)); rc = KS_ERR_LIB; } }
+  if (!rc) { hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(double) * ksc::ILU_BS_MAX);
+             if (e != hipSuccess) { ks_set_error("hipFuncSetAttribute(%s) failed: %s", kname, hipGetErrorString(e)); rc = KS_ERR_LIB; } }
   if (rc) { ks_pc_ilu_free(p); return rc; }
+  *out = p;
+  return KS_SUCCESS;
+}
+} // namespace
+
+int ks_pc_ilu_build(ks_ctx ctx, int n, int row_start, int bs, const int *rp, const int *col, const double *val, bool transpose, KsIlu **out)
+{
+  static_assert(sizeof(ksc::IluBlock) == 24, "the kernel reads the host's block records as they are");
+  KS_CHECK(bs >= 64 && bs <= ksc::ILU_BS_MAX, KS_ERR_ARG_OUTOFRANGE, "block size %d (64..%d)", bs, ksc::ILU_BS_MAX);
+  ksc::IluPlan plan, tplan;
+  try { ksc::csr_ilu0_blocks(n, row_start, bs, rp, col, val, false, plan, transpose ? &tplan : nullptr); }
+  catch (const std::exception &e) { KS_FAIL(KS_ERR_MEM, "ILU(0) block set-up: %s", e.what()); }
+  KS_CHECK(plan.status != ksc::ILU_NO_DIAGONAL, KS_ERR_ARG_WRONGSTATE, "Matrix is missing diagonal entry in local row %d (block %d of the block-Jacobi preconditioner)", plan.bad_row, plan.bad_block);
+  KS_CHECK(plan.status != ksc::ILU_ZERO_PIVOT, KS_ERR_MAT_LU_ZRPVT, "Zero pivot in the ILU(0) factorisation of block %d (local rows %d..%d), row %d", plan.bad_block,
+           plan.bad_block * bs, std::min(n, (plan.bad_block + 1) * bs) - 1, plan.bad_row);
+  KsIlu *p = nullptr;
+  KS_CALL(upload_plan(ctx, n, bs, plan, (const void *)k_bjacobi_ilu_apply, "k_bjacobi_ilu_apply", &p));
+  if (transpose) { const int rc = upload_plan(ctx, n, bs, tplan, (const void *)k_bjacobi_ilu_apply_t, "k_bjacobi_ilu_apply_t", &p->t); if (rc) { ks_pc_ilu_free(p); return rc; } }
   *out = p;
   return KS_SUCCESS;
 }
@@ -111,6 +143,17 @@ int ks_pc_ilu_apply(ks_ctx ctx, const KsIlu *p, const double *in, double *out)
   if (p->nblk == 0) return KS_SUCCESS;                       // a rank without rows
   hipLaunchKernelGGL(k_bjacobi_ilu_apply, dim3((unsigned)p->nblk), dim3(ILU_THREADS), sizeof(double) * (size_t)p->bs, ctx->stream,
                      p->n, p->bs, p->blk, p->lev, p->val, p->code, p->rows, p->dinv, in, out);
+  KS_HIP(hipGetLastError());
+  return KS_SUCCESS;
+}
+
+int ks_pc_ilu_apply_transpose(ks_ctx ctx, const KsIlu *p, const double *in, double *out)
+{
+  KS_CHECK(p->t, KS_ERR_PLIB, "the transposed ILU(0) plan was not built");
+  const KsIlu *t = p->t;
+  if (t->nblk == 0) return KS_SUCCESS;
+  hipLaunchKernelGGL(k_bjacobi_ilu_apply_t, dim3((unsigned)t->nblk), dim3(ILU_THREADS), sizeof(double) * (size_t)t->bs, ctx->stream,
+                     t->n, t->bs, t->blk, t->lev, t->val, t->code, t->rows, t->dinv, in, out);
   KS_HIP(hipGetLastError());
   return KS_SUCCESS;
 }

@@ -12,6 +12,11 @@
 // error (KSPSetErrorIfNotConverged, stsles.c:58). PETSc's KSP itself is external to the reference; this GMRES runs on
 // the same device kernels as the outer iteration: the Krylov basis is a BV, its Gram-Schmidt is the fused CGS of
 // ks_gs.hip, the update x += K y is BVMultVec.
+//
+// Transposed solves (ks_st_set_transpose_solves; STMatSolveTranspose stsolve.c, KSPSolveTranspose, PCApplyTranspose): P^T is applied through the
+// transposed views of A and B (shell mode) or of the assembled P (copy mode), the preconditioner through its own transpose - point Jacobi is its own,
+// the dense blocks are walked by columns, the ILU(0) blocks have a second plan of the same factors (ks_pc.hip). The KSPs are the same code with a
+// side: left-preconditioned on M^-T P^T y = M^-T b (PCApplyBAorABTranspose, PC_LEFT). STApplyTranspose_Generic (stsolve.c:107-116) sits on top.
 #include "ksgpu_internal.h"
 #include "ks_csr.h"
 #include "ks_ds.h"
@@ -49,6 +54,18 @@ __global__ void k_bjacobi_apply(long long n, int bs, const double *__restrict__ 
   }
 }
 
+// out = M^-T in: row i of out is COLUMN i of its block's inverse times the block's piece of in - the same array, walked with stride bs
+__global__ void k_bjacobi_apply_t(long long n, int bs, const double *__restrict__ binv, const double *__restrict__ in, double *__restrict__ out)
+{
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const long long b0 = i / bs * bs;
+    const double *colm = binv + b0 * bs + (i - b0);
+    double acc = 0.0;
+    for (int c = 0; c < bs && b0 + c < n; c++) acc = fma(colm[(long long)c * bs], in[b0 + c], acc);
+    out[i] = acc;
+  }
+}
+
 } // namespace
 int ksk_lincomb(ks_ctx ctx, long long n, const double *s, double a, const double *u, double b, const double *v, double *out)
 {
@@ -80,49 +97,52 @@ int linop_apply(ks_st st, double a, ks_mat A, double b, ks_mat B, bool identity_
   return lincomb(ctx, n, s, b, x, 0.0, nullptr, out);
 }
 
-// the matrix P of the table above, y = s .* P x
-int apply_P(ks_st st, const double *s, const double *x, double *out, double *tmp)
+// the matrix P of the table above, y = s .* P x; tr: y = s .* P^T x through the transposed views (assembled matrices like the ones they view)
+int apply_P(ks_st st, const double *s, const double *x, double *out, double *tmp, bool tr = false)
 {
-  if (st->Pmat) {                                            // ST_MATMODE_COPY: the assembled A - sigma B, one product
-    if (s && ks_mat_can_rowscale(st->Pmat)) return ks_mat_mult_internal(st->Pmat, x, out, s);
-    KS_CALL(ks_mat_mult_internal(st->Pmat, x, out));
+  ks_mat Pm = tr ? st->PmatT : st->Pmat, A = tr ? st->At : st->A, B = tr ? st->Bt : st->B;
+  if (Pm) {                                                  // ST_MATMODE_COPY: the assembled A - sigma B, one product
+    if (s && ks_mat_can_rowscale(Pm)) return ks_mat_mult_internal(Pm, x, out, s);
+    KS_CALL(ks_mat_mult_internal(Pm, x, out));
     return s ? lincomb(st->ctx, st->n, s, 1.0, out, 0.0, nullptr, out) : KS_SUCCESS;
   }
-  if (st->type == KS_ST_SINVERT || st->type == KS_ST_CAYLEY) return linop_apply(st, 1.0, st->A, -st->sigma, st->B, !st->B, s, x, out, tmp);
-  return linop_apply(st, 0.0, nullptr, 1.0, st->B, false, s, x, out, tmp);           // shift, nmat=2: P = B
+  if (st->type == KS_ST_SINVERT || st->type == KS_ST_CAYLEY) return linop_apply(st, 1.0, A, -st->sigma, B, !B, s, x, out, tmp);
+  return linop_apply(st, 0.0, nullptr, 1.0, B, false, s, x, out, tmp);               // shift, nmat=2: P = B
 }
 
-int bjacobi_apply(ks_st st, const double *in, double *out)
+int bjacobi_apply(ks_st st, const double *in, double *out, bool tr = false)
 {
   if (st->n == 0) return KS_SUCCESS;
   const unsigned nb = (unsigned)std::min<long long>(((long long)st->n + 255) / 256, (long long)st->ctx->num_cu * 16);
-  hipLaunchKernelGGL(k_bjacobi_apply, dim3(nb), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_bs, st->binv, in, out);
+  if (tr) hipLaunchKernelGGL(k_bjacobi_apply_t, dim3(nb), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_bs, st->binv, in, out);
+  else hipLaunchKernelGGL(k_bjacobi_apply, dim3(nb), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_bs, st->binv, in, out);
   KS_HIP(hipGetLastError());
   return KS_SUCCESS;
 }
 // out = M^-1 in for the block preconditioners: the dense inverses, or the ILU(0) factors (k_bjacobi_ilu_apply, ks_pc.hip)
-int blocks_apply(ks_st st, const double *in, double *out)
+int blocks_apply(ks_st st, const double *in, double *out, bool tr = false)
 {
-  if (st->pc_type == KS_PC_BJACOBI_ILU) return ks_pc_ilu_apply(st->ctx, st->ilu, in, out);
-  return bjacobi_apply(st, in, out);
+  if (st->pc_type == KS_PC_BJACOBI_ILU) return tr ? ks_pc_ilu_apply_transpose(st->ctx, st->ilu, in, out) : ks_pc_ilu_apply(st->ctx, st->ilu, in, out);
+  return bjacobi_apply(st, in, out, tr);
 }
-// out = M^-1 (a u + b v) with the left preconditioner M of the KSP: diag(P) (one fused kernel) or the diagonal blocks of P
-int pc_lincomb(ks_st st, double a, const double *u, double b, const double *v, double *out)
+// out = M^-1 (a u + b v) with the left preconditioner M of the KSP: diag(P) (one fused kernel) or the diagonal blocks of P; tr: M^-T (point Jacobi is its own)
+int pc_lincomb(ks_st st, double a, const double *u, double b, const double *v, double *out, bool tr = false)
 {
   if (st->pc_type == KS_PC_JACOBI) return lincomb(st->ctx, st->n, st->dinv, a, u, b, v, out);
   KS_CALL(lincomb(st->ctx, st->n, nullptr, a, u, b, v, st->pcwork));
-  return blocks_apply(st, st->pcwork, out);
+  return blocks_apply(st, st->pcwork, out, tr);
 }
-// out = M^-1 P x
-int apply_MP(ks_st st, const double *x, double *out, double *tmp)
+// out = M^-1 P x; tr: out = M^-T P^T x (PCApplyBAorABTranspose, PC_LEFT)
+int apply_MP(ks_st st, const double *x, double *out, double *tmp, bool tr = false)
 {
-  if (st->pc_type == KS_PC_JACOBI) return apply_P(st, st->dinv, x, out, tmp);
-  KS_CALL(apply_P(st, nullptr, x, st->pcwork, tmp));
-  return blocks_apply(st, st->pcwork, out);
+  if (st->pc_type == KS_PC_JACOBI) return apply_P(st, st->dinv, x, out, tmp, tr);
+  KS_CALL(apply_P(st, nullptr, x, st->pcwork, tmp, tr));
+  return blocks_apply(st, st->pcwork, out, tr);
 }
 
-// Left-preconditioned restarted GMRES for P y = rhs (KSPGMRES defaults: restart 30, classical Gram-Schmidt)
-int gmres_solve(ks_st st, const double *rhs, double *y)
+// Left-preconditioned restarted GMRES for P y = rhs (KSPGMRES defaults: restart 30, classical Gram-Schmidt); tr: for P^T y = rhs (KSPSolveTranspose),
+// the same iteration with every application of P and M^-1 on its transposed side - one solve never mixes the two
+int gmres_solve(ks_st st, const double *rhs, double *y, bool tr)
 {
   ks_ctx ctx = st->ctx; ks_bv K = st->K;
   const int m = st->restart;
@@ -131,7 +151,7 @@ int gmres_solve(ks_st st, const double *rhs, double *y)
   std::vector<double> H((size_t)(m + 1) * m, 0.0), g(m + 1, 0.0), cs(m, 0.0), sn(m, 0.0), h(m + 1, 0.0), yc(m, 0.0);
   st->solves++;
   KS_HIP(hipMemsetAsync(y, 0, sizeof(double) * std::max<long long>(n, 1), ctx->stream));
-  KS_CALL(pc_lincomb(st, 1.0, rhs, 0.0, nullptr, ks_bv_col(K, 0)));
+  KS_CALL(pc_lincomb(st, 1.0, rhs, 0.0, nullptr, ks_bv_col(K, 0), tr));
   double beta = 0.0;
   const bool split = ks_bv_orthonormalize_can_split(K);
   bool k0_normalised = false, applied0 = false;
@@ -140,7 +160,7 @@ int gmres_solve(ks_st st, const double *rhs, double *y)
     // the host learns beta while the product runs
     int lin0 = 0, late0 = 0;
     KS_CALL(ks_bv_orthonormalize_enqueue(K, 0));
-    KS_CALL(apply_MP(st, ks_bv_col(K, 0), ks_bv_col(K, 1), t1));
+    KS_CALL(apply_MP(st, ks_bv_col(K, 0), ks_bv_col(K, 1), t1, tr));
     KS_CALL(ks_bv_orthonormalize_collect(K, 0, nullptr, &beta, &lin0, &late0));
     k0_normalised = true; applied0 = !late0;
   } else KS_CALL(ks_bv_normcolumn(K, 0, KS_NORM_2, &beta));
@@ -156,7 +176,7 @@ int gmres_solve(ks_st st, const double *rhs, double *y)
     bool applied = applied0;                        // K(:, j+1) = P K(:, j) already enqueued (speculatively, during the previous iteration)
     applied0 = false;
     for (int j = 0; j < m; j++) {
-      if (!applied) KS_CALL(apply_MP(st, ks_bv_col(K, j), ks_bv_col(K, j + 1), t1));
+      if (!applied) KS_CALL(apply_MP(st, ks_bv_col(K, j), ks_bv_col(K, j + 1), t1, tr));
       applied = false;
       double hn = 0.0; int lindep = 0;
       if (split) {
@@ -167,7 +187,7 @@ int gmres_solve(ks_st st, const double *rhs, double *y)
         const bool spec = (j + 1 < m) && (its + 1 < st->max_it) && predicted > 3.0 * tol;
         int late = 0;
         KS_CALL(ks_bv_orthonormalize_enqueue(K, j + 1));
-        if (spec) KS_CALL(apply_MP(st, ks_bv_col(K, j + 1), ks_bv_col(K, j + 2), t1));
+        if (spec) KS_CALL(apply_MP(st, ks_bv_col(K, j + 1), ks_bv_col(K, j + 2), t1, tr));
         KS_CALL(ks_bv_orthonormalize_collect(K, j + 1, h.data(), &hn, &lindep, &late));
         applied = spec && !late;                    // a column completed late was multiplied unfinished: apply again
       } else KS_CALL(ks_bv_orthonormalize_coefs(K, j + 1, h.data(), &hn, &lindep));       // the 1/hn scaling rides in the final update; h, hn and the flag arrive in one host wait
@@ -194,8 +214,8 @@ int gmres_solve(ks_st st, const double *rhs, double *y)
     if (res <= tol) break;
     KS_CHECK(its < st->max_it, KS_ERR_NOT_CONVERGED, "KSPSolve has not converged: GMRES reached %d iterations, preconditioned residual %g > %g", its, res, tol);
     // restart from the true preconditioned residual
-    KS_CALL(apply_P(st, nullptr, y, t1, t2));
-    KS_CALL(pc_lincomb(st, 1.0, rhs, -1.0, t1, ks_bv_col(K, 0)));
+    KS_CALL(apply_P(st, nullptr, y, t1, t2, tr));
+    KS_CALL(pc_lincomb(st, 1.0, rhs, -1.0, t1, ks_bv_col(K, 0), tr));
     KS_CALL(ks_bv_normcolumn(K, 0, KS_NORM_2, &beta));
     st->last_rnorm = beta;
     if (beta <= tol) break;
@@ -206,7 +226,7 @@ int gmres_solve(ks_st st, const double *rhs, double *y)
 // Left-preconditioned BiCGStab for P y = rhs (KSPBCGS with PC_LEFT: the iteration runs on D^-1 P, the residual that is tested
 // is the preconditioned one, as for the GMRES above). Two operator applications per iteration, no growing basis: the
 // memory is 7 vectors whatever the iteration count. The dot products of one phase travel in one BVDotVec (one allreduce).
-int bcgs_solve(ks_st st, const double *rhs, double *y)
+int bcgs_solve(ks_st st, const double *rhs, double *y, bool tr)
 {
   ks_ctx ctx = st->ctx; ks_bv K = st->Kb;
   const long long n = st->n;
@@ -214,7 +234,7 @@ int bcgs_solve(ks_st st, const double *rhs, double *y)
   double *r = ks_bv_col(K, 0), *rh = ks_bv_col(K, 1), *p = ks_bv_col(K, 2), *v = ks_bv_col(K, 3), *s = ks_bv_col(K, 4), *t = ks_bv_col(K, 5);
   st->solves++;
   KS_HIP(hipMemsetAsync(y, 0, sizeof(double) * std::max<long long>(n, 1), ctx->stream));
-  KS_CALL(pc_lincomb(st, 1.0, rhs, 0.0, nullptr, r));                   // r = D^-1 b (zero initial guess)
+  KS_CALL(pc_lincomb(st, 1.0, rhs, 0.0, nullptr, r, tr));                   // r = D^-1 b (zero initial guess)
   double beta0 = 0.0;
   KS_CALL(ks_bv_normcolumn(K, 0, KS_NORM_2, &beta0));
   st->last_rnorm = beta0;
@@ -233,13 +253,13 @@ int bcgs_solve(ks_st st, const double *rhs, double *y)
     const double bt = (rho_new / rho) * (alpha / omega);
     KS_CALL(lincomb(ctx, n, nullptr, 1.0, p, -omega, v, p));                         // p = r + beta (p - omega v)
     KS_CALL(lincomb(ctx, n, nullptr, bt, p, 1.0, r, p));
-    KS_CALL(apply_MP(st, p, v, t1));                                                // v = D^-1 P p
+    KS_CALL(apply_MP(st, p, v, t1, tr));                                                // v = D^-1 P p
     KS_CALL(ks_bv_set_active_columns(K, 3, 4));
     KS_CALL(ks_bv_dotvec(K, rh, d));                                                 // (rhat, v)
     KS_CHECK(d[0] != 0.0, KS_ERR_NOT_CONVERGED, "KSPSolve has not converged: BiCGStab breakdown ((rhat,v) = 0)");
     alpha = rho_new / d[0];
     KS_CALL(lincomb(ctx, n, nullptr, 1.0, r, -alpha, v, s));                         // s = r - alpha v
-    KS_CALL(apply_MP(st, s, t, t1));                                                // t = D^-1 P s
+    KS_CALL(apply_MP(st, s, t, t1, tr));                                                // t = D^-1 P s
     KS_CALL(ks_bv_set_active_columns(K, 4, 6));
     KS_CALL(ks_bv_dotvec(K, t, d));                                                  // (s,t), (t,t) in one reduction
     omega = d[1] != 0.0 ? d[0] / d[1] : 0.0;
@@ -255,7 +275,7 @@ int bcgs_solve(ks_st st, const double *rhs, double *y)
   }
   return KS_SUCCESS;
 }
-int inner_solve(ks_st st, const double *rhs, double *y) { return st->ksp_type == KS_KSP_BCGS ? bcgs_solve(st, rhs, y) : gmres_solve(st, rhs, y); }
+int inner_solve(ks_st st, const double *rhs, double *y, bool tr = false) { return st->ksp_type == KS_KSP_BCGS ? bcgs_solve(st, rhs, y, tr) : gmres_solve(st, rhs, y, tr); }
 
 int st_shell_mult(void *user, const double *x, double *y) { return ks_st_apply_internal((ks_st)user, x, y); }
 int st_shell_mult_transpose(void *user, const double *x, double *y) { return ks_st_apply_transpose_internal((ks_st)user, x, y); }
@@ -337,7 +357,7 @@ static int bjacobi_ilu_setup(ks_st st)
   std::vector<int> rp, col; std::vector<double> val;
   const int *prp; const int *pcol; const double *pval;
   KS_CALL(pc_block_source(st, rp, col, val, &prp, &pcol, &pval));
-  KS_CALL(ks_pc_ilu_build(st->ctx, st->n, M0->row_start, st->pc_bs, prp, pcol, pval, &st->ilu));
+  KS_CALL(ks_pc_ilu_build(st->ctx, st->n, M0->row_start, st->pc_bs, prp, pcol, pval, st->tsolves, &st->ilu));
   if (st->pcwork) { hipFree(st->pcwork); st->pcwork = nullptr; }
   KS_HIP(hipMalloc(&st->pcwork, sizeof(double) * std::max(st->n, 1)));
   return KS_SUCCESS;
@@ -361,6 +381,13 @@ int ks_st_setup_internal(ks_st st)
   if (st->Pmat) { ks_mat_destroy(st->Pmat); st->Pmat = nullptr; }           // the assembled P of an earlier shift / type / mode
   if (st->ilu) { ks_pc_ilu_free(st->ilu); st->ilu = nullptr; }              // and its ILU(0) blocks
   const bool need_solve = (st->type == KS_ST_SINVERT) || (st->type == KS_ST_CAYLEY) || (st->type == KS_ST_SHIFT && B);
+  st->At = st->Bt = st->PmatT = nullptr;                                      // views: freed with the matrices they view
+  if (need_solve && st->tsolves) {
+    // the transposed side of P and of the operator's other factor (B^T, (A + nu B)^T): MatTranspose of the kept arrays, one rank
+    KS_CHECK(ctx->comm.size == 1, KS_ERR_SUP, "transposed ST solves (ks_st_set_transpose_solves) run on one rank: the transpose of a row-sharded matrix is a redistribution");
+    KS_CALL(ks_mat_create_transpose(A, &st->At));
+    if (B) KS_CALL(ks_mat_create_transpose(B, &st->Bt));
+  }
   if (st->W) { int wn = 0; ks_bv_get_sizes(st->W, &wn, nullptr, nullptr, nullptr); if (wn != A->n) { ks_bv_destroy(st->W); ks_bv_destroy(st->K); ks_bv_destroy(st->Kb); st->W = st->K = st->Kb = nullptr; if (st->dinv) hipFree(st->dinv); st->dinv = nullptr; } }
   if (!st->W) KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 3, 0, &st->W));
   if (need_solve) {
@@ -375,7 +402,8 @@ int ks_st_setup_internal(ks_st st)
     if (st->matmode == KS_ST_MATMODE_COPY && (st->type == KS_ST_SINVERT || st->type == KS_ST_CAYLEY)) {
       // STMatMAXPY_Private, ST_MATMODE_COPY (stsolve.c:603-631): P = A - sigma B assembled (nmat = 1: MatShift); a zero shift takes A itself
       // there (:611-614) - here a copy of it, so that the ST owns what it destroys
-      KS_CALL(ks_mat_create_axpy(A, -st->sigma, B, 0u, &st->Pmat));
+      KS_CALL(ks_mat_create_axpy(A, -st->sigma, B, st->tsolves ? (unsigned)KS_MAT_KEEP_CSR : 0u, &st->Pmat));     // its transposed view needs its arrays
+      if (st->tsolves) KS_CALL(ks_mat_create_transpose(st->Pmat, &st->PmatT));
       KS_CALL(ks_mat_get_diagonal_internal(st->Pmat, da));
       hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 1.0, da, 0.0, (const double *)nullptr, st->dinv);
     } else if (st->type == KS_ST_SINVERT || st->type == KS_ST_CAYLEY) {
@@ -531,11 +559,50 @@ extern "C" int ks_st_pc_apply(ks_st st, const double *x_dev, double *y_dev)     
   if (st->pc_type == KS_PC_JACOBI) return lincomb(st->ctx, st->n, st->dinv, 1.0, x_dev, 0.0, nullptr, y_dev);
   return blocks_apply(st, x_dev, y_dev);
 }
-// STApplyHermitianTranspose_Generic (stsolve.c:153-162), real scalars: only the branch without a solve (st->M alone: shift with one matrix)
+extern "C" int ks_st_set_transpose_solves(ks_st st, int enable)
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  if (st->tsolves != (enable != 0)) { st->tsolves = enable != 0; st->ready = false; }
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_get_transpose_solves(ks_st st, int *enable) { KS_CHECK(st && enable, KS_ERR_ARG_NULL, "NULL argument"); *enable = st->tsolves ? 1 : 0; return KS_SUCCESS; }
+// the checks the two transposed entries share; `what` names the caller
+static int transpose_entry(ks_st st, const double *x_dev, double *y_dev, const char *what)
+{
+  KS_CHECK(st && x_dev && y_dev, KS_ERR_ARG_NULL, "NULL argument");
+  KS_CHECK(x_dev != y_dev, KS_ERR_ARG_IDN, "x and y must be different vectors");
+  KS_CHECK(st->A, KS_ERR_ORDER, "STSetMatrices must be called first");
+  KS_CHECK(st->type != KS_ST_SHIFT || st->B, KS_ERR_ORDER, "this transformation has no linear solve, so no %s (STSHIFT with one matrix)", what);
+  KS_CHECK(st->tsolves, KS_ERR_SUP, "%s needs the transposed side of the solves: ks_st_set_transpose_solves(st, 1) before the set-up", what);
+  KS_HIP(hipSetDevice(st->ctx->device));
+  if (!st->ready) KS_CALL(ks_st_setup_internal(st));
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_matsolve_transpose(ks_st st, const double *b_dev, double *y_dev)      // STMatSolveTranspose stsolve.c (KSPSolveTranspose on STGetKSP)
+{
+  KS_CALL(transpose_entry(st, b_dev, y_dev, "STMatSolveTranspose"));
+  return inner_solve(st, b_dev, y_dev, true);
+}
+extern "C" int ks_st_pc_apply_transpose(ks_st st, const double *x_dev, double *y_dev)      // PCApplyTranspose on KSPGetPC(STGetKSP)
+{
+  KS_CALL(transpose_entry(st, x_dev, y_dev, "PCApplyTranspose"));
+  if (st->pc_type == KS_PC_JACOBI) return lincomb(st->ctx, st->n, st->dinv, 1.0, x_dev, 0.0, nullptr, y_dev);
+  return blocks_apply(st, x_dev, y_dev, true);
+}
+// STApplyTranspose_Generic (stsolve.c:107-116; the Hermitian form :153-162 with real scalars): y = M^T P^-T x. The branch without a solve (st->M alone:
+// shift with one matrix) always; the ones with a solve when the ST prepares transposed solves (ks_st_set_transpose_solves)
 int ks_st_apply_transpose_internal(ks_st st, const double *x, double *y)
 {
   KS_CALL(ks_st_setup_internal(st));
-  KS_CHECK(st->type == KS_ST_SHIFT && !st->B, KS_ERR_SUP, "STApplyHermitianTranspose is built for STSHIFT with one matrix (the others need a solve with the transposed matrix)");
+  KS_CHECK((st->type == KS_ST_SHIFT && !st->B) || st->tsolves, KS_ERR_SUP, "STApplyHermitianTranspose is built for STSHIFT with one matrix (the others need a solve with the transposed matrix: ks_st_set_transpose_solves)");
+  if (st->type != KS_ST_SHIFT || st->B) {
+    double *w = ks_bv_col(st->W, 0), *t1 = ks_bv_col(st->W, 1);
+    if (st->type == KS_ST_SINVERT && !st->B) return inner_solve(st, x, y, true);                       // y = P^-T x
+    KS_CALL(inner_solve(st, x, w, true));                                                              // w = P^-T x
+    if (st->type == KS_ST_SINVERT) return ks_mat_mult_internal(st->Bt, w, y);                          // y = B^T w
+    if (st->type == KS_ST_CAYLEY) return linop_apply(st, 1.0, st->At, st->nu, st->Bt, !st->Bt, nullptr, w, y, t1);      // y = (A + nu B)^T w
+    return linop_apply(st, 1.0, st->At, -st->sigma, st->Bt, false, nullptr, w, y, t1);                 // shift, two matrices: P = B, y = (A - sigma B)^T w
+  }
   KS_CALL(ks_mat_mult_transpose_internal(st->A, x, y));
   if (st->sigma != 0.0) KS_CALL(ksk_lincomb(st->ctx, st->n, nullptr, 1.0, y, -st->sigma, x, y));      // (A - sigma I)^T x
   return KS_SUCCESS;

@@ -252,8 +252,10 @@ int ks_mat_norm_inf_local(ks_mat A, double *val);           // max row sum of |a
 
 // ---- block Jacobi with ILU(0) blocks (ks_pc.hip): factors and level schedule from CSR arrays with global columns, y = U^-1 L^-1 x ----
 struct KsIlu;
-int ks_pc_ilu_build(ks_ctx ctx, int n, int row_start, int bs, const int *rp, const int *col, const double *val, KsIlu **out);
+// transpose: also the plan of the transposed triangles of the same factors, y = L^-T U^-T x (the device bytes of the factors double)
+int ks_pc_ilu_build(ks_ctx ctx, int n, int row_start, int bs, const int *rp, const int *col, const double *val, bool transpose, KsIlu **out);
 int ks_pc_ilu_apply(ks_ctx ctx, const KsIlu *p, const double *in, double *out);      // enqueued; in != out
+int ks_pc_ilu_apply_transpose(ks_ctx ctx, const KsIlu *p, const double *in, double *out);      // enqueued; in != out; needs the transposed plan
 void ks_pc_ilu_free(KsIlu *p);
 
 // ---- ST: spectral transformation (ks_st.hip) ----------------------------------------------------
@@ -277,6 +279,10 @@ struct ks_st_s {
   int matmode = KS_ST_MATMODE_SHELL;          // STSetMatMode: how P = A - sigma B exists (shell: applied term by term; copy: assembled, stsolve.c:603-631)
   ks_mat Pmat = nullptr;                      // ST_MATMODE_COPY: the assembled P (owned)
   ks_mat op = nullptr;                        // shell matrix whose MatMult is STApply
+  // ks_st_set_transpose_solves: set-up also prepares P^T (transposed views of A and B, or of the assembled P) and the transposed preconditioner.
+  // The views belong to the matrices they view (ks_mat_create_transpose); nothing here is allocated with the switch off.
+  bool tsolves = false;
+  ks_mat At = nullptr, Bt = nullptr, PmatT = nullptr;
   int n = 0; bool ready = false;
   long long solves = 0, its = 0; double last_rnorm = 0.0;
 };
