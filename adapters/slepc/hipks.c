@@ -582,7 +582,8 @@ static PetscErrorCode MatMult_HIPKS(Mat S,Vec x,Vec y)
 }
 
 /* MATOP_MULT_TRANSPOSE (what EPS_BALANCE_TWOSIDE asks of the operator, epsdefault.c:409): the library builds the transpose once from the CSR arrays
-   the matrix keeps (one rank; on more ranks it returns PETSC_ERR_SUP) */
+   the matrix keeps; on more ranks (the matrix is created with KS_MAT_SHARDED_TRANSPOSE) it is MatMultTranspose_MPIAIJ's scheme on the library's
+   halo plan: transposed off-diagonal block, transposed diagonal block, the forward scatter in reverse with ADD */
 static PetscErrorCode MatMultTranspose_HIPKS(Mat S,Vec x,Vec y)
 {
   MatHIPKS          *c;
@@ -660,7 +661,7 @@ SLEPC_EXTERN PetscErrorCode MatCreateHIPKSFromAIJ(Mat A,Mat *S)
   PetscCallMPI(MPI_Comm_size(comm,&size));
   c->comm.comm = comm;
   if (size>1) KS(ks_comm_set_ops(c->kctx,(int)rank,(int)size,&SlepcKsMpiOps,&c->comm));
-  KS(ks_mat_create_csr_flags(c->kctx,(int)nloc,(int)rstart,(int)N,ia,ja,aa,KS_MAT_KEEP_CSR,&c->A));   /* the arrays stay with the matrix: MatMultTranspose, MatAXPY */
+  KS(ks_mat_create_csr_flags(c->kctx,(int)nloc,(int)rstart,(int)N,ia,ja,aa,KS_MAT_KEEP_CSR|KS_MAT_SHARDED_TRANSPOSE,&c->A));   /* the arrays stay with the matrix: MatMultTranspose (also across ranks), MatAXPY */
   PetscCall(PetscFree3(ia,ja,aa));
   PetscCall(MatCreateShell(comm,nloc,nloc,N,N,c,S));
   PetscCall(MatShellSetOperation(*S,MATOP_MULT,(void(*)(void))MatMult_HIPKS));

@@ -176,14 +176,20 @@ int ks_mat_create_csr(ks_ctx ctx, int n_local, int row_start, int n_global,
                       const int *rowptr, const int *col, const double *val, ks_mat *A);
 /* The same with options. KS_MAT_KEEP_CSR: the matrix keeps a host copy of the arrays it was created from, as a PETSc AIJ Mat keeps its
    own - what MatDuplicate / MatAXPY need later (ks_mat_create_axpy, ST_MATMODE_COPY); without it only the layout the product runs on
-   survives the assembly. Matrices read by ks_mat_load_petsc_binary keep theirs. */
+   survives the assembly. Matrices read by ks_mat_load_petsc_binary keep theirs.
+   KS_MAT_SHARDED_TRANSPOSE: a row-sharded matrix (more than one rank) gets a transposed product: ks_mat_mult_transpose and
+   ks_mat_create_transpose work on it instead of returning KS_ERR_SUP. Needs KS_MAT_KEEP_CSR (KS_ERR_ARG_INCOMP without it); the matrix also keeps
+   its ghost list and pack list on the host, and the plan and its device buffers are built at the first transposed product. On one rank the
+   flag changes nothing. Without it nothing changes on any number of ranks. */
 #define KS_MAT_KEEP_CSR 1u
+#define KS_MAT_SHARDED_TRANSPOSE 2u
 int ks_mat_create_csr_flags(ks_ctx ctx, int n_local, int row_start, int n_global,
                             const int *rowptr, const int *col, const double *val, unsigned flags, ks_mat *A);
 /* P = A + alpha B as a new matrix: MatDuplicate(A,MAT_COPY_VALUES,&P) + MatAXPY(P,alpha,B,DIFFERENT_NONZERO_PATTERN), B == NULL:
    MatShift(P,alpha) - the assembly of A - sigma B in ST_MATMODE_COPY (src/sys/classes/st/interface/stsolve.c:611-626). Entry by
    entry p_ij = a_ij + (alpha b_ij); rows with ascending columns come out ascending. A and B must hold their CSR arrays
-   (KS_MAT_KEEP_CSR; KS_ERR_ORDER otherwise) and the same row block. flags as above, for P. */
+   (KS_MAT_KEEP_CSR; KS_ERR_ORDER otherwise) and the same row block. flags as above, for P; when every operand was created with
+   KS_MAT_SHARDED_TRANSPOSE (more than one rank), P gets that flag and KS_MAT_KEEP_CSR whatever flags says. */
 int ks_mat_create_axpy(ks_mat A, double alpha, ks_mat B, unsigned flags, ks_mat *P);
 /* Synthetic generators that build the SAME CSR arrays directly in device memory (bench inputs):
    3-D 7-pt Laplacian of ex19.c:47-78 (rows of z-planes [z0,z0+nz_local) of an nx*ny*nz grid) and
@@ -230,6 +236,11 @@ int ks_mat_mult(ks_mat A, const double *x_dev, double *y_dev);
 /* MatMultTranspose: y = A^T x. An assembled matrix builds its transpose on first use (MatTranspose on the host from the kept CSR arrays:
    KS_MAT_KEEP_CSR, KS_ERR_ORDER otherwise; one rank - the transpose of a row-sharded matrix is a redistribution, KS_ERR_SUP) and multiplies
    with it like any other matrix; a shell matrix needs ks_mat_shell_set_mult_transpose (MATOP_MULT_TRANSPOSE, as ex9.c:123 sets it).
+   A row-sharded matrix created with KS_MAT_SHARDED_TRANSPOSE has the product without a redistribution (MatMultTranspose_MPIAIJ): the transposed
+   off-diagonal block times the local x into a ghost-length buffer, the transposed diagonal block (its own device layout) times x into y, and
+   the forward halo run in reverse - always through the communicator's exchange, also when KS_HALO_PEER is active - after which every listed
+   row adds what the other ranks sent. Summation order of an entry of y, fixed: first the diagonal block's sum, in its layout's order, then the
+   contributions of the other ranks in ascending rank. No atomics: the same bits on every run. Enqueued, no host wait of the library's own.
    Used by the two-sided balancing (EPSBuildBalance_Krylov epsdefault.c:402-411). */
 int ks_mat_mult_transpose(ks_mat A, const double *x_dev, double *y_dev);
 int ks_mat_shell_set_mult_transpose(ks_mat A, ks_shell_mult_fn mult_transpose);
@@ -238,7 +249,11 @@ int ks_mat_shell_set_mult_transpose(ks_mat A, ks_shell_mult_fn mult_transpose);
    conditions: KS_MAT_KEEP_CSR or KS_ERR_ORDER, one rank or KS_ERR_SUP), an assembled matrix in its own device layout - Krylov runs are enqueued
    ahead through it and ks_mat_mult on it is bit for bit ks_mat_mult_transpose(A). Shell A: a shell over the transposed callback (KS_ERR_SUP
    without one) with the same enqueue-only flag. The view does not own A and A does not wait for it: destroy the view (ks_mat_destroy) before
-   A; destroying A first and using or destroying the view afterwards is the caller's error. */
+   A; destroying A first and using or destroying the view afterwards is the caller's error.
+   Row-sharded A created with KS_MAT_SHARDED_TRANSPOSE: the view is the transposed diagonal block with the plan of the reverse exchange; its
+   ks_mat_mult is ks_mat_mult_transpose(A) as described there, ks_mat_get_layout reports the transposed diagonal block's layout,
+   ks_mat_get_diagonal answers with A's diagonal, ks_mat_mult_multi goes column by column, ks_mat_norm_inf returns KS_ERR_SUP (it would be a
+   1-norm of A across ranks). Not collective: the plan is built from what the rank holds. */
 int ks_mat_create_transpose(ks_mat A, ks_mat *At);
 int ks_mat_mult_host(ks_mat A, const double *x_host, double *y_host);  /* convenience for tests (single rank) */
 /* MatMatMult / MatProductNumeric(AB) with a dense column-major block: Y(:,j) = A X(:,j), j < ncols (X(:,j) at X_dev + j*ldx, Y(:,j) at
@@ -457,7 +472,9 @@ int ks_eps_get_stats(ks_eps eps, long long *arnoldi_steps, long long *gs_passes,
      - the extraction is harmonic
      - the true residual is asked for
      - a deflation space is set
-     - the context has more than one rank
+     - the context has more than one rank and the operator has no transposed product across ranks: that takes a matrix created with
+       KS_MAT_SHARDED_TRANSPOSE, STSHIFT (any shift) and no B matrix; transposed ST solves are one rank, so sinvert, Cayley and B stay refused
+       there. Every rank refuses at the same point, before any collective. Left eigenvectors are returned as each rank's local part.
    Without the flag ks_eps_get_left_eigenvector returns the right eigenvector for KS_EPS_HEP / KS_EPS_GHEP (the left one of a symmetric problem)
    and KS_ERR_ARG_WRONGSTATE for a non-symmetric one. */
 int ks_eps_set_two_sided(ks_eps eps, int twosided);

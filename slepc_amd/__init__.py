@@ -232,8 +232,10 @@ class Mat:
         self.n, self.N, self.nnz = n.value, N.value, nnz.value
 
     @classmethod
-    def from_csr(cls, ctx, rowptr, col, val, row_start=0, n_global=None, keep_csr=False):
-        """keep_csr: KS_MAT_KEEP_CSR - the matrix keeps the arrays it was created from (MatAXPY, ST_MATMODE_COPY)."""
+    def from_csr(cls, ctx, rowptr, col, val, row_start=0, n_global=None, keep_csr=False, sharded_transpose=False):
+        """keep_csr: KS_MAT_KEEP_CSR - the matrix keeps the arrays it was created from (MatAXPY, ST_MATMODE_COPY).
+        sharded_transpose: KS_MAT_SHARDED_TRANSPOSE - a row-sharded matrix gets a transposed product (mult_transpose, transpose_view, two-sided
+        solves and two-sided balancing across ranks); needs keep_csr. On one rank it changes nothing."""
         rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
         col = np.ascontiguousarray(col, dtype=np.int32)
         val = _f64(val)
@@ -241,11 +243,12 @@ class Mat:
         if n_global is None:
             n_global = n
         h = C.c_void_p()
-        _lib.check(ctx.L.ks_mat_create_csr_flags(ctx.h, n, row_start, n_global, _pi(rowptr), _pi(col), _p(val), 1 if keep_csr else 0, C.byref(h)))
+        _lib.check(ctx.L.ks_mat_create_csr_flags(ctx.h, n, row_start, n_global, _pi(rowptr), _pi(col), _p(val), (1 if keep_csr else 0) | (2 if sharded_transpose else 0), C.byref(h)))
         return cls(ctx, h)
 
     def axpy_new(self, alpha, B=None, keep_csr=False):
-        """MatDuplicate(self) + MatAXPY(P, alpha, B, DIFFERENT_NONZERO_PATTERN); B None: MatShift(P, alpha)."""
+        """MatDuplicate(self) + MatAXPY(P, alpha, B, DIFFERENT_NONZERO_PATTERN); B None: MatShift(P, alpha). P has a transposed product across
+        ranks (and keeps its arrays) when every operand was created with sharded_transpose (ks_mat_create_axpy)."""
         h = C.c_void_p()
         _lib.check(self.ctx.L.ks_mat_create_axpy(self.h, alpha, None if B is None else B.h, 1 if keep_csr else 0, C.byref(h)))
         return Mat(self.ctx, h)
@@ -312,9 +315,9 @@ class Mat:
         _lib.check(self.ctx.L.ks_mat_mult_transpose(self.h, C.c_void_p(x_ptr), C.c_void_p(y_ptr)))
 
     def mult_transpose(self, x):
-        """y = A^T x with host vectors (test convenience, single rank)."""
+        """y = A^T x with host vectors (test convenience; x and y are this rank's rows)."""
         x = _f64(x)
-        W = BV(self.ctx, len(x), 2)
+        W = BV(self.ctx, len(x), 2, N=self.N)
         W.set_column(0, x)
         self.mult_transpose_dev(W.column_ptr(0), W.column_ptr(1))
         return W.column(1)

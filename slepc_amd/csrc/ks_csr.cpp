@@ -84,6 +84,41 @@ void csr_transpose(int nrows, int ncols, const int *rp, const int *col, const do
   for (int r = 0; r < nrows; r++)
     for (int p = rp[r]; p < rp[r + 1]; p++) { const int q = cur[col[p]]++; colt[q] = r; valt[q] = val[p]; }
 }
+void sharded_transpose_plan(int n, int row_start, const int *rp, const int *col, const double *val, int nghost, const int *ghosts,
+                            int nsend, const int *send_idx, ShardedTransposePlan &out)
+{
+  out = ShardedTransposePlan();
+  // split the rows as the assembly does: local columns to the diagonal block, the others to their position in the sorted ghost list
+  std::vector<int> rpd((size_t)n + 1, 0), rpo((size_t)n + 1, 0), cd, co; std::vector<double> vd, vo;
+  for (int r = 0; r < n; r++) {
+    for (int p = rp[r]; p < rp[r + 1]; p++) {
+      const long long c = (long long)col[p] - row_start;
+      if (c >= 0 && c < n) { cd.push_back((int)c); vd.push_back(val[p]); }
+      else { co.push_back((int)(std::lower_bound(ghosts, ghosts + nghost, col[p]) - ghosts)); vo.push_back(val[p]); }
+    }
+    rpd[r + 1] = (int)cd.size(); rpo[r + 1] = (int)co.size();
+  }
+  csr_transpose(n, n, rpd.data(), cd.data(), vd.data(), out.d_rp, out.d_col, out.d_val);
+  csr_transpose(n, nghost, rpo.data(), co.data(), vo.data(), out.o_rp, out.o_row, out.o_val);
+  // the inverse of send_idx, by the same stable counting sort: positions of a row come out ascending
+  std::vector<int> cnt((size_t)n + 1, 0);
+  for (int e = 0; e < nsend; e++) cnt[(size_t)send_idx[e] + 1]++;
+  out.acc_ptr.assign(1, 0);
+  std::vector<int> slot((size_t)n, -1);
+  for (int r = 0; r < n; r++) if (cnt[(size_t)r + 1]) { slot[r] = (int)out.acc_rows.size(); out.acc_rows.push_back(r); out.acc_ptr.push_back(out.acc_ptr.back() + cnt[(size_t)r + 1]); }
+  out.acc_pos.resize((size_t)nsend);
+  std::vector<int> cur(out.acc_ptr.begin(), out.acc_ptr.end() - 1);
+  for (int e = 0; e < nsend; e++) out.acc_pos[(size_t)cur[slot[send_idx[e]]]++] = e;
+}
+void sharded_transpose_local_host(const ShardedTransposePlan &p, int n, int nghost, const double *x, double *rsend, double *y)
+{
+  for (int g = 0; g < nghost; g++) { double acc = 0.0; for (int q = p.o_rp[g]; q < p.o_rp[g + 1]; q++) acc = __builtin_fma(p.o_val[q], x[p.o_row[q]], acc); rsend[g] = acc; }
+  for (int c = 0; c < n; c++) { double acc = 0.0; for (int q = p.d_rp[c]; q < p.d_rp[c + 1]; q++) acc = __builtin_fma(p.d_val[q], x[p.d_col[q]], acc); y[c] = acc; }
+}
+void sharded_transpose_add_host(const ShardedTransposePlan &p, const double *rrecv, double *y)
+{
+  for (size_t i = 0; i < p.acc_rows.size(); i++) { double s = y[p.acc_rows[i]]; for (int q = p.acc_ptr[i]; q < p.acc_ptr[i + 1]; q++) s = s + rrecv[p.acc_pos[q]]; y[p.acc_rows[i]] = s; }
+}
 void csr_window_plan(int n, const int *rp, const int *col, int block_rows, int max_segments, int pad, WindowPlan &out)
 {
   out = WindowPlan();
@@ -266,6 +301,34 @@ void ksc_csr_transpose(int n, const int *rp, const int *col, const double *val, 
   std::vector<int> r, c; std::vector<double> v;
   ksc::csr_transpose(n, n, rp, col, val, r, c, v);
   std::copy(r.begin(), r.end(), rpt); std::copy(c.begin(), c.end(), colt); std::copy(v.begin(), v.end(), valt);
+}
+// test hook: one rank's plan of the transposed product of a row-sharded matrix. The arrays have room for: d_rp n + 1, d_col / d_val and o_row / o_val
+// nnz each, o_rp nghost + 1, acc_rows nsend, acc_ptr nsend + 1, acc_pos nsend. info: entries of the two transposed blocks, listed rows.
+void ksc_sharded_transpose_plan(int n, int row_start, const int *rp, const int *col, const double *val, int nghost, const int *ghosts, int nsend, const int *send_idx,
+                                int *d_rp, int *d_col, double *d_val, int *o_rp, int *o_row, double *o_val, int *acc_rows, int *acc_ptr, int *acc_pos, long long *info)
+{
+  ksc::ShardedTransposePlan p;
+  ksc::sharded_transpose_plan(n, row_start, rp, col, val, nghost, ghosts, nsend, send_idx, p);
+  std::copy(p.d_rp.begin(), p.d_rp.end(), d_rp); std::copy(p.d_col.begin(), p.d_col.end(), d_col); std::copy(p.d_val.begin(), p.d_val.end(), d_val);
+  std::copy(p.o_rp.begin(), p.o_rp.end(), o_rp); std::copy(p.o_row.begin(), p.o_row.end(), o_row); std::copy(p.o_val.begin(), p.o_val.end(), o_val);
+  std::copy(p.acc_rows.begin(), p.acc_rows.end(), acc_rows); std::copy(p.acc_ptr.begin(), p.acc_ptr.end(), acc_ptr); std::copy(p.acc_pos.begin(), p.acc_pos.end(), acc_pos);
+  info[0] = (long long)p.d_col.size(); info[1] = (long long)p.o_row.size(); info[2] = (long long)p.acc_rows.size();
+}
+// test hooks: the host walk of that plan for one rank (the plan is built again from the same inputs): first the two local products - rsend (nghost) is
+// what the rank sends back to the owners of its ghosts, y (n) the transposed diagonal block's part - then, with the receive buffer the reverse
+// exchange filled (nsend), the accumulation into y
+void ksc_sharded_transpose_local(int n, int row_start, const int *rp, const int *col, const double *val, int nghost, const int *ghosts, const double *x, double *rsend, double *y)
+{
+  ksc::ShardedTransposePlan p;
+  ksc::sharded_transpose_plan(n, row_start, rp, col, val, nghost, ghosts, 0, nullptr, p);
+  ksc::sharded_transpose_local_host(p, n, nghost, x, rsend, y);
+}
+void ksc_sharded_transpose_add(int n, int nsend, const int *send_idx, const double *rrecv, double *y)
+{
+  ksc::ShardedTransposePlan p;
+  std::vector<int> rp((size_t)n + 1, 0);                                                     // an empty matrix: only the accumulate list is needed here
+  ksc::sharded_transpose_plan(n, 0, rp.data(), nullptr, nullptr, 0, nullptr, nsend, send_idx, p);
+  ksc::sharded_transpose_add_host(p, rrecv, y);
 }
 // test hook: P = A + alpha B (B arrays NULL: the identity); returns nnz(P), fills rp always and col/val when they are given (capacity cap entries)
 long long ksc_csr_axpy(int n, int row_start, const int *rpa, const int *ca, const double *va, double alpha, const int *rpb, const int *cb, const double *vb,

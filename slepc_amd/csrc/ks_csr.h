@@ -16,6 +16,28 @@ bool csr_axpy(int n, int row_start, const int *rpa, const int *ca, const double 
 // ascending row order of A (sorted columns out whatever the order inside A's rows; repeated entries of A stay separate entries).
 void csr_transpose(int nrows, int ncols, const int *rp, const int *col, const double *val, std::vector<int> &rpt, std::vector<int> &colt, std::vector<double> &valt);
 
+// The plan of y = A^T x for a row-sharded A (KS_MAT_SHARDED_TRANSPOSE), rank by rank and without communication: MatMultTranspose_MPIAIJ's three
+// steps on this library's halo plan. From the rank's rows (global columns), its sorted ghost list (the distinct columns other ranks own) and
+// send_idx (the local rows it packs for its peers in a forward product, peer after peer in ascending rank):
+//   d_*    the transposed DIAGONAL block (entries whose column this rank owns), n x n with local indices, by the counting sort of csr_transpose:
+//          row c lists the entries of column c by ascending original row, duplicates in their original order.
+//   o_*    the transposed OFF-DIAGONAL block, a CSR of nghost rows: row g lists the local rows of A that hold ghost column g (ascending, stable)
+//          with their values. o_rp * x[o_row] summed per row is what the owner of ghost g has to add to its y.
+//   acc_*  the inverse of send_idx. The reverse exchange delivers, at position e of the receive buffer, a peer's sum for local row send_idx[e].
+//          acc_rows: the distinct local rows any peer reads, ascending; acc_pos[acc_ptr[i] .. acc_ptr[i+1]) the positions of row acc_rows[i],
+//          ascending - and so by ascending peer rank, the buffer being ordered by peer. acc_pos is a permutation of 0 .. nsend-1.
+struct ShardedTransposePlan {
+  std::vector<int> d_rp, d_col; std::vector<double> d_val;
+  std::vector<int> o_rp, o_row; std::vector<double> o_val;
+  std::vector<int> acc_rows, acc_ptr, acc_pos;
+};
+void sharded_transpose_plan(int n, int row_start, const int *rp, const int *col, const double *val, int nghost, const int *ghosts,
+                            int nsend, const int *send_idx, ShardedTransposePlan &out);
+// what the device runs, on the host, for one rank: rsend[g] = sum of o_val * x[o_row] over ghost row g (fma, stored order) and y = (diagonal block)^T x
+// (fma, stored order); then, once the exchange has filled rrecv, y[acc_rows[i]] += rrecv[pos] over the row's positions in ascending order
+void sharded_transpose_local_host(const ShardedTransposePlan &p, int n, int nghost, const double *x, double *rsend, double *y);
+void sharded_transpose_add_host(const ShardedTransposePlan &p, const double *rrecv, double *y);
+
 // The plan of the windowed CSR layout (KS_MAT_LAYOUT_WINDOW; the kernel that walks it: k_spmv_window, ks_spmv.hip). Rows are cut into blocks of
 // block_rows; a block lists, ascending, the 64-double segments of x (col >> 6) its entries reference. With at most max_segments of them it is a
 // WINDOW block: its entries keep one 16-bit code each, slot * 64 + (col & 63), slot being the segment's position in the block's list. With more

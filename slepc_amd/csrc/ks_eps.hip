@@ -334,6 +334,14 @@ static int ds_synchronize(ks_eps eps, std::vector<double> *M1, std::vector<doubl
   return KS_SUCCESS;
 }
 
+// The same for values outside the DS that the two-sided variant computes with allreduces and then feeds into host arithmetic every rank must
+// repeat bit for bit (M = W^T V, the coefficients that go through its LU, the two residual norms)
+static int ds_synchronize_values(ks_eps eps, double *v, size_t count)
+{
+  if (!ks_is_multi(eps->ctx) || eps->ds_parallel != KS_DS_PARALLEL_SYNCHRONIZED) return KS_SUCCESS;
+  return ks_comm_bcast0_host(eps->ctx, v, (int)(count * sizeof(double)));
+}
+
 extern "C" int ks_eps_set_max_steps(ks_eps eps, long long s) { KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL"); eps->max_steps = s > 0 ? s : 0; return KS_SUCCESS; }
 
 // EPSStoppingBasic epsdefault.c:290-307; user functions may call it first, as ex29.c does
@@ -642,7 +650,11 @@ static int set_up(ks_eps eps, long long *passes0)
     KS_CHECK(eps->extraction == KS_EPS_RITZ, KS_ERR_SUP, "two-sided Krylov-Schur with harmonic extraction is not built");
     KS_CHECK(!eps->trueres, KS_ERR_SUP, "two-sided Krylov-Schur with the true residual is not built");
     KS_CHECK(!eps->nds, KS_ERR_SUP, "two-sided Krylov-Schur with a deflation space is not built");
-    KS_CHECK(eps->ctx->comm.size == 1, KS_ERR_SUP, "two-sided Krylov-Schur runs on one rank (the transpose of a row-sharded matrix is a redistribution)");
+    // more than one rank: the operator needs a transposed product across ranks - a matrix created with KS_MAT_SHARDED_TRANSPOSE, alone or under the
+    // ST's shift operator (STSHIFT, one matrix). Transposed ST solves across ranks are not built (ks_st.hip), so sinvert, Cayley and B stay refused.
+    // Decided from what every rank knows alike, before any collective of the set-up.
+    KS_CHECK(eps->ctx->comm.size == 1 || (ks_mat_has_transpose_across_ranks(A) && !eps->B && (!eps->st || eps->st->type == KS_ST_SHIFT)), KS_ERR_SUP,
+             "two-sided Krylov-Schur on more than one rank needs an operator with a transposed product across ranks: a matrix created with KS_MAT_SHARDED_TRANSPOSE, under STSHIFT and without B (the transpose of a row-sharded matrix is a redistribution otherwise)");
   }
   if (eps->conv == KS_EPS_CONV_NORM) KS_CALL(matrix_norms(eps));
   ks_st st = eps->st;
@@ -854,12 +866,14 @@ static int rq_update1(ks_eps eps, const std::vector<double> &M, int nv, double b
   std::vector<double> w(nv), LU((size_t)nv * nv); std::vector<int> piv(nv);
   for (int j = 0; j < nv; j++) std::copy(M.begin() + (size_t)j * ds.ld, M.begin() + (size_t)j * ds.ld + nv, LU.begin() + (size_t)j * nv);
   KS_CALL(ks_bv_dotvec(W, ks_bv_col(V, nv), w.data()));
+  KS_CALL(ds_synchronize_values(eps, w.data(), w.size()));
   const int info = ksd::lu_factor(nv, LU.data(), nv, piv.data());
   KS_CHECK(info == 0, KS_ERR_LIB, "two-sided Krylov-Schur: W^T V is singular (zero pivot %d of %d): serious breakdown of the two-sided recurrence", info, nv);
   ksd::lu_solve(nv, LU.data(), nv, piv.data(), w.data(), false);
   KS_CALL(ks_bv_multcolumn(V, -1.0, 1.0, nv, w.data()));
   for (int i = 0; i < nv; i++) ds.a(i, nv - 1) += beta * w[i];
   KS_CALL(ks_bv_dotvec(V, ks_bv_col(W, nv), w.data()));
+  KS_CALL(ds_synchronize_values(eps, w.data(), w.size()));
   ksd::lu_solve(nv, LU.data(), nv, piv.data(), w.data(), true);
   KS_CALL(ks_bv_multcolumn(W, -1.0, 1.0, nv, w.data()));
   for (int i = 0; i < nv; i++) ds.hb.a(i, nv - 1) += betat * w[i];
@@ -923,6 +937,7 @@ static int restart_loop_twosided(ks_eps eps)
     // update M, modify the Rayleigh quotients
     KS_CALL(ks_bv_set_active_columns(V, k0, nv)); KS_CALL(ks_bv_set_active_columns(W, k0, nv));
     KS_CALL(matproject_lshape(V, W, k0, nv, M.data(), ld));
+    KS_CALL(ds_synchronize_values(eps, M.data(), M.size()));
     KS_CALL(rq_update1(eps, M, nv, beta, betat));
 
     // solve projected problem
@@ -939,6 +954,7 @@ static int restart_loop_twosided(ks_eps eps)
     double norm = 0.0, norm2 = 0.0;
     KS_CALL(ks_bv_normcolumn(V, nv, KS_NORM_2, &norm));
     KS_CALL(ks_bv_normcolumn(W, nv, KS_NORM_2, &norm2));
+    { double nn[2] = {norm, norm2}; KS_CALL(ds_synchronize_values(eps, nn, 2)); norm = nn[0]; norm2 = nn[1]; }
     int marker = -1, k;
     for (k = eps->nconv; k < nv; k++) {
       double re = eps->eigr[k], im = eps->eigi[k];

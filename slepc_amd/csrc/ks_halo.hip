@@ -114,6 +114,22 @@ __global__ __launch_bounds__(256) void k_halo_unpack(HaloArgs a, double *__restr
   if (tid < a.npeers && a.recv_cnt[tid] > 0) __hip_atomic_store(a.rack[tid], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// The last step of the transposed product of a row-sharded matrix (ks_spmv.hip: mult_sharded_transpose): the reverse exchange has left, at
+// position e of rrecv, a peer's sum for local row send_idx[e]; the accumulate list (ksc::sharded_transpose_plan) is the inverse of send_idx.
+// A thread per listed row, gather form: it alone reads and writes y[row] and adds the row's positions in ascending order - ascending peer rank
+// behind the diagonal block's sum. Plain loads and stores, no atomics, nothing shared between threads: the same bits on every run. The lists
+// are read coalesced; the rows ascend, so y is touched in order; a row has at most one position per peer.
+__global__ __launch_bounds__(256) void k_halo_add(int nacc, const int *__restrict__ acc_rows, const int *__restrict__ acc_ptr, const int *__restrict__ acc_pos,
+                                                  const double *__restrict__ rrecv, double *__restrict__ y)
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nacc) return;
+  const int r = acc_rows[i], p1 = acc_ptr[i + 1];
+  double s = y[r];
+  for (int p = acc_ptr[i]; p < p1; p++) s += rrecv[acc_pos[p]];
+  y[r] = s;
+}
+
 struct HaloHello {
   int ok, pid, device, npeers, nghost, nohandle;
   unsigned long long ptr;
@@ -122,6 +138,14 @@ struct HaloHello {
 };
 
 } // namespace
+
+int ks_halo_add(hipStream_t st, int nacc, const int *acc_rows, const int *acc_ptr, const int *acc_pos, const double *rrecv, double *y)
+{
+  if (nacc <= 0) return KS_SUCCESS;
+  hipLaunchKernelGGL(k_halo_add, dim3((unsigned)((nacc + 255) / 256)), dim3(256), 0, st, nacc, acc_rows, acc_ptr, acc_pos, rrecv, y);
+  KS_HIP(hipGetLastError());
+  return KS_SUCCESS;
+}
 
 // Release in the order that keeps every remote store inside live memory: this rank's own streams are idle (the callers synchronise them), but a
 // neighbour's last unpack may still be writing its acknowledgement into THIS rank's mailbox, and the neighbours hold this mailbox mapped.

@@ -297,6 +297,7 @@ int build_halo_plan(ks_mat A, const std::vector<int> &garray)
   for (int i = 0; i < nsend; i++) { sidx[i] -= A->row_start; KS_CHECK(sidx[i] >= 0 && sidx[i] < A->n, KS_ERR_PLIB, "peer requested a row this rank does not own"); }
   KS_HIP(hipMemcpy(d_sidx, sidx.data(), sizeof(int) * nsend, hipMemcpyHostToDevice));
   A->send_idx = d_sidx; A->nsend = nsend;
+  if (A->sharded_transpose) { try { A->h_send_idx.assign(sidx.begin(), sidx.begin() + nsend); } catch (const std::exception &e) { KS_FAIL(KS_ERR_MEM, "KS_MAT_SHARDED_TRANSPOSE: %s", e.what()); } }
   KS_HIP(hipMalloc(&A->send_buf, sizeof(double) * std::max(nsend, 1)));
   KS_HIP(hipMalloc(&A->ghost, sizeof(double) * std::max(A->nghost, 1)));
   hipFree(d_g);
@@ -770,10 +771,13 @@ extern "C" int ks_mat_create_csr(ks_ctx ctx, int n_local, int row_start, int n_g
   return ks_mat_create_csr_flags(ctx, n_local, row_start, n_global, rowptr, col, val, 0u, out);
 }
 
-extern "C" int ks_mat_create_csr_flags(ks_ctx ctx, int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val, unsigned flags, ks_mat *out)
+// the one assembly path. local_only: the block is assembled as a matrix of its own whatever the communicator - no halo plan, so no collective
+// (every column must then be the rank's own): the transposed diagonal block of a row-sharded matrix
+static int mat_assemble(ks_ctx ctx, int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val, unsigned flags, bool local_only, ks_mat *out)
 {
   KS_CHECK(ctx && out, KS_ERR_ARG_NULL, "ctx/out is NULL");
-  KS_CHECK((flags & ~KS_MAT_KEEP_CSR) == 0, KS_ERR_ARG_OUTOFRANGE, "unknown matrix creation flags 0x%x", flags);
+  KS_CHECK((flags & ~(KS_MAT_KEEP_CSR | KS_MAT_SHARDED_TRANSPOSE)) == 0, KS_ERR_ARG_OUTOFRANGE, "unknown matrix creation flags 0x%x", flags);
+  KS_CHECK(!(flags & KS_MAT_SHARDED_TRANSPOSE) || (flags & KS_MAT_KEEP_CSR), KS_ERR_ARG_INCOMP, "KS_MAT_SHARDED_TRANSPOSE builds its plan from the CSR arrays of the matrix: it needs KS_MAT_KEEP_CSR");
   KS_CHECK(n_local >= 0 && row_start >= 0 && row_start + n_local <= n_global, KS_ERR_ARG_OUTOFRANGE, "bad row range [%d,%d) of %d", row_start, row_start + n_local, n_global);
   KS_CHECK(rowptr && (rowptr[n_local] == 0 || (col && val)), KS_ERR_ARG_NULL, "CSR arrays are NULL");
   KS_CHECK(rowptr[0] == 0, KS_ERR_ARG_WRONG, "rowptr[0] must be 0");
@@ -812,7 +816,13 @@ extern "C" int ks_mat_create_csr_flags(ks_ctx ctx, int n_local, int row_start, i
     KS_HIP(hipMemcpy(A->o_col, co.data(), sizeof(int) * co.size(), hipMemcpyHostToDevice));
     KS_HIP(hipMemcpy(A->o_val, vo.data(), sizeof(double) * vo.size(), hipMemcpyHostToDevice));
   }
-  int rc = build_halo_plan(A, garray);
+  A->sharded_transpose = (flags & KS_MAT_SHARDED_TRANSPOSE) && ctx->comm.size > 1 && !local_only;      // (one rank: the flag changes nothing)
+  int rc = KS_SUCCESS;
+  if (local_only) { if (!garray.empty()) { ks_set_error("a block assembled on its own has a column outside its rows"); rc = KS_ERR_PLIB; } }
+  else rc = build_halo_plan(A, garray);
+  if (!rc && A->sharded_transpose) {
+    try { A->h_ghosts = garray; } catch (const std::exception &e) { ks_set_error("KS_MAT_SHARDED_TRANSPOSE: %s", e.what()); rc = KS_ERR_MEM; }
+  }
   if (!rc) rc = compact_offdiag_rows(A);
   if (!rc) rc = choose_layout(A);
   if (rc) { ks_mat_destroy(A); return rc; }
@@ -823,6 +833,20 @@ extern "C" int ks_mat_create_csr_flags(ks_ctx ctx, int n_local, int row_start, i
   }
   *out = A;
   return KS_SUCCESS;
+}
+extern "C" int ks_mat_create_csr_flags(ks_ctx ctx, int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val, unsigned flags, ks_mat *out)
+{
+  return mat_assemble(ctx, n_local, row_start, n_global, rowptr, col, val, flags, false, out);
+}
+int ks_mat_assemble_local(ks_ctx ctx, int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val, ks_mat *out)
+{
+  return mat_assemble(ctx, n_local, row_start, n_global, rowptr, col, val, 0u, true, out);
+}
+bool ks_mat_has_transpose_across_ranks(ks_mat A)
+{
+  if (!A || A->shell_mult) return false;
+  if (A->transpose_of) A = A->transpose_of;
+  return A->sharded_transpose && A->keep_csr;
 }
 
 // MatDuplicate + MatAXPY / MatShift on the kept CSR arrays (ks_csr.cpp), then the ordinary assembly of the result
@@ -837,6 +861,8 @@ extern "C" int ks_mat_create_axpy(ks_mat A, double alpha, ks_mat B, unsigned fla
   try { fits = ksc::csr_axpy(A->n, A->row_start, A->k_rowptr.data(), A->k_col.data(), A->k_val.data(), alpha, B ? B->k_rowptr.data() : nullptr, B ? B->k_col.data() : nullptr, B ? B->k_val.data() : nullptr, rp, col, val); }
   catch (const std::exception &e) { KS_FAIL(KS_ERR_MEM, "MatAXPY on the host: %s", e.what()); }
   KS_CHECK(fits, KS_ERR_ARG_OUTOFRANGE, "the sum exceeds 32-bit PetscInt indices");
+  // P of two matrices with a transposed product across ranks has one too (then it keeps its arrays as well: the plan is made from them)
+  if (A->sharded_transpose && (!B || B->sharded_transpose)) flags |= KS_MAT_SHARDED_TRANSPOSE | KS_MAT_KEEP_CSR;
   return ks_mat_create_csr_flags(A->ctx, A->n, A->row_start, A->n_global, rp.data(), col.data(), val.data(), flags, out);
 }
 
@@ -918,6 +944,11 @@ extern "C" int ks_mat_destroy(ks_mat A)
   if (A->ctx->halo_stream) hipStreamSynchronize(A->ctx->halo_stream);
   ks_halo_release(A);                 // not collective: waits for the neighbours' last acknowledgements (ks_halo.hip); ks_mat_set_halo(A, KS_HALO_PROVIDER) first is the collective way
   hipFree(A->ghost); hipFree(A->send_idx); hipFree(A->send_buf);
+  if (A->sht) {
+    hipFree(A->sht->o_rp); hipFree(A->sht->o_row); hipFree(A->sht->o_val); hipFree(A->sht->acc_rows); hipFree(A->sht->acc_ptr); hipFree(A->sht->acc_pos);
+    hipFree(A->sht->rsend); hipFree(A->sht->rrecv);
+    delete A->sht; A->sht = nullptr;
+  }
   hipFree(A->s_ptr); hipFree(A->s_len); hipFree(A->s_col); hipFree(A->s_val);
   hipFree(A->dc_codes); hipFree(A->dc_rowpat); hipFree(A->dc_pats); hipFree(A->dc_val); hipFree(A->dc_off); hipFree(A->dc_codes8); hipFree(A->dc_vals);
   hipFree(A->sl_rowptr); hipFree(A->sl_col); hipFree(A->sl_val); hipFree(A->sl_base); hipFree(A->ypart); hipFree(A->diag_cache); hipFree(A->mm_xi);
@@ -994,6 +1025,7 @@ int ks_mat_get_diagonal_internal(ks_mat A, double *d)
 {
   ks_ctx ctx = A->ctx;
   KS_CHECK(!A->shell_mult, KS_ERR_SUP, "a matrix-free operator has no stored diagonal");
+  if (A->sht) A = A->transpose_of;            // the transposed view of a row-sharded matrix: the diagonal of the matrix it views
   if (A->n == 0) return KS_SUCCESS;
   if (A->diag_cache) { KS_HIP(hipMemcpyAsync(d, A->diag_cache, sizeof(double) * A->n, hipMemcpyDeviceToDevice, ctx->stream)); return KS_SUCCESS; }
   const unsigned nb = (unsigned)((A->n + 255) / 256);
@@ -1054,6 +1086,7 @@ extern "C" int ks_mat_norm_inf(ks_mat A, double *val)
 {
   KS_CHECK(A && val, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(!A->shell_mult, KS_ERR_SUP, "a matrix-free operator has no norm operation");      // MatHasOperation(A,MATOP_NORM) epssolve.c:786
+  KS_CHECK(!A->sht, KS_ERR_SUP, "the infinity norm of the transposed view of a row-sharded matrix is not built (it is a 1-norm of the matrix across ranks)");
   ks_ctx ctx = A->ctx;
   KS_HIP(hipSetDevice(ctx->device));
   double local = 0.0;

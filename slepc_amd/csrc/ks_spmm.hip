@@ -303,7 +303,7 @@ int ks_mat_mult_multi_internal(ks_mat A, int ncols, const double *X, int ldx, do
   if (ncols <= 0) return KS_SUCCESS;
   ks_ctx ctx = A->ctx;
   const bool halo = ctx->comm.size > 1 && (A->nsend > 0 || A->nghost > 0);       // several columns through the halo at once: not built
-  bool loop = ncols == 1 || A->shell_mult || halo || A->n_orows > 0;
+  bool loop = ncols == 1 || A->shell_mult || halo || A->n_orows > 0 || A->sht;      // sht: the transposed view of a row-sharded matrix, a reverse exchange per column
   switch (A->layout) {
   case KS_MAT_LAYOUT_DICT: case KS_MAT_LAYOUT_ODICT: case KS_MAT_LAYOUT_SELL: break;
   case KS_MAT_LAYOUT_CSR: if (A->n < 2048 || A->csr_form == ks_mat_s::CSR_VEC) loop = true; break;      // the CSR-vector kernel: its sums are not in entry order

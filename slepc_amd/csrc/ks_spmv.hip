@@ -789,13 +789,26 @@ int ks_mat_mult_dot_fused(ks_mat A, ks_bv bv, const double *x, int jy, bool gate
 // y = A x.  Multi-rank: pack boundary entries, exchange with the neighbours (RCCL send/recv over xGMI),
 // diagonal block product, then the off-diagonal rows add their ghost contributions.
 // a row scaling can ride in the product's last pass: the binned layout on a rank without off-diagonal rows (their contribution is added afterwards)
-bool ks_mat_can_rowscale(ks_mat A) { return A && !A->shell_mult && A->layout == KS_MAT_LAYOUT_BINNED && A->n_orows == 0; }
+// (nor the transposed view of a row-sharded matrix: the other ranks' contributions are added behind the diagonal block's product)
+bool ks_mat_can_rowscale(ks_mat A) { return A && !A->shell_mult && A->layout == KS_MAT_LAYOUT_BINNED && A->n_orows == 0 && !A->sht; }
 
-int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *rowscale)
+static int spmv_variant(ks_mat A)
+{
+  switch (A->layout) {
+  case KS_MAT_LAYOUT_BINNED: return KS_SPMV_BINNED;
+  case KS_MAT_LAYOUT_DICT: return KS_SPMV_DICT;
+  case KS_MAT_LAYOUT_ODICT: return KS_SPMV_ODICT;
+  case KS_MAT_LAYOUT_SELL: return KS_SPMV_SELL;
+  case KS_MAT_LAYOUT_WINDOW: return KS_SPMV_WINDOW;
+  }
+  return KS_SPMV_CSR;
+}
+
+// tail (the transposed view of a row-sharded matrix, mult_sharded_transpose): behind the diagonal block's product the main stream waits for the
+// reverse exchange (tail_overlap: it ran on the halo stream) and adds what the other ranks sent - where the forward product runs its off-diagonal rows
+static int mult_assembled(ks_mat A, const double *x, double *y, const double *rowscale, const ks_mat_s::ShT *tail, bool tail_overlap)
 {
   ks_ctx ctx = A->ctx;
-  if (rowscale && !ks_mat_can_rowscale(A)) KS_FAIL(KS_ERR_PLIB, "row scaling asked of a product that cannot fold it in");
-  if (A->shell_mult) return A->shell_mult(A->shell_user, x, y);
   const bool multi = ctx->comm.size > 1 && (A->nsend > 0 || A->nghost > 0);
   // Halo under the diagonal-block product (PETSc: VecScatterBegin / local product / VecScatterEnd in MatMult_MPIAIJ): pack and
   // neighbour exchange go to the halo stream once x is complete on the main stream; the main stream runs the diagonal block
@@ -821,14 +834,8 @@ int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *row
   }
   {
     const double csr_bytes = 12.0 * A->nnz + 4.0 * (A->n + 1) + 16.0 * A->n;                    // what the CSR algorithm moves
-    int variant = KS_SPMV_CSR; double own = layout_own_bytes(A) + 16.0 * A->n + 12.0 * A->nnz_o;      // the layout's own compulsory bytes
-    switch (A->layout) {
-    case KS_MAT_LAYOUT_BINNED: variant = KS_SPMV_BINNED; break;
-    case KS_MAT_LAYOUT_DICT: variant = KS_SPMV_DICT; break;
-    case KS_MAT_LAYOUT_ODICT: variant = KS_SPMV_ODICT; break;
-    case KS_MAT_LAYOUT_SELL: variant = KS_SPMV_SELL; own = csr_bytes; break;                            // filed under the CSR stream's bytes (its padding is at most 12.5 %)
-    case KS_MAT_LAYOUT_WINDOW: variant = KS_SPMV_WINDOW; break;
-    }
+    const int variant = spmv_variant(A); double own = layout_own_bytes(A) + 16.0 * A->n + 12.0 * A->nnz_o;      // the layout's own compulsory bytes
+    if (A->layout == KS_MAT_LAYOUT_SELL) own = csr_bytes;                                               // filed under the CSR stream's bytes (its padding is at most 12.5 %)
     KsProfScope ps(ctx, KS_K_SPMV, csr_bytes, variant, own);
     switch (A->layout) {
     case KS_MAT_LAYOUT_BINNED:
@@ -892,9 +899,58 @@ int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *row
     if (overlap) KS_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_halo, 0));          // also when this rank has no off-diagonal rows: keeps the two streams in step
     if (A->n_orows > 0)
       launch_spmv<true, true>(ctx->stream, ctx->num_cu, 2, A->n_orows, A->o_rowptr, A->o_col, A->o_val, A->ghost, y, A->o_rows);
+    if (tail) {
+      if (tail_overlap) KS_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_halo, 0));
+      KS_CALL(ks_halo_add(ctx->stream, tail->nacc, tail->acc_rows, tail->acc_ptr, tail->acc_pos, tail->rrecv, y));
+    }
   }
   KS_HIP(hipGetLastError());
   return KS_SUCCESS;
+}
+
+// y = A^T x of a row-sharded A through its view At (MatMultTranspose_MPIAIJ: the transposed off-diagonal block times the local x into a ghost-length
+// vector, the transposed diagonal block times x into y, the forward scatter in reverse with ADD). The mirror image of the forward product above:
+//   main stream   rsend = Bo^T x   | ev_x |   y = Ad^T x (the view's own layout)   | wait ev_halo |   k_halo_add: y[r] += rrecv[...]
+//   halo stream                    | wait ev_x |   exchange rsend -> rrecv (provider)   | ev_halo |
+// The ghost rows are short and ragged and x is local: launch_spmv<false, false>, the CSR row walk of the forward path, serves unchanged (two lanes
+// per ghost row, as for the forward off-diagonal rows). The exchange is the forward plan with send and receive swapped and ALWAYS the provider's:
+// the peer-mapped mailboxes (KS_HALO_PEER) are laid out for the forward direction only, and a matrix with the peer halo active still takes the
+// provider here. rsend and rrecv belong to the view, apart from ghost and send_buf: forward and transposed products may alternate freely.
+// Back to back: the next product's Bo^T x (main stream) comes behind this one's k_halo_add, which waited for the exchange that read rsend; the next
+// exchange (halo stream) waits for the next ev_x, recorded behind this k_halo_add, the last reader of rrecv.
+static int mult_sharded_transpose(ks_mat At, const double *x, double *y)
+{
+  ks_mat A = At->transpose_of;
+  ks_ctx ctx = At->ctx;
+  const ks_mat_s::ShT *t = At->sht;
+  if (A->nsend == 0 && A->nghost == 0) return mult_assembled(At, x, y, nullptr, nullptr, false);      // a rank without peers takes no part in any exchange
+  const bool overlap = ctx->halo_overlap;
+  if (A->nghost > 0) {
+    KsProfScope ps(ctx, KS_K_SPMV, 12.0 * t->nnz_o + 4.0 * (A->nghost + 1) + 8.0 * A->nghost, spmv_variant(At));
+    launch_spmv<false, false>(ctx->stream, ctx->num_cu, 2, A->nghost, t->o_rp, t->o_row, t->o_val, x, t->rsend, nullptr);
+  }
+  hipStream_t hs = ctx->stream;
+  if (overlap) {
+    KS_CALL(ks_ctx_halo_stream(ctx));
+    hs = ctx->halo_stream;
+    KS_HIP(hipEventRecord(ctx->ev_x, ctx->stream));
+    KS_HIP(hipStreamWaitEvent(hs, ctx->ev_x, 0));
+  }
+  {
+    KsProfScope ps(ctx, KS_K_HALO, 8.0 * (A->nsend + A->nghost));
+    KS_CALL(ks_comm_exchange(ctx, (int)A->peers.size(), A->peers.data(), t->rsend, A->recv_off.data(), A->recv_cnt.data(),
+                             t->rrecv, A->send_off.data(), A->send_cnt.data(), (int)sizeof(double), hs));
+  }
+  if (overlap) KS_HIP(hipEventRecord(ctx->ev_halo, hs));
+  return mult_assembled(At, x, y, nullptr, t, overlap);
+}
+
+int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *rowscale)
+{
+  if (rowscale && !ks_mat_can_rowscale(A)) KS_FAIL(KS_ERR_PLIB, "row scaling asked of a product that cannot fold it in");
+  if (A->shell_mult) return A->shell_mult(A->shell_user, x, y);
+  if (A->sht) return mult_sharded_transpose(A, x, y);
+  return mult_assembled(A, x, y, rowscale, nullptr, false);
 }
 
 extern "C" int ks_mat_mult(ks_mat A, const double *x_dev, double *y_dev)
@@ -906,9 +962,42 @@ extern "C" int ks_mat_mult(ks_mat A, const double *x_dev, double *y_dev)
 }
 
 // MatMultTranspose: through the transposed matrix, built once (MatTranspose on the host, ks_csr.cpp) and multiplied like any other
+// The view of a row-sharded matrix created with KS_MAT_SHARDED_TRANSPOSE: the plan (ksc::sharded_transpose_plan, host only, no communication),
+// the transposed diagonal block assembled like any matrix - it gets its own layout from the chooser, as the one-rank At does - and the rest of the
+// plan with the two exchange buffers on the device
+static int upload_ints(const std::vector<int> &h, int **d)
+{
+  KS_HIP(hipMalloc(d, sizeof(int) * std::max<size_t>(h.size(), 1)));
+  if (!h.empty()) KS_HIP(hipMemcpy(*d, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice));
+  return KS_SUCCESS;
+}
+static int build_sharded_transpose(ks_mat A)
+{
+  ksc::ShardedTransposePlan p;
+  try {
+    ksc::sharded_transpose_plan(A->n, A->row_start, A->k_rowptr.data(), A->k_col.data(), A->k_val.data(), A->nghost, A->h_ghosts.data(), A->nsend, A->h_send_idx.data(), p);
+    for (auto &c : p.d_col) c += A->row_start;                 // the assembly takes global columns
+  } catch (const std::exception &e) { KS_FAIL(KS_ERR_MEM, "plan of the transposed product on the host: %s", e.what()); }
+  ks_mat At = nullptr;
+  KS_CALL(ks_mat_assemble_local(A->ctx, A->n, A->row_start, A->n_global, p.d_rp.data(), p.d_col.data(), p.d_val.data(), &At));
+  At->transpose_of = A; A->At = At;                            // from here on A frees it (ks_mat_destroy), half-built or not
+  ks_mat_s::ShT *t = At->sht = new ks_mat_s::ShT();
+  t->nnz_o = (long long)p.o_row.size(); t->nacc = (int)p.acc_rows.size();
+  KS_CALL(upload_ints(p.o_rp, &t->o_rp)); KS_CALL(upload_ints(p.o_row, &t->o_row));
+  KS_CALL(upload_ints(p.acc_rows, &t->acc_rows)); KS_CALL(upload_ints(p.acc_ptr, &t->acc_ptr)); KS_CALL(upload_ints(p.acc_pos, &t->acc_pos));
+  KS_HIP(hipMalloc(&t->o_val, sizeof(double) * std::max<size_t>(p.o_val.size(), 1)));
+  if (!p.o_val.empty()) KS_HIP(hipMemcpy(t->o_val, p.o_val.data(), sizeof(double) * p.o_val.size(), hipMemcpyHostToDevice));
+  KS_HIP(hipMalloc(&t->rsend, sizeof(double) * std::max(A->nghost, 1)));
+  KS_HIP(hipMalloc(&t->rrecv, sizeof(double) * std::max(A->nsend, 1)));
+  return KS_SUCCESS;
+}
 static int build_transpose(ks_mat A)
 {
-  if (A->At) return KS_SUCCESS;
+  if (A->At && (!A->sharded_transpose || (A->At->sht && A->At->sht->rrecv))) return KS_SUCCESS;
+  if (A->sharded_transpose && A->keep_csr) {
+    KS_CHECK(!A->At, KS_ERR_MEM, "the transposed view of this matrix could not be completed earlier");
+    return build_sharded_transpose(A);
+  }
   KS_CHECK(A->ctx->comm.size == 1 && A->n == A->n_global, KS_ERR_SUP, "MatMultTranspose of a row-sharded matrix is not built (the transpose is a redistribution)");
   KS_CHECK(A->keep_csr, KS_ERR_ORDER, "MatMultTranspose builds the transpose from the CSR arrays of the matrix: create it with KS_MAT_KEEP_CSR");
   std::vector<int> rp, col; std::vector<double> val;

@@ -150,6 +150,15 @@ struct ks_mat_s {
   bool keep_csr = false; std::vector<int> k_rowptr, k_col; std::vector<double> k_val;
   ks_mat At = nullptr;                        // MatMultTranspose: the transpose, built on first use from the kept arrays (owned)
   ks_mat transpose_of = nullptr;              // set on such an At: the matrix that owns it. ks_mat_create_transpose hands the At out as a view; only its owner frees it
+  // KS_MAT_SHARDED_TRANSPOSE (more than one rank): the matrix keeps its sorted ghost list and its pack list on the host, what the plan of the
+  // transposed product is made from (ksc::sharded_transpose_plan) together with the kept CSR arrays. The At of such a matrix is the transposed
+  // DIAGONAL block assembled on its own (no halo of its own) and carries the rest of the plan in `sht`; its product is mult_sharded_transpose (ks_spmv.hip)
+  bool sharded_transpose = false; std::vector<int> h_ghosts, h_send_idx;
+  struct ShT {
+    int *o_rp = nullptr, *o_row = nullptr; double *o_val = nullptr; long long nnz_o = 0;   // transposed off-diagonal block: nghost rows of local row indices
+    int *acc_rows = nullptr, *acc_ptr = nullptr, *acc_pos = nullptr; int nacc = 0;         // inverse of send_idx
+    double *rsend = nullptr, *rrecv = nullptr;                                              // [nghost] sums for the ghosts' owners, [nsend] the peers' sums for this rank's rows
+  } *sht = nullptr;
   // diagonal block (columns owned by this rank, LOCAL column indices)
   int *d_rowptr = nullptr; int *d_col = nullptr; double *d_val = nullptr; long long nnz_d = 0;
   int lanes_per_row = 8;
@@ -247,6 +256,9 @@ int ks_mat_mult_transpose_internal(ks_mat A, const double *x, double *y);
 int ks_st_apply_transpose_internal(ks_st st, const double *x, double *y);
 void ks_halo_release(ks_mat A);
 int ks_halo_peer_exchange(ks_mat A, const double *x, hipStream_t hs);     // pack into the neighbours' mailboxes, unpack this rank's own (ks_halo.hip)
+int ks_halo_add(hipStream_t st, int nacc, const int *acc_rows, const int *acc_ptr, const int *acc_pos, const double *rrecv, double *y);   // y[acc_rows[i]] += rrecv[acc_pos[..]] (ks_halo.hip)
+int ks_mat_assemble_local(ks_ctx ctx, int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val, ks_mat *out);   // a diagonal block on its own: no halo plan, no collective (ks_mat.hip)
+bool ks_mat_has_transpose_across_ranks(ks_mat A);     // an assembled matrix created with KS_MAT_SHARDED_TRANSPOSE | KS_MAT_KEEP_CSR, or a view of one
 
 int ks_mat_norm_inf_local(ks_mat A, double *val);           // max row sum of |a_ij| over this rank's rows
 
