@@ -104,7 +104,7 @@ int ks_ctx_synchronize(ks_ctx ctx);
  * ks_comm_init_rccl / ks_comm_set_ops, ONESHOT_SEQ0 (first stamp of the one-shot allreduce) at ks_comm_set_allreduce, NO_DICT_PATTERNS (keep the
  * dictionary layout's 2-byte codes per entry, never its row-pattern form) at matrix assembly; the others per call. */
 enum { KS_DEBUG_NO_FUSED_GS = 0, KS_DEBUG_NO_MFMA = 1, KS_DEBUG_NO_SPMV_DOT = 2, KS_DEBUG_FORCE_MULTI = 3, KS_DEBUG_HALO_OVERLAP = 4, KS_DEBUG_ONESHOT_SEQ0 = 5,
-       KS_DEBUG_NO_DICT_PATTERNS = 6 };
+       KS_DEBUG_NO_DICT_PATTERNS = 6, KS_DEBUG_NO_RESTART_FUSION = 7 /* the final update of a run's last column, the restart product and the copy as the launches of their own */ };
 int ks_ctx_set_debug(ks_ctx ctx, int key, long long value);
 int ks_ctx_sync_count(ks_ctx ctx, long long *count);   /* instrumentation: host waits on the context's stream made by the library so far */
 int ks_ctx_device_info(ks_ctx ctx, char *arch, int arch_len, int *num_cu, size_t *mem_total);
@@ -309,6 +309,15 @@ int ks_bv_multvec(ks_bv X, double alpha, double beta, double *y_dev, const doubl
 int ks_bv_multcolumn(ks_bv X, double alpha, double beta, int j, const double *q);               /* BVMultColumn bvops.c:165 */
 int ks_bv_multinplace(ks_bv V, const double *Q, int ldq, int s, int e);                          /* ops->multinplace */
 int ks_bv_multinplace_trans(ks_bv V, const double *Q, int ldq, int s, int e);                    /* ops->multinplacetrans */
+/* The end of a restart cycle: BVMultInPlace(V,Q,s,e) followed by BVCopyColumn(V,src,dst). With ks_bv_set_defer_final on, a Krylov run
+   (ks_bv_matlanczos / ks_bv_matarnoldi) keeps the final Gram-Schmidt update of its last column back; this call then applies it inside the
+   product's sweep: one launch and one read of the panel for update, product and copy. Every other entry point that reads or writes
+   column data or Gram-Schmidt state applies a waiting update first, so the deferral is never visible in results: memory and coefficients are
+   bit for bit what the separate launches leave. One rank, at most 32 columns before src, at most 16 product columns; other shapes run the
+   separate launches. ks_bv_restart_stats: whether an update is waiting, how many were applied on their own, how many inside a restart. */
+int ks_bv_restart(ks_bv V, const double *Q, int ldq, int s, int e, int src, int dst);
+int ks_bv_set_defer_final(ks_bv bv, int on);
+int ks_bv_restart_stats(ks_bv bv, int *pending, long long *flushes, long long *fused);
 int ks_bv_dot(ks_bv X, ks_bv Y, double *M, int ldm);                                             /* ops->dot: M = Y^H X (+allreduce) */
 int ks_bv_dotvec(ks_bv X, const double *y_dev, double *m);                                       /* ops->dotvec; m NULL -> buffer */
 int ks_bv_dotvec_local(ks_bv X, const double *y_dev, double *m);                                 /* ops->dotvec_local (no reduction) */

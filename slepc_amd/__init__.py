@@ -66,6 +66,8 @@ def kernel_symbol(name, var):
     if name == "gs_bookkeeping":
         return "k_gs_finish<true, true>"
     if name in ("bv_multinplace", "bv_mult"):
+        if var == 1:
+            return "k_restart_fused<PLAIN>"     # final update + restart product + copy (ks_panel.hip ksp_restart_fused)
         return "k_panel_mult_direct<%d, NT, U>" % (var // 4) if var else "k_multvec<2>"       # variant = 4 * KS4 (ks_panel.hip ksp_mult_mfma)
     if name == "bv_dot_panel":
         return "k_panel_dot_direct<MT, NT, SAME, U>"
@@ -114,7 +116,7 @@ class Context:
     def synchronize(self):
         _lib.check(self.L.ks_ctx_synchronize(self.h))
 
-    DEBUG_KEYS = {"no_fused_gs": 0, "no_mfma": 1, "no_spmv_dot": 2, "force_multi": 3, "halo_overlap": 4, "oneshot_seq0": 5, "no_dict_patterns": 6}
+    DEBUG_KEYS = {"no_fused_gs": 0, "no_mfma": 1, "no_spmv_dot": 2, "force_multi": 3, "halo_overlap": 4, "oneshot_seq0": 5, "no_dict_patterns": 6, "no_restart_fusion": 7}
 
     def set_debug(self, key, value=1):
         """Test hooks (ks_ctx_set_debug): run the path a fast one replaces, or the multi-rank path on one rank."""
@@ -555,6 +557,20 @@ class BV:
         Qf = np.asfortranarray(Q, dtype=np.float64)
         f = self.ctx.L.ks_bv_multinplace_trans if trans else self.ctx.L.ks_bv_multinplace
         _lib.check(f(self.h, _p(Qf), Qf.shape[0], s, e))
+
+    def Restart(self, Q, s, e, src, dst):
+        """BVMultInPlace(V,Q,s,e) then BVCopyColumn(V,src,dst); one launch when a deferred final update waits on column src."""
+        Qf = np.asfortranarray(Q, dtype=np.float64)
+        _lib.check(self.ctx.L.ks_bv_restart(self.h, _p(Qf), Qf.shape[0], s, e, src, dst))
+
+    def SetDeferFinal(self, on=True):
+        """Krylov runs keep the final update of their last column back for Restart (any other use of the basis applies it first)."""
+        _lib.check(self.ctx.L.ks_bv_set_defer_final(self.h, int(bool(on))))
+
+    def restart_stats(self):
+        p = C.c_int(); fl = C.c_longlong(); fu = C.c_longlong()
+        _lib.check(self.ctx.L.ks_bv_restart_stats(self.h, C.byref(p), C.byref(fl), C.byref(fu)))
+        return {"pending": bool(p.value), "flushes": fl.value, "fused": fu.value}
 
     def Dot(self, Y, M):
         assert M.flags.f_contiguous and M.dtype == np.float64

@@ -98,6 +98,9 @@ _SIG = {
     "ks_bv_multcolumn": [vp, C.c_double, C.c_double, C.c_int, dp],
     "ks_bv_multinplace": [vp, dp, C.c_int, C.c_int, C.c_int],
     "ks_bv_multinplace_trans": [vp, dp, C.c_int, C.c_int, C.c_int],
+    "ks_bv_restart": [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    "ks_bv_set_defer_final": [vp, C.c_int],
+    "ks_bv_restart_stats": [vp, ip, llp, llp],
     "ks_bv_dot": [vp, vp, dp, C.c_int],
     "ks_bv_dotvec": [vp, vp, dp],
     "ks_bv_dotvec_local": [vp, vp, dp],

@@ -215,7 +215,7 @@ __global__ void k_copy_mapped(const double *__restrict__ src, double *__restrict
 }
 
 // stage host coefficients into the BV's device scratch (async from pinned memory when they fit)
-static int stage_coefs(ks_bv bv, const double *host, size_t len, double **dev)
+int ksb_stage_coefs(ks_bv bv, const double *host, size_t len, double **dev)
 {
   ks_ctx ctx = bv->ctx;
   if (len > bv->coef_len) {                                 // a wider coefficient block than this BV's own m x m: grow the scratch
@@ -306,6 +306,7 @@ extern "C" int ks_bv_destroy(ks_bv bv)
 // ownership start) and the leading dimension stay. Active columns are reset to [0, m) as in the reference.
 extern "C" int ks_bv_resize(ks_bv bv, int m, int copy)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
   KS_CHECK(m > 0, KS_ERR_ARG_OUTOFRANGE, "Number of columns %d must be positive", m);
   if (m == bv->m) return KS_SUCCESS;
@@ -328,6 +329,7 @@ extern "C" int ks_bv_resize(ks_bv bv, int m, int copy)
 // BVSetRandom bvops.c:380-407: every active column, reproducible (value depends on seed, column and global row only)
 extern "C" int ks_bv_set_random(ks_bv bv, uint64_t seed)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
   for (int j = bv->l; j < bv->k; j++) KS_CALL(ks_bv_set_random_column(bv, j, seed));
   return KS_SUCCESS;
@@ -336,6 +338,7 @@ extern "C" int ks_bv_set_random(ks_bv bv, uint64_t seed)
 // BVInsertVec bvops.c:568 / BVCopyVec bvops.c:484 on device vectors of n_local doubles
 extern "C" int ks_bv_insert_vec(ks_bv bv, int j, const double *w_dev)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && w_dev, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(j >= 0 && j < bv->m, KS_ERR_ARG_OUTOFRANGE, "Argument j has wrong value %d, the number of columns is %d", j, bv->m);
   KS_HIP(hipSetDevice(bv->ctx->device));
@@ -343,6 +346,7 @@ extern "C" int ks_bv_insert_vec(ks_bv bv, int j, const double *w_dev)
 }
 extern "C" int ks_bv_copy_vec(ks_bv bv, int j, double *w_dev)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && w_dev, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(j >= 0 && j < bv->m, KS_ERR_ARG_OUTOFRANGE, "Argument j has wrong value %d, the number of columns is %d", j, bv->m);
   KS_HIP(hipSetDevice(bv->ctx->device));
@@ -353,6 +357,7 @@ extern "C" int ks_bv_copy_vec(ks_bv bv, int j, double *w_dev)
 // orthogonalised against everything before it (constraints included), normalised, or dropped when dependent.
 extern "C" int ks_bv_insert_vecs(ks_bv bv, int s, int *m, const double *const *W_dev, int orth)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && m, KS_ERR_ARG_NULL, "NULL argument");
   if (!*m) return KS_SUCCESS;
   KS_CHECK(*m > 0, KS_ERR_ARG_OUTOFRANGE, "Number of vectors (given %d) cannot be negative", *m);
@@ -380,6 +385,7 @@ extern "C" int ks_bv_insert_vecs(ks_bv bv, int s, int *m, const double *const *W
 // Gram-Schmidt sweep starts there, everything else keeps addressing the m regular columns.
 extern "C" int ks_bv_insert_constraints(ks_bv bv, int *nc, const double *const *C_dev)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && nc, KS_ERR_ARG_NULL, "NULL argument");
   if (!*nc) return KS_SUCCESS;
   KS_CHECK(*nc > 0, KS_ERR_ARG_OUTOFRANGE, "Number of constraints (given %d) cannot be negative", *nc);
@@ -397,6 +403,7 @@ extern "C" int ks_bv_insert_constraints(ks_bv bv, int *nc, const double *const *
 // into regular columns at the end (EPSSolve drops its deflation space this way, epssolve.c:201-205)
 extern "C" int ks_bv_set_num_constraints(ks_bv bv, int nc)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
   KS_CHECK(nc >= 0, KS_ERR_ARG_OUTOFRANGE, "Number of constraints (given %d) cannot be negative", nc);
   const int diff = nc - bv->nc, total = bv->nc + bv->m;
@@ -412,6 +419,7 @@ extern "C" int ks_bv_get_num_constraints(ks_bv bv, int *nc) { KS_CHECK(bv && nc,
 
 extern "C" int ks_bv_duplicate(ks_bv bv, ks_bv *out)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && out, KS_ERR_ARG_NULL, "NULL argument");
   KS_CALL(ks_bv_create(bv->ctx, bv->n, bv->N, bv->m, bv->ld, out));
   (*out)->orthog_type = bv->orthog_type; (*out)->orthog_ref = bv->orthog_ref; (*out)->orthog_eta = bv->orthog_eta;
@@ -464,13 +472,14 @@ extern "C" int ks_bv_set_orthogonalization(ks_bv bv, int type, int refine, doubl
   return KS_SUCCESS;
 }
 
-extern "C" int ks_bv_get_array(ks_bv bv, double **dev) { KS_CHECK(bv && dev, KS_ERR_ARG_NULL, "NULL argument"); *dev = bv->array; bv->spec.valid = false; return KS_SUCCESS; }   // a writable view: whatever a Gram-Schmidt pass left for its successor no longer counts
-extern "C" int ks_bv_get_buffer(ks_bv bv, double **dev) { KS_CHECK(bv && dev, KS_ERR_ARG_NULL, "NULL argument"); *dev = bv->buffer; return KS_SUCCESS; }
+extern "C" int ks_bv_get_array(ks_bv bv, double **dev) { KS_CHECK(bv && dev, KS_ERR_ARG_NULL, "NULL argument"); KS_CALL(ksb_flush(bv)); *dev = bv->array; bv->spec.valid = false; return KS_SUCCESS; }   // a writable view: whatever a Gram-Schmidt pass left for its successor no longer counts
+extern "C" int ks_bv_get_buffer(ks_bv bv, double **dev) { KS_CHECK(bv && dev, KS_ERR_ARG_NULL, "NULL argument"); KS_CALL(ksb_flush(bv)); *dev = bv->buffer; return KS_SUCCESS; }
 // BVSetBufferVec bvbasic.c:720 on a raw device array of (nc+m)*m doubles: the adapter hands over the array of the reference's
 // bv->buffer Vec, so that BV_CleanCoefficients / BV_SetValue / BV_StoreCoefficients of the caller and the kernels of this library
 // work on the same memory. NULL returns to the library's own allocation.
 extern "C" int ks_bv_set_buffer(ks_bv bv, double *dev)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
   if (dev != bv->buffer) bv->spec.valid = false;
   if (dev) { if (bv->own_buffer) { bv->buffer_own = bv->buffer; bv->own_buffer = false; } bv->buffer = dev; }
@@ -481,6 +490,7 @@ extern "C" int ks_bv_set_buffer(ks_bv bv, double *dev)
 // without going through an ops slot): no data moves here. nc + m must equal the number of allocated columns.
 extern "C" int ks_bv_set_layout(ks_bv bv, int nc, int m)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
   KS_CHECK(nc >= 0 && m > 0 && nc + m == bv->nc + bv->m, KS_ERR_ARG_OUTOFRANGE, "nc=%d, m=%d do not add up to the %d allocated columns", nc, m, bv->nc + bv->m);
   if (nc != bv->nc) bv->spec.valid = false;
@@ -490,6 +500,7 @@ extern "C" int ks_bv_set_layout(ks_bv bv, int nc, int m)
 }
 extern "C" int ks_bv_get_column(ks_bv bv, int j, double **dev)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && dev, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(j < bv->m, KS_ERR_ARG_OUTOFRANGE, "You requested column %d but only columns 0 to %d are available", j, bv->m - 1);
   KS_CHECK(j >= -bv->nc, KS_ERR_ARG_OUTOFRANGE, "You requested constraint %d but only %d are available", -j, bv->nc);       // bvbasic.c BVGetColumn: negative = constraint
@@ -500,6 +511,7 @@ extern "C" int ks_bv_get_column(ks_bv bv, int j, double **dev)
 
 extern "C" int ks_bv_set_column_host(ks_bv bv, int j, const double *host)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && host, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(j >= 0 && j < bv->m, KS_ERR_ARG_OUTOFRANGE, "column %d out of range", j);
   bv->spec.valid = false;
@@ -511,6 +523,7 @@ extern "C" int ks_bv_set_column_host(ks_bv bv, int j, const double *host)
 
 extern "C" int ks_bv_get_column_host(ks_bv bv, int j, double *host)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && host, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(j >= -bv->nc && j < bv->m, KS_ERR_ARG_OUTOFRANGE, "column %d out of range", j);
   KS_HIP(hipSetDevice(bv->ctx->device));
@@ -521,6 +534,7 @@ extern "C" int ks_bv_get_column_host(ks_bv bv, int j, double *host)
 
 extern "C" int ks_bv_get_buffer_host(ks_bv bv, double *host)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && host, KS_ERR_ARG_NULL, "NULL argument");
   KS_HIP(hipSetDevice(bv->ctx->device));
   KS_HIP(hipMemcpyAsync(host, bv->buffer, sizeof(double) * (bv->nc + bv->m) * bv->m, hipMemcpyDeviceToHost, bv->ctx->stream));
@@ -530,6 +544,7 @@ extern "C" int ks_bv_get_buffer_host(ks_bv bv, double *host)
 
 extern "C" int ks_bv_set_random_column(ks_bv bv, int j, uint64_t seed)   // BVSetRandomColumn bvops.c:482, reproducible variant :368-376
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
   KS_CHECK(j >= 0 && j < bv->m, KS_ERR_ARG_OUTOFRANGE, "Argument j has wrong value %d, the number of columns is %d", j, bv->m);
   KS_HIP(hipSetDevice(bv->ctx->device));
@@ -598,6 +613,8 @@ static int panel_mult64(ks_ctx ctx, int kclass, const double *A, int lda, int n,
 
 extern "C" int ks_bv_mult(ks_bv Y, double alpha, double beta, ks_bv X, const double *Q, int ldq)   // bvops.c:49, svec.c:17-36
 {
+  KS_CALL(ksb_flush(X));
+  KS_CALL(ksb_flush(Y));
   KS_CHECK(Y && X, KS_ERR_ARG_NULL, "BV is NULL");
   KS_CHECK(X != Y, KS_ERR_ARG_WRONG, "X and Y arguments must be different");
   KS_CHECK(X->n == Y->n, KS_ERR_ARG_INCOMP, "Mismatching local dimension X %d, Y %d", X->n, Y->n);
@@ -620,18 +637,19 @@ extern "C" int ks_bv_mult(ks_bv Y, double alpha, double beta, ks_bv X, const dou
   // stage the (X->k) x (Y->k) leading block of Q on the device (bvimpl.h:565-586 does the same per call)
   const size_t qlen = (size_t)ldq * Y->k;
   double *qdev = nullptr;
-  KS_CALL(stage_coefs(Y, Q, qlen, &qdev));
+  KS_CALL(ksb_stage_coefs(Y, Q, qlen, &qdev));
   return panel_mult(ctx, KS_K_MULT, px, X->ld, Y->n, kx, qdev + (size_t)Y->l * ldq + X->l, ldq, false, ny, alpha, beta, py, Y->ld);
 }
 
 extern "C" int ks_bv_multvec(ks_bv X, double alpha, double beta, double *y_dev, const double *q)   // bvops.c:110, svec.c:38-52
 {
+  KS_CALL(ksb_flush(X));
   KS_CHECK(X && y_dev, KS_ERR_ARG_NULL, "NULL argument");
   ks_ctx ctx = X->ctx;
   KS_HIP(hipSetDevice(ctx->device));
   const int kx = X->k - X->l;
   const double *qdev = X->buffer;            // q==NULL: coefficients are in the buffer Vec (svec.c:46)
-  if (q && kx > 0) { double *tmp; KS_CALL(stage_coefs(X, q, (size_t)kx, &tmp)); qdev = tmp; }
+  if (q && kx > 0) { double *tmp; KS_CALL(ksb_stage_coefs(X, q, (size_t)kx, &tmp)); qdev = tmp; }
   if (kx <= 0) { if (beta != 1.0) return ksk_scale(ctx, y_dev, X->n, beta); return KS_SUCCESS; }
   const double *A = X->array + (size_t)(X->nc + X->l) * X->ld;
   for (int c0 = 0; c0 < kx; c0 += KS_MAX_COLS) {
@@ -656,6 +674,7 @@ extern "C" int ks_bv_multcolumn(ks_bv X, double alpha, double beta, int j, const
 static int multinplace(ks_bv V, const double *Q, int ldq, int s, int e, bool trans)   // bvops.c:220-250, svec.c:54-87
 {
   KS_CHECK(V && Q, KS_ERR_ARG_NULL, "NULL argument");
+  KS_CALL(ksb_flush(V));
   KS_CHECK(s >= V->l && s <= V->m, KS_ERR_ARG_OUTOFRANGE, "Argument s has wrong value %d, should be between %d and %d", s, V->l, V->m);
   KS_CHECK(e >= V->l && e <= V->m, KS_ERR_ARG_OUTOFRANGE, "Argument e has wrong value %d, should be between %d and %d", e, V->l, V->m);
   V->spec.valid = false;
@@ -668,7 +687,7 @@ static int multinplace(ks_bv V, const double *Q, int ldq, int s, int e, bool tra
   // Q block needed: rows l..k-1, cols s..e-1 (or transposed); stage the leading max(k,e) x max(k,e) block
   const int ncolsq = trans ? V->k : e;
   double *qdev = nullptr;
-  KS_CALL(stage_coefs(V, Q, (size_t)ldq * ncolsq, &qdev));
+  KS_CALL(ksb_stage_coefs(V, Q, (size_t)ldq * ncolsq, &qdev));
   double *A = V->array + (size_t)(V->nc + V->l) * V->ld;
   const double *B = qdev + (size_t)V->l * ldq + V->l;
   const int ss = s - V->l, ee = e - V->l;
@@ -678,10 +697,37 @@ static int multinplace(ks_bv V, const double *Q, int ldq, int s, int e, bool tra
 extern "C" int ks_bv_multinplace(ks_bv V, const double *Q, int ldq, int s, int e) { return multinplace(V, Q, ldq, s, e, false); }
 extern "C" int ks_bv_multinplace_trans(ks_bv V, const double *Q, int ldq, int s, int e) { return multinplace(V, Q, ldq, s, e, true); }
 
+// The end of a restart cycle: BVMultInPlace(V,Q,s,e), then BVCopyColumn(V,src,dst). With a deferred final update waiting on column src and a shape
+// the fused kernel takes (at most 32 columns before src, at most 16 product columns, 16-byte aligned columns) the update, the product and the copy
+// are one launch and one read of the panel (ks_panel.hip: k_restart_fused); anything else flushes the update and makes today's two launches.
+int ksb_restart(ks_bv V, const double *Q, int ldq, int s, int e, int src, int dst)
+{
+  KS_CHECK(V && Q, KS_ERR_ARG_NULL, "NULL argument");
+  KS_CHECK(src >= 0 && src < V->m && dst >= 0 && dst < V->m, KS_ERR_ARG_OUTOFRANGE, "column index out of range (%d -> %d, m=%d)", src, dst, V->m);
+  ks_ctx ctx = V->ctx;
+  const int kin = V->k - V->l;
+  const bool fuse = V->defer.pending && V->defer.one_pass && V->defer.col == src && !ctx->dbg.no_restart_fusion && !ctx->dbg.no_mfma
+                    && V->n > 0 && s >= V->l && s < e && e <= V->m && e - s <= 16 && kin >= 1 && V->l + kin <= src && V->k <= ldq && dst != src && (dst < s || dst >= e)
+                    && V->defer.k == V->nc + src && V->defer.k >= 1 && V->defer.k <= 32 && V->ld % 2 == 0 && aligned16(ks_bv_col(V, -V->nc));
+  if (!fuse) {
+    KS_CALL(multinplace(V, Q, ldq, s, e, false));               // (flushes)
+    return ks_bv_copycolumn(V, src, dst);
+  }
+  KS_HIP(hipSetDevice(ctx->device));
+  V->spec.valid = false;
+  double *qdev = nullptr;
+  KS_CALL(ksb_stage_coefs(V, Q, (size_t)ldq * e, &qdev));        // as BVMultInPlace stages it
+  const double *B = qdev + (size_t)V->l * ldq + V->l + (size_t)(s - V->l) * ldq;
+  V->defer.pending = false; V->defer.one_pass = false; V->defer.fused++;
+  return ksp_restart_fused(V, ks_bv_col(V, -V->nc), V->defer.k, ks_bv_col(V, src), ks_bv_col(V, dst), ks_bv_col(V, V->l), kin, B, ldq, e - s, ks_bv_col(V, s));
+}
+extern "C" int ks_bv_restart(ks_bv V, const double *Q, int ldq, int s, int e, int src, int dst) { return ksb_restart(V, Q, ldq, s, e, src, dst); }
+
 // ---- ops->dot / dotvec -----------------------------------------------------------------------------
 // BVSetMatrix bvfunc.c:200-250 with indef = PETSC_FALSE: inner products become y^H B x
 extern "C" int ks_bv_set_matrix(ks_bv bv, ks_mat B)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
   if (B) {
     KS_CHECK(B->n == bv->n && B->n_global == bv->N, KS_ERR_ARG_INCOMP, "Mismatching dimensions of the inner-product matrix (%d) and the BV (%d)", B->n, bv->n);
@@ -719,6 +765,7 @@ int ksb_norm_b(ks_bv bv, const double *x, double *val)              // BVNorm_Pr
 
 static int dotvec_impl(ks_bv X, const double *y_dev, double *m, bool reduce)
 {
+  KS_CALL(ksb_flush(X));
   KS_CHECK(X && y_dev, KS_ERR_ARG_NULL, "NULL argument");
   ks_ctx ctx = X->ctx;
   KS_HIP(hipSetDevice(ctx->device));
@@ -742,6 +789,7 @@ extern "C" int ks_bv_dotvec_local(ks_bv X, const double *y_dev, double *m) { ret
 
 extern "C" int ks_bv_dotcolumn(ks_bv X, int j, double *q)   // bvglobal.c:302-327
 {
+  KS_CALL(ksb_flush(X));
   KS_CHECK(X, KS_ERR_ARG_NULL, "BV is NULL");
   KS_CHECK(j >= 0, KS_ERR_ARG_OUTOFRANGE, "Index j must be non-negative");
   KS_CHECK(j < X->m, KS_ERR_ARG_OUTOFRANGE, "Index j=%d but BV only has %d columns", j, X->m);
@@ -755,6 +803,7 @@ extern "C" int ks_bv_dotcolumn(ks_bv X, int j, double *q)   // bvglobal.c:302-32
 // M(ys:ye, xs:xe) = Y(:,ys:ye)^H X(:,xs:xe); X and Y may be the same BV
 int ksb_dot_range(ks_bv X, int xs, int xe, ks_bv Y, int ys, int ye, double *M, int ldm)
 {
+  KS_CALL(ksb_flush(X)); KS_CALL(ksb_flush(Y));
   if (xs >= xe || ys >= ye) return KS_SUCCESS;
   ks_ctx ctx = X->ctx;
   KS_HIP(hipSetDevice(ctx->device));
@@ -805,6 +854,8 @@ int ksb_dot_range(ks_bv X, int xs, int xe, ks_bv Y, int ys, int ye, double *M, i
 
 extern "C" int ks_bv_dot(ks_bv X, ks_bv Y, double *M, int ldm)   // bvglobal.c:86-116, svec.c:89-107: M = Y^H X
 {
+  KS_CALL(ksb_flush(X));
+  KS_CALL(ksb_flush(Y));
   KS_CHECK(X && Y && M, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(ldm >= Y->k, KS_ERR_ARG_SIZ, "Mat argument has %d rows, should have at least %d", ldm, Y->k);
   KS_CHECK(X->n == Y->n, KS_ERR_ARG_INCOMP, "Mismatching local dimension X %d, Y %d", X->n, Y->n);
@@ -814,12 +865,13 @@ extern "C" int ks_bv_dot(ks_bv X, ks_bv Y, double *M, int ldm)   // bvglobal.c:8
 // Y(:,ys:ye) = beta*Y(:,ys:ye) + alpha*X(:,xs:xe)*Q(xs:xe, ys:ye); X and Y may be the same BV when the ranges are disjoint
 int ksb_mult_range(ks_bv Y, int ys, int ye, double alpha, double beta, ks_bv X, int xs, int xe, const double *Q, int ldq)
 {
+  KS_CALL(ksb_flush(X)); KS_CALL(ksb_flush(Y));
   const int ny = ye - ys, kx = xe - xs;
   if (ny <= 0 || kx <= 0) return KS_SUCCESS;
   ks_ctx ctx = Y->ctx;
   KS_HIP(hipSetDevice(ctx->device));
   double *qdev = nullptr;
-  KS_CALL(stage_coefs(Y, Q, (size_t)ldq * ye, &qdev));
+  KS_CALL(ksb_stage_coefs(Y, Q, (size_t)ldq * ye, &qdev));
   return panel_mult(ctx, KS_K_MULT, X->array + (size_t)(X->nc + xs) * X->ld, X->ld, Y->n, kx, qdev + (size_t)ys * ldq + xs, ldq, false, ny, alpha, beta,
                     Y->array + (size_t)(Y->nc + ys) * Y->ld, Y->ld);
 }
@@ -827,6 +879,7 @@ int ksb_mult_range(ks_bv Y, int ys, int ye, double alpha, double beta, ks_bv X, 
 // ---- ops->scale / norm / copy ------------------------------------------------------------------------
 extern "C" int ks_bv_scale(ks_bv bv, double alpha)   // bvops.c:311, svec.c:150-162 (j<0: (k-l)*ld contiguous scalars)
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
   if (alpha == 1.0 || !bv->n || bv->k <= bv->l) return KS_SUCCESS;
   bv->spec.valid = false;
@@ -836,6 +889,7 @@ extern "C" int ks_bv_scale(ks_bv bv, double alpha)   // bvops.c:311, svec.c:150-
 
 extern "C" int ks_bv_scalecolumn(ks_bv bv, int j, double alpha)   // bvops.c:341
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
   KS_CHECK(j >= 0 && j < bv->m, KS_ERR_ARG_OUTOFRANGE, "Argument j has wrong value %d, the number of columns is %d", j, bv->m);
   if (alpha == 1.0 || !bv->n) return KS_SUCCESS;
@@ -847,6 +901,7 @@ extern "C" int ks_bv_scalecolumn(ks_bv bv, int j, double alpha)   // bvops.c:341
 static int norm_core(ks_bv bv, const double *A, int ncols, int j, int type, double *val, bool reduce);
 static int norm_impl(ks_bv bv, int j, int type, double *val, bool reduce)   // svec.c:164-190, bvlapack.c:37-83
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && val, KS_ERR_ARG_NULL, "NULL argument");
   KS_HIP(hipSetDevice(bv->ctx->device));
   const double *A; int ncols;
@@ -924,11 +979,13 @@ static int norm_core(ks_bv bv, const double *A, int ncols, int j, int type, doub
 }
 extern "C" int ks_bv_norm(ks_bv bv, int type, double *val)                   // bvglobal.c:498
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(type != KS_NORM_2, KS_ERR_SUP, "Requested norm not available");
   return norm_impl(bv, -1, type, val, true);
 }
 extern "C" int ks_bv_normcolumn(ks_bv bv, int j, int type, double *val)      // bvglobal.c:662
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(j >= 0, KS_ERR_ARG_OUTOFRANGE, "Argument j has wrong value %d", j);
   if (bv && bv->matrix) {                                                   // bvglobal.c:683-687: sqrt(V[j]'*B*V[j]), type ignored
     KS_CHECK(val, KS_ERR_ARG_NULL, "NULL argument");
@@ -941,6 +998,7 @@ extern "C" int ks_bv_normcolumn(ks_bv bv, int j, int type, double *val)      // 
 extern "C" int ks_bv_norm_local(ks_bv bv, int j, int type, double *val) { return norm_impl(bv, j, type, val, false); }
 extern "C" int ks_bv_normvec(ks_bv bv, const double *v_dev, int type, double *val)   // BVNormVec bvglobal.c:530-571: B-norm when a matrix is set
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && v_dev && val, KS_ERR_ARG_NULL, "NULL argument");
   KS_HIP(hipSetDevice(bv->ctx->device));
   if (bv->matrix) return ksb_norm_b(bv, v_dev, val);
@@ -996,6 +1054,7 @@ static int dots_local(ks_bv X, const double *A, int kx, const double *y_dev, dou
 }
 extern "C" int ks_bv_dotvec_begin(ks_bv X, const double *y_dev, double *m)   // BVDotVecBegin bvglobal.c:207
 {
+  KS_CALL(ksb_flush(X));
   KS_CHECK(X && y_dev && m, KS_ERR_ARG_NULL, "NULL argument");
   KS_HIP(hipSetDevice(X->ctx->device));
   const int kx = X->k - X->l;
@@ -1007,6 +1066,7 @@ extern "C" int ks_bv_dotvec_begin(ks_bv X, const double *y_dev, double *m)   // 
 }
 extern "C" int ks_bv_dotvec_end(ks_bv X, const double *y_dev, double *m)     // BVDotVecEnd bvglobal.c:256
 {
+  KS_CALL(ksb_flush(X));
   KS_CHECK(X && m, KS_ERR_ARG_NULL, "NULL argument");
   (void)y_dev;
   const int kx = X->k - X->l;
@@ -1015,6 +1075,7 @@ extern "C" int ks_bv_dotvec_end(ks_bv X, const double *y_dev, double *m)     // 
 }
 extern "C" int ks_bv_dotcolumn_begin(ks_bv X, int j, double *q)              // BVDotColumnBegin bvglobal.c:343
 {
+  KS_CALL(ksb_flush(X));
   KS_CHECK(X && q, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(j >= 0 && j < X->m, KS_ERR_ARG_OUTOFRANGE, "Index j=%d but BV only has %d columns", j, X->m);
   const int ksave = X->k; X->k = j;
@@ -1024,6 +1085,7 @@ extern "C" int ks_bv_dotcolumn_begin(ks_bv X, int j, double *q)              // 
 }
 extern "C" int ks_bv_dotcolumn_end(ks_bv X, int j, double *q)                // BVDotColumnEnd bvglobal.c:395
 {
+  KS_CALL(ksb_flush(X));
   KS_CHECK(X && q, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(j >= 0 && j < X->m, KS_ERR_ARG_OUTOFRANGE, "Index j=%d but BV only has %d columns", j, X->m);
   const int ksave = X->k; X->k = j;
@@ -1041,6 +1103,7 @@ static int norm2_begin(ks_bv bv, const double *v_dev)
 }
 extern "C" int ks_bv_normvec_begin(ks_bv bv, const double *v_dev, int type, double *val)   // BVNormVecBegin bvglobal.c:573
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && v_dev && val, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(type == KS_NORM_2 || type == KS_NORM_FROBENIUS || bv->matrix, KS_ERR_SUP, "the split form is built for the 2-norm (a SUM reduction)");
   KS_HIP(hipSetDevice(bv->ctx->device));
@@ -1048,18 +1111,21 @@ extern "C" int ks_bv_normvec_begin(ks_bv bv, const double *v_dev, int type, doub
 }
 extern "C" int ks_bv_normvec_end(ks_bv bv, const double *v_dev, int type, double *val)     // BVNormVecEnd bvglobal.c:615
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && val, KS_ERR_ARG_NULL, "NULL argument");
   (void)v_dev; (void)type;
   return split_end(bv->ctx, 1, 1, val, bv->deftol);
 }
 extern "C" int ks_bv_normcolumn_begin(ks_bv bv, int j, int type, double *val)              // BVNormColumnBegin bvglobal.c:705
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && val, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(j >= 0 && j < bv->m, KS_ERR_ARG_OUTOFRANGE, "Argument j has wrong value %d, the number of columns is %d", j, bv->m);
   return ks_bv_normvec_begin(bv, ks_bv_col(bv, j), type, val);
 }
 extern "C" int ks_bv_normcolumn_end(ks_bv bv, int j, int type, double *val)                // BVNormColumnEnd bvglobal.c:751
 {
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(bv && val, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(j >= 0 && j < bv->m, KS_ERR_ARG_OUTOFRANGE, "Argument j has wrong value %d, the number of columns is %d", j, bv->m);
   return ks_bv_normvec_end(bv, nullptr, type, val);
@@ -1067,6 +1133,8 @@ extern "C" int ks_bv_normcolumn_end(ks_bv bv, int j, int type, double *val)     
 
 extern "C" int ks_bv_copy(ks_bv V, ks_bv W)   // svec.c:232-247
 {
+  KS_CALL(ksb_flush(V));
+  KS_CALL(ksb_flush(W));
   KS_CHECK(V && W, KS_ERR_ARG_NULL, "BV is NULL");
   KS_CHECK(V->n == W->n, KS_ERR_ARG_INCOMP, "Mismatching local dimension V %d, W %d", V->n, W->n);
   KS_CHECK(V->k - V->l == W->k - W->l, KS_ERR_ARG_SIZ, "W has %d active columns, should match %d active columns in V", W->k - W->l, V->k - V->l);
@@ -1078,6 +1146,7 @@ extern "C" int ks_bv_copy(ks_bv V, ks_bv W)   // svec.c:232-247
 
 extern "C" int ks_bv_copycolumn(ks_bv V, int j, int i)   // svec.c:249-259
 {
+  KS_CALL(ksb_flush(V));
   KS_CHECK(V, KS_ERR_ARG_NULL, "BV is NULL");
   KS_CHECK(j >= 0 && j < V->m && i >= 0 && i < V->m, KS_ERR_ARG_OUTOFRANGE, "column index out of range (%d -> %d, m=%d)", j, i, V->m);
   if (j == i) return KS_SUCCESS;
@@ -1089,6 +1158,7 @@ extern "C" int ks_bv_copycolumn(ks_bv V, int j, int i)   // svec.c:249-259
 // ---- ops->matmult -----------------------------------------------------------------------------------
 extern "C" int ks_bv_matmultcolumn(ks_bv V, ks_mat A, int j)   // bvops.c:862-885
 {
+  KS_CALL(ksb_flush(V));
   KS_CHECK(V && A, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(j >= 0, KS_ERR_ARG_OUTOFRANGE, "Index j must be non-negative");
   KS_CHECK(j + 1 < V->m, KS_ERR_ARG_OUTOFRANGE, "Result should go in index j+1=%d but BV only has %d columns", j + 1, V->m);
@@ -1099,6 +1169,8 @@ extern "C" int ks_bv_matmultcolumn(ks_bv V, ks_mat A, int j)   // bvops.c:862-88
 
 extern "C" int ks_bv_matmult(ks_bv V, ks_mat A, ks_bv W)   // bvops.c BVMatMult, svec.c:213-222 (column loop)
 {
+  KS_CALL(ksb_flush(V));
+  KS_CALL(ksb_flush(W));
   KS_CHECK(V && A && W, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(A->n == W->n && A->n == V->n, KS_ERR_ARG_INCOMP, "Mismatching local row dimension");
   KS_CHECK(V->k - V->l == W->k - W->l, KS_ERR_ARG_SIZ, "Y has %d active columns, should match %d active columns in V", W->k - W->l, V->k - V->l);

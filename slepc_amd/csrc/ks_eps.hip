@@ -755,8 +755,12 @@ static int restart_loop(ks_eps eps, ksd::Ds &ds)
     ds.set_dimensions(nv, eps->nconv, eps->nconv + l);
     double beta = 0.0; int breakdown = 0;
     const int k0 = eps->nconv + l;
-    KS_CALL(hermitian ? ks_bv_matlanczos(V, eps->op, ds.M().data(), ds.ld, k0, &nv, &beta, &breakdown)
-                      : ks_bv_matarnoldi(V, eps->op, ds.M().data(), ds.ld, k0, &nv, &beta, &breakdown));
+    // the run's last final update may wait for the restart product below (ksb_restart); whatever touches the basis before that flushes it
+    const bool defer0 = V->defer.want; V->defer.want = true;
+    const int rck = hermitian ? ks_bv_matlanczos(V, eps->op, ds.M().data(), ds.ld, k0, &nv, &beta, &breakdown)
+                              : ks_bv_matarnoldi(V, eps->op, ds.M().data(), ds.ld, k0, &nv, &beta, &breakdown);
+    V->defer.want = defer0;
+    KS_CALL(rck);
     eps->steps += nv - k0;
     ds.set_dimensions(nv, eps->nconv, eps->nconv + l);
     ds.state = l ? ksd::DS_RAW : ksd::DS_INTERMEDIATE;
@@ -836,8 +840,8 @@ static int restart_loop(ks_eps eps, ksd::Ds &ds)
       }
     }
     // V(:,nconv:k+l) = V(:,nconv:nv) * Q(nconv:nv, nconv:k+l)      krylovschur.c:324-327
-    KS_CALL(ks_bv_multinplace(V, ds.Q.data(), ds.ld, eps->nconv, k + l));
-    if (eps->reason == KS_EPS_CONVERGED_ITERATING && !breakdown) KS_CALL(ks_bv_copycolumn(V, nv, k + l));
+    if (eps->reason == KS_EPS_CONVERGED_ITERATING && !breakdown) KS_CALL(ksb_restart(V, ds.Q.data(), ds.ld, eps->nconv, k + l, nv, k + l));   // product, then BVCopyColumn(V,nv,k+l)
+    else KS_CALL(ks_bv_multinplace(V, ds.Q.data(), ds.ld, eps->nconv, k + l));
     eps->nconv = k;
     KS_CALL(monitor(eps, nconv_mon, nv));
     eps->restarts++;

@@ -542,7 +542,8 @@ int launch_reduce_allreduce(ks_bv bv, const GsArgs &a)
 }
 
 // fold: the slot's GsArgs when the kernel carries its own bookkeeping, nullptr after a k_gs_finish launch
-int launch_update(ks_bv bv, int col, double *v, int slot, const GsArgs *fold = nullptr)
+// rev_saved >= 0: a deferred update (ksb_flush_pending) runs in the direction it was given when it was put off; the toggle has been made
+int launch_update(ks_bv bv, int col, double *v, int slot, const GsArgs *fold = nullptr, int rev_saved = -1)
 {
   ks_ctx ctx = bv->ctx;
   const int k = bv->nc + col;
@@ -556,7 +557,8 @@ int launch_update(ks_bv bv, int col, double *v, int slot, const GsArgs *fold = n
   const int upd_per_cu = ntl >= 16LL * ctx->num_cu ? 1 : (ntl >= 4LL * ctx->num_cu ? 2 : 0);
   (void)slot;
   const int plain = ks_basis_is_cache_resident((size_t)(bv->nc + bv->m), (size_t)bv->ld);
-  const int rev = bv->sweep_dir; bv->sweep_dir ^= 1;   // every sweep over the basis runs opposite to the one before it (dot sweeps included): it starts on
+  const int rev = rev_saved >= 0 ? rev_saved : bv->sweep_dir;
+  if (rev_saved < 0) bv->sweep_dir ^= 1;               // every sweep over the basis runs opposite to the one before it (dot sweeps included): it starts on
                                                        // the tail the previous one left in the 256 MB Infinity Cache (about a tenth of a 2.4 GB basis)
   KsProfScope ps(ctx, KS_K_UPD_FUSED, 8.0 * bv->n * (k + 2), ks_kt_for(kk));
   ps.tag(col, slot, k, bv->n);
@@ -644,7 +646,7 @@ int enqueue_scale_if(ks_bv bv, int j, bool clear)
   return KS_SUCCESS;
 }
 
-int enqueue_gs_slots(ks_bv bv, int j, int normalize, int krylov, int first, int last, bool halt_at_last, bool resolution_and_scale)
+int enqueue_gs_slots(ks_bv bv, int j, int normalize, int krylov, int first, int last, bool halt_at_last, bool resolution_and_scale, bool defer_last = false)
 {
   ks_ctx ctx = bv->ctx;
   const bool bmat = bv->matrix != nullptr;
@@ -659,6 +661,15 @@ int enqueue_gs_slots(ks_bv bv, int j, int normalize, int krylov, int first, int 
       KS_CALL(launch_finish_wide(bv, a));
       KS_CALL(enqueue_update_wide(bv, j));
       if (normalize) KS_CALL(enqueue_scale_if(bv, j, true));
+      continue;
+    }
+    if (defer_last && p == last && !wide && !bmat && !multi) {
+      // The last update of the run is put off: the slot's bookkeeping runs as a launch of its own (the same pure function on the same reduced
+      // partials as the folded prologue), the update waits in bv->defer for the restart, or for whoever touches the basis first. The sweep
+      // direction is taken and toggled here, where the update would have been launched.
+      KS_CALL(launch_finish(bv, a));
+      bv->defer.pending = true; bv->defer.one_pass = false; bv->defer.col = j; bv->defer.k = a.k; bv->defer.rev = bv->sweep_dir; bv->sweep_dir ^= 1;
+      bv->spec.valid = false;
       continue;
     }
     if (bmat) KS_CALL(enqueue_dots(bv, j, krylov));          // every pass takes its dots with B v afresh (a pass that turns out not to be needed gates itself off in the bookkeeping)
@@ -679,14 +690,14 @@ int enqueue_gs_slots(ks_bv bv, int j, int normalize, int krylov, int first, int 
 }
 
 // Optimistic program of column j (against columns 0..j-1).
-int enqueue_fused_gs(ks_bv bv, int j, int normalize, int krylov, bool dots_done = false)
+int enqueue_fused_gs(ks_bv bv, int j, int normalize, int krylov, bool dots_done = false, bool defer_last = false)
 {
   KS_CHECK(bv->nc + j + 1 <= 8000, KS_ERR_SUP, "device-resident Gram-Schmidt supports at most 8000 columns");
   if (!dots_done && !bv->matrix && bv->nc + j + 1 <= KS_MAX_COLS) KS_CALL(enqueue_dots(bv, j, krylov));      // with a matrix, or more than 64 coefficients, every slot starts with its own dots
   const int ns = spec_slots(bv), nt = total_slots(bv);
   const bool whole = (ns >= nt) && bv->orthog_ref == KS_BV_ORTHOG_REFINE_NEVER;
   if (whole) return enqueue_gs_slots(bv, j, normalize, krylov, 1, nt, false, true);
-  return enqueue_gs_slots(bv, j, normalize, krylov, 1, ns, true, false);
+  return enqueue_gs_slots(bv, j, normalize, krylov, 1, ns, true, false, defer_last && ns == 2);
 }
 
 // Completion program of the column the device flagged: remaining passes + resolution + scaling.
@@ -1042,10 +1053,21 @@ int orthogonalize_column(ks_bv bv, int j, int normalize, double *H, double *norm
 
 } // namespace
 
+// A deferred final update, applied now: the non-folded form of the update kernel reads do_update, npend, alpha and store_now from the state
+// k_gs_finish left and the coefficients from bv->pend - a launch that does nothing when the column had become final earlier or the run had halted
+int ksb_flush_pending(ks_bv bv)
+{
+  if (!bv->defer.pending) return KS_SUCCESS;
+  bv->defer.pending = false; bv->defer.one_pass = false; bv->defer.flushes++;
+  KS_HIP(hipSetDevice(bv->ctx->device));
+  return launch_update(bv, bv->defer.col, ks_bv_col(bv, bv->defer.col), 2, nullptr, bv->defer.rev);
+}
+
 // ---- public GS entry points ----------------------------------------------------------------------
 extern "C" int ks_bv_orthogonalizecolumn(ks_bv bv, int j, double *H, double *norm, int *lindep)   // bvorthog.c:315-339
 {
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(j >= 0, KS_ERR_ARG_OUTOFRANGE, "Index j must be non-negative");
   KS_CHECK(j < bv->m, KS_ERR_ARG_OUTOFRANGE, "Index j=%d but BV only has %d columns", j, bv->m);
   return orthogonalize_column(bv, j, 0, H, norm, lindep);
@@ -1055,17 +1077,19 @@ extern "C" int ks_bv_orthogonalizecolumn(ks_bv bv, int j, double *H, double *nor
 // final update, coefficients, norm and flag come back in one host wait
 int ks_bv_orthonormalize_coefs(ks_bv bv, int j, double *H, double *norm, int *lindep)
 {
+  KS_CALL(ksb_flush(bv));
   return orthogonalize_column(bv, j, 1, H, norm, lindep);
 }
 // the same in two halves, for a caller that has work to enqueue behind the orthogonalisation before it looks at the result (the next operator
 // application of a GMRES): available when the fused program runs (classical Gram-Schmidt)
 bool ks_bv_orthonormalize_can_split(ks_bv bv) { return use_fused(bv); }
-int ks_bv_orthonormalize_enqueue(ks_bv bv, int j) { KS_HIP(hipSetDevice(bv->ctx->device)); return gs_enqueue_column(bv, j, 1, true, true); }
+int ks_bv_orthonormalize_enqueue(ks_bv bv, int j) { KS_CALL(ksb_flush(bv)); KS_HIP(hipSetDevice(bv->ctx->device)); return gs_enqueue_column(bv, j, 1, true, true); }
 int ks_bv_orthonormalize_collect(ks_bv bv, int j, double *H, double *norm, int *lindep, int *late_completion) { return gs_collect_column(bv, j, 1, H, norm, lindep, late_completion); }
 
 extern "C" int ks_bv_orthonormalizecolumn(ks_bv bv, int j, int replace, double *norm, int *lindep)   // bvorthog.c:380-427
 {
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(j >= 0, KS_ERR_ARG_OUTOFRANGE, "Index j must be non-negative");
   KS_CHECK(j < bv->m, KS_ERR_ARG_OUTOFRANGE, "Index j=%d but BV only has %d columns", j, bv->m);
   double nrm = 0.0; int lin = 0;
@@ -1087,6 +1111,7 @@ extern "C" int ks_bv_orthonormalizecolumn(ks_bv bv, int j, int replace, double *
 extern "C" int ks_bv_orthogonalizevec(ks_bv bv, double *v_dev, double *H, double *norm, int *lindep)   // bvorthog.c:247-269
 {
   KS_CHECK(bv && v_dev, KS_ERR_ARG_NULL, "NULL argument");
+  KS_CALL(ksb_flush(bv));
   KS_HIP(hipSetDevice(bv->ctx->device));
   std::vector<double> hh(bv->nc + bv->m + 1, 0.0);
   const int lsave = bv->l, ksave = bv->k;
@@ -1103,6 +1128,7 @@ extern "C" int ks_bv_orthogonalizevec(ks_bv bv, double *v_dev, double *H, double
 extern "C" int ks_bv_orthogonalizesomecolumn(ks_bv bv, int j, const int *which, double *H, double *norm, int *lindep)   // bvorthog.c:432-470
 {
   KS_CHECK(bv && which, KS_ERR_ARG_NULL, "NULL argument");
+  KS_CALL(ksb_flush(bv));
   KS_CHECK(j >= 0, KS_ERR_ARG_OUTOFRANGE, "Index j must be non-negative");
   KS_CHECK(j < bv->m, KS_ERR_ARG_OUTOFRANGE, "Index j=%d but BV only has %d columns", j, bv->m);
   KS_CHECK(bv->orthog_type == KS_BV_ORTHOG_MGS, KS_ERR_SUP, "Operation only available for MGS orthogonalization");
@@ -1230,6 +1256,7 @@ int gs1_fused_column(ks_bv bv, int j, double *onrm, double *nrm)
 extern "C" int ks_bv_gramschmidt_pass(ks_bv bv, int j, double *v_dev, const int *which, double *h, double *c, double *onrm, double *nrm)
 {
   KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
+  KS_CALL(ksb_flush(bv));
   KS_CHECK((h == nullptr) == (c == nullptr), KS_ERR_ARG_WRONG, "h and c must both be host arrays or both be NULL (the BV's buffer)");
   KS_CHECK(v_dev || (j >= 0 && j < bv->m), KS_ERR_ARG_OUTOFRANGE, "Index j=%d but BV only has %d columns", j, bv->m);
   KS_CHECK(!v_dev || (j >= 0 && j <= bv->m), KS_ERR_ARG_OUTOFRANGE, "Argument j=%d (number of columns to orthogonalize against) out of range", j);
@@ -1289,6 +1316,7 @@ extern "C" int ks_bv_gs_passes(ks_bv bv, long long *total, int *last)
 static int krylov_run(ks_bv V, ks_mat A, int k, int *m, double *beta, int *breakdown, std::vector<double> &buf)
 {
   KS_CHECK(V && A && m, KS_ERR_ARG_NULL, "NULL argument");
+  KS_CALL(ksb_flush(V));
   KS_CHECK(k >= 0 && k <= V->m, KS_ERR_ARG_OUTOFRANGE, "Argument k has wrong value %d, should be between 0 and %d", k, V->m);
   KS_CHECK(*m > 0 && *m <= V->m, KS_ERR_ARG_OUTOFRANGE, "Argument m has wrong value %d, should be between 1 and %d", *m, V->m);
   KS_CHECK(*m > k, KS_ERR_ARG_OUTOFRANGE, "Argument m should be at least equal to k+1");
@@ -1305,18 +1333,26 @@ static int krylov_run(ks_bv V, ks_mat A, int k, int *m, double *beta, int *break
     // column that needs more than the optimistic program, turns the remaining steps into no-ops. In the second
     // case the host completes that one column and re-enqueues the rest of the run.
     int mm = m0, j0 = k;
+    // the final update of the run's last column may wait for the restart product (ks_bv_set_defer_final): one rank, a basis the fused restart kernel takes
+    const bool defer = V->defer.want && !ctx->dbg.no_restart_fusion && !ks_is_multi(ctx) && !V->matrix && V->nc + m0 <= 32 && V->ld % 2 == 0 && aligned16(ks_bv_col(V, -V->nc));
     while (j0 < m0 && !lin) {
       KS_CALL(begin_run(V));
       for (int j = j0; j < m0; j++) {
         bool dots_done = false;                                                      // the product inside the first dot sweep where that pays (small problems)
         KS_CALL(ks_mat_mult_dot_fused(A, V, ks_bv_col(V, j), j + 1, true, &dots_done));
         if (!dots_done) KS_CALL(ks_mat_mult_internal(A, ks_bv_col(V, j), ks_bv_col(V, j + 1)));    // BVMatMultColumn (not gated: harmless after a halt)
-        KS_CALL(enqueue_fused_gs(V, j + 1, 1, 1, dots_done));
+        KS_CALL(enqueue_fused_gs(V, j + 1, 1, 1, dots_done, defer && j == m0 - 1));
       }
       KsGsState st; std::vector<KsStepRec> recs(m0 - j0);
       buf.resize((size_t)V->m * (V->nc + V->m));
       KS_CALL(fetch_state(V, &st, recs.data(), j0 + 1, m0, buf.data(), buf.size()));          // the coefficient buffer travels with the state (VecGetArrayRead(buf) bvkrylov.c:103,215)
       buf_fresh = true;
+      if (V->defer.pending) {
+        // the optimistic program was enough for every column, and the update left over is the plain scaled store of a two-pass column: it may wait.
+        // Anything else (a halt, a breakdown, a last column that was final after one pass) is flushed here and the run goes on as it always has.
+        const bool waits = st.active && st.halt_col < 0 && !st.err && st.do_update && st.store_now && !st.fuse_dot && st.npend >= 1 && st.npend <= 3 && !recs[m0 - 1 - j0].lindep;
+        if (waits) V->defer.one_pass = true; else KS_CALL(ksb_flush_pending(V));
+      }
       const int hc = st.halt_col;                    // column awaiting completion, or -1
       if (ctx->prof_on) {
         // columns after a halt never ran (0 passes, everything gated off); the flagged column ran both optimistic
@@ -1401,5 +1437,22 @@ extern "C" int ks_bv_matlanczos(ks_bv V, ks_mat A, double *T, int ldt, int k, in
     double *alpha = T, *betat = T + ldt;
     for (int j = k; j < *m; j++) { alpha[j] = a[V->nc + j + (size_t)(j + 1) * nb]; betat[j] = a[V->nc + j + 1 + (size_t)(j + 1) * nb]; }
   }
+  return KS_SUCCESS;
+}
+
+// ---- deferred final update ----------------------------------------------------------------------------
+extern "C" int ks_bv_set_defer_final(ks_bv bv, int on)
+{
+  KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
+  if (!on) KS_CALL(ksb_flush(bv));
+  bv->defer.want = on != 0;
+  return KS_SUCCESS;
+}
+extern "C" int ks_bv_restart_stats(ks_bv bv, int *pending, long long *flushes, long long *fused)
+{
+  KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
+  if (pending) *pending = bv->defer.pending ? 1 : 0;
+  if (flushes) *flushes = bv->defer.flushes;
+  if (fused) *fused = bv->defer.fused;
   return KS_SUCCESS;
 }

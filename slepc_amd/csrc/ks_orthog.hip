@@ -264,6 +264,7 @@ extern "C" int ks_bv_set_orthog_block(ks_bv bv, int block)            // BVSetOr
 
 extern "C" int ks_bv_orthogonalize(ks_bv V, double *R, int ldr)       // BVOrthogonalize bvorthog.c:729-767
 {
+  KS_CALL(ksb_flush(V));
   KS_CHECK(V, KS_ERR_ARG_NULL, "BV is NULL");
   if (R) KS_CHECK(ldr >= V->k, KS_ERR_ARG_SIZ, "Mat size %d is smaller than the number of BV active columns %d", ldr, V->k);
   KS_CHECK(!V->nc, KS_ERR_SUP, "Not implemented for BV with constraints, use BVOrthogonalizeColumn() instead");
@@ -341,6 +342,8 @@ extern "C" int ks_bv_orthogonalize(ks_bv V, double *R, int ldr)       // BVOrtho
 // BVMatProject bvglobal.c:1014-1160 (no inner-product matrix): M(ly:ky, lx:kx) = Y(:,ly:ky)^H A X(:,lx:kx); A NULL = identity
 extern "C" int ks_bv_matproject(ks_bv X, ks_mat A, ks_bv Y, double *M, int ldm)
 {
+  KS_CALL(ksb_flush(X));
+  KS_CALL(ksb_flush(Y));
   KS_CHECK(X && Y && M, KS_ERR_ARG_NULL, "NULL argument");
   KS_CHECK(X->n == Y->n, KS_ERR_ARG_INCOMP, "Mismatching local dimension X %d, Y %d", X->n, Y->n);
   KS_CHECK(ldm >= Y->k, KS_ERR_ARG_SIZ, "Matrix M has %d rows, should have at least %d", ldm, Y->k);
@@ -364,6 +367,7 @@ extern "C" int ks_bv_matproject(ks_bv X, ks_mat A, ks_bv Y, double *M, int ldm)
 // a complex-conjugate pair (eigi[j] != 0) are scaled together by the norm of xr + i*xi
 extern "C" int ks_bv_normalize(ks_bv V, const double *eigi)
 {
+  KS_CALL(ksb_flush(V));
   KS_CHECK(V, KS_ERR_ARG_NULL, "BV is NULL");
   for (int j = V->l; j < V->k; j++) {
     double nr = 0.0;

@@ -213,6 +213,96 @@ __global__ __launch_bounds__(PB) void k_panel_mult_direct(const double *A, long 
   }
 }
 
+// ---- the end of a restart cycle in one read of the panel ----------------------------------------------------------------------
+// Three row-local operations the restart ran as three launches: the final CGS update of the last column (k_gs_update, store form),
+// v = ((y - V c1) - V c2) * alpha over the k columns before it; the restart product (k_panel_mult_direct) over the active columns; the copy of the
+// updated vector to its place behind the product. Here a wave owns a tile of RF_ROWS rows: it loads V(r,0:k) and y(r) in the update kernel's shape
+// (lane <-> two rows, one wave-instruction reads 1 KiB of one column), applies the pending passes with the update kernel's fma chain (pass by pass,
+// coefficients negated, i ascending, then * alpha), puts the panel tile into LDS column by column, reads it back in the MFMA fragment layout of
+// k_panel_mult_direct (lane (j, kq): rows 2j, 2j + 1 of column 4 ks + kq of a 32-row group) and issues that kernel's MFMA sequence: ks ascending,
+// zero-padded Q fragments, a padded column repeating the last active one. Every output element gets the arithmetic the three kernels gave it.
+// The tile is private to its wave and complete in LDS before the first store, so the product may overwrite its own inputs (column dst is one).
+// One workgroup of four waves per CU (4 x 32 KB of LDS); stores written through like both kernels this replaces.
+constexpr int RF_ROWS = 128, RF_KMAX = 32;
+constexpr size_t RF_LDS = (size_t)(PB / 64) * RF_KMAX * RF_ROWS * sizeof(double);
+template <bool PLAIN>
+__global__ __launch_bounds__(PB) void k_restart_fused(const double *V0, long long ld, int n, int k, double *vsrc, double *vdst, const double *__restrict__ pend,
+                                                       const KsGsState *__restrict__ st, int a0, int kin, const double *__restrict__ Q, int ldq, int nout, double *C)
+{
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, j = lane & 15, kq = lane >> 4;
+  double *tile = lds + (size_t)w * RF_KMAX * RF_ROWS;                 // [column][row of the tile]
+  const int upd = st->do_update;
+  const int npend = upd ? st->npend : 0;
+  const bool scal = upd && st->scale_now != 0;
+  const double alpha = st->alpha;
+  const int ks4 = ((kin + 15) / 16) * 4;                                // k-steps, as ksp_mult_mfma rounds them
+  double qf[8];
+#pragma unroll
+  for (int ks = 0; ks < 8; ks++) { const int kk = ks * 4 + kq; qf[ks] = (ks < ks4 && kk < kin && j < nout) ? Q[(size_t)kk + (size_t)j * ldq] : 0.0; }
+  const long long ntiles = ((long long)n + RF_ROWS - 1) / RF_ROWS;
+  const long long gw = (long long)blockIdx.x * (PB / 64) + w, GW = (long long)gridDim.x * (PB / 64);
+  for (long long t = gw; t < ntiles; t += GW) {
+    const long long r0 = t * RF_ROWS, r = r0 + 2 * lane;
+    double2 xv[RF_KMAX], sv;
+    if (r0 + RF_ROWS <= n) {
+#pragma unroll
+      for (int i = 0; i < RF_KMAX; i++) { const int ii = i < k ? i : k - 1; xv[i] = ksk::ldbasis2<PLAIN>(V0 + (long long)ii * ld + r); }
+      sv = *reinterpret_cast<const double2 *>(vsrc + r);
+    } else {
+#pragma unroll
+      for (int i = 0; i < RF_KMAX; i++) { const int ii = i < k ? i : k - 1; const double *p = V0 + (long long)ii * ld + r; xv[i].x = r < n ? p[0] : 0.0; xv[i].y = r + 1 < n ? p[1] : 0.0; }
+      sv.x = r < n ? vsrc[r] : 0.0; sv.y = r + 1 < n ? vsrc[r + 1] : 0.0;
+    }
+    __builtin_amdgcn_sched_barrier(0);                                  // all loads of the tile in flight before the first use waits
+    // the pending passes, one after the other, exactly as if each had stored its result (ks_gs.hip upd_tiles)
+    for (int p = 0; p < npend; p++) {
+      const double *cp = pend + (size_t)p * KS_PSTRIDE;
+#pragma unroll
+      for (int i = 0; i < RF_KMAX; i++) if (i < k) { const double c = -cp[i]; sv.x = fma(c, xv[i].x, sv.x); sv.y = fma(c, xv[i].y, sv.y); }
+    }
+    if (scal) { sv.x *= alpha; sv.y *= alpha; }
+#pragma unroll
+    for (int i = 0; i < RF_KMAX; i++) *reinterpret_cast<double2 *>(tile + i * RF_ROWS + 2 * lane) = xv[i];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int u = 0; u < RF_ROWS / 32; u++) {
+      d4 e = (d4){0.0, 0.0, 0.0, 0.0}, o = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int ks = 0; ks < 8; ks++)
+        if (ks < ks4) {
+          const int kk = ks * 4 + kq;
+          const double2 b = *reinterpret_cast<const double2 *>(tile + (a0 + (kk < kin ? kk : kin - 1)) * RF_ROWS + 32 * u + 2 * j);
+          e = __builtin_amdgcn_mfma_f64_16x16x4f64(qf[ks], b.x, e, 0, 0, 0);
+          o = __builtin_amdgcn_mfma_f64_16x16x4f64(qf[ks], b.y, o, 0, 0, 0);
+        }
+      const long long row = r0 + 32 * u + 2 * j;
+      if (row < n) {
+#pragma unroll
+        for (int reg = 0; reg < 4; reg++) {
+          const int col = kq + 4 * reg;
+          if (col < nout) {
+            double *c = C + (long long)col * ld + row;
+            if (row + 1 < n) {
+              ksk::ks_d2v rv; rv.x = e[reg]; rv.y = o[reg];
+              asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(reinterpret_cast<ksk::ks_d2v *>(c)), "v"(rv) : "memory");
+            } else c[0] = e[reg];
+          }
+        }
+      }
+    }
+    // the updated vector: where it was computed (bench and callers read column src) and behind the product
+    if (r + 1 < n) {
+      const ksk::ks_d2v rv = {sv.x, sv.y};
+      asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(reinterpret_cast<ksk::ks_d2v *>(vsrc + r)), "v"(rv) : "memory");
+      asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(reinterpret_cast<ksk::ks_d2v *>(vdst + r)), "v"(rv) : "memory");
+    } else if (r < n) { vsrc[r] = sv.x; vdst[r] = sv.x; }
+    __builtin_amdgcn_wave_barrier();                                    // the next tile overwrites the LDS this one was read from
+  }
+}
+
 } // namespace
 
 // ---- launchers -------------------------------------------------------------------------------------------------
@@ -282,6 +372,30 @@ int ksp_mult_mfma(ks_ctx ctx, int kclass, const double *A, int lda, int n, int k
     default: KS_FAIL(KS_ERR_PLIB, "bad tile counts");
   }
 #undef MULT_CASE
+  KS_HIP(hipGetLastError());
+  return KS_SUCCESS;
+}
+
+// The pending final update of column vsrc (k previous columns from V0; state and coefficients as k_gs_finish left them in bv->gs, bv->pend), the product
+// C(:,0:nout) = A(:,0:kin) Q over the active columns A = V0 + a0 columns, and the updated vector to vsrc and vdst: k_restart_fused, one launch.
+// The caller has checked the shape: k <= 32, nout <= 16, even ld, 16-byte aligned columns, vdst outside C.
+int ksp_restart_fused(ks_bv bv, const double *V0, int k, double *vsrc, double *vdst, const double *A, int kin, const double *Qdev, int ldq, int nout, double *C)
+{
+  ks_ctx ctx = bv->ctx;
+  const int n = bv->n, a0 = (int)((A - V0) / bv->ld);
+  KS_CHECK(k >= 1 && k <= RF_KMAX && nout >= 1 && nout <= 16 && kin >= 1 && a0 >= 0 && a0 + kin <= k, KS_ERR_PLIB, "fused restart %d columns, %d active from %d, %d out", k, kin, a0, nout);
+  KS_CHECK(bv->ld % 2 == 0 && (((uintptr_t)V0 | (uintptr_t)vsrc | (uintptr_t)vdst | (uintptr_t)C) & 15) == 0, KS_ERR_PLIB, "fused restart needs 16-byte aligned columns");
+  const int plain = ksk::ks_basis_is_cache_resident((size_t)(bv->nc + bv->m), (size_t)bv->ld);
+  static thread_local std::vector<int> prepared[2];               // devices on which this symbol may already have 128 KB of dynamic LDS
+  if (std::find(prepared[plain].begin(), prepared[plain].end(), ctx->device) == prepared[plain].end()) {
+    KS_HIP(hipFuncSetAttribute(plain ? (const void *)k_restart_fused<true> : (const void *)k_restart_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RF_LDS));
+    prepared[plain].push_back(ctx->device);
+  }
+  const long long ntiles = ((long long)n + RF_ROWS - 1) / RF_ROWS;
+  const int grid = (int)std::max<long long>(1, std::min<long long>((ntiles + 3) / 4, (long long)ctx->num_cu));
+  KsProfScope ps(ctx, KS_K_MULTINPLACE, 8.0 * n * (k + 1 + nout + 2), 1);       // variant 1: this kernel (the panel kernels file under 4 * KS4)
+  if (plain) hipLaunchKernelGGL((k_restart_fused<true>), dim3(grid), dim3(PB), RF_LDS, ctx->stream, V0, (long long)bv->ld, n, k, vsrc, vdst, bv->pend, bv->gs, a0, kin, Qdev, ldq, nout, C);
+  else hipLaunchKernelGGL((k_restart_fused<false>), dim3(grid), dim3(PB), RF_LDS, ctx->stream, V0, (long long)bv->ld, n, k, vsrc, vdst, bv->pend, bv->gs, a0, kin, Qdev, ldq, nout, C);
   KS_HIP(hipGetLastError());
   return KS_SUCCESS;
 }

@@ -70,7 +70,7 @@ struct ks_ctx_s {
   hipStream_t halo_stream = nullptr; hipEvent_t ev_x = nullptr, ev_halo = nullptr;
   bool halo_overlap = true;
   // test hooks (ks_ctx_set_debug; each makes a test run the path the fast one replaces, or a multi-rank path on one rank)
-  struct { bool no_fused_gs = false, no_mfma = false, no_spmv_dot = false, force_multi = false, no_dict_patterns = false; unsigned oneshot_seq0 = 0; } dbg;
+  struct { bool no_fused_gs = false, no_mfma = false, no_spmv_dot = false, force_multi = false, no_dict_patterns = false, no_restart_fusion = false; unsigned oneshot_seq0 = 0; } dbg;
   long long nsync = 0;              // host synchronisations of the context's stream made by the library (ks_ctx_sync_count)
   int num_cu = 256;
   char arch[64] = {0};
@@ -367,6 +367,11 @@ struct ks_bv_s {
   int last_grid = 1;            // grid size of the sweep LAUNCHED last (profiling byte counts, and reductions that directly follow their sweep); the
                                 // Gram-Schmidt bookkeeping reads the grid from KsGsState::pgrid instead
   double *panel = nullptr; size_t panel_len = 0;   // block partials of the MFMA panel dot (grid x 64 x 64 max)
+  // Deferred final update (ks_bv_set_defer_final): the last column of an enqueued Krylov run keeps its final CGS update back. Its bookkeeping has run
+  // (k_gs_finish: state, pend, buffer column and record are complete), the update itself is still to be applied to column `col` against the
+  // k = nc + col columns before it, in sweep direction `rev` (taken, and toggled, where the update would have been launched). Whoever touches
+  // column data or Gram-Schmidt state next flushes it (ksb_flush); the restart (ksb_restart) applies it inside the restart product instead.
+  struct { bool want = false, pending = false, one_pass = false; int col = 0, k = 0, rev = 0; long long flushes = 0, fused = 0; } defer;
 };
 
 constexpr size_t KS_PINNED_D2H_BYTES = 65536;
@@ -398,6 +403,13 @@ int ksb_ipmatmult(ks_bv bv, const double *x, const double **z);   // z = x, or B
 int ksb_norm_b(ks_bv bv, const double *x, double *val);            // sqrt(x' B x) with the BV_SafeSqrt check (BVNorm_Private)
 int ksb_dot_range(ks_bv X, int xs, int xe, ks_bv Y, int ys, int ye, double *M, int ldm);          // M(ys:ye,xs:xe) = Y(:,ys:ye)^T X(:,xs:xe)
 int ksb_mult_range(ks_bv Y, int ys, int ye, double alpha, double beta, ks_bv X, int xs, int xe, const double *Q, int ldq);
+int ksb_flush_pending(ks_bv bv);                                   // applies a deferred final update now (ks_gs.hip)
+static inline int ksb_flush(ks_bv bv) { return (bv && bv->defer.pending) ? ksb_flush_pending(bv) : KS_SUCCESS; }   // first line of every entry that touches column data or Gram-Schmidt state
+int ksb_restart(ks_bv V, const double *Q, int ldq, int s, int e, int src, int dst);   // BVMultInPlace(V,Q,s,e) then BVCopyColumn(V,src,dst); one launch with a pending update on src (ks_bv.hip)
+int ksb_stage_coefs(ks_bv bv, const double *host, size_t len, double **dev);
+// the fused restart kernel (ks_panel.hip): pending update of column src (k previous columns from V0, coefficients / state as k_gs_finish left them), product
+// of the kin active columns A with Q into C(:,0:nout), the updated vector to columns src and dst
+int ksp_restart_fused(ks_bv bv, const double *V0, int k, double *vsrc, double *vdst, const double *A, int kin, const double *Qdev, int ldq, int nout, double *C);
 // MFMA f64 panel contractions (ks_panel.hip)
 int ksp_dot_mfma(ks_bv bv, const double *Y, int ldy, int my, const double *X, int ldx, int nx, int n, double *M_dev);
 int ksp_mult_mfma(ks_ctx ctx, int kclass, const double *A, int lda, int n, int kin, const double *Qdev, int qsk, int qsi, int nout,
