@@ -80,7 +80,8 @@ enum { KS_EPS_LARGEST_MAGNITUDE = 1, KS_EPS_SMALLEST_MAGNITUDE = 2, KS_EPS_LARGE
 /* SlepcEigenvalueComparisonFn (include/slepcsc.h): *res < 0 if a is preferred to b, > 0 if b is preferred, 0 if equal */
 typedef int (*ks_eig_compare_fn)(double ar, double ai, double br, double bi, int *res, void *ctx);
 enum { KS_EPS_HEP = 1, KS_EPS_GHEP = 2, KS_EPS_NHEP = 3, KS_EPS_GNHEP = 4 };   /* EPSProblemType, slepceps.h */
-enum { KS_ST_SHIFT = 0, KS_ST_SINVERT = 1, KS_ST_CAYLEY = 2 };   /* STType "shift", "sinvert", "cayley" */
+enum { KS_ST_SHIFT = 0, KS_ST_SINVERT = 1, KS_ST_CAYLEY = 2, KS_ST_PRECOND = 3 };   /* STType "shift", "sinvert", "cayley", "precond" (precond.c: K = A - sigma B is only preconditioned, never solved) */
+enum { KS_EPS_KRYLOVSCHUR = 0, KS_EPS_LOBPCG = 1 };   /* EPSType "krylovschur", "lobpcg" */
 enum { KS_EPS_ERROR_ABSOLUTE = 0, KS_EPS_ERROR_RELATIVE = 1, KS_EPS_ERROR_BACKWARD = 2 };   /* EPSErrorType */
 enum { KS_EPS_RITZ = 0, KS_EPS_HARMONIC = 1, KS_EPS_HARMONIC_RELATIVE, KS_EPS_HARMONIC_RIGHT, KS_EPS_HARMONIC_LARGEST, KS_EPS_REFINED, KS_EPS_REFINED_HARMONIC };  /* EPSExtraction slepceps.h:94-100; Krylov-Schur offers the first two */
 enum { KS_EPS_BALANCE_NONE = 0, KS_EPS_BALANCE_ONESIDE = 1, KS_EPS_BALANCE_TWOSIDE = 2, KS_EPS_BALANCE_USER = 3 };   /* EPSBalance slepceps.h; the two-sided form needs the transposed product (ks_mat_mult_transpose) */
@@ -345,6 +346,12 @@ int ks_bv_matmultcolumn(ks_bv V, ks_mat A, int j);                              
 enum { KS_BV_MATMULT_VECS = 0, KS_BV_MATMULT_MAT = 1, KS_BV_MATMULT_MAT_SAVE = 2 };
 int ks_bv_set_matmult_method(ks_bv bv, int method);
 int ks_bv_get_matmult_method(ks_bv bv, int *method);                                             /* BVGetMatMultMethod bvbasic.c:1064 */
+/* The residual block of a block eigensolver with its norms (what lobpcg.c:176-202 does with BVCopy, one VecAXPY and one VecNorm per column - bs host
+   waits): R(:,j) = AX(:,j) - theta[j - l] * BX(:,j) for the active columns [l, k) of R, at most 16, the same column indices in AX and BX, and
+   norms[j - l] = ||R(:,j)||_2 over all ranks (host array). One kernel reads the two blocks once and writes the third, one reduction and one D2H bring
+   all the norms. r = fma(-theta, bx, ax): one rounding where the reference has two. BX may be the BV of the vectors themselves (a standard problem);
+   R must be a BV of its own (KS_ERR_ARG_WRONG). Columns of R outside [l, k) are not touched. theta: host array. */
+int ks_bv_block_residual(ks_bv R, ks_bv AX, ks_bv BX, const double *theta, double *norms);
 
 /* ops->gramschmidt (bvimpl.h:53): ONE Gram-Schmidt pass, the function BVOrthogonalizeGS1 dispatches to (bvorthog.c:134) in place
    of BVOrthogonalizeCGS1 (:91-132) / BVOrthogonalizeMGS1 (:52-85), chosen by the BV's orthogonalization type. The caller
@@ -453,6 +460,27 @@ int ks_eps_set_arbitrary_selection(ks_eps eps, ks_eps_arbitrary_fn fn, void *ctx
 int ks_eps_monitor_set(ks_eps eps, ks_eps_monitor_fn fn, void *ctx);                    /* EPSMonitorSet (one slot; NULL cancels): called once per restart with the DS-ordered values, untransformed */
 int ks_eps_set_purify(ks_eps eps, int purify);                              /* EPSSetPurify: 0 skips the purification of GHEP eigenvectors (test1_1_ks_nopurify) */
 int ks_eps_get_purify(ks_eps eps, int *purify);
+/* EPSSetType (epsbasic.c): KS_EPS_KRYLOVSCHUR (the default: nothing changes for existing callers) or KS_EPS_LOBPCG, the block solver for the smallest
+   (or largest) eigenvalues of symmetric problems without inner solves (src/eps/impls/cg/lobpcg/lobpcg.c; ks_lobpcg.hip). Choosing LOBPCG makes
+   KS_ST_PRECOND the type of the solver's ST unless the caller set one (EPSSetDefaultST_Precond); a Krylov-Schur solve with KS_ST_PRECOND is KS_ERR_SUP.
+   ks_eps_solve with LOBPCG (EPSSetUp_LOBPCG lobpcg.c:55-83) returns
+     KS_ERR_SUP         problem type other than KS_EPS_HEP / KS_EPS_GHEP; `which` other than smallest / largest real (unset: smallest real); arbitrary
+                        selection, harmonic extraction or the two-sided flag set; n_global - (deflation vectors) < 5 bs
+     KS_ERR_USER_INPUT  ncv given and smaller than max(3 bs, ((nev - 1) / bs + 3) bs); mpd given and different from 3 bs
+   Balancing is ignored; the default max_it is max(100, 2 n / ncv). Every getter of results, the monitor, the convergence and stopping tests, the
+   deflation space, track-all and the random seed work as after a Krylov-Schur solve; ks_eps_set_initial_space, called after the type is set, hands ALL its vectors to the first blocks (with the default type only the first is kept, as before).
+   Convergence is tested on the residual norm ||A x - theta B x||_2 with the EPS's criterion. Stated deviations: block sizes 1..16 only (the projected
+   problem has at most 48 columns; larger is KS_ERR_ARG_OUTOFRANGE), and those listed at the top of ks_lobpcg.hip. */
+int ks_eps_set_type(ks_eps eps, int type);
+int ks_eps_get_type(ks_eps eps, int *type);
+int ks_eps_lobpcg_set_blocksize(ks_eps eps, int bs);      /* EPSLOBPCGSetBlockSize lobpcg.c:422; 0 = default min(16, nev) */
+int ks_eps_lobpcg_get_blocksize(ks_eps eps, int *bs);     /* EPSLOBPCGGetBlockSize (0 until set) */
+int ks_eps_lobpcg_set_restart(ks_eps eps, double r);      /* EPSLOBPCGSetRestart lobpcg.c:472: default 0.9, 0.1..1; guard vectors = min((int)((1 - r) bs + 0.45), bs - 1), 0 for bs = 1 */
+int ks_eps_lobpcg_get_restart(ks_eps eps, double *r);
+int ks_eps_lobpcg_set_locking(ks_eps eps, int lock);      /* EPSLOBPCGSetLocking lobpcg.c:536 (soft locking), default on */
+int ks_eps_lobpcg_get_locking(ks_eps eps, int *lock);
+/* instrumentation of the last LOBPCG solve: passes of the main loop, hard locks, columns a matrix was applied to (A and B), columns preconditioned */
+int ks_eps_lobpcg_get_stats(ks_eps eps, long long *iterations, long long *hard_locks, long long *mat_columns, long long *pc_columns);
 int ks_eps_set_track_all(ks_eps eps, int trackall);                          /* EPSSetTrackAll: error estimates of all Ritz pairs at every restart (for monitors) */
 int ks_eps_get_krylovschur(ks_eps eps, double *keep, int *lock);             /* EPSKrylovSchurGetRestart / EPSKrylovSchurGetLocking */
 int ks_eps_set_balance(ks_eps eps, int bal, int its, double cutoff);        /* EPSSetBalance epsopts.c:1050 (non-symmetric problems; EPSBuildBalance_Krylov epsdefault.c:370); its / cutoff 0 keep 5 / 1e-8 */
@@ -522,7 +550,7 @@ int ks_st_set_ksp_type(ks_st st, int type);                                /* KS
 /* KSPGMRESSetCGSRefinementType on STGetKSP, with the BV constants: KS_BV_ORTHOG_REFINE_NEVER (PETSc's default for KSPGMRES: one pass of
    classical Gram-Schmidt, then the norm), _IFNEEDED (PETSc's test is the BV's, eta 0.7071) or _ALWAYS */
 int ks_st_set_gmres_cgs_refinement(ks_st st, int refine);
-/* PCSetType on KSPGetPC(STGetKSP): KS_PC_JACOBI (the default: PCJACOBI, what the shell matrix mode defaults to, stsles.c:51-53) or
+/* PCSetType on KSPGetPC(STGetKSP): KS_PC_NONE (no preconditioner), KS_PC_JACOBI (the default: PCJACOBI, what the shell matrix mode defaults to, stsles.c:51-53) or
    KS_PC_BJACOBI - PCBJACOBI (the reference's choice with a split preconditioner, stsles.c:46-48; -st_pc_type bjacobi in ex46.c:113,
    test34.c:113) with blocks of block_size consecutive local rows (-pc_bjacobi_local_blocks n_local/block_size) solved exactly
    (-sub_pc_type lu): the dense diagonal blocks of P = A - sigma B are inverted on the host at STSetUp and applied by one kernel.
@@ -536,6 +564,7 @@ int ks_st_set_gmres_cgs_refinement(ks_st st, int refine);
 #define KS_PC_JACOBI  0
 #define KS_PC_BJACOBI 1
 #define KS_PC_BJACOBI_ILU 2
+#define KS_PC_NONE 3         /* -st_pc_type none: M = I; takes block_size 0 (anything else is KS_ERR_SUP: there is no blocked form of it) */
 int ks_st_set_pc(ks_st st, int type, int block_size);
 int ks_st_set_ksp(ks_st st, double rtol, int max_it, int restart);        /* KSPSetTolerances / KSPGMRESSetRestart on STGetKSP; 0 keeps */
 int ks_st_setup(ks_st st);                                                /* STSetUp */
@@ -570,6 +599,20 @@ int ks_st_pc_apply_transpose(ks_st st, const double *x_dev, double *y_dev);
    preconditioner of the inner solves, whichever of the three types is set. Runs STSetUp if needed; x == y is KS_ERR_ARG_IDN; a transformation
    without a linear solve (STSHIFT with one matrix) has no preconditioner: KS_ERR_ORDER. Enqueued on the context's stream, no host wait. */
 int ks_st_pc_apply(ks_st st, const double *x_dev, double *y_dev);
+/* KS_ST_PRECOND (STPRECOND, src/sys/classes/st/impls/precond/precond.c): the ST of the preconditioned eigensolvers. ks_st_apply gives y = M^-1 x with the
+   preconditioner M built on K = A - sigma B, sigma the shift, or the EPS's target when none was set (precond.c:65); the KSP is preonly, nothing is
+   solved. Default PC: point Jacobi (what the shell matrix mode defaults to, precond.c:30); all four PC types work. ks_st_backtransform leaves values alone.
+   PCMatApply on KSPGetPC(STGetKSP): Y(:,j) = M^-1 X(:,j), j < ncols (X(:,j) at X_dev + j*ldx, Y(:,j) at Y_dev + j*ldy), every column bit for bit
+   ks_st_pc_apply of that column. Point Jacobi, PCNONE and the dense blocks run their single-vector kernels with the column on the grid; the ILU(0)
+   blocks of up to 512 rows keep eight right-hand sides of a block in LDS at once, read every factor entry once for all of them and pay one barrier
+   per level instead of one per level and column (more columns go in several passes); larger blocks go column by column through the single-vector
+   kernel, which measured no slower there (ks_pc.hip).
+   Arguments as ks_mat_mult_multi: ncols == 0 does nothing, ldx, ldy >= max(1, n_local) (KS_ERR_ARG_SIZ), X and Y must not overlap
+   (KS_ERR_ARG_WRONG). Enqueued, no host wait. */
+int ks_st_pc_apply_multi(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy);
+int ks_st_pc_multi_columns(ks_st st, int *columns);   /* instrumentation: columns of one pass of the above with the PC as set up (ILU blocks: 8 up to block size 512, 1 above; the other types: 65535, one launch) */
+/* STApplyMat stsolve.c:62: Y(:,j) = Op X(:,j). KS_ST_PRECOND: ks_st_pc_apply_multi; the other transformations: ks_st_apply column by column. Same arguments. */
+int ks_st_apply_mat(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy);
 int ks_st_backtransform(ks_st st, int n, double *eigr, double *eigi);     /* STBackTransform stsolve.c:563 */
 int ks_st_get_ksp_stats(ks_st st, long long *solves, long long *iterations, double *last_rnorm);
 

@@ -31,7 +31,9 @@ WHICH = {"largest_magnitude": 1, "smallest_magnitude": 2, "largest_real": 3, "sm
          "largest_imaginary": 5, "smallest_imaginary": 6, "target_magnitude": 7, "target_real": 8, "user": 11}
 BLOCK = {"gs": 0, "chol": 1, "tsqr": 2, "tsqrchol": 3, "svqb": 4}
 SHELL_MULT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
-ST_SHIFT, ST_SINVERT, ST_CAYLEY = 0, 1, 2
+ST_SHIFT, ST_SINVERT, ST_CAYLEY, ST_PRECOND = 0, 1, 2, 3
+EPS_KRYLOVSCHUR, EPS_LOBPCG = 0, 1
+PC_JACOBI, PC_BJACOBI, PC_BJACOBI_ILU, PC_NONE = 0, 1, 2, 3
 BV_MATMULT_VECS, BV_MATMULT_MAT, BV_MATMULT_MAT_SAVE = 0, 1, 2
 MATMULT = {"vecs": BV_MATMULT_VECS, "mat": BV_MATMULT_MAT, "mat_save": BV_MATMULT_MAT_SAVE}
 EIG_COMPARE_FN = C.CFUNCTYPE(C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int), C.c_void_p)
@@ -625,6 +627,12 @@ class BV:
     def MatMultColumn(self, A, j):
         _lib.check(self.ctx.L.ks_bv_matmultcolumn(self.h, A.h, j))
 
+    def BlockResidual(self, AX, BX, theta):
+        """R(:,j) = AX(:,j) - theta[j - l] BX(:,j) over this BV's active columns [l, k) (self is R); returns their 2-norms."""
+        th = _f64(theta); nrm = np.zeros(max(len(th), 1))
+        _lib.check(self.ctx.L.ks_bv_block_residual(self.h, AX.h, BX.h, _p(th), _p(nrm)))
+        return nrm[:len(th)]
+
     def SetMatMultMethod(self, method):
         """BVSetMatMultMethod: "vecs" / "mat" / "mat_save" (or the BV_MATMULT_* number)."""
         _lib.check(self.ctx.L.ks_bv_set_matmult_method(self.h, MATMULT.get(method, method)))
@@ -765,7 +773,7 @@ class ST:
             pass
 
     def SetType(self, t):
-        _lib.check(self.ctx.L.ks_st_set_type(self.h, {"shift": ST_SHIFT, "sinvert": ST_SINVERT, "cayley": ST_CAYLEY}.get(t, t)))
+        _lib.check(self.ctx.L.ks_st_set_type(self.h, {"shift": ST_SHIFT, "sinvert": ST_SINVERT, "cayley": ST_CAYLEY, "precond": ST_PRECOND}.get(t, t)))
 
     def SetShift(self, sigma):
         _lib.check(self.ctx.L.ks_st_set_shift(self.h, sigma))
@@ -792,8 +800,8 @@ class ST:
 
     def SetPC(self, t, block_size=0):
         """PCSetType on the ST's KSP: "jacobi" (default), "bjacobi" with blocks of block_size (2..32) consecutive local rows, solved exactly, or
-        "bjacobi-ilu" with blocks of block_size (64..8192) rows, each factored by ILU(0)."""
-        _lib.check(self.ctx.L.ks_st_set_pc(self.h, {"jacobi": 0, "bjacobi": 1, "bjacobi-ilu": 2}.get(t, t), block_size))
+        "bjacobi-ilu" with blocks of block_size (64..8192) rows, each factored by ILU(0), or "none"."""
+        _lib.check(self.ctx.L.ks_st_set_pc(self.h, {"jacobi": 0, "bjacobi": 1, "bjacobi-ilu": 2, "none": 3}.get(t, t), block_size))
 
     def SetMatMode(self, mode):
         """STSetMatMode: "shell" (default here) or "copy" (P = A - sigma B assembled; the matrices need keep_csr)."""
@@ -828,6 +836,33 @@ class ST:
         W.set_column(0, x)
         self.PCApplyDev(W.column_ptr(0), W.column_ptr(1))
         return W.column(1)
+
+    def PCApplyMultiDev(self, Xp, ldx, Yp, ldy, ncols):
+        """Y(:,j) = M^-1 X(:,j) for a block of ncols device vectors (PCMatApply); enqueued, no host wait."""
+        _lib.check(self.ctx.L.ks_st_pc_apply_multi(self.h, ncols, C.c_void_p(Xp), ldx, C.c_void_p(Yp), ldy))
+
+    def PCMultiColumns(self):
+        """Columns ks_st_pc_apply_multi handles per pass with the preconditioner as set up."""
+        v = C.c_int(); _lib.check(self.ctx.L.ks_st_pc_multi_columns(self.h, C.byref(v))); return v.value
+
+    def ApplyMatDev(self, Xp, ldx, Yp, ldy, ncols):
+        """STApplyMat on a block of ncols device vectors."""
+        _lib.check(self.ctx.L.ks_st_apply_mat(self.h, ncols, C.c_void_p(Xp), ldx, C.c_void_p(Yp), ldy))
+
+    def _block(self, X, call):
+        X = np.asarray(X, dtype=np.float64)
+        W = BV(self.ctx, X.shape[0], 2 * max(X.shape[1], 1))
+        W.set_dense(np.hstack([X, np.zeros_like(X)]) if X.shape[1] else np.zeros((X.shape[0], 2)))
+        call(W.column_ptr(0), W.ld, W.column_ptr(max(X.shape[1], 1)), W.ld, X.shape[1])
+        return W.dense()[:, max(X.shape[1], 1):max(X.shape[1], 1) + X.shape[1]]
+
+    def PCApplyMulti(self, X):
+        """Y = M^-1 X with the columns of a host matrix (this rank's rows)."""
+        return self._block(X, self.PCApplyMultiDev)
+
+    def ApplyMat(self, X):
+        """Y = Op X with the columns of a host matrix (STApplyMat; single rank)."""
+        return self._block(X, self.ApplyMatDev)
 
     def ApplyTranspose(self, x):
         """y = Op^T x with host vectors (STApplyHermitianTranspose, real scalars; test convenience, single rank)."""
@@ -924,6 +959,36 @@ class EPS:
 
     def SetProblemType(self, t):
         _lib.check(self.ctx.L.ks_eps_set_problem_type(self.h, t))
+
+    def SetType(self, t):
+        """EPSSetType: "krylovschur" (default) or "lobpcg"."""
+        _lib.check(self.ctx.L.ks_eps_set_type(self.h, {"krylovschur": EPS_KRYLOVSCHUR, "lobpcg": EPS_LOBPCG}.get(t, t)))
+
+    def GetType(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_get_type(self.h, C.byref(v))); return {0: "krylovschur", 1: "lobpcg"}[v.value]
+
+    def LOBPCGSetBlockSize(self, bs):
+        _lib.check(self.ctx.L.ks_eps_lobpcg_set_blocksize(self.h, bs))
+
+    def LOBPCGGetBlockSize(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_lobpcg_get_blocksize(self.h, C.byref(v))); return v.value
+
+    def LOBPCGSetRestart(self, restart):
+        _lib.check(self.ctx.L.ks_eps_lobpcg_set_restart(self.h, restart))
+
+    def LOBPCGGetRestart(self):
+        v = C.c_double(); _lib.check(self.ctx.L.ks_eps_lobpcg_get_restart(self.h, C.byref(v))); return v.value
+
+    def LOBPCGSetLocking(self, lock):
+        _lib.check(self.ctx.L.ks_eps_lobpcg_set_locking(self.h, int(bool(lock))))
+
+    def LOBPCGGetLocking(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_lobpcg_get_locking(self.h, C.byref(v))); return bool(v.value)
+
+    def LOBPCGGetStats(self):
+        v = [C.c_longlong() for _ in range(4)]
+        _lib.check(self.ctx.L.ks_eps_lobpcg_get_stats(self.h, *[C.byref(x) for x in v]))
+        return {"iterations": v[0].value, "hard_locks": v[1].value, "mat_columns": v[2].value, "pc_columns": v[3].value}
 
     def SetDimensions(self, nev, ncv=0, mpd=0):
         _lib.check(self.ctx.L.ks_eps_set_dimensions(self.h, nev, ncv or 0, mpd or 0))

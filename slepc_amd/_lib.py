@@ -121,6 +121,7 @@ _SIG = {
     "ks_bv_matmultcolumn": [vp, vp, C.c_int],
     "ks_bv_set_matmult_method": [vp, C.c_int],
     "ks_bv_get_matmult_method": [vp, ip],
+    "ks_bv_block_residual": [vp, vp, vp, dp, dp],
     "ks_bv_gramschmidt_pass": [vp, C.c_int, vp, ip, dp, dp, dp, dp],
     "ks_bv_orthogonalizecolumn": [vp, C.c_int, dp, dp, ip],
     "ks_bv_orthonormalizecolumn": [vp, C.c_int, C.c_int, dp, ip],
@@ -206,6 +207,11 @@ _SIG = {
     "ks_eps_set_left_initial_space": [vp, C.c_int, C.POINTER(C.c_void_p)],
     "ks_eps_get_left_eigenvector": [vp, C.c_int, vp, vp],
     "ks_eps_get_left_eigenvector_host": [vp, C.c_int, dp, dp],
+    "ks_eps_set_type": [vp, C.c_int], "ks_eps_get_type": [vp, ip],
+    "ks_eps_lobpcg_set_blocksize": [vp, C.c_int], "ks_eps_lobpcg_get_blocksize": [vp, ip],
+    "ks_eps_lobpcg_set_restart": [vp, C.c_double], "ks_eps_lobpcg_get_restart": [vp, dp],
+    "ks_eps_lobpcg_set_locking": [vp, C.c_int], "ks_eps_lobpcg_get_locking": [vp, ip],
+    "ks_eps_lobpcg_get_stats": [vp, llp, llp, llp, llp],
     "ks_st_create": [vp, C.POINTER(vp)],
     "ks_st_destroy": [vp],
     "ks_st_set_type": [vp, C.c_int],
@@ -223,6 +229,9 @@ _SIG = {
     "ks_st_setup": [vp],
     "ks_st_apply": [vp, vp, vp],
     "ks_st_pc_apply": [vp, vp, vp],
+    "ks_st_pc_apply_multi": [vp, C.c_int, vp, C.c_int, vp, C.c_int],
+    "ks_st_pc_multi_columns": [vp, ip],
+    "ks_st_apply_mat": [vp, C.c_int, vp, C.c_int, vp, C.c_int],
     "ks_st_set_transpose_solves": [vp, C.c_int],
     "ks_st_get_transpose_solves": [vp, ip],
     "ks_st_matsolve_transpose": [vp, vp, vp],

@@ -354,6 +354,68 @@ int DsNhepTs::sort(double *wr, double *wi, const double *, const double *)
   return sort_with_permutation(p.data());
 }
 
+// ---- DS GHEP ---------------------------------------------------------------------------------------
+int DsGhep::solve(double *w)
+{
+  if (n <= 0) return 0;
+  std::vector<double> U((size_t)n * n), C((size_t)n * n);
+  for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) { U[(size_t)i + (size_t)j * n] = i <= j ? b(i, j) : 0.0; C[(size_t)i + (size_t)j * n] = a(i, j); }
+  const int info = potrf_upper(n, U.data(), n);
+  if (info) return info;
+  auto u = [&](int i, int j) -> double { return U[(size_t)i + (size_t)j * n]; };
+  // C <- U^-T C: forward substitution down every column; then C <- C U^-1: the same down every row (sygs2, itype 1, upper)
+  for (int j = 0; j < n; j++) { double *c = C.data() + (size_t)j * n; for (int i = 0; i < n; i++) { double t = c[i]; for (int p = 0; p < i; p++) t -= u(p, i) * c[p]; c[i] = t / u(i, i); } }
+  for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) { double t = C[(size_t)i + (size_t)j * n]; for (int p = 0; p < j; p++) t -= C[(size_t)i + (size_t)p * n] * u(p, j); C[(size_t)i + (size_t)j * n] = t / u(j, j); }
+  for (int j = 0; j < n; j++) for (int i = j + 1; i < n; i++) { const double t = 0.5 * (C[(size_t)i + (size_t)j * n] + C[(size_t)j + (size_t)i * n]); C[(size_t)i + (size_t)j * n] = C[(size_t)j + (size_t)i * n] = t; }
+  std::vector<double> C0(C);
+  if (sym_eig(n, C.data(), n, w)) return -1;
+  // One step of symmetric re-orthogonalisation, Z <- Z (I - (Z^T Z - I) / 2), in extended precision: the rotations leave Z^T Z - I at a few n eps,
+  // the step squares that, so the B-orthonormality of Q = U^-1 Z is limited by the back substitution alone
+  {
+    std::vector<long double> E((size_t)n * n), Zn((size_t)n * n);
+    for (int j = 0; j < n; j++) for (int i = 0; i <= j; i++) {
+      long double t = 0.0L; for (int q = 0; q < n; q++) t += (long double)C[(size_t)q + (size_t)i * n] * C[(size_t)q + (size_t)j * n];
+      if (i == j) t -= 1.0L;
+      E[(size_t)i + (size_t)j * n] = E[(size_t)j + (size_t)i * n] = 0.5L * t;
+    }
+    for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) {
+      long double t = C[(size_t)i + (size_t)j * n]; for (int q = 0; q < n; q++) t -= (long double)C[(size_t)i + (size_t)q * n] * E[(size_t)q + (size_t)j * n];
+      Zn[(size_t)i + (size_t)j * n] = t;
+    }
+    for (size_t i = 0; i < Zn.size(); i++) C[i] = (double)Zn[i];
+  }
+  // Rayleigh quotients of the computed vectors, accumulated in extended precision: an eigenvector good to O(n eps) gives its eigenvalue to
+  // O((n eps)^2) ||C||, so what is left is the rounding of this sum - the Jacobi sweeps alone leave a few ulps of ||C||
+  for (int j = 0; j < n; j++) {
+    const double *z = C.data() + (size_t)j * n;
+    long double num = 0.0L, den = 0.0L;
+    for (int q = 0; q < n; q++) { long double t = 0.0L; for (int i = 0; i < n; i++) t += (long double)C0[(size_t)i + (size_t)q * n] * z[i]; num += t * z[q]; den += (long double)z[q] * z[q]; }
+    if (den > 0.0L) w[j] = (double)(num / den);
+  }
+  // Q = U^-1 Z: back substitution up every column
+  for (int j = 0; j < n; j++) {
+    double *z = C.data() + (size_t)j * n;
+    for (int i = n - 1; i >= 0; i--) { double t = z[i]; for (int p = i + 1; p < n; p++) t -= u(i, p) * z[p]; z[i] = t / u(i, i); }
+    for (int i = 0; i < n; i++) Q[(size_t)i + (size_t)j * ld] = z[i];
+  }
+  return 0;
+}
+
+void DsGhep::sort(double *w)
+{
+  // insertion sort, as DSSortEigenvalues_Private does it (dsutil.c): stable, so the ascending order of the solve survives among equals
+  std::vector<int> perm(n);
+  for (int i = 0; i < n; i++) perm[i] = i;
+  for (int i = 1; i < n; i++) {
+    const int pi = perm[i]; int j = i - 1;
+    while (j >= 0 && compare_eig(which, w[perm[j]], 0.0, w[pi], 0.0) > 0) { perm[j + 1] = perm[j]; j--; }
+    perm[j + 1] = pi;
+  }
+  std::vector<double> w2(w, w + n), Q2((size_t)n * n);
+  for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) Q2[(size_t)i + (size_t)j * n] = Q[(size_t)i + (size_t)perm[j] * ld];
+  for (int j = 0; j < n; j++) { w[j] = w2[perm[j]]; for (int i = 0; i < n; i++) Q[(size_t)i + (size_t)j * ld] = Q2[(size_t)i + (size_t)j * n]; }
+}
+
 } // namespace ksd
 
 #ifdef KSD_TEST_HOOKS
@@ -419,6 +481,16 @@ int ksd_nhepts(int op, int ld, int *dims, double *A, double *Q, double *X, doubl
   ksd_store(ds, dims, A, Q); std::copy(ds.X.begin(), ds.X.end(), X);
   std::copy(ds.hb.A.begin(), ds.hb.A.end(), B); std::copy(ds.hb.Q.begin(), ds.hb.Q.end(), Z); std::copy(ds.hb.X.begin(), ds.hb.X.end(), Y);
   std::copy(ds.wr2.begin(), ds.wr2.end(), wr2); std::copy(ds.wi2.begin(), ds.wi2.end(), wi2);
+  return rc;
+}
+// DS GHEP on caller-owned ld x ld arrays (tests/test_ds_ghep_host.py): solve and sort with `which`; returns what DsGhep::solve returns
+int ksd_ghep(int n, int ld, const double *A, const double *B, double *Q, double *w, int which)
+{
+  ksd::DsGhep ds; ds.allocate(ld); ds.n = n; ds.which.which = which;
+  std::copy(A, A + ds.A.size(), ds.A.begin()); std::copy(B, B + ds.B.size(), ds.B.begin());
+  const int rc = ds.solve(w);
+  if (!rc) ds.sort(w);
+  std::copy(ds.Q.begin(), ds.Q.end(), Q);
   return rc;
 }
 void ksd_backtransform(int st_type, double sigma, double nu, int n, double *eigr, double *eigi) { ksd::StMap{st_type, sigma, nu}.backtransform(n, eigr, eigi); }

@@ -129,4 +129,20 @@ struct DsNhepTs : DsNhep {
   int vectors_side(int kk, bool left, bool back, double *rnorm) { if (!left) return vectors(kk, back, rnorm); dims_to_b(); return hb.vectors(kk, back, rnorm); }
 };
 
+// DS type GHEP (src/sys/classes/ds/impls/ghep/dsghep.c): A q = theta B q for symmetric A and symmetric positive definite B of order n <= ld, the
+// projected problem of LOBPCG (lobpcg.c:145-158, 350-365). The reference calls LAPACK sygvd (dsghep.c:115-170); here B = U^T U (potrf_upper), the
+// reduction C = U^-T A U^-1 by triangular substitution (what sygst does), sym_eig of C and Q = U^-1 Z, so Q^T B Q = I. Not part of the Ds
+// hierarchy above: no extra row, no truncation, nothing a restart loop would ask of it.
+struct DsGhep {
+  int ld = 0, n = 0; KsCompare which;
+  std::vector<double> A, B, Q;        // DS_MAT_A, DS_MAT_B (full symmetric matrices; the upper triangle of B and the lower one of the reduced A are read), DS_MAT_Q = DS_MAT_X
+  void allocate(int ld_) { ld = ld_; A.assign((size_t)ld * ld, 0.0); B.assign((size_t)ld * ld, 0.0); Q.assign((size_t)ld * ld, 0.0); }
+  double &a(int i, int j) { return A[(size_t)i + (size_t)j * ld]; }
+  double &b(int i, int j) { return B[(size_t)i + (size_t)j * ld]; }
+  // DSSolve_GHEP: w ascending, Q B-orthonormal; A and B are left as they came. Returns 0, k > 0 when the leading minor of order k of B is not
+  // positive definite (potrf's info: the caller's breakdown), -1 when the Jacobi iteration of the reduced problem failed
+  int solve(double *w);
+  void sort(double *w);               // DSSort_GHEP dsghep.c:172-195: eigenvalues and the columns of Q in the order of `which`
+};
+
 } // namespace ksd

@@ -13,58 +13,13 @@
 //   EPSSolve_KrylovSchur_TwoSided   krylovschur/ks-twosided.c:27-241 (with EPSGetLeftStartVector epssolve.c:879-900 and the left
 //                                   branches of EPSKrylovConvergence, EPSComputeVectors_Schur, EPSGetLeftEigenvector, EPSComputeError)
 #include "ksgpu_internal.h"
-#include "ks_ds.h"
+#include "ks_eps_impl.h"
 #include "ks_dense.h"
 #include <algorithm>
 #include <limits>
 
-using ksd::KsCompare;
 
 
-struct ks_eps_s {
-  ks_ctx ctx = nullptr;
-  ks_mat A = nullptr, B = nullptr;
-  ks_mat op = nullptr;                 // operator of the expansion: A itself, or the ST's shell matrix
-  // EPSSetBalance (non-symmetric problems): D from EPSBuildBalance_Krylov, the expansion then runs on D Op D^-1 (STApply with st->D, stsolve.c:252-256)
-  int balance = KS_EPS_BALANCE_NONE, balance_its = 5; double balance_cutoff = 1e-8;
-  double *D = nullptr, *wb = nullptr; int D_n = 0; ks_mat op_inner = nullptr, bal_op = nullptr; bool balanced = false;
-  ks_st st = nullptr;                  // owned (EPSGetST)
-  ks_bv V = nullptr, W = nullptr;      // basis (ncv+1 columns), work vectors (3 columns)
-  int problem_type = 0;               // not set: EPSSetUp picks NHEP (one matrix) or GNHEP (two), epssetup.c:318-322
-  int nev = 1, ncv = 0, mpd = 0, ncv_user = 0, mpd_user = 0;
-  double tol = 1e-8; int max_it = 0, max_it_user = 0;
-  KsCompare which;                     // user settings; cmp_ds / cmp_final are what a solve uses
-  KsCompare cmp_ds, cmp_final;
-  double keep = 0.5; bool lock = true;   // EPSKrylovSchurSetRestart / SetLocking
-  uint64_t seed = 0x12345678ULL;
-  std::vector<double> v0; bool have_v0 = false;
-  ks_bv defl = nullptr; int nds = 0;       // deflation space handed over by EPSSetDeflationSpace, consumed by the next solve
-  long long max_steps = 0;
-  int ds_parallel = KS_DS_PARALLEL_SYNCHRONIZED;   // DSSetParallel: broadcast rank 0's projected solve after every restart (krylovschur.c:281)
-  // results
-  std::vector<double> eigr, eigi, errest; std::vector<int> perm;
-  int nconv = 0, its = 0, reason = 0;
-  long long steps = 0, passes = 0; int restarts = 0;
-  bool solved = false, ghep = false;
-  ks_eps_converged_fn conv_fn = nullptr; void *conv_ctx = nullptr;     // EPSSetConvergenceTestFunction (conv = KS_EPS_CONV_USER)
-  ks_eps_stopping_fn stop_fn = nullptr; void *stop_ctx = nullptr;      // EPSSetStoppingTestFunction; NULL = EPSStoppingBasic
-  ks_eps_monitor_fn mon_fn = nullptr; void *mon_ctx = nullptr;         // EPSMonitorSet (one monitor)
-  ks_eps_arbitrary_fn arb_fn = nullptr; void *arb_ctx = nullptr;       // EPSSetArbitrarySelection
-  bool problem_type_resolved_hermitian = false;                        // the last solve ran the symmetric (Lanczos) variant
-  bool vectors_done = true;                                            // non-symmetric variant: V holds Schur vectors until the eigenvectors are first asked for (EPS_STATE_EIGENVECTORS)
-  int cb_err = 0;                                                      // first non-zero return of a user callback
-  bool purify = true, trackall = false;                               // EPSSetPurify, EPSSetTrackAll
-  bool trueres = false;                                          // EPSSetTrueResidual
-  int extraction = KS_EPS_RITZ;                                  // EPSSetExtraction: Ritz or harmonic (krylovschur.c:120)
-  int conv = KS_EPS_CONV_REL; double nrma = 0.0, nrmb = 0.0;   // EPSSetConvergenceTest; ||A||_inf, ||B||_inf for CONV_NORM / ERROR_BACKWARD
-  ksd::DsHep dsh; ksd::DsNhep dsn;                                     // the projected problem of the last solve: the symmetric or the general variant
-  // EPSSetTwoSided: the left basis (a duplicate of V), Op^T as a matrix (a view: ks_mat_create_transpose), the left start vector, DS NHEPTS
-  bool twosided = false, twosided_solved = false;                      // the flag; the last solve ran the two-sided variant
-  ks_bv VL = nullptr; ks_mat opT = nullptr; bool opT_owned = false;   // a shell view is this solver's to destroy; the view of an assembled matrix belongs to that matrix
-  bool left_trivial = false;                                           // symmetric problem type: the left eigenvectors are the right ones (epssolve.c:585)
-  std::vector<double> w0; bool have_w0 = false;
-  ksd::DsNhepTs dst;
-};
 
 extern "C" int ks_eps_create(ks_ctx ctx, ks_eps *out)
 {
@@ -76,7 +31,7 @@ extern "C" int ks_eps_create(ks_ctx ctx, ks_eps *out)
 extern "C" int ks_eps_destroy(ks_eps eps)
 {
   if (!eps) return KS_SUCCESS;
-  ks_bv_destroy(eps->V); ks_bv_destroy(eps->W); ks_bv_destroy(eps->defl); ks_bv_destroy(eps->VL);
+  ks_bv_destroy(eps->V); ks_bv_destroy(eps->W); ks_bv_destroy(eps->defl); ks_bv_destroy(eps->VL); ks_bv_destroy(eps->ini);
   if (eps->opT_owned) ks_mat_destroy(eps->opT);
   ks_st_destroy(eps->st);
   if (eps->D) hipFree(eps->D); if (eps->wb) hipFree(eps->wb); if (eps->bal_op) ks_mat_destroy(eps->bal_op);
@@ -92,7 +47,7 @@ extern "C" int ks_eps_set_operators(ks_eps eps, ks_mat A, ks_mat B)   // epssetu
     ks_bv_destroy(eps->V); ks_bv_destroy(eps->W); ks_bv_destroy(eps->VL); eps->V = eps->W = eps->VL = nullptr;
     eps->have_w0 = false; eps->w0.clear();
     ks_bv_destroy(eps->defl); eps->defl = nullptr; eps->nds = 0;
-    eps->have_v0 = false; eps->v0.clear();
+    eps->have_v0 = false; eps->v0.clear(); ks_bv_destroy(eps->ini); eps->ini = nullptr; eps->nini = 0;
     if (eps->D) { hipFree(eps->D); eps->D = nullptr; } if (eps->wb) { hipFree(eps->wb); eps->wb = nullptr; } eps->D_n = 0;
     if (eps->balance == KS_EPS_BALANCE_USER) eps->balance = KS_EPS_BALANCE_NONE;
   }
@@ -265,10 +220,16 @@ extern "C" int ks_eps_set_initial_space(ks_eps eps, int n, const double *const *
 {
   KS_CHECK(eps && eps->A, KS_ERR_ORDER, "set the operators first");
   KS_CHECK(n >= 0, KS_ERR_ARG_OUTOFRANGE, "Argument n cannot be negative");
+  ks_bv_destroy(eps->ini); eps->ini = nullptr; eps->nini = 0;
   if (!n) { eps->have_v0 = false; return KS_SUCCESS; }
   KS_CHECK(v_dev && v_dev[0], KS_ERR_ARG_NULL, "NULL argument");
   eps->v0.resize(std::max(eps->A->n, 1));
   KS_HIP(hipSetDevice(eps->ctx->device));
+  if (eps->type == KS_EPS_LOBPCG) {                    // a block solver uses all of them (lobpcg.c:133): device copies, made only for that solver type
+    KS_CALL(ks_bv_create(eps->ctx, eps->A->n, eps->A->n_global, n, 0, &eps->ini));
+    for (int i = 0; i < n; i++) { KS_CHECK(v_dev[i], KS_ERR_ARG_NULL, "vector %d is NULL", i); KS_CALL(ks_bv_insert_vec(eps->ini, i, v_dev[i])); }
+    eps->nini = n;
+  }
   KS_HIP(hipMemcpyAsync(eps->v0.data(), v_dev[0], sizeof(double) * eps->A->n, hipMemcpyDeviceToHost, eps->ctx->stream));
   KS_HIP(ks_sync(eps->ctx));
   eps->have_v0 = true; eps->solved = false;
@@ -658,6 +619,7 @@ static int set_up(ks_eps eps, long long *passes0)
   }
   if (eps->conv == KS_EPS_CONV_NORM) KS_CALL(matrix_norms(eps));
   ks_st st = eps->st;
+  KS_CHECK(!st || st->type != KS_ST_PRECOND, KS_ERR_SUP, "STPRECOND only preconditions: a Krylov solver needs a transformation that can be applied (EPSCheckSinvertCayley and friends)");
   const bool cayley = st && st->type == KS_ST_CAYLEY;
   const bool sinvert = (st && st->type == KS_ST_SINVERT) || cayley;   // the set-up rules below are those of EPSCheckSinvertCayley
   if (sinvert && !st->sigma_set) { if (st->sigma != eps->which.target) st->ready = false; st->sigma = eps->which.target; }   // the shift of sinvert defaults to the target (STSetDefaultShift epsbasic.c:386, sinvert.c:64); STSHIFT keeps 0
@@ -1082,6 +1044,15 @@ static void sort_eigenvalues(ks_eps eps)
 extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119 -> EPSSolve_KrylovSchur_Default krylovschur.c:227
 {
   long long passes0 = 0;
+  KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
+  if (eps->type == KS_EPS_LOBPCG) {                                    // EPSSolve_LOBPCG; V(:,0:nconv) holds the eigenvectors, nothing to map back or purify
+    KS_CALL(ks_lobpcg_solve(eps));
+    KS_CALL(ks_bv_set_active_columns(eps->V, 0, eps->nconv));
+    sort_eigenvalues(eps);
+    KS_CALL(ks_bv_set_num_constraints(eps->V, 0));
+    eps->solved = true;
+    return KS_SUCCESS;
+  }
   KS_CALL(set_up(eps, &passes0));
   const bool hermitian = eps->problem_type_resolved_hermitian;
   ksd::Ds &ds = hermitian ? static_cast<ksd::Ds &>(eps->dsh) : eps->twosided ? static_cast<ksd::Ds &>(eps->dst) : eps->dsn;
@@ -1309,5 +1280,66 @@ extern "C" int ks_eps_get_stats(ks_eps eps, long long *steps, long long *passes,
 {
   KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
   if (steps) *steps = eps->steps; if (passes) *passes = eps->passes; if (restarts) *restarts = eps->restarts;
+  return KS_SUCCESS;
+}
+
+// ---- what the solvers share (ks_eps_impl.h) ----
+double ks_eps_converged_estimate(ks_eps eps, double re, double im, double res) { return converged_estimate(eps, re, im, res); }
+int ks_eps_synchronize_values(ks_eps eps, double *v, size_t count) { return ds_synchronize_values(eps, v, count); }
+int ks_eps_stopping_call(ks_eps eps, int its, int nconv)
+{
+  int reason = KS_EPS_CONVERGED_ITERATING;
+  if (eps->stop_fn) { const int rc = eps->stop_fn(eps, its, eps->max_it, nconv, eps->nev, &reason, eps->stop_ctx); KS_CHECK(!rc, rc, "the user's stopping test returned %d", rc); }
+  else ks_eps_stopping_basic(eps, its, eps->max_it, nconv, eps->nev, &reason, nullptr);
+  eps->reason = reason;
+  return KS_SUCCESS;
+}
+int ks_eps_monitor_call(ks_eps eps, int its, int nconv, int nest)
+{
+  if (!eps->mon_fn) return KS_SUCCESS;
+  const int rc = eps->mon_fn(eps, its, nconv, eps->eigr.data(), eps->eigi.data(), eps->errest.data(), nest, eps->mon_ctx);
+  KS_CHECK(!rc, rc, "the user's monitor returned %d", rc);
+  return KS_SUCCESS;
+}
+int ks_eps_matrix_norms(ks_eps eps) { return matrix_norms(eps); }
+
+// EPSSetType epsbasic.c: Krylov-Schur (the default) or LOBPCG. LOBPCG makes STPRECOND the default of the solver's ST (EPSSetDefaultST_Precond
+// epsdefault.c) unless the caller chose a type; going back to Krylov-Schur undoes that default
+extern "C" int ks_eps_set_type(ks_eps eps, int type)
+{
+  KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
+  KS_CHECK(type == KS_EPS_KRYLOVSCHUR || type == KS_EPS_LOBPCG, KS_ERR_SUP, "only EPSKRYLOVSCHUR and EPSLOBPCG are built");
+  if (type == eps->type) return KS_SUCCESS;
+  eps->type = type; eps->solved = false;
+  if (type == KS_EPS_LOBPCG) {
+    ks_st st = nullptr;
+    KS_CALL(ks_eps_get_st(eps, &st));
+    if (!st->type_set) { st->type = KS_ST_PRECOND; st->ready = false; }
+  } else if (eps->st && !eps->st->type_set && eps->st->type == KS_ST_PRECOND) { eps->st->type = KS_ST_SHIFT; eps->st->ready = false; }
+  return KS_SUCCESS;
+}
+extern "C" int ks_eps_get_type(ks_eps eps, int *type) { KS_CHECK(eps && type, KS_ERR_ARG_NULL, "NULL argument"); *type = eps->type; return KS_SUCCESS; }
+extern "C" int ks_eps_lobpcg_set_blocksize(ks_eps eps, int bs)         // EPSLOBPCGSetBlockSize lobpcg.c:398-420
+{
+  KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
+  KS_CHECK(bs >= 0, KS_ERR_ARG_OUTOFRANGE, "Invalid block size %d", bs);
+  KS_CHECK(bs <= 16, KS_ERR_ARG_OUTOFRANGE, "block size %d: this build keeps the blocks of LOBPCG to 16 columns (48 in the projected problem)", bs);
+  eps->lob.bs = bs; eps->solved = false; return KS_SUCCESS;
+}
+extern "C" int ks_eps_lobpcg_get_blocksize(ks_eps eps, int *bs) { KS_CHECK(eps && bs, KS_ERR_ARG_NULL, "NULL argument"); *bs = eps->lob.bs; return KS_SUCCESS; }
+extern "C" int ks_eps_lobpcg_set_restart(ks_eps eps, double r)          // EPSLOBPCGSetRestart lobpcg.c:472-500
+{
+  KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
+  KS_CHECK(r >= 0.1 && r <= 1.0, KS_ERR_ARG_OUTOFRANGE, "The restart argument %g must be in the range [0.1,1.0]", r);
+  eps->lob.restart = r; eps->solved = false; return KS_SUCCESS;
+}
+extern "C" int ks_eps_lobpcg_get_restart(ks_eps eps, double *r) { KS_CHECK(eps && r, KS_ERR_ARG_NULL, "NULL argument"); *r = eps->lob.restart ? eps->lob.restart : 0.9; return KS_SUCCESS; }
+extern "C" int ks_eps_lobpcg_set_locking(ks_eps eps, int lock) { KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL"); eps->lob.lock = lock != 0; eps->solved = false; return KS_SUCCESS; }   // EPSLOBPCGSetLocking
+extern "C" int ks_eps_lobpcg_get_locking(ks_eps eps, int *lock) { KS_CHECK(eps && lock, KS_ERR_ARG_NULL, "NULL argument"); *lock = eps->lob.lock ? 1 : 0; return KS_SUCCESS; }
+extern "C" int ks_eps_lobpcg_get_stats(ks_eps eps, long long *iterations, long long *hard_locks, long long *mat_columns, long long *pc_columns)
+{
+  KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
+  if (iterations) *iterations = eps->lob.iterations; if (hard_locks) *hard_locks = eps->lob.hard_locks;
+  if (mat_columns) *mat_columns = eps->lob.mat_columns; if (pc_columns) *pc_columns = eps->lob.pc_columns;
   return KS_SUCCESS;
 }

@@ -84,6 +84,59 @@ __global__ void __launch_bounds__(ILU_THREADS) k_bjacobi_ilu_apply_t(int n, int 
   ilu_level_walk<true>(n, bs, blk, lev, val, code, rows, dinv, in, out);
 }
 
+// NC right-hand sides of a block at once (ks_st_pc_apply_multi: the preconditioned residuals of a block eigensolver). The walk is ilu_level_walk<false>:
+// a lane still owns a row of the level, now with NC accumulators; every factor value and 16-bit code is read ONCE for all columns, each column runs
+// the same fma chain in the same slot order - the bits of k_bjacobi_ilu_apply column by column - and a level costs one barrier instead of NC.
+// LDS layout: column-major, column j of the block at xs + j * bs. The gather xs[j * bs + c] of one column is then the single-vector kernel's gather
+// shifted by a constant, so the bank-conflict argument above holds per instruction unchanged (lanes p, p + 1 a constant stride apart: conflict-free
+// for odd strides, two-way for 2 mod 4). Interleaving the columns (xs[c * NC + j]) would multiply every lane stride by NC: with NC = 8 all 8-byte
+// words of a column fall on 4 of the 32 bank pairs, an eight-way conflict on every gather; the one thing it would buy, two columns per
+// ds_read_b128, costs four LDS cycles where two ds_read_b64 cost the same four.
+template <int NC>
+__global__ void __launch_bounds__(ILU_THREADS) k_bjacobi_ilu_apply_multi(int n, int bs, const ksc::IluBlock *__restrict__ blk, const int2 *__restrict__ lev,
+                                                                         const double *__restrict__ val, const unsigned short *__restrict__ code,
+                                                                         const unsigned short *__restrict__ rows, const double *__restrict__ dinv,
+                                                                         const double *__restrict__ in, long long ldin, double *__restrict__ out, long long ldout)
+{
+  extern __shared__ double xs[];
+  const int tid = threadIdx.x;
+  const long long b0 = (long long)blockIdx.x * bs;
+  const int bl = (int)std::min<long long>(bs, n - b0);
+#pragma unroll
+  for (int j = 0; j < NC; j++) for (int i = tid; i < bl; i += ILU_THREADS) xs[j * bs + i] = in[j * ldin + b0 + i];
+  const ksc::IluBlock B = blk[blockIdx.x];
+  const double *v = val + B.ell; const unsigned short *c = code + B.ell;
+  const unsigned short *rw = rows + 2 * b0; const double *dv = dinv + b0;
+  const int2 *lv = lev + B.lev;
+  const int nlev = B.nL + B.nU;
+  int2 d = lv[0];
+  __syncthreads();
+  for (int l = 0; l < nlev; l++) {
+    const int2 next = (l + 1 < nlev) ? lv[l + 1] : make_int2(0, 0);
+    const int nl = d.x, w = d.y;
+    const bool upper = l >= B.nL;
+    for (int i = tid; i < nl; i += ILU_THREADS) {
+      const int r = rw[i];
+      double acc[NC];
+#pragma unroll
+      for (int j = 0; j < NC; j++) acc[j] = 0.0;
+      for (int s = 0; s < w; s++) {
+        const double vv = v[(size_t)s * nl + i]; const int cc = c[(size_t)s * nl + i];
+#pragma unroll
+        for (int j = 0; j < NC; j++) acc[j] = fma(vv, xs[j * bs + cc], acc[j]);
+      }
+      const double dd = upper ? dv[i] : 1.0;
+#pragma unroll
+      for (int j = 0; j < NC; j++) { const double t = xs[j * bs + r] - acc[j]; xs[j * bs + r] = upper ? t * dd : t; }
+    }
+    v += (size_t)nl * w; c += (size_t)nl * w; rw += nl; if (upper) dv += nl;
+    d = next;
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < NC; j++) for (int i = tid; i < bl; i += ILU_THREADS) out[j * ldout + b0 + i] = xs[j * bs + i];
+}
+
 template <class T> int upload(ks_ctx ctx, T **dst, const void *src, size_t count)
 {
   KS_HIP(hipMalloc((void **)dst, sizeof(T) * std::max<size_t>(count, 1)));
@@ -155,5 +208,37 @@ int ks_pc_ilu_apply_transpose(ks_ctx ctx, const KsIlu *p, const double *in, doub
   hipLaunchKernelGGL(k_bjacobi_ilu_apply_t, dim3((unsigned)t->nblk), dim3(ILU_THREADS), sizeof(double) * (size_t)t->bs, ctx->stream,
                      t->n, t->bs, t->blk, t->lev, t->val, t->code, t->rows, t->dinv, in, out);
   KS_HIP(hipGetLastError());
+  return KS_SUCCESS;
+}
+
+// Columns of a pass of the block apply, 0 = one at a time through the single-vector kernel. Measured on the MI355X (profiles/r11_lobpcg_probe.txt: 7-point
+// Laplacian, 4.1e6 rows, factors past the Infinity Cache, 20 applies per timed window): at block size 512 the multi-column kernel takes 1.45 / 1.60 / 3.26 /
+// 6.51 ms for 2 / 4 / 8 / 16 columns where the column loop takes 2.61 / 5.18 / 10.28 / 20.61 ms (1.8 to 3.2 times faster); at 2048 it is level at 2 columns and
+// 3 to 14 % slower from 4 on, at 8192 (two columns per pass, 128 KB of LDS, one workgroup per CU) 6 % slower throughout. So: blocks of up to 512 rows, eight
+// columns per pass (32 KB of LDS at most); larger blocks - 2048 and 8192 measured, those between not - stay on the loop, which is what the kernel would replace.
+constexpr int ILU_MULTI_BS_MAX = 512;
+int ks_pc_ilu_multi_columns(ks_ctx, const KsIlu *p) { return p->bs <= ILU_MULTI_BS_MAX ? 8 : 0; }
+
+// Y(:,j) = U^-1 L^-1 X(:,j), j < ncols: passes of up to ks_pc_ilu_multi_columns columns through k_bjacobi_ilu_apply_multi, a last single column
+// through the single-vector kernel (the same bits either way). Enqueued; X and Y do not overlap.
+int ks_pc_ilu_apply_multi(ks_ctx ctx, const KsIlu *p, int ncols, const double *X, long long ldx, double *Y, long long ldy)
+{
+  if (p->nblk == 0) return KS_SUCCESS;
+  const int cpp = ks_pc_ilu_multi_columns(ctx, p);
+  for (int c0 = 0; c0 < ncols;) {
+    const int nc = cpp ? std::min(cpp, ncols - c0) : 1;
+    const double *in = X + (size_t)c0 * ldx; double *out = Y + (size_t)c0 * ldy;
+    if (nc == 1) KS_CALL(ks_pc_ilu_apply(ctx, p, in, out));
+    else {
+      const size_t lds = sizeof(double) * (size_t)nc * p->bs;
+#define KS_ILU_MULTI(NC) case NC: {                                                                                                                     \
+        hipLaunchKernelGGL((k_bjacobi_ilu_apply_multi<NC>), dim3((unsigned)p->nblk), dim3(ILU_THREADS), lds, ctx->stream,                                \
+                           p->n, p->bs, p->blk, p->lev, p->val, p->code, p->rows, p->dinv, in, ldx, out, ldy); } break;
+      switch (nc) { KS_ILU_MULTI(2) KS_ILU_MULTI(3) KS_ILU_MULTI(4) KS_ILU_MULTI(5) KS_ILU_MULTI(6) KS_ILU_MULTI(7) KS_ILU_MULTI(8) }
+#undef KS_ILU_MULTI
+      KS_HIP(hipGetLastError());
+    }
+    c0 += nc;
+  }
   return KS_SUCCESS;
 }

@@ -43,8 +43,10 @@ __global__ void k_jacobi_setup(long long n, double a, const double *__restrict__
 }
 
 // out = M^-1 in for the block-Jacobi M: row i of out is row i of its block's inverse times the block's piece of in (binv: n x bs, row-major)
-__global__ void k_bjacobi_apply(long long n, int bs, const double *__restrict__ binv, const double *__restrict__ in, double *__restrict__ out)
+// (blockIdx.y: the column of a block of vectors, ks_st_pc_apply_multi; a single vector is the launch with gridDim.y = 1)
+__global__ void k_bjacobi_apply(long long n, int bs, const double *__restrict__ binv, const double *__restrict__ in, long long ldin, double *__restrict__ out, long long ldout)
 {
+  in += blockIdx.y * ldin; out += blockIdx.y * ldout;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const long long b0 = i / bs * bs;
     const double *row = binv + i * bs;
@@ -52,6 +54,14 @@ __global__ void k_bjacobi_apply(long long n, int bs, const double *__restrict__ 
     for (int c = 0; c < bs && b0 + c < n; c++) acc = fma(row[c], in[b0 + c], acc);
     out[i] = acc;
   }
+}
+
+// out(:,j) = s .* in(:,j) for the columns j = blockIdx.y of a block (s NULL: a copy): point Jacobi and PCNONE applied to a block of vectors. The product
+// is the one k_lincomb forms for a single vector (1.0 * u is exact), so every column has the bits of ks_st_pc_apply.
+__global__ void k_diag_apply_multi(long long n, const double *__restrict__ s, const double *__restrict__ in, long long ldin, double *__restrict__ out, long long ldout)
+{
+  in += blockIdx.y * ldin; out += blockIdx.y * ldout;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = s ? s[i] * in[i] : in[i];
 }
 
 // out = M^-T in: row i of out is COLUMN i of its block's inverse times the block's piece of in - the same array, walked with stride bs
@@ -106,7 +116,7 @@ int apply_P(ks_st st, const double *s, const double *x, double *out, double *tmp
     KS_CALL(ks_mat_mult_internal(Pm, x, out));
     return s ? lincomb(st->ctx, st->n, s, 1.0, out, 0.0, nullptr, out) : KS_SUCCESS;
   }
-  if (st->type == KS_ST_SINVERT || st->type == KS_ST_CAYLEY) return linop_apply(st, 1.0, A, -st->sigma, B, !B, s, x, out, tmp);
+  if (st->type != KS_ST_SHIFT) return linop_apply(st, 1.0, A, -st->sigma, B, !B, s, x, out, tmp);     // sinvert, cayley (and the K of STPRECOND)
   return linop_apply(st, 0.0, nullptr, 1.0, B, false, s, x, out, tmp);               // shift, nmat=2: P = B
 }
 
@@ -115,7 +125,7 @@ int bjacobi_apply(ks_st st, const double *in, double *out, bool tr = false)
   if (st->n == 0) return KS_SUCCESS;
   const unsigned nb = (unsigned)std::min<long long>(((long long)st->n + 255) / 256, (long long)st->ctx->num_cu * 16);
   if (tr) hipLaunchKernelGGL(k_bjacobi_apply_t, dim3(nb), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_bs, st->binv, in, out);
-  else hipLaunchKernelGGL(k_bjacobi_apply, dim3(nb), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_bs, st->binv, in, out);
+  else hipLaunchKernelGGL(k_bjacobi_apply, dim3(nb), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_bs, st->binv, in, 0LL, out, 0LL);
   KS_HIP(hipGetLastError());
   return KS_SUCCESS;
 }
@@ -128,14 +138,14 @@ int blocks_apply(ks_st st, const double *in, double *out, bool tr = false)
 // out = M^-1 (a u + b v) with the left preconditioner M of the KSP: diag(P) (one fused kernel) or the diagonal blocks of P; tr: M^-T (point Jacobi is its own)
 int pc_lincomb(ks_st st, double a, const double *u, double b, const double *v, double *out, bool tr = false)
 {
-  if (st->pc_type == KS_PC_JACOBI) return lincomb(st->ctx, st->n, st->dinv, a, u, b, v, out);
+  if (st->pc_type == KS_PC_JACOBI || st->pc_type == KS_PC_NONE) return lincomb(st->ctx, st->n, st->pc_type == KS_PC_NONE ? nullptr : st->dinv, a, u, b, v, out);
   KS_CALL(lincomb(st->ctx, st->n, nullptr, a, u, b, v, st->pcwork));
   return blocks_apply(st, st->pcwork, out, tr);
 }
 // out = M^-1 P x; tr: out = M^-T P^T x (PCApplyBAorABTranspose, PC_LEFT)
 int apply_MP(ks_st st, const double *x, double *out, double *tmp, bool tr = false)
 {
-  if (st->pc_type == KS_PC_JACOBI) return apply_P(st, st->dinv, x, out, tmp, tr);
+  if (st->pc_type == KS_PC_JACOBI || st->pc_type == KS_PC_NONE) return apply_P(st, st->pc_type == KS_PC_NONE ? nullptr : st->dinv, x, out, tmp, tr);
   KS_CALL(apply_P(st, nullptr, x, st->pcwork, tmp, tr));
   return blocks_apply(st, st->pcwork, out, tr);
 }
@@ -381,6 +391,8 @@ int ks_st_setup_internal(ks_st st)
   if (st->Pmat) { ks_mat_destroy(st->Pmat); st->Pmat = nullptr; }           // the assembled P of an earlier shift / type / mode
   if (st->ilu) { ks_pc_ilu_free(st->ilu); st->ilu = nullptr; }              // and its ILU(0) blocks
   const bool need_solve = (st->type == KS_ST_SINVERT) || (st->type == KS_ST_CAYLEY) || (st->type == KS_ST_SHIFT && B);
+  // STPRECOND (precond.c:36-110): K = A - sigma B is only preconditioned, the KSP is preonly - the preconditioner is built, no Krylov basis
+  const bool precond = st->type == KS_ST_PRECOND;
   st->At = st->Bt = st->PmatT = nullptr;                                      // views: freed with the matrices they view
   if (need_solve && st->tsolves) {
     // the transposed side of P and of the operator's other factor (B^T, (A + nu B)^T): MatTranspose of the kept arrays, one rank
@@ -390,11 +402,12 @@ int ks_st_setup_internal(ks_st st)
   }
   if (st->W) { int wn = 0; ks_bv_get_sizes(st->W, &wn, nullptr, nullptr, nullptr); if (wn != A->n) { ks_bv_destroy(st->W); ks_bv_destroy(st->K); ks_bv_destroy(st->Kb); st->W = st->K = st->Kb = nullptr; if (st->dinv) hipFree(st->dinv); st->dinv = nullptr; } }
   if (!st->W) KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 3, 0, &st->W));
-  if (need_solve) {
+  if (need_solve || precond) {
+    if (st->K && !need_solve) { ks_bv_destroy(st->K); st->K = nullptr; }
     if (st->K) { int km = 0; ks_bv_get_sizes(st->K, nullptr, nullptr, &km, nullptr); if (km != st->restart + 1) { ks_bv_destroy(st->K); st->K = nullptr; } }
-    if (!st->K) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, st->restart + 1, 0, &st->K)); st->K->row_start = A->row_start; }
-    KS_CALL(ks_bv_set_orthogonalization(st->K, KS_BV_ORTHOG_CGS, st->gmres_refine, 0.7071));      // KSPGMRESClassicalGramSchmidtOrthogonalization + refinement type
-    if (st->ksp_type == KS_KSP_BCGS && !st->Kb) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 7, 0, &st->Kb)); st->Kb->row_start = A->row_start; }
+    if (need_solve && !st->K) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, st->restart + 1, 0, &st->K)); st->K->row_start = A->row_start; }
+    if (need_solve) KS_CALL(ks_bv_set_orthogonalization(st->K, KS_BV_ORTHOG_CGS, st->gmres_refine, 0.7071));      // KSPGMRESClassicalGramSchmidtOrthogonalization + refinement type
+    if (need_solve && st->ksp_type == KS_KSP_BCGS && !st->Kb) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 7, 0, &st->Kb)); st->Kb->row_start = A->row_start; }
     if (!st->dinv) KS_HIP(hipMalloc(&st->dinv, sizeof(double) * std::max(A->n, 1)));
     // Jacobi: diag(P)
     double *da = ks_bv_col(st->W, 1), *db = ks_bv_col(st->W, 2);
@@ -406,7 +419,7 @@ int ks_st_setup_internal(ks_st st)
       if (st->tsolves) KS_CALL(ks_mat_create_transpose(st->Pmat, &st->PmatT));
       KS_CALL(ks_mat_get_diagonal_internal(st->Pmat, da));
       hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 1.0, da, 0.0, (const double *)nullptr, st->dinv);
-    } else if (st->type == KS_ST_SINVERT || st->type == KS_ST_CAYLEY) {
+    } else if (st->type != KS_ST_SHIFT) {
       KS_CALL(ks_mat_get_diagonal_internal(A, da));
       if (B) KS_CALL(ks_mat_get_diagonal_internal(B, db));
       hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 1.0, da, -st->sigma, B ? db : nullptr, st->dinv);
@@ -442,6 +455,7 @@ int ks_st_apply_internal(ks_st st, const double *x, double *y)     // STApply_Ge
     KS_CALL(linop_apply(st, 1.0, st->A, st->nu, st->B, !st->B, nullptr, x, w, t1));
     return inner_solve(st, w, y);
   }
+  if (st->type == KS_ST_PRECOND) return pc_lincomb(st, 1.0, x, 0.0, nullptr, y);      // y = M^-1 x, KSPPREONLY (precond.c:93)
   // shift
   if (st->B) { KS_CALL(linop_apply(st, 1.0, st->A, -st->sigma, st->B, false, nullptr, x, w, t1)); return inner_solve(st, w, y); }
   return linop_apply(st, 1.0, st->A, -st->sigma, nullptr, st->sigma != 0.0, nullptr, x, y, t1);
@@ -472,8 +486,9 @@ extern "C" int ks_st_destroy(ks_st st)
 extern "C" int ks_st_set_type(ks_st st, int type)                    // STSetType
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  KS_CHECK(type == KS_ST_SHIFT || type == KS_ST_SINVERT || type == KS_ST_CAYLEY, KS_ERR_SUP, "only STSHIFT, STSINVERT and STCAYLEY are built");
+  KS_CHECK(type == KS_ST_SHIFT || type == KS_ST_SINVERT || type == KS_ST_CAYLEY || type == KS_ST_PRECOND, KS_ERR_SUP, "only STSHIFT, STSINVERT, STCAYLEY and STPRECOND are built");
   if (st->type != type) { st->type = type; st->ready = false; }
+  st->type_set = true;
   return KS_SUCCESS;
 }
 extern "C" int ks_st_set_shift(ks_st st, double sigma)               // STSetShift stfunc.c
@@ -525,10 +540,11 @@ extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType
 extern "C" int ks_st_set_pc(ks_st st, int type, int block_size)       // PCSetType (+ PCBJacobiSetLocalBlocks, -sub_pc_type lu | ilu) on the KSP's PC
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  KS_CHECK(type == KS_PC_JACOBI || type == KS_PC_BJACOBI || type == KS_PC_BJACOBI_ILU, KS_ERR_SUP, "only PCJACOBI and PCBJACOBI (sub-solves: LU on dense blocks, or ILU(0)) are built");
+  KS_CHECK(type == KS_PC_JACOBI || type == KS_PC_BJACOBI || type == KS_PC_BJACOBI_ILU || type == KS_PC_NONE, KS_ERR_SUP, "only PCNONE, PCJACOBI and PCBJACOBI (sub-solves: LU on dense blocks, or ILU(0)) are built");
+  KS_CHECK(type != KS_PC_NONE || block_size == 0, KS_ERR_SUP, "PCNONE has no blocks: a block size (%d) with it names no preconditioner this build has", block_size);
   KS_CHECK(type != KS_PC_BJACOBI || (block_size >= 2 && block_size <= 32), KS_ERR_ARG_OUTOFRANGE, "block size %d (2..32)", block_size);
   KS_CHECK(type != KS_PC_BJACOBI_ILU || (block_size >= 64 && block_size <= ksc::ILU_BS_MAX), KS_ERR_ARG_OUTOFRANGE, "block size %d (64..%d)", block_size, ksc::ILU_BS_MAX);
-  if (type == KS_PC_JACOBI) block_size = 0;
+  if (type == KS_PC_JACOBI || type == KS_PC_NONE) block_size = 0;
   if (st->pc_type != type || st->pc_bs != block_size) { st->pc_type = type; st->pc_bs = block_size; st->ready = false; }
   return KS_SUCCESS;
 }
@@ -556,8 +572,66 @@ extern "C" int ks_st_pc_apply(ks_st st, const double *x_dev, double *y_dev)     
   KS_HIP(hipSetDevice(st->ctx->device));
   if (!st->ready) KS_CALL(ks_st_setup_internal(st));
   KS_CHECK(st->type != KS_ST_SHIFT || st->B, KS_ERR_ORDER, "this transformation has no linear solve, so no preconditioner (STSHIFT with one matrix)");
+  if (st->pc_type == KS_PC_NONE) return ksk_copy(st->ctx, x_dev, y_dev, st->n);
   if (st->pc_type == KS_PC_JACOBI) return lincomb(st->ctx, st->n, st->dinv, 1.0, x_dev, 0.0, nullptr, y_dev);
   return blocks_apply(st, x_dev, y_dev);
+}
+// the argument checks a block entry shares with ks_mat_mult_multi; *empty: nothing to do
+static int block_entry(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy, bool *empty)
+{
+  KS_CHECK(st && X_dev && Y_dev, KS_ERR_ARG_NULL, "NULL argument");
+  KS_CHECK(st->A, KS_ERR_ORDER, "STSetMatrices must be called first");
+  KS_CHECK(ncols >= 0, KS_ERR_ARG_OUTOFRANGE, "Number of columns %d must be non-negative", ncols);
+  const int n = st->A->n;
+  KS_CHECK(ldx >= std::max(1, n) && ldy >= std::max(1, n), KS_ERR_ARG_SIZ, "Leading dimensions ldx %d, ldy %d must be at least %d (local rows)", ldx, ldy, std::max(1, n));
+  *empty = ncols == 0;
+  if (*empty) return KS_SUCCESS;
+  const uintptr_t x0 = (uintptr_t)X_dev, x1 = x0 + sizeof(double) * ((size_t)(ncols - 1) * ldx + n);
+  const uintptr_t y0 = (uintptr_t)Y_dev, y1 = y0 + sizeof(double) * ((size_t)(ncols - 1) * ldy + n);
+  KS_CHECK(X_dev != Y_dev && (x1 <= y0 || y1 <= x0), KS_ERR_ARG_WRONG, "X and Y must be different blocks: they overlap");
+  KS_HIP(hipSetDevice(st->ctx->device));
+  if (!st->ready) KS_CALL(ks_st_setup_internal(st));
+  return KS_SUCCESS;
+}
+// PCMatApply on KSPGetPC(STGetKSP): Y(:,j) = M^-1 X(:,j). The pointwise preconditioners and the dense blocks are their single-vector kernels with the
+// column on the grid's second dimension; the ILU(0) blocks keep several columns of a block in LDS at once (ks_pc.hip). One column IS ks_st_pc_apply.
+int ks_st_pc_apply_multi_internal(ks_st st, int ncols, const double *X, int ldx, double *Y, int ldy)
+{
+  if (ncols <= 0 || st->n == 0) return KS_SUCCESS;
+  if (st->pc_type == KS_PC_BJACOBI_ILU) return ks_pc_ilu_apply_multi(st->ctx, st->ilu, ncols, X, ldx, Y, ldy);
+  const unsigned nb = (unsigned)std::min<long long>(((long long)st->n + 255) / 256, (long long)st->ctx->num_cu * 16);
+  if (st->pc_type == KS_PC_BJACOBI) hipLaunchKernelGGL(k_bjacobi_apply, dim3(nb, (unsigned)ncols), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_bs, st->binv, X, (long long)ldx, Y, (long long)ldy);
+  else hipLaunchKernelGGL(k_diag_apply_multi, dim3(nb, (unsigned)ncols), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_type == KS_PC_NONE ? (const double *)nullptr : st->dinv, X, (long long)ldx, Y, (long long)ldy);
+  KS_HIP(hipGetLastError());
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_apply_multi(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy)
+{
+  bool empty = false;
+  KS_CALL(block_entry(st, ncols, X_dev, ldx, Y_dev, ldy, &empty));
+  if (empty) return KS_SUCCESS;
+  KS_CHECK(st->type != KS_ST_SHIFT || st->B, KS_ERR_ORDER, "this transformation has no linear solve, so no preconditioner (STSHIFT with one matrix)");
+  return ks_st_pc_apply_multi_internal(st, ncols, X_dev, ldx, Y_dev, ldy);
+}
+extern "C" int ks_st_pc_multi_columns(ks_st st, int *columns)      // instrumentation: columns ks_st_pc_apply_multi handles per pass with the PC that is set up
+{
+  KS_CHECK(st && columns, KS_ERR_ARG_NULL, "NULL argument");
+  KS_CHECK(st->A, KS_ERR_ORDER, "STSetMatrices must be called first");
+  KS_HIP(hipSetDevice(st->ctx->device));
+  if (!st->ready) KS_CALL(ks_st_setup_internal(st));
+  *columns = (st->pc_type == KS_PC_BJACOBI_ILU && st->ilu) ? std::max(1, ks_pc_ilu_multi_columns(st->ctx, st->ilu)) : 65535;      // the other types take the whole block in one launch (grid.y)
+  return KS_SUCCESS;
+}
+// STApplyMat (stsolve.c:62-80): Y = Op X for a block of vectors. STPRECOND applies its preconditioner to the block; the transformations with a
+// Krylov solve inside go column by column through STApply
+extern "C" int ks_st_apply_mat(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy)
+{
+  bool empty = false;
+  KS_CALL(block_entry(st, ncols, X_dev, ldx, Y_dev, ldy, &empty));
+  if (empty) return KS_SUCCESS;
+  if (st->type == KS_ST_PRECOND) return ks_st_pc_apply_multi_internal(st, ncols, X_dev, ldx, Y_dev, ldy);
+  for (int j = 0; j < ncols; j++) KS_CALL(ks_st_apply_internal(st, X_dev + (size_t)j * ldx, Y_dev + (size_t)j * ldy));
+  return KS_SUCCESS;
 }
 extern "C" int ks_st_set_transpose_solves(ks_st st, int enable)
 {

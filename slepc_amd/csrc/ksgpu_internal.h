@@ -268,12 +268,14 @@ struct KsIlu;
 int ks_pc_ilu_build(ks_ctx ctx, int n, int row_start, int bs, const int *rp, const int *col, const double *val, bool transpose, KsIlu **out);
 int ks_pc_ilu_apply(ks_ctx ctx, const KsIlu *p, const double *in, double *out);      // enqueued; in != out
 int ks_pc_ilu_apply_transpose(ks_ctx ctx, const KsIlu *p, const double *in, double *out);      // enqueued; in != out; needs the transposed plan
+int ks_pc_ilu_apply_multi(ks_ctx ctx, const KsIlu *p, int ncols, const double *X, long long ldx, double *Y, long long ldy);   // enqueued; blocks do not overlap; every column the bits of ks_pc_ilu_apply
+int ks_pc_ilu_multi_columns(ks_ctx ctx, const KsIlu *p);   // columns of a pass of the above (0: one at a time)
 void ks_pc_ilu_free(KsIlu *p);
 
 // ---- ST: spectral transformation (ks_st.hip) ----------------------------------------------------
 struct ks_st_s {
   ks_ctx ctx = nullptr;
-  int type = KS_ST_SHIFT;
+  int type = KS_ST_SHIFT; bool type_set = false;   // type_set: chosen by the caller (STSetType), not a solver's default
   double sigma = 0.0; bool sigma_set = false;
   double nu = 0.0; bool nu_set = false;      // STCAYLEY antishift (defaults to sigma, cayley.c:140)
   ks_mat bil = nullptr;                       // STCAYLEY: shell matrix A + nu B, the bilinear form of symmetric problems (cayley.c:70-77)
@@ -301,6 +303,7 @@ struct ks_st_s {
 bool ks_st_is_plain(ks_st st);                // shift with sigma = 0 on a standard problem: Op = A itself
 int ks_st_setup_internal(ks_st st);
 int ks_st_apply_internal(ks_st st, const double *x, double *y);
+int ks_st_pc_apply_multi_internal(ks_st st, int ncols, const double *X, int ldx, double *Y, int ldy);   // set-up done, arguments checked by the caller
 void ks_st_backtransform_internal(ks_st st, int n, double *eigr, double *eigi);
 int ksk_lincomb(ks_ctx ctx, long long n, const double *s, double a, const double *u, double b, const double *v, double *out);   // out = s.*(a*u + b*v)   // diagonal of the local diagonal block (MatGetDiagonal)
 
