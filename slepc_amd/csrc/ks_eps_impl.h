@@ -1,4 +1,5 @@
-// The EPS object and the few pieces of the driver that its solvers share (ks_eps.hip: Krylov-Schur; ks_lobpcg.hip: LOBPCG).
+// The EPS object and what crosses the files of its driver: ks_eps.hip (the object, the generic set-up, ks_eps_solve, results), ks_krylovschur.hip
+// (both Krylov-Schur variants), ks_lobpcg.hip (LOBPCG) and ks_balance.hip (balancing of non-symmetric problems, the driver's only device code).
 #pragma once
 #include "ksgpu_internal.h"
 #include "ks_ds.h"
@@ -29,6 +30,7 @@ struct ks_eps_s {
   std::vector<double> eigr, eigi, errest; std::vector<int> perm;
   int nconv = 0, its = 0, reason = 0;
   long long steps = 0, passes = 0; int restarts = 0;
+  long long passes0[2] = {0, 0};       // Gram-Schmidt pass counts of V and VL where this solve's count starts (eps->passes is the difference at its end)
   bool solved = false, ghep = false;
   ks_eps_converged_fn conv_fn = nullptr; void *conv_ctx = nullptr;     // EPSSetConvergenceTestFunction (conv = KS_EPS_CONV_USER)
   ks_eps_stopping_fn stop_fn = nullptr; void *stop_ctx = nullptr;      // EPSSetStoppingTestFunction; NULL = EPSStoppingBasic
@@ -61,7 +63,19 @@ int ks_eps_stopping_call(ks_eps eps, int its, int nconv);                       
 int ks_eps_monitor_call(ks_eps eps, int its, int nconv, int nest);                // EPSMonitor
 int ks_eps_matrix_norms(ks_eps eps);                                              // ||A||_inf, ||B||_inf for KS_EPS_CONV_NORM (epssetup.c:345-358)
 int ks_eps_synchronize_values(ks_eps eps, double *v, size_t count);               // rank 0's values to every rank under KS_DS_PARALLEL_SYNCHRONIZED
-// EPSSetUp_LOBPCG + EPSSolve_LOBPCG (ks_lobpcg.hip); ks_eps_solve runs the shared epilogue behind it
-int ks_lobpcg_solve(ks_eps eps);
+int ks_lobpcg_solve(ks_eps eps);                                                  // EPSSolve_LOBPCG, the solve of ks_lobpcg_ops (ks_lobpcg.hip)
 // R(:,j) = AX(:,j) - theta[j] BX(:,j) for ncols <= 16 columns and their 2-norms over all ranks into norms (host), one kernel and one D2H (ks_lobpcg.hip)
 int ksl_block_residual(ks_bv R, int ncols, const double *AX, long long ldax, const double *BX, long long ldbx, double *Rd, long long ldr, const double *theta, double *norms);
+
+#pragma GCC visibility push(hidden)
+// eps->ops of the reference, what ks_eps_solve asks of a solver. setup: its checks and dimension rules around eps_setup_common, its projected problem;
+// solve: up to eps->nconv converged pairs in the leading columns of V; compute_vectors: what EPSSolve's epilogue does to them (NULL: nothing)
+struct ks_eps_ops { int (*setup)(ks_eps); int (*solve)(ks_eps); int (*compute_vectors)(ks_eps); };
+const ks_eps_ops *ks_krylovschur_ops(bool twosided);                              // ks_krylovschur.hip: the one-sided or the two-sided variant
+const ks_eps_ops *ks_lobpcg_ops();                                                // ks_lobpcg.hip
+int eps_setup_common(ks_eps eps, int ncv, ks_mat ip);                             // the generic part of EPSSetUp once a solver knows ncv and its inner product (ks_eps.hip)
+int ks_eps_residual_norm(ks_eps eps, double kr, double ki, const double *xr, const double *xi, double xi_sign, double *out, bool trans = false);   // ks_eps.hip
+int ks_eps_schur_vectors(ks_eps eps);                                             // EPSComputeVectors_Schur on first use of an eigenvector (ks_krylovschur.hip)
+int ks_eps_pointwise(ks_eps eps, const double *a, const double *b, double *out, bool mul);   // ks_balance.hip: out = a .* b or a ./ b on n_local entries
+int ks_eps_setup_balance(ks_eps eps);                                             // ks_balance.hip: D built (or the user's checked), eps->op = the shell D Op D^-1
+#pragma GCC visibility pop

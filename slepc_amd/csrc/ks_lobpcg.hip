@@ -338,12 +338,13 @@ int Lobpcg::solve()
 
 } // namespace
 
-// EPSSetUp_LOBPCG (lobpcg.c:55-83) with the parts of EPSSetUp it relies on (problem type, ST, inner product, solution basis, deflation space), then the solve
-int ks_lobpcg_solve(ks_eps eps)
+// EPSSetUp_LOBPCG (lobpcg.c:55-83) with the parts of EPSSetUp whose rules are this solver's: problem type, sort criterion, dimensions, the ST as a
+// preconditioner, B as the inner product; then the common part and the projected problem
+static int lobpcg_setup(ks_eps eps)
 {
   KS_CHECK(eps->A, KS_ERR_ORDER, "EPSSetOperators must be called first");
-  ks_ctx ctx = eps->ctx; ks_mat A = eps->A;
-  KS_HIP(hipSetDevice(ctx->device));
+  ks_mat A = eps->A;
+  KS_HIP(hipSetDevice(eps->ctx->device));
   const int n = A->n_global;
   int ptype = eps->problem_type;
   if (!eps->B && ptype == KS_EPS_GHEP) ptype = KS_EPS_HEP;
@@ -360,11 +361,7 @@ int ks_lobpcg_solve(ks_eps eps)
   const int kmin = std::max(3 * bs, ((nev - 1) / bs + 3) * bs);
   KS_CHECK(!eps->ncv_user || eps->ncv_user >= kmin, KS_ERR_USER_INPUT, "The value of ncv is not sufficiently large");
   KS_CHECK(!eps->mpd_user || eps->mpd_user == 3 * bs, KS_ERR_USER_INPUT, "This solver does not allow a value of mpd different from 3*blocksize");
-  const int ncv = eps->ncv_user ? eps->ncv_user : kmin;
-  eps->ncv = ncv; eps->mpd = 3 * bs;
-  eps->max_it = eps->max_it_user ? eps->max_it_user : std::max(100, 2 * n / ncv);
-  const double restart = eps->lob.restart ? eps->lob.restart : 0.9;
-  const int guard = bs == 1 ? 0 : std::min((int)((1.0 - restart) * bs + 0.45), bs - 1);
+  eps->mpd = 3 * bs;                                                   // the block size of this solve, for ks_lobpcg_solve
   if (eps->conv == KS_EPS_CONV_NORM) KS_CALL(ks_eps_matrix_norms(eps));
   eps->cmp_final = eps->which; eps->cmp_final.which = which; eps->cmp_ds = eps->cmp_final;
   // the ST only preconditions: K = A - sigma B with sigma the shift, or the target when none was set (precond.c:65)
@@ -375,32 +372,28 @@ int ks_lobpcg_solve(ks_eps eps)
   KS_CALL(ks_st_set_matrices(st, A, eps->B)); st->ready = false;
   KS_CALL(ks_st_setup_internal(st));
   eps->op = A;
-  // EPSAllocateSolution, EPS_SetInnerProduct, the deflation space (epssetup.c:397-404)
-  if (eps->V) { int vm = 0; ks_bv_get_sizes(eps->V, nullptr, nullptr, &vm, nullptr); if (vm != ncv + 1 || eps->V->nc) { ks_bv_destroy(eps->V); eps->V = nullptr; } }
-  if (!eps->V) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, ncv + 1, 0, &eps->V)); eps->V->row_start = A->row_start; }
-  if (!eps->W) KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 5, 0, &eps->W));
-  eps->eigr.assign(ncv + 1, 0.0); eps->eigi.assign(ncv + 1, 0.0); eps->errest.assign(ncv + 1, 0.0);
-  eps->perm.resize(ncv + 1); for (int i = 0; i <= ncv; i++) eps->perm[i] = i;
-  eps->cb_err = 0; eps->nconv = 0; eps->its = 0; eps->reason = KS_EPS_CONVERGED_ITERATING; eps->steps = 0; eps->passes = 0; eps->restarts = 0; eps->solved = false;
-  eps->lob.iterations = eps->lob.hard_locks = eps->lob.mat_columns = eps->lob.pc_columns = 0;
-  eps->ghep = ptype == KS_EPS_GHEP; eps->problem_type_resolved_hermitian = true; eps->vectors_done = true; eps->left_trivial = true; eps->twosided_solved = false; eps->balanced = false;
-  ks_bv V = eps->V;
-  KS_CALL(ks_bv_set_active_columns(V, 0, ncv + 1));
-  KS_CALL(ks_bv_set_matrix(V, eps->ghep ? eps->B : nullptr));
-  if (eps->nds) {
-    KS_CHECK(eps->defl && eps->defl->n == A->n, KS_ERR_ARG_INCOMP, "the deflation space was set for an operator of another size");
-    std::vector<const double *> cp(eps->nds);
-    for (int i = 0; i < eps->nds; i++) cp[i] = ks_bv_col(eps->defl, i);
-    int kd = eps->nds;
-    const int rc = ks_bv_insert_constraints(V, &kd, cp.data());
-    ks_bv_destroy(eps->defl); eps->defl = nullptr; eps->nds = 0;
-    if (rc) return rc;
-  }
-  Lobpcg s;
-  s.eps = eps; s.ctx = ctx; s.A = A; s.B = eps->ghep ? eps->B : nullptr; s.st = st; s.V = V;
-  s.bs = bs; s.guard = guard; s.lock = eps->lob.lock; s.flip = which == KS_EPS_LARGEST_REAL; s.ld = 3 * bs;
+  KS_CALL(eps_setup_common(eps, eps->ncv_user ? eps->ncv_user : kmin, ptype == KS_EPS_GHEP ? eps->B : nullptr));
+  eps->ghep = ptype == KS_EPS_GHEP; eps->problem_type_resolved_hermitian = true; eps->left_trivial = true;
   eps->dsg.allocate(3 * bs); eps->dsg.which = ksd::KsCompare(); eps->dsg.which.which = KS_EPS_SMALLEST_REAL;     // the flipped spectrum is sorted like the other (lobpcg.c:103-107)
+  return KS_SUCCESS;
+}
+
+// EPSSolve_LOBPCG. It leaves the eigenvectors in V(:,0:nconv): nothing for the epilogue to map back, purify or normalise again (no compute_vectors)
+int ks_lobpcg_solve(ks_eps eps)
+{
+  Lobpcg s;
+  s.eps = eps; s.ctx = eps->ctx; s.A = eps->A; s.B = eps->ghep ? eps->B : nullptr; s.st = eps->st; s.V = eps->V;
+  s.bs = eps->mpd / 3; s.ld = eps->mpd; s.lock = eps->lob.lock; s.flip = eps->cmp_final.which == KS_EPS_LARGEST_REAL;
+  const double restart = eps->lob.restart ? eps->lob.restart : 0.9;
+  s.guard = s.bs == 1 ? 0 : std::min((int)((1.0 - restart) * s.bs + 0.45), s.bs - 1);
   const int rc = s.solve();
   ks_bv_destroy(eps->ini); eps->ini = nullptr; eps->nini = 0;                                                     // the initial space is consumed like the deflation space
+  ks_bv_gs_passes(eps->V, &eps->passes0[0], nullptr);     // the passes stat counts the Gram-Schmidt passes of Krylov expansions: none here, the initial vectors in V are not one
   return rc;
+}
+
+const ks_eps_ops *ks_lobpcg_ops()
+{
+  static const ks_eps_ops ops = {lobpcg_setup, ks_lobpcg_solve, nullptr};
+  return &ops;
 }

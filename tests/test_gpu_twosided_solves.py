@@ -1,5 +1,5 @@
 """Two-sided Krylov-Schur behind a solve and with a B matrix, and two-sided balancing behind a solve: what ks_st_set_transpose_solves on the
-EPS's ST opens (ks_eps.hip: the left basis is expanded with Op^T = M^T P^-T, the converged left vectors of a generalized problem go through
+EPS's ST opens (ks_krylovschur.hip: the left basis is expanded with Op^T = M^T P^-T, the converged left vectors of a generalized problem go through
 P^-T, the left residual is ||A^T y - conj(k) B^T y||).
 
 References: the value columns of the reference's ex41_1.out and eps_test29_1.out, numpy's dense eigenvalues, and residuals computed on the host

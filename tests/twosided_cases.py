@@ -12,7 +12,7 @@ import numpy as np
 from oracle import oracle as O
 
 SQRT_EPS = np.sqrt(np.finfo(float).eps)
-LEFT_SEED_XOR = 0x9E3779B97F4A7C15          # the left start vectors draw from their own stream (ks_eps.hip: left_start_vector)
+LEFT_SEED_XOR = 0x9E3779B97F4A7C15          # the left start vectors draw from their own stream (ks_krylovschur.hip: left_start_vector)
 
 
 def transpose(A):
