@@ -81,7 +81,7 @@ enum { KS_EPS_LARGEST_MAGNITUDE = 1, KS_EPS_SMALLEST_MAGNITUDE = 2, KS_EPS_LARGE
 typedef int (*ks_eig_compare_fn)(double ar, double ai, double br, double bi, int *res, void *ctx);
 enum { KS_EPS_HEP = 1, KS_EPS_GHEP = 2, KS_EPS_NHEP = 3, KS_EPS_GNHEP = 4 };   /* EPSProblemType, slepceps.h */
 enum { KS_ST_SHIFT = 0, KS_ST_SINVERT = 1, KS_ST_CAYLEY = 2, KS_ST_PRECOND = 3 };   /* STType "shift", "sinvert", "cayley", "precond" (precond.c: K = A - sigma B is only preconditioned, never solved) */
-enum { KS_EPS_KRYLOVSCHUR = 0, KS_EPS_LOBPCG = 1 };   /* EPSType "krylovschur", "lobpcg" */
+enum { KS_EPS_KRYLOVSCHUR = 0, KS_EPS_LOBPCG = 1, KS_EPS_GD = 2 };   /* EPSType "krylovschur", "lobpcg", "gd" */
 enum { KS_EPS_ERROR_ABSOLUTE = 0, KS_EPS_ERROR_RELATIVE = 1, KS_EPS_ERROR_BACKWARD = 2 };   /* EPSErrorType */
 enum { KS_EPS_RITZ = 0, KS_EPS_HARMONIC = 1, KS_EPS_HARMONIC_RELATIVE, KS_EPS_HARMONIC_RIGHT, KS_EPS_HARMONIC_LARGEST, KS_EPS_REFINED, KS_EPS_REFINED_HARMONIC };  /* EPSExtraction slepceps.h:94-100; Krylov-Schur offers the first two */
 enum { KS_EPS_BALANCE_NONE = 0, KS_EPS_BALANCE_ONESIDE = 1, KS_EPS_BALANCE_TWOSIDE = 2, KS_EPS_BALANCE_USER = 3 };   /* EPSBalance slepceps.h; the two-sided form needs the transposed product (ks_mat_mult_transpose) */
@@ -352,6 +352,21 @@ int ks_bv_get_matmult_method(ks_bv bv, int *method);                            
    all the norms. r = fma(-theta, bx, ax): one rounding where the reference has two. BX may be the BV of the vectors themselves (a standard problem);
    R must be a BV of its own (KS_ERR_ARG_WRONG). Columns of R outside [l, k) are not touched. theta: host array. */
 int ks_bv_block_residual(ks_bv R, ks_bv AX, ks_bv BX, const double *theta, double *norms);
+/* The Ritz vectors of a Davidson iteration with their residuals (what dvd_calcpairs_res_0, dvdcalcpairs.c:523-560, does with two or three BVMult, a
+   BVMultVec and two VecNorm per pair): one sweep over the search basis and its images.
+   For j < ncols, m = k - l the active columns [l,k) of V, the same column indices in AV and BV:
+     x_j  = sum_c V (:, l+c) S(c,j)          (never stored)
+     ax_j = sum_c AV(:, l+c) S(c,j)
+     bx_j = sum_c BV(:, l+c) S(c,j)          (BV == NULL: a standard problem, bx_j = x_j)
+     R(:, lR + j) = ax_j - theta[j] * bx_j,   lR = first active column of R
+     rnorm[j] = ||R(:, lR+j)||_2,  xnorm[j] = ||x_j||_2   over all ranks (host arrays; xnorm may be NULL)
+   S: host, column-major, m x ncols, lds >= m (staged on the device by the call).  theta: host.
+   Every sum starts at 0 and takes c in ascending order with one fma per term, r = fma(-theta, bx, ax): an entry of R depends on its own row alone,
+   its bits do not change with the grid, the alignment of the columns or the way the rows are cut over ranks. With a BV, more than 8 result columns
+   run as two passes over the panels inside the call (the register budget of a pass: 8 columns generalized, 16 standard). One reduction, one allreduce and one D2H bring all 2 ncols norms. Columns of R outside [lR, lR + ncols) are
+   not touched. Errors: ncols outside 1..16, or no active column in V: KS_ERR_ARG_OUTOFRANGE; lds < m, AV / BV with fewer than k columns, R with
+   fewer than lR + ncols: KS_ERR_ARG_SIZ; R the same BV as V, AV or BV: KS_ERR_ARG_WRONG; different local sizes: KS_ERR_ARG_INCOMP. */
+int ks_bv_ritz_residual(ks_bv R, ks_bv V, ks_bv AV, ks_bv BV, const double *S, int lds, int ncols, const double *theta, double *rnorm, double *xnorm);
 
 /* ops->gramschmidt (bvimpl.h:53): ONE Gram-Schmidt pass, the function BVOrthogonalizeGS1 dispatches to (bvorthog.c:134) in place
    of BVOrthogonalizeCGS1 (:91-132) / BVOrthogonalizeMGS1 (:52-85), chosen by the BV's orthogonalization type. The caller
@@ -460,7 +475,7 @@ int ks_eps_set_arbitrary_selection(ks_eps eps, ks_eps_arbitrary_fn fn, void *ctx
 int ks_eps_monitor_set(ks_eps eps, ks_eps_monitor_fn fn, void *ctx);                    /* EPSMonitorSet (one slot; NULL cancels): called once per restart with the DS-ordered values, untransformed */
 int ks_eps_set_purify(ks_eps eps, int purify);                              /* EPSSetPurify: 0 skips the purification of GHEP eigenvectors (test1_1_ks_nopurify) */
 int ks_eps_get_purify(ks_eps eps, int *purify);
-/* EPSSetType (epsbasic.c): KS_EPS_KRYLOVSCHUR (the default: nothing changes for existing callers) or KS_EPS_LOBPCG, the block solver for the smallest
+/* EPSSetType (epsbasic.c): KS_EPS_KRYLOVSCHUR (the default: nothing changes for existing callers), KS_EPS_GD (below) or KS_EPS_LOBPCG, the block solver for the smallest
    (or largest) eigenvalues of symmetric problems without inner solves (src/eps/impls/cg/lobpcg/lobpcg.c; ks_lobpcg.hip). Choosing LOBPCG makes
    KS_ST_PRECOND the type of the solver's ST unless the caller set one (EPSSetDefaultST_Precond); a Krylov-Schur solve with KS_ST_PRECOND is KS_ERR_SUP.
    ks_eps_solve with LOBPCG (EPSSetUp_LOBPCG lobpcg.c:55-83) returns
@@ -481,6 +496,32 @@ int ks_eps_lobpcg_set_locking(ks_eps eps, int lock);      /* EPSLOBPCGSetLocking
 int ks_eps_lobpcg_get_locking(ks_eps eps, int *lock);
 /* instrumentation of the last LOBPCG solve: passes of the main loop, hard locks, columns a matrix was applied to (A and B), columns preconditioned */
 int ks_eps_lobpcg_get_stats(ks_eps eps, long long *iterations, long long *hard_locks, long long *mat_columns, long long *pc_columns);
+/* KS_EPS_GD: Generalized Davidson (src/eps/impls/davidson: davidson.c, dvdinitv.c, dvdcalcpairs.c, dvdimprovex.c, dvdupdatev.c, dvdtestconv.c;
+   ks_gd.hip) for KS_EPS_HEP and KS_EPS_GHEP with a B-orthonormal search basis and Ritz extraction. Every iteration multiplies the new basis columns by
+   A (and B), solves the projected problem, forms the Ritz vectors and residuals of the best bs pairs (ks_bv_ritz_residual), tests them in order on
+   ||r|| / ||x|| with the EPS's criterion, and then locks the converged pairs, or restarts (minv Ritz vectors plus plusk vectors of the previous
+   iteration), or expands the basis by the preconditioned residuals D = M^-1 R. Choosing GD makes KS_ST_PRECOND the type of the solver's ST unless the
+   caller set one; the preconditioner is built on A - sigma B with sigma the ST's shift if set, else the target for the target criteria, else 0; for the
+   largest-* criteria with no shift set the default shift is infinite (davidson.c:80): M is built on B alone, and a standard problem is not preconditioned.
+   ks_eps_solve with GD (EPSSetUp_XD davidson.c:51-77) returns KS_ERR_SUP for: ncv given and < nev; mpd > ncv or mpd < 2; nev + bs > ncv; the true
+   residual, the two-sided flag, an extraction other than Ritz or arbitrary selection set; minv + bs > mpd; initial size > mpd; and, stated deviations
+   from the reference, a non-symmetric problem type and B-orthogonalisation switched off with a B matrix. Defaults: ncv = max(nev, min(n - bs,
+   max(2 nev, nev + 15)) + bs) (n + nev + bs for n < 10, mpd + nev + bs with mpd given), mpd = min(n, ncv), max_it = max(100 ncv, 2 n), `which` = largest
+   magnitude, minv = min(max(bs, 6), mpd / 2), plusk = 1, initial size 6 (minv and initial size 1 for n < 10). Balancing is ignored. Further stated
+   deviations (block sizes 1..16, one of lock / restart / expand per iteration, the restart test) are listed at the top of ks_gd.hip. The result
+   getters, ks_eps_compute_error, the deflation space, the initial space (all its vectors up to the initial size), track-all, the monitor and the user's
+   convergence and stopping functions work as after a LOBPCG solve. */
+int ks_eps_gd_set_blocksize(ks_eps eps, int bs);          /* EPSGDSetBlockSize gd.c; 0 = default 1; outside 0..16: KS_ERR_ARG_OUTOFRANGE */
+int ks_eps_gd_get_blocksize(ks_eps eps, int *bs);         /* EPSGDGetBlockSize */
+int ks_eps_gd_set_restart(ks_eps eps, int minv, int plusk);   /* EPSGDSetRestart gd.c; minv 0 or -1 and plusk -1: the default */
+int ks_eps_gd_get_restart(ks_eps eps, int *minv, int *plusk); /* EPSGDGetRestart: what was set, else what the last set-up resolved (minv 0 before one) */
+int ks_eps_gd_set_initial_size(ks_eps eps, int initialsize);  /* EPSGDSetInitialSize gd.c; 0 or -1 = default */
+int ks_eps_gd_get_initial_size(ks_eps eps, int *initialsize); /* EPSGDGetInitialSize */
+int ks_eps_gd_set_borth(ks_eps eps, int borth);           /* EPSGDSetBOrth gd.c, default on; off with a B matrix: KS_ERR_SUP at the solve */
+int ks_eps_gd_get_borth(ks_eps eps, int *borth);          /* EPSGDGetBOrth */
+/* instrumentation of the last GD solve: passes of the main loop, restarts, locking steps, columns a matrix was applied to (A and B), columns
+   preconditioned, calls of the fused Ritz-residual sweep */
+int ks_eps_gd_get_stats(ks_eps eps, long long *iterations, long long *restarts, long long *locks, long long *mat_columns, long long *pc_columns, long long *fused_residuals);
 int ks_eps_set_track_all(ks_eps eps, int trackall);                          /* EPSSetTrackAll: error estimates of all Ritz pairs at every restart (for monitors) */
 int ks_eps_get_krylovschur(ks_eps eps, double *keep, int *lock);             /* EPSKrylovSchurGetRestart / EPSKrylovSchurGetLocking */
 int ks_eps_set_balance(ks_eps eps, int bal, int its, double cutoff);        /* EPSSetBalance epsopts.c:1050 (non-symmetric problems; EPSBuildBalance_Krylov epsdefault.c:370); its / cutoff 0 keep 5 / 1e-8 */

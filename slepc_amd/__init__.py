@@ -32,7 +32,7 @@ WHICH = {"largest_magnitude": 1, "smallest_magnitude": 2, "largest_real": 3, "sm
 BLOCK = {"gs": 0, "chol": 1, "tsqr": 2, "tsqrchol": 3, "svqb": 4}
 SHELL_MULT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
 ST_SHIFT, ST_SINVERT, ST_CAYLEY, ST_PRECOND = 0, 1, 2, 3
-EPS_KRYLOVSCHUR, EPS_LOBPCG = 0, 1
+EPS_KRYLOVSCHUR, EPS_LOBPCG, EPS_GD = 0, 1, 2
 PC_JACOBI, PC_BJACOBI, PC_BJACOBI_ILU, PC_NONE = 0, 1, 2, 3
 BV_MATMULT_VECS, BV_MATMULT_MAT, BV_MATMULT_MAT_SAVE = 0, 1, 2
 MATMULT = {"vecs": BV_MATMULT_VECS, "mat": BV_MATMULT_MAT, "mat_save": BV_MATMULT_MAT_SAVE}
@@ -633,6 +633,19 @@ class BV:
         _lib.check(self.ctx.L.ks_bv_block_residual(self.h, AX.h, BX.h, _p(th), _p(nrm)))
         return nrm[:len(th)]
 
+    def RitzResidual(self, V, AV, BV, S, theta, ncols=None, lds=None, want_xnorm=True):
+        """One sweep over the active columns of V and the same columns of AV (and BV; None: a standard problem): R(:, lR + j) = AV S(:,j) -
+        theta[j] BV S(:,j) into this BV from its first active column (self is R); returns (rnorm, xnorm) with xnorm[j] = ||V S(:,j)||_2.
+        S: column-major (Fortran-ordered 2-D array, or a flat array with lds)."""
+        S = np.asarray(S, dtype=np.float64)
+        if S.ndim == 2:
+            S = np.asfortranarray(S); lds = S.shape[0] if lds is None else lds; ncols = S.shape[1] if ncols is None else ncols; flat = S.ravel(order="F")
+        else:
+            flat = np.ascontiguousarray(S)
+        th = _f64(theta); rn = np.zeros(max(ncols, 1)); xn = np.zeros(max(ncols, 1))
+        _lib.check(self.ctx.L.ks_bv_ritz_residual(self.h, V.h, AV.h, BV.h if BV is not None else None, _p(flat), lds, ncols, _p(th), _p(rn), _p(xn) if want_xnorm else None))
+        return rn[:ncols], (xn[:ncols] if want_xnorm else None)
+
     def SetMatMultMethod(self, method):
         """BVSetMatMultMethod: "vecs" / "mat" / "mat_save" (or the BV_MATMULT_* number)."""
         _lib.check(self.ctx.L.ks_bv_set_matmult_method(self.h, MATMULT.get(method, method)))
@@ -961,11 +974,40 @@ class EPS:
         _lib.check(self.ctx.L.ks_eps_set_problem_type(self.h, t))
 
     def SetType(self, t):
-        """EPSSetType: "krylovschur" (default) or "lobpcg"."""
-        _lib.check(self.ctx.L.ks_eps_set_type(self.h, {"krylovschur": EPS_KRYLOVSCHUR, "lobpcg": EPS_LOBPCG}.get(t, t)))
+        """EPSSetType: "krylovschur" (default), "lobpcg" or "gd"."""
+        _lib.check(self.ctx.L.ks_eps_set_type(self.h, {"krylovschur": EPS_KRYLOVSCHUR, "lobpcg": EPS_LOBPCG, "gd": EPS_GD}.get(t, t)))
 
     def GetType(self):
-        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_get_type(self.h, C.byref(v))); return {0: "krylovschur", 1: "lobpcg"}[v.value]
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_get_type(self.h, C.byref(v))); return {0: "krylovschur", 1: "lobpcg", 2: "gd"}[v.value]
+
+    def GDSetBlockSize(self, bs):
+        _lib.check(self.ctx.L.ks_eps_gd_set_blocksize(self.h, bs))
+
+    def GDGetBlockSize(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_gd_get_blocksize(self.h, C.byref(v))); return v.value
+
+    def GDSetRestart(self, minv=0, plusk=-1):
+        _lib.check(self.ctx.L.ks_eps_gd_set_restart(self.h, minv, plusk))
+
+    def GDGetRestart(self):
+        a, b = C.c_int(), C.c_int(); _lib.check(self.ctx.L.ks_eps_gd_get_restart(self.h, C.byref(a), C.byref(b))); return a.value, b.value
+
+    def GDSetInitialSize(self, initialsize):
+        _lib.check(self.ctx.L.ks_eps_gd_set_initial_size(self.h, initialsize))
+
+    def GDGetInitialSize(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_gd_get_initial_size(self.h, C.byref(v))); return v.value
+
+    def GDSetBOrth(self, borth):
+        _lib.check(self.ctx.L.ks_eps_gd_set_borth(self.h, int(bool(borth))))
+
+    def GDGetBOrth(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_gd_get_borth(self.h, C.byref(v))); return bool(v.value)
+
+    def GDGetStats(self):
+        v = [C.c_longlong() for _ in range(6)]
+        _lib.check(self.ctx.L.ks_eps_gd_get_stats(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("iterations", "restarts", "locks", "mat_columns", "pc_columns", "fused_residuals"), (x.value for x in v)))
 
     def LOBPCGSetBlockSize(self, bs):
         _lib.check(self.ctx.L.ks_eps_lobpcg_set_blocksize(self.h, bs))

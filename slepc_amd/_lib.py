@@ -122,6 +122,7 @@ _SIG = {
     "ks_bv_set_matmult_method": [vp, C.c_int],
     "ks_bv_get_matmult_method": [vp, ip],
     "ks_bv_block_residual": [vp, vp, vp, dp, dp],
+    "ks_bv_ritz_residual": [vp, vp, vp, vp, dp, C.c_int, C.c_int, dp, dp, dp],
     "ks_bv_gramschmidt_pass": [vp, C.c_int, vp, ip, dp, dp, dp, dp],
     "ks_bv_orthogonalizecolumn": [vp, C.c_int, dp, dp, ip],
     "ks_bv_orthonormalizecolumn": [vp, C.c_int, C.c_int, dp, ip],
@@ -212,6 +213,11 @@ _SIG = {
     "ks_eps_lobpcg_set_restart": [vp, C.c_double], "ks_eps_lobpcg_get_restart": [vp, dp],
     "ks_eps_lobpcg_set_locking": [vp, C.c_int], "ks_eps_lobpcg_get_locking": [vp, ip],
     "ks_eps_lobpcg_get_stats": [vp, llp, llp, llp, llp],
+    "ks_eps_gd_set_blocksize": [vp, C.c_int], "ks_eps_gd_get_blocksize": [vp, ip],
+    "ks_eps_gd_set_restart": [vp, C.c_int, C.c_int], "ks_eps_gd_get_restart": [vp, ip, ip],
+    "ks_eps_gd_set_initial_size": [vp, C.c_int], "ks_eps_gd_get_initial_size": [vp, ip],
+    "ks_eps_gd_set_borth": [vp, C.c_int], "ks_eps_gd_get_borth": [vp, ip],
+    "ks_eps_gd_get_stats": [vp, llp, llp, llp, llp, llp, llp],
     "ks_st_create": [vp, C.POINTER(vp)],
     "ks_st_destroy": [vp],
     "ks_st_set_type": [vp, C.c_int],

@@ -416,6 +416,81 @@ void DsGhep::sort(double *w)
   for (int j = 0; j < n; j++) { w[j] = w2[perm[j]]; for (int i = 0; i < n; i++) Q[(size_t)i + (size_t)j * ld] = Q2[(size_t)i + (size_t)j * n]; }
 }
 
+// ---- the projected problem of Generalized Davidson ---------------------------------------------------
+void DsGd::grow(int nnew, const double *C, int ldc)
+{
+  const int nn = n + nnew;
+  for (int j = 0; j < nnew; j++) for (int i = 0; i < nn; i++) { const double v = C[(size_t)i + (size_t)j * ldc]; if (i <= n + j) { h(i, n + j) = v; h(n + j, i) = v; } }
+  n = nn;
+}
+
+int DsGd::solve_sort()
+{
+  if (n <= 0) return 0;
+  std::vector<double> Z((size_t)n * n), ww(n);
+  for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) Z[(size_t)i + (size_t)j * n] = i >= j ? h(i, j) : h(j, i);
+  if (sym_eig(n, Z.data(), n, ww.data())) return -1;
+  // insertion sort as DSSortEigenvalues_Private does it: stable, the ascending order of the solve survives among equals
+  std::vector<int> perm(n);
+  for (int i = 0; i < n; i++) perm[i] = i;
+  for (int i = 1; i < n; i++) {
+    const int pi = perm[i]; int j = i - 1;
+    while (j >= 0 && compare_eig(which, ww[perm[j]], 0.0, ww[pi], 0.0) > 0) { perm[j + 1] = perm[j]; j--; }
+    perm[j + 1] = pi;
+  }
+  for (int j = 0; j < n; j++) { w[j] = ww[perm[j]]; for (int i = 0; i < n; i++) q(i, j) = Z[(size_t)i + (size_t)perm[j] * n]; }
+  return 0;
+}
+
+void DsGd::lock(int npre)
+{
+  const int nn = n - npre;
+  for (int j = 0; j < nn; j++) for (int i = 0; i < nn; i++) h(i, j) = i == j ? w[npre + j] : 0.0;
+  for (int j = 0; j < nn; j++) w[j] = w[npre + j];
+  n = nn; size_oldU = 0;
+}
+
+void DsGd::save_oldU()
+{
+  std::fill(oldU.begin(), oldU.end(), 0.0);
+  for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) oldU[(size_t)i + (size_t)j * ld] = q(i, j);
+  size_oldU = n;
+}
+
+int DsGd::restart_basis(int size_X, int size_plusk, double *Z, int ldz) const
+{
+  const double thr = 64.0 * n * std::numeric_limits<double>::epsilon();
+  int kept = 0;
+  std::vector<double> z(n);
+  for (int c = 0; c < size_X + size_plusk; c++) {
+    if (c < size_X) for (int i = 0; i < n; i++) z[i] = Q[(size_t)i + (size_t)c * ld];
+    else for (int i = 0; i < n; i++) z[i] = (i < size_oldU && c - size_X < size_oldU) ? oldU[(size_t)i + (size_t)(c - size_X) * ld] : 0.0;
+    double nrm0 = 0.0; for (int i = 0; i < n; i++) nrm0 += z[i] * z[i];
+    nrm0 = sqrt(nrm0);
+    for (int pass = 0; pass < 2; pass++)
+      for (int k = 0; k < kept; k++) {
+        const double *zk = Z + (size_t)k * ldz;
+        double d = 0.0; for (int i = 0; i < n; i++) d += zk[i] * z[i];
+        for (int i = 0; i < n; i++) z[i] -= d * zk[i];
+      }
+    double nrm = 0.0; for (int i = 0; i < n; i++) nrm += z[i] * z[i];
+    nrm = sqrt(nrm);
+    if (!(nrm > thr * nrm0)) continue;
+    for (int i = 0; i < n; i++) Z[(size_t)i + (size_t)kept * ldz] = z[i] / nrm;
+    kept++;
+  }
+  return kept;
+}
+
+void DsGd::project(const double *Z, int ldz, int kept)
+{
+  std::vector<double> T((size_t)n * kept), G((size_t)kept * kept);
+  for (int j = 0; j < kept; j++) for (int i = 0; i < n; i++) { double t = 0.0; for (int p = 0; p < n; p++) t += H[(size_t)i + (size_t)p * ld] * Z[(size_t)p + (size_t)j * ldz]; T[(size_t)i + (size_t)j * n] = t; }
+  for (int j = 0; j < kept; j++) for (int i = 0; i <= j; i++) { double t = 0.0; for (int p = 0; p < n; p++) t += Z[(size_t)p + (size_t)i * ldz] * T[(size_t)p + (size_t)j * n]; G[(size_t)i + (size_t)j * kept] = t; }
+  for (int j = 0; j < kept; j++) for (int i = 0; i <= j; i++) { h(i, j) = G[(size_t)i + (size_t)j * kept]; h(j, i) = h(i, j); }
+  n = kept; size_oldU = 0;
+}
+
 } // namespace ksd
 
 #ifdef KSD_TEST_HOOKS
@@ -491,6 +566,27 @@ int ksd_ghep(int n, int ld, const double *A, const double *B, double *Q, double 
   const int rc = ds.solve(w);
   if (!rc) ds.sort(w);
   std::copy(ds.Q.begin(), ds.Q.end(), Q);
+  return rc;
+}
+// The projected problem of Generalized Davidson on caller-owned ld x ld arrays (tests/test_gd_host.py). dims = {n, size_oldU}, read and written back.
+// op 0 grow(a0 columns from Z, ldz), 1 solve_sort (returns its code), 2 lock(a0), 3 restart_basis(a0 = size_X, a1 = size_plusk) into Z (returns the kept
+// count), 4 project(Z, ldz, a0 = kept), 5 save_oldU
+int ksd_gd(int op, int ld, int *dims, double *H, double *Q, double *oldU, double *w, int which, double target, int a0, int a1, double *Z, int ldz)
+{
+  ksd::DsGd ds; ds.allocate(ld); ds.n = dims[0]; ds.size_oldU = dims[1]; ds.which.which = which; ds.which.target = target;
+  std::copy(H, H + ds.H.size(), ds.H.begin()); std::copy(Q, Q + ds.Q.size(), ds.Q.begin()); std::copy(oldU, oldU + ds.oldU.size(), ds.oldU.begin()); std::copy(w, w + ld, ds.w.begin());
+  int rc = 0;
+  switch (op) {
+    case 0: ds.grow(a0, Z, ldz); break;
+    case 1: rc = ds.solve_sort(); break;
+    case 2: ds.lock(a0); break;
+    case 3: rc = ds.restart_basis(a0, a1, Z, ldz); break;
+    case 4: ds.project(Z, ldz, a0); break;
+    case 5: ds.save_oldU(); break;
+    default: return -1;
+  }
+  dims[0] = ds.n; dims[1] = ds.size_oldU;
+  std::copy(ds.H.begin(), ds.H.end(), H); std::copy(ds.Q.begin(), ds.Q.end(), Q); std::copy(ds.oldU.begin(), ds.oldU.end(), oldU); std::copy(ds.w.begin(), ds.w.end(), w);
   return rc;
 }
 void ksd_backtransform(int st_type, double sigma, double nu, int n, double *eigr, double *eigi) { ksd::StMap{st_type, sigma, nu}.backtransform(n, eigr, eigi); }

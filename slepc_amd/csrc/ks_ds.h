@@ -145,4 +145,28 @@ struct DsGhep {
   void sort(double *w);               // DSSort_GHEP dsghep.c:172-195: eigenvalues and the columns of Q in the order of `which`
 };
 
+// The projected problem of Generalized Davidson (ks_gd.hip): H = V^T A V of the active search columns - a standard symmetric problem, the basis being
+// B-orthonormal -, its eigenvectors Q in the order of `which`, and the Q of the previous iteration (oldU, dvdupdatev.c:297-307) for the thick restart
+// with "+k" vectors. Host only and outside the Ds hierarchy, like DsGhep: the order changes at every step (grow, lock, restart), there is no extra row.
+// All three matrices are ld x ld column-major; oldU has order size_oldU and counts as zero-padded to the current order n.
+struct DsGd {
+  int ld = 0, n = 0, size_oldU = 0; KsCompare which;
+  std::vector<double> H, Q, oldU, w;
+  void allocate(int ld_) { ld = ld_; n = 0; size_oldU = 0; H.assign((size_t)ld * ld, 0.0); Q.assign((size_t)ld * ld, 0.0); oldU.assign((size_t)ld * ld, 0.0); w.assign(ld, 0.0); }
+  double &h(int i, int j) { return H[(size_t)i + (size_t)j * ld]; }
+  double &q(int i, int j) { return Q[(size_t)i + (size_t)j * ld]; }
+  // nnew new search columns: C (ldc x nnew) holds V^T A v for each, n + nnew rows (the new order); H keeps both triangles (dvdcalcpairs.c:372-418)
+  void grow(int nnew, const double *C, int ldc);
+  // H = Q diag(w) Q^T with w and the columns of Q in the order of `which` (DSSolve + DSSort, dvdcalcpairs.c:497-521); H is kept. Non-zero: sym_eig failed
+  int solve_sort();
+  // the leading npre pairs leave (dvd_updateV_conv_gen, dvdupdatev.c:82-149): the basis having been rotated by Q, H is the diagonal of the other Ritz values
+  void lock(int npre);
+  void save_oldU();                                                                         // oldU <- Q (dvdupdatev.c:297-307)
+  // Z = orth([Q(:, 0:size_X), oldU(:, 0:size_plusk)]) (n x kept into Z, ldz >= n): DSOrthogonalize's contract as dvd_updateV_restart_gen uses it
+  // (dvdupdatev.c:151-224) - orthonormal columns spanning the block, dependent columns dropped, the kept count returned. Gram-Schmidt with one
+  // re-orthogonalisation; a column is dependent when what is left of it is below 64 n eps of its norm (what two passes leave of a column of the span)
+  int restart_basis(int size_X, int size_plusk, double *Z, int ldz) const;
+  void project(const double *Z, int ldz, int kept);                                         // H <- Z^T H Z of order kept; oldU is forgotten
+};
+
 } // namespace ksd

@@ -1,5 +1,5 @@
 // Host side of the path, the part every eigensolver shares: the EPS object with its options and getters, the generic set-up, ks_eps_solve over the
-// solver table (ks_eps_impl.h; the solvers are ks_krylovschur.hip and ks_lobpcg.hip), the epilogue of a solve, the results and their errors.
+// solver table (ks_eps_impl.h; the solvers are ks_krylovschur.hip, ks_lobpcg.hip and ks_gd.hip), the epilogue of a solve, the results and their errors.
 //
 // Restates, in plain C++ on host scalars:
 //   EPSSetUp (generic part)         src/eps/interface/epssetup.c:286-420
@@ -217,7 +217,7 @@ extern "C" int ks_eps_set_initial_space(ks_eps eps, int n, const double *const *
   KS_CHECK(v_dev && v_dev[0], KS_ERR_ARG_NULL, "NULL argument");
   eps->v0.resize(std::max(eps->A->n, 1));
   KS_HIP(hipSetDevice(eps->ctx->device));
-  if (eps->type == KS_EPS_LOBPCG) {                    // a block solver uses all of them (lobpcg.c:133): device copies, made only for that solver type
+  if (eps->type == KS_EPS_LOBPCG || eps->type == KS_EPS_GD) {   // a block solver uses all of them (lobpcg.c:133, dvdinitv.c:45): device copies, made only for those solver types
     KS_CALL(ks_bv_create(eps->ctx, eps->A->n, eps->A->n_global, n, 0, &eps->ini));
     for (int i = 0; i < n; i++) { KS_CHECK(v_dev[i], KS_ERR_ARG_NULL, "vector %d is NULL", i); KS_CALL(ks_bv_insert_vec(eps->ini, i, v_dev[i])); }
     eps->nini = n;
@@ -390,6 +390,7 @@ int eps_setup_common(ks_eps eps, int ncv, ks_mat ip)
   eps->nconv = 0; eps->its = 0; eps->reason = KS_EPS_CONVERGED_ITERATING; eps->solved = false;
   eps->steps = 0; eps->passes = 0; eps->restarts = 0;
   eps->lob.iterations = eps->lob.hard_locks = eps->lob.mat_columns = eps->lob.pc_columns = 0;
+  eps->gd.iterations = eps->gd.restarts = eps->gd.locks = eps->gd.mat_columns = eps->gd.pc_columns = eps->gd.fused_residuals = 0;
   eps->dst.permuted = 0;
   eps->ghep = false; eps->problem_type_resolved_hermitian = false; eps->left_trivial = false; eps->twosided_solved = false; eps->balanced = false;
   eps->vectors_done = true;
@@ -436,7 +437,7 @@ static void sort_eigenvalues(ks_eps eps)
 extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119-208
 {
   KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
-  const ks_eps_ops &ops = eps->type == KS_EPS_LOBPCG ? *ks_lobpcg_ops() : *ks_krylovschur_ops(eps->twosided);
+  const ks_eps_ops &ops = eps->type == KS_EPS_LOBPCG ? *ks_lobpcg_ops() : eps->type == KS_EPS_GD ? *ks_gd_ops() : *ks_krylovschur_ops(eps->twosided);
   KS_CALL(ops.setup(eps));                                             // takes the pass counters (eps->passes0) and allocates the solver's DS
   KS_CALL(ops.solve(eps));
   // ---- EPSSolve epilogue ----
@@ -631,15 +632,16 @@ extern "C" int ks_eps_get_stats(ks_eps eps, long long *steps, long long *passes,
   return KS_SUCCESS;
 }
 
-// EPSSetType epsbasic.c: Krylov-Schur (the default) or LOBPCG. LOBPCG makes STPRECOND the default of the solver's ST (EPSSetDefaultST_Precond
-// epsdefault.c) unless the caller chose a type; going back to Krylov-Schur undoes that default
+// EPSSetType epsbasic.c: Krylov-Schur (the default), LOBPCG or GD. LOBPCG and GD make STPRECOND the default of the solver's ST (EPSSetDefaultST_Precond
+// epsdefault.c) unless the caller chose a type; going back to Krylov-Schur undoes that default. The infinite default shift is GD's alone (davidson.c:80)
 extern "C" int ks_eps_set_type(ks_eps eps, int type)
 {
   KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
-  KS_CHECK(type == KS_EPS_KRYLOVSCHUR || type == KS_EPS_LOBPCG, KS_ERR_SUP, "only EPSKRYLOVSCHUR and EPSLOBPCG are built");
+  KS_CHECK(type == KS_EPS_KRYLOVSCHUR || type == KS_EPS_LOBPCG || type == KS_EPS_GD, KS_ERR_SUP, "only EPSKRYLOVSCHUR, EPSLOBPCG and EPSGD are built");
   if (type == eps->type) return KS_SUCCESS;
   eps->type = type; eps->solved = false;
-  if (type == KS_EPS_LOBPCG) {
+  if (eps->st && eps->st->sigma_inf) { eps->st->sigma_inf = false; eps->st->ready = false; }
+  if (type == KS_EPS_LOBPCG || type == KS_EPS_GD) {
     ks_st st = nullptr;
     KS_CALL(ks_eps_get_st(eps, &st));
     if (!st->type_set) { st->type = KS_ST_PRECOND; st->ready = false; }

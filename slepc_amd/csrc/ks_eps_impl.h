@@ -1,5 +1,5 @@
 // The EPS object and what crosses the files of its driver: ks_eps.hip (the object, the generic set-up, ks_eps_solve, results), ks_krylovschur.hip
-// (both Krylov-Schur variants), ks_lobpcg.hip (LOBPCG) and ks_balance.hip (balancing of non-symmetric problems, the driver's only device code).
+// (both Krylov-Schur variants), ks_lobpcg.hip (LOBPCG), ks_gd.hip (Generalized Davidson) and ks_balance.hip (balancing of non-symmetric problems, the driver's only device code).
 #pragma once
 #include "ksgpu_internal.h"
 #include "ks_ds.h"
@@ -55,6 +55,11 @@ struct ks_eps_s {
   struct { int bs = 0; double restart = 0.0; bool lock = true; long long iterations = 0, hard_locks = 0, mat_columns = 0, pc_columns = 0; } lob;
   ksd::DsGhep dsg;
   ks_bv ini = nullptr; int nini = 0;     // EPSSetInitialSpace: all the vectors (a block solver uses every one; the Krylov solvers use v0, the first)
+  // KS_EPS_GD (ks_gd.hip): the settings of EPS_DAVIDSON that GD has (davidson.h: blocksize, minv, plusk, initialsize, ipB; 0 / -1: the default), what the
+  // last set-up resolved them to, the counters of the last solve and its projected problem
+  struct { int bs = 0, minv = 0, plusk = -1, initv = 0; bool borth = true; int r_bs = 0, r_minv = 0, r_plusk = 0, r_initv = 0;
+           long long iterations = 0, restarts = 0, locks = 0, mat_columns = 0, pc_columns = 0, fused_residuals = 0; } gd;
+  ksd::DsGd dsd;
 };
 
 // the callbacks of a solve as every solver calls them (ks_eps.hip)
@@ -73,6 +78,7 @@ int ksl_block_residual(ks_bv R, int ncols, const double *AX, long long ldax, con
 struct ks_eps_ops { int (*setup)(ks_eps); int (*solve)(ks_eps); int (*compute_vectors)(ks_eps); };
 const ks_eps_ops *ks_krylovschur_ops(bool twosided);                              // ks_krylovschur.hip: the one-sided or the two-sided variant
 const ks_eps_ops *ks_lobpcg_ops();                                                // ks_lobpcg.hip
+const ks_eps_ops *ks_gd_ops();                                                    // ks_gd.hip
 int eps_setup_common(ks_eps eps, int ncv, ks_mat ip);                             // the generic part of EPSSetUp once a solver knows ncv and its inner product (ks_eps.hip)
 int ks_eps_residual_norm(ks_eps eps, double kr, double ki, const double *xr, const double *xi, double xi_sign, double *out, bool trans = false);   // ks_eps.hip
 int ks_eps_schur_vectors(ks_eps eps);                                             // EPSComputeVectors_Schur on first use of an eigenvector (ks_krylovschur.hip)

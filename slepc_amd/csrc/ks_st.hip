@@ -87,6 +87,7 @@ int ksk_lincomb(ks_ctx ctx, long long n, const double *s, double a, const double
 }
 namespace {
 inline int lincomb(ks_ctx ctx, long long n, const double *s, double a, const double *u, double b, const double *v, double *out) { return ksk_lincomb(ctx, n, s, a, u, b, v, out); }
+inline bool pc_none(ks_st st) { return st->pc_type == KS_PC_NONE || st->pc_identity; }      // no preconditioner: the caller's choice, or STPRECOND's infinite default shift on one matrix
 
 // out = s .* (a*A*x + b*(B*x | x)); tmp is scratch of n doubles (used when both terms are present)
 int linop_apply(ks_st st, double a, ks_mat A, double b, ks_mat B, bool identity_term, const double *s, const double *x, double *out, double *tmp)
@@ -138,7 +139,7 @@ int blocks_apply(ks_st st, const double *in, double *out, bool tr = false)
 // out = M^-1 (a u + b v) with the left preconditioner M of the KSP: diag(P) (one fused kernel) or the diagonal blocks of P; tr: M^-T (point Jacobi is its own)
 int pc_lincomb(ks_st st, double a, const double *u, double b, const double *v, double *out, bool tr = false)
 {
-  if (st->pc_type == KS_PC_JACOBI || st->pc_type == KS_PC_NONE) return lincomb(st->ctx, st->n, st->pc_type == KS_PC_NONE ? nullptr : st->dinv, a, u, b, v, out);
+  if (st->pc_type == KS_PC_JACOBI || pc_none(st)) return lincomb(st->ctx, st->n, pc_none(st) ? nullptr : st->dinv, a, u, b, v, out);
   KS_CALL(lincomb(st->ctx, st->n, nullptr, a, u, b, v, st->pcwork));
   return blocks_apply(st, st->pcwork, out, tr);
 }
@@ -304,7 +305,7 @@ int st_bilinear_mult(void *user, const double *x, double *y)
 static int pc_block_source(ks_st st, std::vector<int> &rp, std::vector<int> &col, std::vector<double> &val, const int **prp, const int **pcol, const double **pval)
 {
   ks_mat A = st->A, B = st->B;
-  const bool p_is_b = (st->type == KS_ST_SHIFT);                   // shift, nmat = 2: P = B
+  const bool p_is_b = (st->type == KS_ST_SHIFT) || st->pc_on_b;    // shift, nmat = 2: P = B; STPRECOND with the infinite default shift: M from B alone
   ks_mat M0 = p_is_b ? B : A;
   KS_CHECK(M0 && M0->keep_csr && (p_is_b || !B || B->keep_csr), KS_ERR_ORDER, "the block-Jacobi preconditioner takes its blocks from the CSR arrays of the matrices: create them with KS_MAT_KEEP_CSR");
   if (p_is_b) { *prp = B->k_rowptr.data(); *pcol = B->k_col.data(); *pval = B->k_val.data(); }
@@ -324,7 +325,7 @@ static int bjacobi_setup(ks_st st)
 {
   ks_ctx ctx = st->ctx;
   const int n = st->n, bs = st->pc_bs;
-  ks_mat M0 = (st->type == KS_ST_SHIFT) ? st->B : st->A;
+  ks_mat M0 = (st->type == KS_ST_SHIFT || st->pc_on_b) ? st->B : st->A;
   std::vector<int> rp, col; std::vector<double> val;
   const int *prp; const int *pcol; const double *pval;
   KS_CALL(pc_block_source(st, rp, col, val, &prp, &pcol, &pval));
@@ -363,7 +364,7 @@ static int bjacobi_setup(ks_st st)
 // on the host (ksc::csr_ilu0_blocks), uploaded once per set-up (ks_pc.hip)
 static int bjacobi_ilu_setup(ks_st st)
 {
-  ks_mat M0 = (st->type == KS_ST_SHIFT) ? st->B : st->A;
+  ks_mat M0 = (st->type == KS_ST_SHIFT || st->pc_on_b) ? st->B : st->A;
   std::vector<int> rp, col; std::vector<double> val;
   const int *prp; const int *pcol; const double *pval;
   KS_CALL(pc_block_source(st, rp, col, val, &prp, &pcol, &pval));
@@ -393,6 +394,9 @@ int ks_st_setup_internal(ks_st st)
   const bool need_solve = (st->type == KS_ST_SINVERT) || (st->type == KS_ST_CAYLEY) || (st->type == KS_ST_SHIFT && B);
   // STPRECOND (precond.c:36-110): K = A - sigma B is only preconditioned, the KSP is preonly - the preconditioner is built, no Krylov basis
   const bool precond = st->type == KS_ST_PRECOND;
+  // the infinite default shift (precond.c:70-74: K = -B, or no K at all with one matrix): only a solver asks for it (GD, davidson.c:80), a shift the caller set wins
+  const bool inf = precond && st->sigma_inf && !st->sigma_set;
+  st->pc_on_b = inf && B; st->pc_identity = inf && !B;
   st->At = st->Bt = st->PmatT = nullptr;                                      // views: freed with the matrices they view
   if (need_solve && st->tsolves) {
     // the transposed side of P and of the operator's other factor (B^T, (A + nu B)^T): MatTranspose of the kept arrays, one rank
@@ -419,17 +423,17 @@ int ks_st_setup_internal(ks_st st)
       if (st->tsolves) KS_CALL(ks_mat_create_transpose(st->Pmat, &st->PmatT));
       KS_CALL(ks_mat_get_diagonal_internal(st->Pmat, da));
       hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 1.0, da, 0.0, (const double *)nullptr, st->dinv);
-    } else if (st->type != KS_ST_SHIFT) {
+    } else if (st->type != KS_ST_SHIFT && !inf) {
       KS_CALL(ks_mat_get_diagonal_internal(A, da));
       if (B) KS_CALL(ks_mat_get_diagonal_internal(B, db));
       hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 1.0, da, -st->sigma, B ? db : nullptr, st->dinv);
-    } else {
+    } else if (B) {                                                    // shift with two matrices, or the infinite default shift: diag(B); one matrix there: nothing to build
       KS_CALL(ks_mat_get_diagonal_internal(B, db));
       hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 0.0, (const double *)nullptr, 1.0, db, st->dinv);
     }
     KS_HIP(hipGetLastError());
-    if (st->pc_type == KS_PC_BJACOBI) KS_CALL(bjacobi_setup(st));
-    if (st->pc_type == KS_PC_BJACOBI_ILU) KS_CALL(bjacobi_ilu_setup(st));
+    if (st->pc_type == KS_PC_BJACOBI && !st->pc_identity) KS_CALL(bjacobi_setup(st));
+    if (st->pc_type == KS_PC_BJACOBI_ILU && !st->pc_identity) KS_CALL(bjacobi_ilu_setup(st));
   }
   if (!st->op) KS_CALL(ks_mat_create_shell(ctx, A->n, A->row_start, A->n_global, st_shell_mult, st, &st->op));
   st->op->n = A->n; st->op->row_start = A->row_start; st->op->n_global = A->n_global;
@@ -572,7 +576,7 @@ extern "C" int ks_st_pc_apply(ks_st st, const double *x_dev, double *y_dev)     
   KS_HIP(hipSetDevice(st->ctx->device));
   if (!st->ready) KS_CALL(ks_st_setup_internal(st));
   KS_CHECK(st->type != KS_ST_SHIFT || st->B, KS_ERR_ORDER, "this transformation has no linear solve, so no preconditioner (STSHIFT with one matrix)");
-  if (st->pc_type == KS_PC_NONE) return ksk_copy(st->ctx, x_dev, y_dev, st->n);
+  if (pc_none(st)) return ksk_copy(st->ctx, x_dev, y_dev, st->n);
   if (st->pc_type == KS_PC_JACOBI) return lincomb(st->ctx, st->n, st->dinv, 1.0, x_dev, 0.0, nullptr, y_dev);
   return blocks_apply(st, x_dev, y_dev);
 }
@@ -598,10 +602,10 @@ static int block_entry(ks_st st, int ncols, const double *X_dev, int ldx, double
 int ks_st_pc_apply_multi_internal(ks_st st, int ncols, const double *X, int ldx, double *Y, int ldy)
 {
   if (ncols <= 0 || st->n == 0) return KS_SUCCESS;
-  if (st->pc_type == KS_PC_BJACOBI_ILU) return ks_pc_ilu_apply_multi(st->ctx, st->ilu, ncols, X, ldx, Y, ldy);
+  if (st->pc_type == KS_PC_BJACOBI_ILU && !st->pc_identity) return ks_pc_ilu_apply_multi(st->ctx, st->ilu, ncols, X, ldx, Y, ldy);
   const unsigned nb = (unsigned)std::min<long long>(((long long)st->n + 255) / 256, (long long)st->ctx->num_cu * 16);
-  if (st->pc_type == KS_PC_BJACOBI) hipLaunchKernelGGL(k_bjacobi_apply, dim3(nb, (unsigned)ncols), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_bs, st->binv, X, (long long)ldx, Y, (long long)ldy);
-  else hipLaunchKernelGGL(k_diag_apply_multi, dim3(nb, (unsigned)ncols), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_type == KS_PC_NONE ? (const double *)nullptr : st->dinv, X, (long long)ldx, Y, (long long)ldy);
+  if (st->pc_type == KS_PC_BJACOBI && !st->pc_identity) hipLaunchKernelGGL(k_bjacobi_apply, dim3(nb, (unsigned)ncols), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_bs, st->binv, X, (long long)ldx, Y, (long long)ldy);
+  else hipLaunchKernelGGL(k_diag_apply_multi, dim3(nb, (unsigned)ncols), dim3(256), 0, st->ctx->stream, (long long)st->n, pc_none(st) ? (const double *)nullptr : st->dinv, X, (long long)ldx, Y, (long long)ldy);
   KS_HIP(hipGetLastError());
   return KS_SUCCESS;
 }

@@ -277,6 +277,9 @@ struct ks_st_s {
   ks_ctx ctx = nullptr;
   int type = KS_ST_SHIFT; bool type_set = false;   // type_set: chosen by the caller (STSetType), not a solver's default
   double sigma = 0.0; bool sigma_set = false;
+  // STPRECOND with the infinite default shift GD asks for with the largest-* criteria (STSetDefaultShift(PETSC_MAX_REAL) davidson.c:80, precond.c:70-74),
+  // ignored once the caller sets a shift. The set-up resolves it: the preconditioner is built on B alone (pc_on_b), or there is none (pc_identity)
+  bool sigma_inf = false, pc_on_b = false, pc_identity = false;
   double nu = 0.0; bool nu_set = false;      // STCAYLEY antishift (defaults to sigma, cayley.c:140)
   ks_mat bil = nullptr;                       // STCAYLEY: shell matrix A + nu B, the bilinear form of symmetric problems (cayley.c:70-77)
   ks_mat A = nullptr, B = nullptr;            // borrowed
