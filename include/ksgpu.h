@@ -105,7 +105,8 @@ int ks_ctx_synchronize(ks_ctx ctx);
  * ks_comm_init_rccl / ks_comm_set_ops, ONESHOT_SEQ0 (first stamp of the one-shot allreduce) at ks_comm_set_allreduce, NO_DICT_PATTERNS (keep the
  * dictionary layout's 2-byte codes per entry, never its row-pattern form) at matrix assembly; the others per call. */
 enum { KS_DEBUG_NO_FUSED_GS = 0, KS_DEBUG_NO_MFMA = 1, KS_DEBUG_NO_SPMV_DOT = 2, KS_DEBUG_FORCE_MULTI = 3, KS_DEBUG_HALO_OVERLAP = 4, KS_DEBUG_ONESHOT_SEQ0 = 5,
-       KS_DEBUG_NO_DICT_PATTERNS = 6, KS_DEBUG_NO_RESTART_FUSION = 7 /* the final update of a run's last column, the restart product and the copy as the launches of their own */ };
+       KS_DEBUG_NO_DICT_PATTERNS = 6, KS_DEBUG_NO_RESTART_FUSION = 7 /* the final update of a run's last column, the restart product and the copy as the launches of their own */,
+       KS_DEBUG_NO_DICT_PAIRS = 8 /* read at launch: the dictionary product one row per lane also where the matrix has the pair form */ };
 int ks_ctx_set_debug(ks_ctx ctx, int key, long long value);
 int ks_ctx_sync_count(ks_ctx ctx, long long *count);   /* instrumentation: host waits on the context's stream made by the library so far */
 int ks_ctx_device_info(ks_ctx ctx, char *arch, int arch_len, int *num_cu, size_t *mem_total);
@@ -231,6 +232,8 @@ int ks_mat_get_window_info(ks_mat A, int *block_rows, int *max_segments, long lo
    codes. *patterns = 1 in that form, 0 otherwise; *npatterns = 0 and *index_bytes = 2 W n with the codes, n (plus padding to 256 rows) with the
    patterns: the device memory held per row of the diagonal block. Any other layout: all four 0. */
 int ks_mat_get_dict_info(ks_mat A, int *patterns, int *npatterns, int *w, long long *index_bytes);
+/* the pair form of the row-pattern form (two rows per lane, 16-byte loads of x): whether the matrix has it, its bases, and how many products (the fused dot sweep included) ran in either form */
+int ks_mat_get_dict_pairs_info(ks_mat A, int *eligible, int *nbases, long long *pair_launches, long long *row_launches);
 /* MatMult: y = A x on device pointers (x, y: n_local doubles owned by this rank).
    Multi-rank: performs the halo exchange of x (PETSc VecScatter inside MatMult_MPIAIJ).        */
 int ks_mat_mult(ks_mat A, const double *x_dev, double *y_dev);

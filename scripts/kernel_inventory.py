@@ -21,8 +21,10 @@ _PAT = re.compile(r"\b(%s)<([^<>()]*)>\(" % "|".join(FAMILIES))
 
 # instantiations no input reaches (the dispatch compiles them, nothing selects them)
 UNREACHABLE = {
-    "k_dot_spmv_dict<1,8>": "a Krylov step dots the new column and the one before it at least: ncols >= 2 (ks_gs.hip krylov_run, j + 2 columns)",
-    "k_dot_spmv_dict<1,16>": "as k_dot_spmv_dict<1,8>",
+    "k_dot_spmv_dict<1,8,0>": "a Krylov step dots the new column and the one before it at least: ncols >= 2 (ks_gs.hip krylov_run, j + 2 columns)",
+    "k_dot_spmv_dict<1,16,0>": "as k_dot_spmv_dict<1,8,0>",
+    "k_dot_spmv_dict<1,8,5>": "as k_dot_spmv_dict<1,8,0> (the pair form of the same sweep)",
+    "k_dot_spmv_dict<1,16,5>": "as k_dot_spmv_dict<1,8,0>",
 }
 
 

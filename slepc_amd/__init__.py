@@ -118,7 +118,7 @@ class Context:
     def synchronize(self):
         _lib.check(self.L.ks_ctx_synchronize(self.h))
 
-    DEBUG_KEYS = {"no_fused_gs": 0, "no_mfma": 1, "no_spmv_dot": 2, "force_multi": 3, "halo_overlap": 4, "oneshot_seq0": 5, "no_dict_patterns": 6, "no_restart_fusion": 7}
+    DEBUG_KEYS = {"no_fused_gs": 0, "no_mfma": 1, "no_spmv_dot": 2, "force_multi": 3, "halo_overlap": 4, "oneshot_seq0": 5, "no_dict_patterns": 6, "no_restart_fusion": 7, "no_dict_pairs": 8}
 
     def set_debug(self, key, value=1):
         """Test hooks (ks_ctx_set_debug): run the path a fast one replaces, or the multi-rank path on one rank."""
@@ -352,6 +352,12 @@ class Mat:
         p, k, w, b = C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
         _lib.check(self.ctx.L.ks_mat_get_dict_info(self.h, C.byref(p), C.byref(k), C.byref(w), C.byref(b)))
         return {"patterns": bool(p.value), "npatterns": k.value, "w": w.value, "index_bytes": b.value}
+
+    def dict_pairs_info(self):
+        """The pair form of the dictionary layout (ks_mat_get_dict_pairs_info): whether the matrix has it, and how many products ran in either form."""
+        e, b, p, r = C.c_int(), C.c_int(), C.c_longlong(), C.c_longlong()
+        _lib.check(self.ctx.L.ks_mat_get_dict_pairs_info(self.h, C.byref(e), C.byref(b), C.byref(p), C.byref(r)))
+        return {"eligible": bool(e.value), "nbases": b.value, "pair_launches": p.value, "row_launches": r.value}
 
     def norm_inf(self):
         v = C.c_double(); _lib.check(self.ctx.L.ks_mat_norm_inf(self.h, C.byref(v))); return v.value

@@ -204,6 +204,7 @@ extern "C" int ks_ctx_set_debug(ks_ctx ctx, int key, long long value)
     case KS_DEBUG_ONESHOT_SEQ0: ctx->dbg.oneshot_seq0 = (unsigned)value; break;
     case KS_DEBUG_NO_DICT_PATTERNS: ctx->dbg.no_dict_patterns = value != 0; break;
     case KS_DEBUG_NO_RESTART_FUSION: ctx->dbg.no_restart_fusion = value != 0; break;
+    case KS_DEBUG_NO_DICT_PAIRS: ctx->dbg.no_dict_pairs = value != 0; break;
     default: KS_FAIL(KS_ERR_ARG_OUTOFRANGE, "unknown debug key %d", key);
   }
   return KS_SUCCESS;

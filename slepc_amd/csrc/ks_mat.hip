@@ -589,6 +589,22 @@ int build_sliced(ks_mat A)
 // The row-pattern form of the dictionary layout (see k_spmv_dict): the distinct rows of codes are found the way build_dict finds its dictionaries -
 // match every row against the sorted table, extend the table by the rows that missed, repeat; every round with a miss adds at least one word, so the
 // loop ends with every row matched or with more than 256 words, and then the matrix keeps its codes as they are.
+// The pair form of the row-pattern form (ks_dict_pairs.h): whether the matrix qualifies is decided here, once, from the host copies of the dictionaries
+// and the pattern table (pats: dict_npat words of dict_w codes); a matrix that does not keeps the one-row walk alone.
+static int build_dict_pairs(ks_mat A, const unsigned short *pats)
+{
+  std::vector<double> dv(256); std::vector<int> dof(256);
+  KS_HIP(hipMemcpy(dv.data(), A->dc_val, sizeof(double) * 256, hipMemcpyDeviceToHost));
+  KS_HIP(hipMemcpy(dof.data(), A->dc_off, sizeof(int) * 256, hipMemcpyDeviceToHost));
+  const ksp::PairPlan P = ksp::dict_pair_plan(A->dict_w, A->dict_npat, pats, dof.data(), A->dict_noff, dv.data(), A->dict_nval);
+  if (!P.ok) return KS_SUCCESS;
+  KS_HIP(hipMalloc(&A->pr_coef, sizeof(double) * P.coef.size())); KS_HIP(hipMalloc(&A->pr_mask, sizeof(unsigned) * P.mask.size()));
+  KS_HIP(hipMemcpy(A->pr_coef, P.coef.data(), sizeof(double) * P.coef.size(), hipMemcpyHostToDevice));
+  KS_HIP(hipMemcpy(A->pr_mask, P.mask.data(), sizeof(unsigned) * P.mask.size(), hipMemcpyHostToDevice));
+  A->pr_args = P.args; A->pr_ok = true;
+  return KS_SUCCESS;
+}
+
 int build_dict_patterns(ks_mat A)
 {
   ks_ctx ctx = A->ctx;
@@ -625,7 +641,9 @@ int build_dict_patterns(ks_mat A)
   A->dc_rowpat = rowpat; rowpat = nullptr; A->dc_pats = (unsigned short *)d_pats; d_pats = nullptr; A->dict_npat = (int)table.size();
   hipFree(A->dc_codes); A->dc_codes = nullptr;
   cleanup();
-  return KS_SUCCESS;
+  flat.clear();
+  for (const Word &w : table) flat.insert(flat.end(), w.begin(), w.end());
+  return build_dict_pairs(A, (const unsigned short *)flat.data());
 }
 
 // Try the dictionary layout (see k_spmv_dict); offsets_only: the offset-dictionary form at once. Needs the CSR arrays of the diagonal block on the device.
@@ -950,7 +968,7 @@ extern "C" int ks_mat_destroy(ks_mat A)
     delete A->sht; A->sht = nullptr;
   }
   hipFree(A->s_ptr); hipFree(A->s_len); hipFree(A->s_col); hipFree(A->s_val);
-  hipFree(A->dc_codes); hipFree(A->dc_rowpat); hipFree(A->dc_pats); hipFree(A->dc_val); hipFree(A->dc_off); hipFree(A->dc_codes8); hipFree(A->dc_vals);
+  hipFree(A->dc_codes); hipFree(A->dc_rowpat); hipFree(A->dc_pats); hipFree(A->dc_val); hipFree(A->dc_off); hipFree(A->dc_codes8); hipFree(A->dc_vals); hipFree(A->pr_coef); hipFree(A->pr_mask);
   hipFree(A->sl_rowptr); hipFree(A->sl_col); hipFree(A->sl_val); hipFree(A->sl_base); hipFree(A->ypart); hipFree(A->diag_cache); hipFree(A->mm_xi);
   hipFree(A->bn_col16); hipFree(A->bn_row16); hipFree(A->bn_val); hipFree(A->bn_g); hipFree(A->bn_off1); hipFree(A->bn_off2t); hipFree(A->bn_wseg); hipFree(A->bn_sbase); hipFree(A->bn_off2); hipFree(A->bn_log2);
   hipFree(A->wn_codes); hipFree(A->wn_dcol); hipFree(A->wn_segptr); hipFree(A->wn_seg); hipFree(A->wn_dbase);
@@ -981,6 +999,14 @@ extern "C" int ks_mat_get_dict_info(ks_mat A, int *patterns, int *npatterns, int
   *w = A->dict_w;
   if (A->dc_rowpat) { *patterns = 1; *npatterns = A->dict_npat; *index_bytes = ((long long)A->n + 255) / 256 * 256; }
   else *index_bytes = 2LL * A->dict_w * A->n;
+  return KS_SUCCESS;
+}
+extern "C" int ks_mat_get_dict_pairs_info(ks_mat A, int *eligible, int *nbases, long long *pair_launches, long long *row_launches)
+{
+  KS_CHECK(A && eligible && nbases && pair_launches && row_launches, KS_ERR_ARG_NULL, "NULL argument");
+  *eligible = *nbases = 0; *pair_launches = *row_launches = 0;
+  if (A->shell_mult || A->layout != KS_MAT_LAYOUT_DICT) return KS_SUCCESS;
+  *eligible = A->pr_ok ? 1 : 0; *nbases = A->pr_args.nb; *pair_launches = A->pr_launches; *row_launches = A->dc_row_launches;
   return KS_SUCCESS;
 }
 extern "C" int ks_mat_get_window_info(ks_mat A, int *block_rows, int *max_segments, long long *blocks, long long *direct_blocks, long long *window_entries, long long *index_bytes)

@@ -161,12 +161,47 @@ __device__ __forceinline__ double dict_word_row(const uint4 (&c)[W / 8], long lo
   return acc;
 }
 
+// ---- the pair form of the row-pattern form (ks_dict_pairs.h: the walk itself, ksp::dict_pair_walk, and its plan) ------------------------------------
+// how a lane of the walk reaches x and its neighbours on the device. Loads go through a buffer descriptor of exactly [x, x + n): an element outside it
+// is 0.0 by the hardware's range check (per dword: the pair at n - 1 of an odd n has its first half), no memory access is made for it and no branch stands
+// between two loads. An index outside [0, n) is sent to PAIR_OOB_OFFSET, which lies past the end of every descriptor the launch admits (pair_fits32: 8 n <=
+// PAIR_OOB_OFFSET), so nothing rests on the 32-bit offset wrapping. The shift is ds_bpermute through __shfl_up / __shfl_down: the wave's first and last lane get their own
+// value back and do not use it.
+constexpr unsigned PAIR_OOB_OFFSET = 0xfffffff0u;
+struct PairLane {
+  __amdgpu_buffer_rsrc_t rs; long long n;
+  __device__ __forceinline__ PairLane(const double *x, long long n_) : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(x), 0, (int)(unsigned)(n_ * 8), 0x00020000)), n(n_) {}
+  __device__ __forceinline__ unsigned off(long long i, bool want = true) const { return want && (unsigned long long)i < (unsigned long long)n ? (unsigned)(i * 8) : PAIR_OOB_OFFSET; }
+  __device__ __forceinline__ int lane() const { return threadIdx.x & 63; }
+  __device__ __forceinline__ ksp::D2 pair(long long i) const { ksp::D2 v; const auto t = __builtin_amdgcn_raw_buffer_load_b128(rs, off(i), 0, 0); __builtin_memcpy(&v, &t, 16); return v; }
+  __device__ __forceinline__ double one(long long i, bool want) const { double v; const auto t = __builtin_amdgcn_raw_buffer_load_b64(rs, off(i, want), 0, 0); __builtin_memcpy(&v, &t, 8); return v; }
+  __device__ __forceinline__ double up(double v, long long) const { return __shfl_up(v, 1); }
+  __device__ __forceinline__ double down(double v, long long) const { return __shfl_down(v, 1); }
+};
+// the plan's tables into dynamic LDS (in place of the pattern table, which the pair walk does not read): coefficients, then masks
+#define KS_PAIR_LDS_FILL(BLOCK, pa, coef, mask, npat, sc, sm)                                                                      \
+  double *sc = reinterpret_cast<double *>(dict_pat_lds);                                                                           \
+  unsigned *sm = reinterpret_cast<unsigned *>(sc + (npat) * 3 * (pa).nb);                                                          \
+  do {                                                                                                                             \
+    for (int i = threadIdx.x; i < (npat) * 3 * (pa).nb; i += (BLOCK)) sc[i] = coef[i];                                             \
+    for (int i = threadIdx.x; i < (npat); i += (BLOCK)) sm[i] = mask[i];                                                           \
+    __syncthreads();                                                                                                               \
+  } while (0)
+// the two pattern indices of rows r, r + 1 (r even) in one 2-byte load. rowpat is padded to a multiple of 256 rows, so r < n has both bytes; a lane
+// past the last row reads the first pair instead (any valid pattern: its results are dropped) - no branch in front of the loads of x
+__device__ __forceinline__ void pair_patterns(const unsigned char *__restrict__ rowpat, long long r, long long n, int &p0, int &p1)
+{
+  const unsigned pp = *reinterpret_cast<const unsigned short *>(rowpat + (r < n ? r : 0));
+  p0 = (int)(pp & 255u); p1 = (int)(pp >> 8);
+}
 // ---- host side: the grid of each walk, the LDS of the pattern table, the bytes a layout must move ----------------------------------------------------
 struct LaunchGrid { unsigned blocks; int remap; };
-static inline LaunchGrid dict_launch_grid(ks_mat A)               // dictionary forms: up to 64 workgroups per CU
+static inline LaunchGrid dict_launch_grid(ks_mat A, int rows_per_lane = 1)   // dictionary forms: up to 64 workgroups per CU (the pair form, rows_per_lane = 2: groups of 512 rows)
 {
-  const long long groups = ((long long)A->n + ROW_BLOCK - 1) / ROW_BLOCK;
-  long long nblk = std::max<long long>(1, std::min<long long>(groups, (long long)A->ctx->num_cu * 64));
+  const long long gr = (long long)ROW_BLOCK * rows_per_lane, groups = ((long long)A->n + gr - 1) / gr;
+  // the pair form: up to 32 per CU - its tables are 3 KB of LDS to fill per workgroup (216^3 Laplacian: 38.3 us with 64, 34.6 with 32, 41.6 with 16:
+  // profiles/r14_dict_pairs.txt)
+  long long nblk = std::max<long long>(1, std::min<long long>(groups, (long long)A->ctx->num_cu * (rows_per_lane == 2 ? 32 : 64)));
   const int remap = nblk >= 64 ? 1 : 0;                   // small matrices: nothing to pin
   if (remap) nblk = std::min<long long>((nblk + 7) / 8, (groups + 7) / 8) * 8;
   return {(unsigned)nblk, remap};
@@ -192,6 +227,9 @@ static inline LaunchGrid window_launch_grid(ks_mat A)              // windowed C
   const int remap = nb >= 64 ? 1 : 0;
   return {(unsigned)(remap ? (nb + 7) / 8 * 8 : nb), remap};
 }
+static inline size_t dict_pair_lds_bytes(ks_mat A) { return (size_t)A->dict_npat * (3 * A->pr_args.nb * sizeof(double) + sizeof(unsigned)); }   // the pair form's tables instead
+static inline bool pair_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+static inline bool pair_fits32(long long n) { return n * 8 <= (long long)PAIR_OOB_OFFSET; }        // the descriptor's 32-bit size, and PAIR_OOB_OFFSET stays outside it
 static inline size_t dict_pattern_lds_bytes(ks_mat A) { return A->layout == KS_MAT_LAYOUT_DICT && A->dc_rowpat ? (size_t)A->dict_npat * A->dict_w * 2 : 0; }   // dynamic LDS: the pattern table beside the dictionaries
 // compulsory bytes of the stored diagonal block per product (the matrix part of a KsProfScope byte model: callers add their x / y traffic)
 static inline double layout_own_bytes(ks_mat A)

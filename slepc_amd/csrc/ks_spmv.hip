@@ -411,12 +411,31 @@ __global__ __launch_bounds__(SPMV_BLOCK) void k_spmv_sell(int nrows, int nslices
 // dictionaries (rowpat != nullptr; codes is then null). A lane takes its row's word from LDS instead of from memory and decodes it as before: the
 // product reads n bytes of matrix instead of 2 W n.
 // One row per lane and at most 64 workgroups per CU also in the pattern form: two rows per lane with 16-byte stores of y measured the same within
-// 2 %, four rows per lane, 16 workgroups per CU and one 256-row group per workgroup slower (profiles/r06_dict_patterns.txt)
-template <int W>
+// 2 %, four rows per lane, 16 workgroups per CU and one 256-row group per workgroup slower (profiles/r06_dict_patterns.txt): the walk is bound by
+// its per-entry instructions (profiles/r14_dict_pairs.txt), which is what the pair form below cuts (52 -> 37 us on the 216^3 Laplacian)
+// Pair form (NBT > 0: the compiled number of bases; ks_dict_pairs.h): a lane owns rows r, r + 1 of a group of 512 and loads x 16 bytes at a time, the
+// same XCD-contiguous walk over the row groups. No lane leaves the loop early: a lane past the last row still lends its loads to the lane below it.
+template <int W, int NBT = 0>
 __global__ __launch_bounds__(SPMV_BLOCK) void k_spmv_dict(int nrows, const uint4 *__restrict__ codes, const unsigned char *__restrict__ rowpat, const uint4 *__restrict__ pats, int npat,
                                                           const double *__restrict__ dval, int nval, const int *__restrict__ doff, int noff,
-                                                          const double *__restrict__ x, double *__restrict__ y, int xcd_remap)
+                                                          const double *__restrict__ x, double *__restrict__ y, int xcd_remap,
+                                                          ksp::PairArgs pa = ksp::PairArgs(), const double *__restrict__ pcoef = nullptr, const unsigned *__restrict__ pmask = nullptr)
 {
+  if constexpr (NBT > 0) {
+    KS_PAIR_LDS_FILL(SPMV_BLOCK, pa, pcoef, pmask, npat, sc, sm);
+    const RowGroups rg = row_groups_xcd(nrows, 2 * SPMV_BLOCK, xcd_remap);
+    const PairLane ln(x, nrows);
+    for (long long g = rg.g0 + rg.lb; g < rg.g1; g += rg.nb) {
+      const long long r = g * (2 * SPMV_BLOCK) + 2 * (long long)threadIdx.x;
+      int p0, p1;
+      pair_patterns(rowpat, r, nrows, p0, p1);
+      double y0, y1;
+      ksp::dict_pair_walk<NBT>(pa, sc, sm, p0, p1, r, ln, y0, y1);
+      if (r + 1 < nrows) __builtin_nontemporal_store(ksk::ks_d2v{y0, y1}, reinterpret_cast<ksk::ks_d2v *>(y + r));
+      else if (r < nrows) __builtin_nontemporal_store(ksp::dict_row_from_tables<W>(rowpat, reinterpret_cast<const unsigned short *>(pats), r, dval, doff, x), y + r);
+    }
+    return;
+  }
   __shared__ double sv[256];
   __shared__ int so[256];
   KS_DICT_LDS_FILL(SPMV_BLOCK, W, sv, so, dval, nval, doff, noff, rowpat, pats, npat);
@@ -463,21 +482,32 @@ __device__ __forceinline__ double dict_row(const uint4 *__restrict__ codes, cons
   }
   return dict_word_row<W>(c, r, sv, so, x);
 }
-template <int KT, int W>
+// Pair form (NBT > 0, ks_dict_pairs.h): the sweep already holds two consecutive rows per lane, so an eligible matrix has them computed by the pair walk -
+// same tiles, grid and partials, and y with the one-row walk's bits, so the dots keep theirs. Every lane of a wave enters the walk, also past the last row.
+template <int KT, int W, int NBT = 0>
 __global__ __launch_bounds__(ksk::SW_BLOCK) void k_dot_spmv_dict(const double *__restrict__ Vb, long long ld, int n, int ncols, const uint4 *__restrict__ codes,
                                                                  const unsigned char *__restrict__ rowpat, const uint4 *__restrict__ pats, int npat,
                                                                  const double *__restrict__ dval, int nval, const int *__restrict__ doff, int noff,
                                                                  const double *__restrict__ x, double *__restrict__ y, double *__restrict__ partials,
-                                                                 const KsGsState *__restrict__ gate, int *__restrict__ pgrid, int rev)
+                                                                 const KsGsState *__restrict__ gate, int *__restrict__ pgrid, int rev,
+                                                                 ksp::PairArgs pa = ksp::PairArgs(), const double *__restrict__ pcoef = nullptr, const unsigned *__restrict__ pmask = nullptr)
 {
   using namespace ksk;
   if (gate && !gate->active) return;
   __shared__ double sv[256];
   __shared__ int so[256];
-  for (int i = threadIdx.x; i < nval; i += SW_BLOCK) sv[i] = dval[i];               // as KS_DICT_LDS_FILL (ks_rows.cuh), in place
-  for (int i = threadIdx.x; i < noff; i += SW_BLOCK) so[i] = doff[i];
-  if (rowpat) for (int i = threadIdx.x; i < npat * (W / 8); i += SW_BLOCK) dict_pat_lds[i] = pats[i];
+  double *sc = nullptr; unsigned *sm = nullptr;
+  if constexpr (NBT > 0) {
+    sc = reinterpret_cast<double *>(dict_pat_lds); sm = reinterpret_cast<unsigned *>(sc + npat * 3 * pa.nb);
+    for (int i = threadIdx.x; i < npat * 3 * pa.nb; i += SW_BLOCK) sc[i] = pcoef[i];      // as KS_PAIR_LDS_FILL (ks_rows.cuh)
+    for (int i = threadIdx.x; i < npat; i += SW_BLOCK) sm[i] = pmask[i];
+  } else {
+    for (int i = threadIdx.x; i < nval; i += SW_BLOCK) sv[i] = dval[i];               // as KS_DICT_LDS_FILL (ks_rows.cuh), in place
+    for (int i = threadIdx.x; i < noff; i += SW_BLOCK) so[i] = doff[i];
+    if (rowpat) for (int i = threadIdx.x; i < npat * (W / 8); i += SW_BLOCK) dict_pat_lds[i] = pats[i];
+  }
   __syncthreads();
+  const ksr::PairLane ln(x, n);
   if (pgrid && blockIdx.x == 0 && threadIdx.x == 0) *pgrid = gridDim.x;
   double acc[KT];
 #pragma unroll
@@ -487,12 +517,18 @@ __global__ __launch_bounds__(ksk::SW_BLOCK) void k_dot_spmv_dict(const double *_
   for (long long t0 = blockIdx.x; t0 < ntiles; t0 += gridDim.x) {
     const long long t = rev ? ntiles - 1 - t0 : t0;
     const long long r = t * tile + (long long)threadIdx.x * 2;
+    double2 yp = {0.0, 0.0};
+    if constexpr (NBT > 0) {
+      int p0, p1;
+      ksr::pair_patterns(rowpat, r, n, p0, p1);
+      ksp::dict_pair_walk<NBT>(pa, sc, sm, p0, p1, r, ln, yp.x, yp.y);
+    }
     if (r + 1 < n) {
       double2 xv[KT];
 #pragma unroll
       for (int i = 0; i < KT; i++) { const int ii = i < nprev ? i : (nprev > 0 ? nprev - 1 : 0); if (nprev > 0) xv[i] = ldplain2(Vb + (long long)ii * ld + r); else xv[i] = double2{0.0, 0.0}; }
-      double2 yv;
-      yv.x = dict_row<W>(codes, rowpat, r, sv, so, x); yv.y = dict_row<W>(codes, rowpat, r + 1, sv, so, x);
+      double2 yv = yp;
+      if constexpr (NBT == 0) { yv.x = dict_row<W>(codes, rowpat, r, sv, so, x); yv.y = dict_row<W>(codes, rowpat, r + 1, sv, so, x); }
       *reinterpret_cast<double2 *>(y + r) = yv;
 #pragma unroll
       for (int i = 0; i < KT; i++) {
@@ -500,7 +536,9 @@ __global__ __launch_bounds__(ksk::SW_BLOCK) void k_dot_spmv_dict(const double *_
         acc[i] = fma(c.x, yv.x, acc[i]); acc[i] = fma(c.y, yv.y, acc[i]);
       }
     } else if (r < n) {
-      const double yv = dict_row<W>(codes, rowpat, r, sv, so, x);
+      double yv;
+      if constexpr (NBT > 0) yv = ksp::dict_row_from_tables<W>(rowpat, reinterpret_cast<const unsigned short *>(pats), r, dval, doff, x);      // odd n: the last row on its own
+      else yv = dict_row<W>(codes, rowpat, r, sv, so, x);
       y[r] = yv;
 #pragma unroll
       for (int i = 0; i < KT; i++) {
@@ -775,8 +813,12 @@ int ks_mat_mult_dot_fused(ks_mat A, ks_bv bv, const double *x, int jy, bool gate
   const KsGsState *g = gate ? bv->gs : nullptr;
   KsProfScope ps(ctx, KS_K_SPMVDOT, 8.0 * bv->n * ncols + 12.0 * A->nnz + 4.0 * (A->n + 1) + 16.0 * A->n, ks_kt_for(ncols), 8.0 * bv->n * ncols + layout_own_bytes(A) + 8.0 * A->n);
   if (A->dict_w != 8 && A->dict_w != 16) return KS_SUCCESS;                              // W = 32 is not compiled for the sweep
-  const size_t lds = dict_pattern_lds_bytes(A);
-#define FD_W(W) hipLaunchKernelGGL((k_dot_spmv_dict<FD_KT, W>), dim3(grid), dim3(ksk::SW_BLOCK), lds, ctx->stream, Vb, (long long)bv->ld, bv->n, ncols, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, bv->partials, g, &bv->gs->pgrid, rev)
+  // the pair form as in MatMult (read at launch; y is 16-byte aligned here), for matrices of up to five bases: the 5- and 7-point stencils
+  const bool pairs = A->pr_ok && A->pr_args.nb <= 5 && !ctx->dbg.no_dict_pairs && pair_aligned16(x) && pair_fits32(A->n);
+  if (pairs) A->pr_launches++; else A->dc_row_launches++;
+  const size_t lds = pairs ? dict_pair_lds_bytes(A) : dict_pattern_lds_bytes(A);
+#define FD_W(W) do { if (pairs) hipLaunchKernelGGL((k_dot_spmv_dict<FD_KT, W, 5>), dim3(grid), dim3(ksk::SW_BLOCK), lds, ctx->stream, Vb, (long long)bv->ld, bv->n, ncols, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, bv->partials, g, &bv->gs->pgrid, rev, A->pr_args, A->pr_coef, A->pr_mask); \
+  else hipLaunchKernelGGL((k_dot_spmv_dict<FD_KT, W>), dim3(grid), dim3(ksk::SW_BLOCK), lds, ctx->stream, Vb, (long long)bv->ld, bv->n, ncols, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, bv->partials, g, &bv->gs->pgrid, rev); } while (0)
 #define LAUNCH_FD(KT) do { constexpr int FD_KT = KT; if (A->dict_w == 8) FD_W(8); else FD_W(16); } while (0)
   KS_KT_DISPATCH(ncols, LAUNCH_FD);
 #undef LAUNCH_FD
@@ -852,14 +894,23 @@ static int mult_assembled(ks_mat A, const double *x, double *y, const double *ro
     }
     case KS_MAT_LAYOUT_DICT:
     case KS_MAT_LAYOUT_ODICT: {
-      const LaunchGrid lg = dict_launch_grid(A);
-      const size_t lds = dict_pattern_lds_bytes(A);
+      // the pair form where the matrix has it (decided at assembly) and both vectors allow 16-byte accesses; read at launch, so a test can run both
+      const bool pairs = A->layout == KS_MAT_LAYOUT_DICT && A->pr_ok && !ctx->dbg.no_dict_pairs && pair_aligned16(x) && pair_aligned16(y) && pair_fits32(A->n);
+      if (A->layout == KS_MAT_LAYOUT_DICT) { if (pairs) A->pr_launches++; else A->dc_row_launches++; }
+      const LaunchGrid lg = dict_launch_grid(A, pairs ? 2 : 1);
+      const size_t lds = pairs ? dict_pair_lds_bytes(A) : dict_pattern_lds_bytes(A);
+#define SPMV_PAIRS_NB(W, NBT) hipLaunchKernelGGL((k_spmv_dict<W, NBT>), dim3(lg.blocks), dim3(SPMV_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, \
+                                        A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, lg.remap, A->pr_args, A->pr_coef, A->pr_mask)
+#define SPMV_PAIRS(W) do { if (A->pr_args.nb <= 5) SPMV_PAIRS_NB(W, 5); else SPMV_PAIRS_NB(W, 9); } while (0)
+      if (pairs) { KS_DICT_W_SWITCH(A->dict_w, SPMV_PAIRS); break; }             // W is the real one: the last row of an odd n decodes its code word with it
 #define SPMV_DICT(W) hipLaunchKernelGGL((k_spmv_dict<W>), dim3(lg.blocks), dim3(SPMV_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, \
                                         A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, lg.remap)
 #define SPMV_ODICT(W) hipLaunchKernelGGL((k_spmv_odict<W>), dim3(lg.blocks), dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->dc_codes8, A->dc_vals, A->dc_off, A->dict_noff, x, y, lg.remap)
       if (A->layout == KS_MAT_LAYOUT_DICT) KS_DICT_W_SWITCH(A->dict_w, SPMV_DICT); else KS_DICT_W_SWITCH(A->dict_w, SPMV_ODICT);
 #undef SPMV_DICT
 #undef SPMV_ODICT
+#undef SPMV_PAIRS
+#undef SPMV_PAIRS_NB
       break;
     }
     case KS_MAT_LAYOUT_SELL: {

@@ -8,6 +8,7 @@
 #include <vector>
 #include <string>
 #include "../../include/ksgpu.h"
+#include "ks_dict_pairs.h"
 
 // ---- error plumbing ---------------------------------------------------------------------------
 void ks_set_error(const char *fmt, ...);
@@ -70,7 +71,7 @@ struct ks_ctx_s {
   hipStream_t halo_stream = nullptr; hipEvent_t ev_x = nullptr, ev_halo = nullptr;
   bool halo_overlap = true;
   // test hooks (ks_ctx_set_debug; each makes a test run the path the fast one replaces, or a multi-rank path on one rank)
-  struct { bool no_fused_gs = false, no_mfma = false, no_spmv_dot = false, force_multi = false, no_dict_patterns = false, no_restart_fusion = false; unsigned oneshot_seq0 = 0; } dbg;
+  struct { bool no_fused_gs = false, no_mfma = false, no_spmv_dot = false, force_multi = false, no_dict_patterns = false, no_restart_fusion = false, no_dict_pairs = false; unsigned oneshot_seq0 = 0; } dbg;
   long long nsync = 0;              // host synchronisations of the context's stream made by the library (ks_ctx_sync_count)
   int num_cu = 256;
   char arch[64] = {0};
@@ -174,6 +175,10 @@ struct ks_mat_s {
   // row-pattern form of the same layout (at most 256 distinct rows): one byte per row, the index of its code word (dict_w 2-byte codes) in dc_pats;
   // dc_codes is then null. dc_rowpat is padded with zeros to a multiple of 256 rows.
   unsigned char *dc_rowpat = nullptr; unsigned short *dc_pats = nullptr; int dict_npat = 0;
+  // pair form of the row-pattern form (ks_dict_pairs.h; decided once at assembly, build_dict_pairs): the bases, and per pattern the coefficient of every
+  // candidate (base, d) and the bit mask of the candidates it has. The matrix bytes that stream are the same; which kernel runs is decided at launch
+  // (16-byte aligned x and y, KS_DEBUG_NO_DICT_PAIRS) and counted in pr_launches / dc_row_launches (ks_mat_get_dict_pairs_info)
+  bool pr_ok = false; ksp::PairArgs pr_args; double *pr_coef = nullptr; unsigned *pr_mask = nullptr; long long pr_launches = 0, dc_row_launches = 0;
   // offset-dictionary ELL: any values, few distinct column offsets: 1 byte per entry for the index, values in SELL order
   unsigned char *dc_codes8 = nullptr; double *dc_vals = nullptr;
   // XCD-sliced copy of the diagonal block for wide-scatter matrices (columns spread over a vector much larger than one
