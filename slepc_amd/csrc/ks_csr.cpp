@@ -35,15 +35,35 @@ inline int merge_row(const int *ca, const double *va, int la, const int *cb, con
   }
   return k;
 }
+
+// helper threads: the CPUs this process may run on (affinity mask: what a cgroup / taskset leaves), at most 16
+unsigned helper_threads()
+{
+  unsigned ncpu = std::thread::hardware_concurrency();
+  { cpu_set_t cs; CPU_ZERO(&cs); if (sched_getaffinity(0, sizeof(cs), &cs) == 0 && CPU_COUNT(&cs) > 0) ncpu = (unsigned)CPU_COUNT(&cs); }
+  return std::max(1u, std::min(16u, ncpu));
+}
+// fn(i) for every i in [0, count) on nthr threads, the calling one included: thread t takes i = t, t + nthr, ... A thread that cannot be started
+// (pids limit) is simply not used - the calling thread takes every stride that has no thread of its own
+template <class F> void parallel_strides(unsigned nthr, int count, const F &fn)
+{
+  std::vector<std::thread> th;
+  unsigned started = 1;                                   // stride 0 belongs to the calling thread
+  for (unsigned t = 1; t < nthr; t++) {
+    try { th.emplace_back([&fn, t, nthr, count] { for (int i = (int)t; i < count; i += (int)nthr) fn(i); }); started = t + 1; }
+    catch (const std::system_error &) { break; }
+  }
+  for (int i = 0; i < count; i += (int)nthr) fn(i);
+  for (unsigned t = started; t < nthr; t++) for (int i = (int)t; i < count; i += (int)nthr) fn(i);      // strides whose thread did not start
+  for (auto &x : th) x.join();
+}
 } // namespace
 
 bool csr_axpy(int n, int row_start, const int *rpa, const int *ca, const double *va, double alpha, const int *rpb, const int *cb, const double *vb,
               std::vector<int> &rp, std::vector<int> &col, std::vector<double> &val)
 {
   rp.assign((size_t)n + 1, 0);
-  unsigned ncpu = std::thread::hardware_concurrency();
-  { cpu_set_t cs; CPU_ZERO(&cs); if (sched_getaffinity(0, sizeof(cs), &cs) == 0 && CPU_COUNT(&cs) > 0) ncpu = (unsigned)CPU_COUNT(&cs); }
-  const unsigned nthr = (n < 100000) ? 1u : std::max(1u, std::min(16u, ncpu));
+  const unsigned nthr = (n < 100000) ? 1u : helper_threads();
   const double one = 1.0;
   auto rows = [&](bool fill, int r0, int r1) {
     for (int r = r0; r < r1; r++) {
@@ -53,18 +73,8 @@ bool csr_axpy(int n, int row_start, const int *rpa, const int *ca, const double 
       else merge_row(ca + rpa[r], va + rpa[r], rpa[r + 1] - rpa[r], bc, bv, lb, alpha, col.data() + rp[r], val.data() + rp[r]);
     }
   };
-  auto parallel = [&](bool fill) {
-    std::vector<std::thread> th;
-    const int chunk = (n + (int)nthr - 1) / (int)nthr;
-    unsigned started = 1;
-    for (unsigned t = 1; t < nthr; t++) {
-      try { th.emplace_back([&, t] { rows(fill, std::min(n, (int)t * chunk), std::min(n, (int)(t + 1) * chunk)); }); started = t + 1; }
-      catch (const std::system_error &) { break; }
-    }
-    rows(fill, 0, std::min(n, chunk));
-    for (unsigned t = started; t < nthr; t++) rows(fill, std::min(n, (int)t * chunk), std::min(n, (int)(t + 1) * chunk));     // chunks whose thread did not start
-    for (auto &x : th) x.join();
-  };
+  const int chunk = (n + (int)nthr - 1) / (int)nthr;         // a chunk of rows per thread
+  auto parallel = [&](bool fill) { parallel_strides(nthr, (int)nthr, [&](int t) { rows(fill, std::min(n, t * chunk), std::min(n, (t + 1) * chunk)); }); };
   parallel(false);
   long long total = 0;
   for (int r = 0; r < n; r++) total += rp[r + 1];
@@ -119,6 +129,163 @@ void sharded_transpose_add_host(const ShardedTransposePlan &p, const double *rre
 {
   for (size_t i = 0; i < p.acc_rows.size(); i++) { double s = y[p.acc_rows[i]]; for (int q = p.acc_ptr[i]; q < p.acc_ptr[i + 1]; q++) s = s + rrecv[p.acc_pos[q]]; y[p.acc_rows[i]] = s; }
 }
+void csr_split_block(int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val, BlockSplit &out)
+{
+  out = BlockSplit();
+  const long long nnz = rowptr[n_local];
+  std::vector<int> &cd = out.col_d, &co = out.col_o; std::vector<double> &vd = out.val_d, &vo = out.val_o;
+  out.rp_d.assign((size_t)n_local + 1, 0); out.rp_o.assign((size_t)n_local + 1, 0);
+  if (nnz > 0) { cd.reserve((size_t)nnz); vd.reserve((size_t)nnz); }
+  for (int r = 0; r < n_local; r++) {
+    if (rowptr[r + 1] < rowptr[r]) { out.status = SPLIT_ROWPTR; out.bad_row = r; return; }
+    for (int p = rowptr[r]; p < rowptr[r + 1]; p++) {
+      const int c = col[p];
+      if (c < 0 || c >= n_global) { out.status = SPLIT_COLUMN; out.bad_row = r; out.bad_col = c; return; }
+      if (c >= row_start && c < row_start + n_local) { cd.push_back(c - row_start); vd.push_back(val[p]); }
+      else { co.push_back(c); vo.push_back(val[p]); }
+    }
+    out.rp_d[r + 1] = (int)cd.size(); out.rp_o[r + 1] = (int)co.size();
+  }
+  out.garray = co;
+  std::sort(out.garray.begin(), out.garray.end()); out.garray.erase(std::unique(out.garray.begin(), out.garray.end()), out.garray.end());
+  for (auto &c : co) c = (int)(std::lower_bound(out.garray.begin(), out.garray.end(), c) - out.garray.begin());
+}
+int halo_recv_counts(const std::vector<int> &garray, const std::vector<int> &starts, int rank, std::vector<int> &recv_cnt)
+{
+  const int size = (int)starts.size() - 1;
+  recv_cnt.assign((size_t)size, 0);
+  for (int p = 0; p < size; p++) if (starts[p] > starts[p + 1]) return HALO_UNORDERED;
+  int p = 0;
+  for (int g : garray) { while (p + 1 < size && g >= starts[p + 1]) p++; if (p == rank) return HALO_SELF; recv_cnt[p]++; }
+  return 0;
+}
+void halo_peers(int rank, int size, const int *recv_cnt, const int *all_cnt, HaloPeers &out)
+{
+  out = HaloPeers();
+  int roff = 0, soff = 0;
+  for (int p = 0; p < size; p++) {
+    const int send = (p == rank) ? 0 : all_cnt[(size_t)p * size + rank];      // what p receives from this rank
+    if (p == rank || (recv_cnt[p] == 0 && send == 0)) continue;
+    out.peers.push_back(p); out.recv_cnt.push_back(recv_cnt[p]); out.send_cnt.push_back(send); out.recv_off.push_back(roff); out.send_off.push_back(soff);
+    roff += recv_cnt[p]; soff += send;
+  }
+  out.nsend = soff;
+}
+int halo_localize_send_idx(int row_start, int n, int nsend, int *sidx)
+{
+  for (int i = 0; i < nsend; i++) { sidx[i] -= row_start; if (sidx[i] < 0 || sidx[i] >= n) return HALO_NOT_OWNED; }
+  return 0;
+}
+
+void binned_geometry(int n, long long nnz, int ncu, int cs_max, int seg_pad, BinnedGeometry &out)
+{
+  out = BinnedGeometry();
+  ncu = std::max(ncu, 1);
+  const long long per_round = (long long)ncu * cs_max;
+  out.ns = (int)(ncu * std::max(1LL, (n + per_round - 1) / per_round));
+  out.cs = (n + out.ns - 1) / out.ns;
+  out.wb = 4 * out.ns; out.wr = (n + out.wb - 1) / out.wb;
+  if (out.cs > 65535 || out.wr + 1 > 65535) out.status = BINNED_16BIT;
+  else if (nnz + (long long)out.ns * out.wb * (seg_pad - 1) >= 2147483647LL) out.status = BINNED_32BIT;      // bin-major positions are 32-bit
+}
+void binned_plan(int n, const int *rp, const int *col, const double *val, const BinnedGeometry &g, int seg_pad, BinnedPlan &out)
+{
+  out = BinnedPlan();
+  const int ns = g.ns, cs = g.cs, wb = g.wb, wr = g.wr;
+  const unsigned nthr = helper_threads();                 // the counting sort per wave-bin is cache friendly and runs on a few threads
+  // segment lengths (padded to seg_pad entries), bin-major [wb][ns]
+  std::vector<int> len((size_t)wb * ns, 0);
+  parallel_strides(nthr, wb, [&](int b) {
+    int *L = len.data() + (size_t)b * ns;
+    const int r0 = std::min((long long)b * wr, (long long)n), r1 = std::min((long long)(b + 1) * wr, (long long)n);
+    for (int p = rp[r0]; p < rp[r1]; p++) L[col[p] / cs]++;
+    for (int s = 0; s < ns; s++) L[s] = (L[s] + seg_pad - 1) / seg_pad * seg_pad;
+  });
+  // Bin-major order, GROUPED: `grp` consecutive wave-bins are interleaved slice by slice - [group][slice][wave-bin of the group]
+  // - so that the segments a slice's workgroup writes in phase 1 for `grp` consecutive wave-bins are one contiguous run (80 KB instead of 64
+  // pieces of 1.26 KB, each 0.6 MB from the next; the gather is store-bound: 436 -> 316-331 us in the stand-alone benchmark with uniform
+  // segments, profiles/r03_micro_binned_group.txt).
+  // A wave-bin's own entries are then no longer one stream but ns pieces: phase 2 walks them through a LOGICAL position (piece after piece)
+  // that a per-wave-bin table log2[wb][ns + 1] maps to the physical one (off2), window by window, the way phase 1 finds its destinations.
+  std::vector<int> &off2 = out.off2, &log2 = out.log2, &off1 = out.off1, &off2t = out.off2t, &wseg = out.wseg;
+  std::vector<long long> &sbase = out.sbase;
+  off2.resize((size_t)wb * ns);                           // physical start of segment (wb, s)
+  log2.resize((size_t)wb * (ns + 1));                     // logical start of segment (wb, s) inside wave-bin wb; [ns]: the wave-bin's entry count
+  long long run = 0;
+  // wave-bins whose segments are adjacent per slice. Measured on config 5's matrix, one box (profiles/r03_ab_binned_groups.txt), phase 1 +
+  // phase 2: 1 (the old order): 445 + 488 us; 4: 404 + 507; 16: 390 + 511; 64: 386 + 500; 256: 388 + 511 - the gather gains what its
+  // stores gain from longer runs, the reduce pays a little for reading its pieces further apart.
+  int grp = 64; while (grp > 1 && wb % grp) grp /= 2;
+  for (int gi = 0; gi < wb / grp; gi++)
+    for (int s = 0; s < ns; s++)
+      for (int wl = 0; wl < grp; wl++) { const int b = grp * gi + wl; off2[(size_t)b * ns + s] = (int)run; run += len[(size_t)b * ns + s]; }
+  const long long entries = out.entries = run;
+  for (int b = 0; b < wb; b++) {
+    int lrun = 0;
+    for (int s = 0; s < ns; s++) { log2[(size_t)b * (ns + 1) + s] = lrun; lrun += len[(size_t)b * ns + s]; }
+    log2[(size_t)b * (ns + 1) + ns] = lrun;
+  }
+  off1.resize((size_t)ns * (wb + 1)); off2t.resize((size_t)ns * wb); sbase.resize((size_t)ns + 1);
+  long long srun = 0; int nwin = 1;
+  for (int s = 0; s < ns; s++) {
+    sbase[s] = srun;
+    int lrun = 0;
+    for (int b = 0; b < wb; b++) { off1[(size_t)s * (wb + 1) + b] = lrun; off2t[(size_t)s * wb + b] = off2[(size_t)b * ns + s]; lrun += len[(size_t)b * ns + s]; }
+    off1[(size_t)s * (wb + 1) + wb] = lrun;
+    srun += lrun;
+    nwin = std::max(nwin, (lrun + 1023) / 1024);
+  }
+  sbase[ns] = srun; out.nwin = nwin;
+  if (srun != entries) { out.status = BINNED_ORDERS; return; }
+  wseg.assign((size_t)ns * nwin, 0);
+  for (int s = 0; s < ns; s++) {
+    const int *o1 = off1.data() + (size_t)s * (wb + 1);
+    int sg = 0;
+    for (int wdw = 0; wdw < nwin; wdw++) {
+      const int base = wdw * 1024;
+      while (sg < wb - 1 && o1[sg + 1] <= base) sg++;
+      wseg[(size_t)s * nwin + wdw] = sg;
+    }
+  }
+  std::vector<double> &val2 = out.val2; std::vector<unsigned short> &row16 = out.row16, &col16 = out.col16;
+  val2.assign((size_t)entries, 0.0);
+  row16.assign((size_t)entries, (unsigned short)wr); col16.assign((size_t)entries, 0);      // padding: value 0 into the spare accumulator, column 0 of its slice
+  parallel_strides(nthr, wb, [&](int b) {
+    std::vector<int> cur(ns, 0);
+    const int r0 = std::min((long long)b * wr, (long long)n), r1 = std::min((long long)(b + 1) * wr, (long long)n);
+    for (int r = r0; r < r1; r++)
+      for (int p = rp[r]; p < rp[r + 1]; p++) {
+        const int s = col[p] / cs, i = cur[s]++;
+        const long long p2 = (long long)off2[(size_t)b * ns + s] + i;
+        val2[p2] = val[p]; row16[p2] = (unsigned short)(r - r0);
+        col16[sbase[s] + off1[(size_t)s * (wb + 1) + b] + i] = (unsigned short)(col[p] - s * cs);
+      }
+  });
+}
+void binned_apply_host(const BinnedPlan &p, const BinnedGeometry &g, int n, const double *x, double *y)
+{
+  const int ns = g.ns, cs = g.cs, wb = g.wb, wr = g.wr;
+  std::vector<double> G((size_t)p.entries, 0.0), xs((size_t)cs), acc((size_t)wr + 1);
+  for (int s = 0; s < ns; s++) {                          // k_binned_gather: a workgroup per slice
+    const long long c0 = (long long)s * cs;
+    for (int i = 0; i < cs; i++) xs[i] = (c0 + i < n) ? x[c0 + i] : 0.0;
+    const int *o1 = p.off1.data() + (size_t)s * (wb + 1), *o2 = p.off2t.data() + (size_t)s * wb;
+    const unsigned short *cg = p.col16.data() + p.sbase[s];
+    const int total = o1[wb];
+    for (int win = 0; win * 1024 < total; win++) {
+      int sg = p.wseg[(size_t)s * p.nwin + win];          // the segment of the window's first entry; the others are found from there
+      for (int e = win * 1024; e < std::min(total, (win + 1) * 1024); e++) { while (e >= o1[sg + 1]) sg++; G[(size_t)((long long)e + (o2[sg] - o1[sg]))] = xs[cg[e]]; }
+    }
+  }
+  for (int b = 0; b < wb; b++) {                          // k_binned_reduce: a wave per wave-bin
+    std::fill(acc.begin(), acc.end(), 0.0);
+    const int *lg = p.log2.data() + (size_t)b * (ns + 1), *ph = p.off2.data() + (size_t)b * ns;
+    for (int s = 0; s < ns; s++)
+      for (long long q = ph[s]; q < (long long)ph[s] + (lg[s + 1] - lg[s]); q++) acc[p.row16[(size_t)q]] += p.val2[(size_t)q] * G[(size_t)q];
+    for (int i = 0; i < wr; i++) { const long long row = (long long)b * wr + i; if (row < n) y[row] = acc[i]; }
+  }
+}
+
 void csr_window_plan(int n, const int *rp, const int *col, int block_rows, int max_segments, int pad, WindowPlan &out)
 {
   out = WindowPlan();
@@ -339,6 +506,70 @@ long long ksc_csr_axpy(int n, int row_start, const int *rpa, const int *ca, cons
   std::copy(r.begin(), r.end(), rp);
   if (col && val && (long long)c.size() <= cap) { std::copy(c.begin(), c.end(), col); std::copy(v.begin(), v.end(), val); }
   return (long long)c.size();
+}
+// test hook: the diagonal / ghost split of a row block. Room for: rp_d, rp_o n_local + 1; col_d, val_d, col_o, val_o, garray rowptr[n_local] each (none of
+// them is written on a rejection). info: status, bad_row, bad_col, entries of the diagonal block, of the ghost block, ghosts. Returns the status.
+int ksc_split_block(int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val,
+                    int *rp_d, int *col_d, double *val_d, int *rp_o, int *col_o, double *val_o, int *garray, long long *info)
+{
+  ksc::BlockSplit s;
+  ksc::csr_split_block(n_local, row_start, n_global, rowptr, col, val, s);
+  info[0] = s.status; info[1] = s.bad_row; info[2] = s.bad_col; info[3] = info[4] = info[5] = 0;
+  if (s.status) return s.status;
+  info[3] = (long long)s.col_d.size(); info[4] = (long long)s.col_o.size(); info[5] = (long long)s.garray.size();
+  std::copy(s.rp_d.begin(), s.rp_d.end(), rp_d); std::copy(s.col_d.begin(), s.col_d.end(), col_d); std::copy(s.val_d.begin(), s.val_d.end(), val_d);
+  std::copy(s.rp_o.begin(), s.rp_o.end(), rp_o); std::copy(s.col_o.begin(), s.col_o.end(), col_o); std::copy(s.val_o.begin(), s.val_o.end(), val_o);
+  std::copy(s.garray.begin(), s.garray.end(), garray);
+  return 0;
+}
+// test hooks: the three host steps of the halo plan. starts: size + 1; recv_cnt: size; all_cnt: size x size, row p = rank p's recv_cnt; the five per-peer
+// lists have room for size entries. ksc_halo_peers returns the number of peers; the other two a HALO_* status.
+int ksc_halo_recv_counts(int nghost, const int *garray, int size, const int *starts, int rank, int *recv_cnt)
+{
+  std::vector<int> cnt;
+  const int st = ksc::halo_recv_counts(std::vector<int>(garray, garray + nghost), std::vector<int>(starts, starts + size + 1), rank, cnt);
+  std::copy(cnt.begin(), cnt.end(), recv_cnt);
+  return st;
+}
+int ksc_halo_peers(int rank, int size, const int *recv_cnt, const int *all_cnt, int *peers, int *rcnt, int *scnt, int *roff, int *soff, int *nsend)
+{
+  ksc::HaloPeers h;
+  ksc::halo_peers(rank, size, recv_cnt, all_cnt, h);
+  std::copy(h.peers.begin(), h.peers.end(), peers); std::copy(h.recv_cnt.begin(), h.recv_cnt.end(), rcnt); std::copy(h.send_cnt.begin(), h.send_cnt.end(), scnt);
+  std::copy(h.recv_off.begin(), h.recv_off.end(), roff); std::copy(h.send_off.begin(), h.send_off.end(), soff);
+  *nsend = h.nsend;
+  return (int)h.peers.size();
+}
+int ksc_halo_localize_send_idx(int row_start, int n, int nsend, int *sidx) { return ksc::halo_localize_send_idx(row_start, n, nsend, sidx); }
+// test hook: the geometry of the binned layout alone (no arrays needed). geo: ns, cs, wb, wr. Returns the status.
+int ksc_binned_geometry(int n, long long nnz, int ncu, int cs_max, int seg_pad, int *geo)
+{
+  ksc::BinnedGeometry g;
+  ksc::binned_geometry(n, nnz, ncu, cs_max, seg_pad, g);
+  geo[0] = g.ns; geo[1] = g.cs; geo[2] = g.wb; geo[3] = g.wr;
+  return g.status;
+}
+// test hook: geometry and plan of the binned layout for ncu compute units, and its host walk. info: geometry status, ns, cs, wb, wr, plan status, nwin,
+// entries. Two calls: with col16 NULL only info is filled; then col16, row16, val2 have room for `entries`, off1 ns (wb + 1), off2t, off2 ns wb,
+// wseg ns nwin, sbase ns + 1, log2 wb (ns + 1). x, y (n each, may be NULL): y = the host walk of the plan. Returns 0, or the status that ended it.
+int ksc_binned_plan(int n, const int *rp, const int *col, const double *val, int ncu, int cs_max, int seg_pad, long long *info,
+                    unsigned short *col16, unsigned short *row16, double *val2, int *off1, int *off2t, int *wseg, long long *sbase, int *off2, int *log2,
+                    const double *x, double *y)
+{
+  ksc::BinnedGeometry g; ksc::BinnedPlan p;
+  ksc::binned_geometry(n, rp[n], ncu, cs_max, seg_pad, g);
+  info[0] = g.status; info[1] = g.ns; info[2] = g.cs; info[3] = g.wb; info[4] = g.wr; info[5] = info[6] = info[7] = 0;
+  if (g.status) return g.status;
+  ksc::binned_plan(n, rp, col, val, g, seg_pad, p);
+  info[5] = p.status; info[6] = p.nwin; info[7] = p.entries;
+  if (p.status) return p.status;
+  if (col16) {
+    std::copy(p.col16.begin(), p.col16.end(), col16); std::copy(p.row16.begin(), p.row16.end(), row16); std::copy(p.val2.begin(), p.val2.end(), val2);
+    std::copy(p.off1.begin(), p.off1.end(), off1); std::copy(p.off2t.begin(), p.off2t.end(), off2t); std::copy(p.wseg.begin(), p.wseg.end(), wseg);
+    std::copy(p.sbase.begin(), p.sbase.end(), sbase); std::copy(p.off2.begin(), p.off2.end(), off2); std::copy(p.log2.begin(), p.log2.end(), log2);
+  }
+  if (x && y) ksc::binned_apply_host(p, g, n, x, y);
+  return 0;
 }
 // test hook: the plan of the windowed layout. nseg, dbase: one per block; codes: one per entry; totals: blocks, direct blocks, window entries,
 // direct entries, segments listed, length of the direct column array without its padding. seg (the concatenated lists) may be NULL or has room

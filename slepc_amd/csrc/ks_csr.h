@@ -1,8 +1,64 @@
-// Host-side CSR helpers of the assembly path (no device code).
+// Host-side planning of the assembly path (no device code, no ks_mat): everything ks_mat.hip decides with index arithmetic on the host - the split of
+// a row block into its diagonal and ghost parts, the halo plan between the ranks, the binned, windowed and ILU(0) layouts, the plan of the transposed
+// product across ranks, MatAXPY on CSR arrays. Plain functions that fill structs of vectors; constants of the device side come in as parameters and a
+// refusal is a status in the result. ks_mat.hip calls a planner and uploads what it filled; KSD_TEST_HOOKS exports each of them as a ksc_* C function,
+// and those run on the CPU (tests/test_csr_host.py, test_assembly_host.py, test_sharded_transpose_host.py, test_ilu_host.py, tests/host/assembly_plans.cpp).
 #pragma once
 #include <vector>
 
 namespace ksc {
+// The split of ks_mat_create_csr: a rank's rows with global columns -> the diagonal block (columns the rank owns, as local indices) and the ghost block
+// (every other column, as its position in garray, the sorted list of the distinct ghost columns). Both keep the entries of a row in stored order.
+// Rows are checked in order, a row's pointer before its columns; the first offence ends the split.
+constexpr int SPLIT_ROWPTR = 1, SPLIT_COLUMN = 2;       // rowptr[bad_row + 1] < rowptr[bad_row]; bad_col of bad_row is outside [0, n_global)
+struct BlockSplit {
+  int status = 0, bad_row = -1, bad_col = 0;
+  std::vector<int> rp_d, col_d, rp_o, col_o, garray;
+  std::vector<double> val_d, val_o;
+};
+void csr_split_block(int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val, BlockSplit &out);
+
+// The halo plan of the forward product, in the three host steps between its collectives (build_halo_plan, ks_mat.hip). Rank p owns rows
+// starts[p] .. starts[p + 1] - 1 (starts has size + 1 entries; a rank may own none).
+//   halo_recv_counts  recv_cnt[p] = how many of the sorted ghosts rank p owns (a ghost goes to the LAST rank whose range starts at or below it,
+//                     i.e. past the ranks without rows). Every rank then learns every rank's counts: all_cnt, row p = rank p's recv_cnt.
+//   halo_peers        the ranks this one exchanges with (ascending; either count non-zero), what it receives from and sends to each, and the
+//                     offsets of those segments in the ghost array and the send buffer. Every rank then sends its ghost segments (global ids) to
+//                     their owners and receives the ids it has to serve, laid out by send_off / send_cnt.
+//   halo_localize_send_idx  those ids as local rows, in place.
+constexpr int HALO_UNORDERED = 1, HALO_SELF = 2, HALO_NOT_OWNED = 3;      // starts not ascending; a ghost inside the rank's own range; a served id outside it
+int halo_recv_counts(const std::vector<int> &garray, const std::vector<int> &starts, int rank, std::vector<int> &recv_cnt);
+struct HaloPeers { std::vector<int> peers, recv_cnt, send_cnt, recv_off, send_off; int nsend = 0; };
+void halo_peers(int rank, int size, const int *recv_cnt, const int *all_cnt, HaloPeers &out);
+int halo_localize_send_idx(int row_start, int n, int nsend, int *sidx);
+
+// The binned layout (KS_MAT_LAYOUT_BINNED; the kernels that walk it: k_binned_gather, k_binned_reduce, ks_spmv.hip).
+// Geometry: ns slices of cs columns - a multiple of the CU count (a workgroup per slice, one resident per CU), each at most cs_max columns - and
+// wb = 4 ns wave-bins of wr rows. status: BINNED_16BIT when a column inside its slice or a row inside its wave-bin (wr is the spare accumulator's
+// index) does not fit 16 bits, BINNED_32BIT when the padded entries may not fit 32-bit positions.
+constexpr int BINNED_16BIT = 1, BINNED_32BIT = 2, BINNED_ORDERS = 3;
+struct BinnedGeometry { int status = 0, ns = 0, cs = 0, wb = 0, wr = 0; };
+void binned_geometry(int n, long long nnz, int ncu, int cs_max, int seg_pad, BinnedGeometry &out);
+// Plan: segment (b, s) holds the entries of wave-bin b's rows with a column in slice s, in stored order, padded to a multiple of seg_pad entries
+// (padding: value 0 into row wr, column 0 of the slice). Two orders of the same segments:
+//   slice-major (phase 1 reads col16 in it): slice s starts at sbase[s], its segment b at off1[s][b] inside it ([ns][wb + 1]; [wb]: the slice's entries);
+//               wseg[s][w] is the segment that holds entry 1024 w of slice s ([ns][nwin]).
+//   bin-major, grouped (phase 1 writes G, phase 2 reads G, val2, row16 in it): segment (b, s) starts at off2[b][s] = off2t[s][b]; up to 64 consecutive
+//               wave-bins are interleaved slice by slice - [group][slice][wave-bin of the group] - so that what a slice's workgroup writes for a group
+//               is one contiguous run. log2[b][s] is the segment's start in wave-bin b's own, logical, stream ([wb][ns + 1]; [ns]: the wave-bin's entries).
+// status: BINNED_ORDERS when the two orders do not hold the same number of entries (sbase[ns] against entries).
+struct BinnedPlan {
+  int status = 0, nwin = 1; long long entries = 0;
+  std::vector<unsigned short> col16, row16; std::vector<double> val2;
+  std::vector<int> off1, off2t, wseg, off2, log2; std::vector<long long> sbase;
+};
+void binned_plan(int n, const int *rp, const int *col, const double *val, const BinnedGeometry &g, int seg_pad, BinnedPlan &out);
+// what the two kernels do with the plan, on the host. Phase 1: slice by slice, window by window from wseg, G[e + off2t - off1] = x_slice[col16[e]];
+// phase 2: wave-bin by wave-bin, its ns pieces through log2 / off2, acc[row16] += val2 * G with acc[wr] the spare, y = acc[0 .. wr).
+// The kernel adds by LDS atomics in an order of its own: this walk says nothing about floating-point order and is for checks with exact (integer) sums only.
+void binned_apply_host(const BinnedPlan &p, const BinnedGeometry &g, int n, const double *x, double *y);
+
+
 // P = A + alpha * B on CSR arrays of the same row block (global column indices): MatDuplicate + MatAXPY(P, alpha, B, DIFFERENT_NONZERO_PATTERN),
 // the way STMatMAXPY_Private assembles A - sigma B in ST_MATMODE_COPY (src/sys/classes/st/interface/stsolve.c:611-626). rpb == nullptr: B = I
 // (MatShift, the nmat = 1 branch, stsolve.c:625), the diagonal of row r being global column row_start + r.

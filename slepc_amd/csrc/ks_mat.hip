@@ -1,18 +1,24 @@
 // Mat: assembly of a matrix - creation from CSR arrays, the Laplacian generators and the PETSc binary loader, the halo plan, the device layouts of the
 // diagonal block and their chooser (the product kernels that walk them: ks_spmv.hip, ks_spmm.hip; the storage rules both sides share: ks_rows.cuh),
 // MatGetDiagonal, MatNorm, shell matrices, destruction.
+// What is decided on the host with index arithmetic alone - the diagonal / ghost split of ks_mat_create_csr, the peers, counts and offsets of the halo
+// plan, the binned and the windowed layout - is planned in ks_csr.cpp (ks_csr.h), which has no device code and is tested on the CPU: here those are
+// "call the planner, upload what it filled". The layouts built by kernels (dictionary, SELL-64, XCD-sliced) and the generators are all here.
 #include "ks_rows.cuh"
 #include "ks_csr.h"
 #include <algorithm>
 #include <numeric>
-#include <thread>
-#include <system_error>
-#include <sched.h>
 #include <new>
-#include <type_traits>
 
 namespace {
 using namespace ksr;
+
+// a host vector's copy in device memory (never an empty allocation); what a failure means is the caller's to say
+template <class T> hipError_t upload(T **dev, const std::vector<T> &host)
+{
+  const hipError_t e = hipMalloc((void **)dev, sizeof(T) * std::max<size_t>(host.size(), 1));
+  return e != hipSuccess ? e : hipMemcpy(*dev, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice);
+}
 
 // one thread per row: encode the row's entries against the sorted candidate dictionaries (binary search); entries that
 // are not covered are counted and the first `cap` of them recorded so that the host can extend the dictionaries
@@ -258,7 +264,8 @@ int exclusive_scan_int(hipStream_t st, const int *in, int *out, long long nitems
 }
 
 // Build the halo plan from the sorted list of needed global columns (garray, host).
-// Owners are found from the allgathered row_start array; every rank tells its owners which rows it needs.
+// Owners are found from the allgathered row_start array; every rank tells its owners which rows it needs. The collectives and the device
+// buffers are here; what is computed between them is ks_csr.cpp's (halo_recv_counts, halo_peers, halo_localize_send_idx).
 int build_halo_plan(ks_mat A, const std::vector<int> &garray)
 {
   ks_ctx ctx = A->ctx;
@@ -269,32 +276,28 @@ int build_halo_plan(ks_mat A, const std::vector<int> &garray)
   std::vector<int> starts(size + 1);
   KS_CALL(ks_comm_allgather_host(ctx, &A->row_start, sizeof(int), starts.data()));
   starts[size] = A->n_global;
-  for (int p = 0; p < size; p++) KS_CHECK(starts[p] <= starts[p + 1], KS_ERR_ARG_WRONG, "row blocks must be contiguous and ordered by rank");
   // 2. how many entries I need from every owner; 3. everybody learns everybody's needs
-  std::vector<int> recv_cnt(size, 0), all_cnt((size_t)size * size, 0), send_cnt(size, 0);
-  { int p = 0; for (int g : garray) { while (p + 1 < size && g >= starts[p + 1]) p++; KS_CHECK(p != rank, KS_ERR_PLIB, "ghost column owned by self"); recv_cnt[p]++; } }
+  std::vector<int> recv_cnt, all_cnt((size_t)size * size, 0);
+  const int owners = ksc::halo_recv_counts(garray, starts, rank, recv_cnt);
+  KS_CHECK(owners != ksc::HALO_UNORDERED, KS_ERR_ARG_WRONG, "row blocks must be contiguous and ordered by rank");
+  KS_CHECK(owners != ksc::HALO_SELF, KS_ERR_PLIB, "ghost column owned by self");
   KS_CALL(ks_comm_allgather_host(ctx, recv_cnt.data(), (int)(sizeof(int) * size), all_cnt.data()));
-  for (int p = 0; p < size; p++) send_cnt[p] = (p == rank) ? 0 : all_cnt[(size_t)p * size + rank];
+  ksc::HaloPeers h;
+  ksc::halo_peers(rank, size, recv_cnt.data(), all_cnt.data(), h);
   // 4. exchange index lists: I send my garray segments (global ids) to their owners and receive the ids I must serve
-  int nsend = 0; for (int p = 0; p < size; p++) nsend += send_cnt[p];
+  const int nsend = h.nsend;
   int *d_g = nullptr, *d_sidx = nullptr;
   KS_HIP(hipMalloc(&d_g, sizeof(int) * std::max<size_t>(garray.size(), 1)));
   KS_HIP(hipMalloc(&d_sidx, sizeof(int) * std::max(nsend, 1)));
   KS_HIP(hipMemcpyAsync(d_g, garray.data(), sizeof(int) * garray.size(), hipMemcpyHostToDevice, ctx->stream));
-  A->peers.clear(); A->send_cnt.clear(); A->recv_cnt.clear(); A->send_off.clear(); A->recv_off.clear();
-  int roff = 0, soff = 0;
-  for (int p = 0; p < size; p++) {
-    if (p == rank || (recv_cnt[p] == 0 && send_cnt[p] == 0)) continue;
-    A->peers.push_back(p); A->recv_cnt.push_back(recv_cnt[p]); A->send_cnt.push_back(send_cnt[p]); A->recv_off.push_back(roff); A->send_off.push_back(soff);
-    roff += recv_cnt[p]; soff += send_cnt[p];
-  }
+  A->peers.swap(h.peers); A->send_cnt.swap(h.send_cnt); A->recv_cnt.swap(h.recv_cnt); A->send_off.swap(h.send_off); A->recv_off.swap(h.recv_off);
   // in this exchange the roles are swapped: what I will RECEIVE during SpMV (ghost segments) is what I SEND now (their ids)
   KS_CALL(ks_comm_exchange(ctx, (int)A->peers.size(), A->peers.data(), d_g, A->recv_off.data(), A->recv_cnt.data(),
                            d_sidx, A->send_off.data(), A->send_cnt.data(), (int)sizeof(int)));
   std::vector<int> sidx(std::max(nsend, 1));
   KS_HIP(hipMemcpyAsync(sidx.data(), d_sidx, sizeof(int) * nsend, hipMemcpyDeviceToHost, ctx->stream));
   KS_HIP(ks_sync(ctx));
-  for (int i = 0; i < nsend; i++) { sidx[i] -= A->row_start; KS_CHECK(sidx[i] >= 0 && sidx[i] < A->n, KS_ERR_PLIB, "peer requested a row this rank does not own"); }
+  KS_CHECK(ksc::halo_localize_send_idx(A->row_start, A->n, nsend, sidx.data()) == 0, KS_ERR_PLIB, "peer requested a row this rank does not own");
   KS_HIP(hipMemcpy(d_sidx, sidx.data(), sizeof(int) * nsend, hipMemcpyHostToDevice));
   A->send_idx = d_sidx; A->nsend = nsend;
   if (A->sharded_transpose) { try { A->h_send_idx.assign(sidx.begin(), sidx.begin() + nsend); } catch (const std::exception &e) { KS_FAIL(KS_ERR_MEM, "KS_MAT_SHARDED_TRANSPOSE: %s", e.what()); } }
@@ -409,14 +412,8 @@ int build_window(ks_mat A)
   ksc::WindowPlan p;
   ksc::csr_window_plan(n, rp.data(), col.data(), WIN_ROWS, WIN_SMAX, CW_PAD, p);
   if (p.dcol.size() >= 2147483647u) return KS_SUCCESS;   // positions in the direct column array are 32-bit
-  bool ok = true;
-  auto up = [&](auto **dev, const auto &host) {
-    using T = typename std::remove_reference<decltype(host)>::type::value_type;
-    if (!ok) return;
-    ok = hipMalloc((void **)dev, sizeof(T) * std::max<size_t>(host.size(), 1)) == hipSuccess &&
-         hipMemcpy(*dev, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice) == hipSuccess;
-  };
-  up(&A->wn_codes, p.codes); up(&A->wn_dcol, p.dcol); up(&A->wn_segptr, p.segptr); up(&A->wn_seg, p.seg); up(&A->wn_dbase, p.dbase);
+  const bool ok = upload(&A->wn_codes, p.codes) == hipSuccess && upload(&A->wn_dcol, p.dcol) == hipSuccess && upload(&A->wn_segptr, p.segptr) == hipSuccess &&
+                  upload(&A->wn_seg, p.seg) == hipSuccess && upload(&A->wn_dbase, p.dbase) == hipSuccess;
   if (!ok) return drop();
   KS_CALL(release_csr(A, true));
   A->layout = KS_MAT_LAYOUT_WINDOW;
@@ -425,125 +422,35 @@ int build_window(ks_mat A)
   return KS_SUCCESS;
 }
 
-// Host-side build of the binned layout from the device CSR of the diagonal block (copied back once; the counting sort per wave-bin is cache
-// friendly and runs on a few threads).
+// The binned layout: geometry and plan are made on the host (ks_csr.cpp) from the CSR arrays of the diagonal block, copied back once. A size the
+// layout does not take, or no host or device memory for the build: the matrix stays CSR and the other layouts take it.
 int build_binned(ks_mat A)
 {
   ks_ctx ctx = A->ctx;
   const int n = A->n;
-  // slices: a multiple of the CU count (a workgroup per slice, one resident per CU), each at most BN_CS_MAX columns
-  const int ncu = std::max(ctx->num_cu, 1);
-  const long long per_round = (long long)ncu * BN_CS_MAX;
-  const int ns = (int)(ncu * ((n + per_round - 1) / per_round));
-  const int cs = (n + ns - 1) / ns;
-  const int wb = 4 * ns, wr = (n + wb - 1) / wb;
-  if (cs > 65535 || wr + 1 > 65535) return KS_SUCCESS;
-  if (ks_binned_lds1(cs, wb) > 156 * 1024 || ks_binned_lds2(wr) > 156 * 1024) return KS_SUCCESS;   // the offset rows of more than ~20 M local rows no longer fit LDS next to the piece of x: the XCD-sliced layout takes those
-  if (A->nnz_d + (long long)ns * wb * (BN_SEG_PAD - 1) >= 2147483647LL) return KS_SUCCESS;          // bin-major positions are 32-bit
   const long long nnz = A->nnz_d;
+  ksc::BinnedGeometry g;
+  ksc::binned_geometry(n, nnz, ctx->num_cu, BN_CS_MAX, BN_SEG_PAD, g);
+  if (g.status) return KS_SUCCESS;
+  if (ks_binned_lds1(g.cs, g.wb) > 156 * 1024 || ks_binned_lds2(g.wr) > 156 * 1024) return KS_SUCCESS;   // the offset rows of more than ~20 M local rows no longer fit LDS next to the piece of x: the XCD-sliced layout takes those
   try {                                               // the build holds about 25 bytes per nonzero in host memory: without it the sliced layout takes the matrix
   std::vector<int> rp(n + 1), col(nnz); std::vector<double> val(nnz);
   KS_HIP(hipMemcpyAsync(rp.data(), A->d_rowptr, sizeof(int) * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
   KS_HIP(hipMemcpyAsync(col.data(), A->d_col, sizeof(int) * nnz, hipMemcpyDeviceToHost, ctx->stream));
   KS_HIP(hipMemcpyAsync(val.data(), A->d_val, sizeof(double) * nnz, hipMemcpyDeviceToHost, ctx->stream));
   KS_HIP(ks_sync(ctx));
-  // helper threads: the CPUs this process may run on (affinity mask: what a cgroup / taskset leaves), at most 16; a thread that cannot
-  // be started (pids limit) is simply not used - the calling thread takes every stride that has no thread of its own
-  unsigned ncpu = std::thread::hardware_concurrency();
-  { cpu_set_t cs_; CPU_ZERO(&cs_); if (sched_getaffinity(0, sizeof(cs_), &cs_) == 0 && CPU_COUNT(&cs_) > 0) ncpu = (unsigned)CPU_COUNT(&cs_); }
-  const unsigned nthr = std::max(1u, std::min(16u, ncpu));
-  auto parallel_bins = [&](auto fn) {
-    std::vector<std::thread> th;
-    unsigned started = 1;                                   // stride 0 belongs to the calling thread
-    for (unsigned t = 1; t < nthr; t++) {
-      try { th.emplace_back([&, t] { for (int b = (int)t; b < wb; b += (int)nthr) fn(b); }); started = t + 1; }
-      catch (const std::system_error &) { break; }
-    }
-    for (int b = 0; b < wb; b += (int)nthr) fn(b);
-    for (unsigned t = started; t < nthr; t++) for (int b = (int)t; b < wb; b += (int)nthr) fn(b);      // strides whose thread did not start
-    for (auto &x : th) x.join();
-  };
-  // segment lengths (padded to BN_SEG_PAD entries), bin-major [wb][ns]
-  std::vector<int> len((size_t)wb * ns, 0);
-  parallel_bins([&](int b) {
-    int *L = len.data() + (size_t)b * ns;
-    const int r0 = std::min((long long)b * wr, (long long)n), r1 = std::min((long long)(b + 1) * wr, (long long)n);
-    for (int p = rp[r0]; p < rp[r1]; p++) L[col[p] / cs]++;
-    for (int s = 0; s < ns; s++) L[s] = (L[s] + BN_SEG_PAD - 1) / BN_SEG_PAD * BN_SEG_PAD;
-  });
-  // Bin-major order, GROUPED: `grp` consecutive wave-bins are interleaved slice by slice - [group][slice][wave-bin of the group]
-  // - so that the segments a slice's workgroup writes in phase 1 for `grp` consecutive wave-bins are one contiguous run (80 KB instead of 64
-  // pieces of 1.26 KB, each 0.6 MB from the next; the gather is store-bound: 436 -> 316-331 us in the stand-alone benchmark with uniform
-  // segments, profiles/r03_micro_binned_group.txt).
-  // A wave-bin's own entries are then no longer one stream but ns pieces: phase 2 walks them through a LOGICAL position (piece after piece)
-  // that a per-wave-bin table log2[wb][ns + 1] maps to the physical one (off2), window by window, the way phase 1 finds its destinations.
-  std::vector<int> off2((size_t)wb * ns);                 // physical start of segment (wb, s)
-  std::vector<int> log2((size_t)wb * (ns + 1));           // logical start of segment (wb, s) inside wave-bin wb; [ns]: the wave-bin's entry count
-  long long run = 0;
-  // wave-bins whose segments are adjacent per slice. Measured on config 5's matrix, one box (profiles/r03_ab_binned_groups.txt), phase 1 +
-  // phase 2: 1 (the old order): 445 + 488 us; 4: 404 + 507; 16: 390 + 511; 64: 386 + 500; 256: 388 + 511 - the gather gains what its
-  // stores gain from longer runs, the reduce pays a little for reading its pieces further apart.
-  int grp = 64; while (grp > 1 && wb % grp) grp /= 2;
-  for (int g = 0; g < wb / grp; g++)
-    for (int s = 0; s < ns; s++)
-      for (int wl = 0; wl < grp; wl++) { const int b = grp * g + wl; off2[(size_t)b * ns + s] = (int)run; run += len[(size_t)b * ns + s]; }
-  const long long entries = run;
-  for (int b = 0; b < wb; b++) {
-    int lrun = 0;
-    for (int s = 0; s < ns; s++) { log2[(size_t)b * (ns + 1) + s] = lrun; lrun += len[(size_t)b * ns + s]; }
-    log2[(size_t)b * (ns + 1) + ns] = lrun;
-  }
-  std::vector<int> off1((size_t)ns * (wb + 1)), off2t((size_t)ns * wb);
-  std::vector<long long> sbase(ns + 1);
-  long long srun = 0; int nwin = 1;
-  for (int s = 0; s < ns; s++) {
-    sbase[s] = srun;
-    int lrun = 0;
-    for (int b = 0; b < wb; b++) { off1[(size_t)s * (wb + 1) + b] = lrun; off2t[(size_t)s * wb + b] = off2[(size_t)b * ns + s]; lrun += len[(size_t)b * ns + s]; }
-    off1[(size_t)s * (wb + 1) + wb] = lrun;
-    srun += lrun;
-    nwin = std::max(nwin, (lrun + 1023) / 1024);
-  }
-  sbase[ns] = srun;
-  KS_CHECK(srun == entries, KS_ERR_PLIB, "binned layout: the two orders disagree (%lld vs %lld entries)", srun, entries);
-  std::vector<int> wseg((size_t)ns * nwin, 0);
-  for (int s = 0; s < ns; s++) {
-    const int *o1 = off1.data() + (size_t)s * (wb + 1);
-    int sg = 0;
-    for (int wdw = 0; wdw < nwin; wdw++) {
-      const int base = wdw * 1024;
-      while (sg < wb - 1 && o1[sg + 1] <= base) sg++;
-      wseg[(size_t)s * nwin + wdw] = sg;
-    }
-  }
-  std::vector<double> val2(entries, 0.0);
-  std::vector<unsigned short> row16(entries, (unsigned short)wr), col16(entries, 0);      // padding: value 0 into the spare accumulator, column 0 of its slice
-  parallel_bins([&](int b) {
-    std::vector<int> cur(ns, 0);
-    const int r0 = std::min((long long)b * wr, (long long)n), r1 = std::min((long long)(b + 1) * wr, (long long)n);
-    for (int r = r0; r < r1; r++)
-      for (int p = rp[r]; p < rp[r + 1]; p++) {
-        const int s = col[p] / cs, i = cur[s]++;
-        const long long p2 = (long long)off2[(size_t)b * ns + s] + i;
-        val2[p2] = val[p]; row16[p2] = (unsigned short)(r - r0);
-        col16[sbase[s] + off1[(size_t)s * (wb + 1) + b] + i] = (unsigned short)(col[p] - s * cs);
-      }
-  });
+  ksc::BinnedPlan p;
+  ksc::binned_plan(n, rp.data(), col.data(), val.data(), g, BN_SEG_PAD, p);
+  KS_CHECK(p.status != ksc::BINNED_ORDERS, KS_ERR_PLIB, "binned layout: the two orders disagree (%lld vs %lld entries)", p.sbase[g.ns], p.entries);
   std::vector<int>().swap(col); std::vector<double>().swap(val);
-  auto up = [&](auto **dev, const auto &host) -> int {
-    using T = typename std::remove_reference<decltype(host)>::type::value_type;
-    KS_HIP(hipMalloc((void **)dev, sizeof(T) * std::max<size_t>(host.size(), 1)));
-    KS_HIP(hipMemcpy(*dev, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice));
-    return KS_SUCCESS;
-  };
-  KS_CALL(up(&A->bn_col16, col16)); KS_CALL(up(&A->bn_row16, row16)); KS_CALL(up(&A->bn_val, val2));
-  KS_CALL(up(&A->bn_off1, off1)); KS_CALL(up(&A->bn_off2t, off2t)); KS_CALL(up(&A->bn_wseg, wseg));
-  KS_CALL(up(&A->bn_sbase, sbase)); KS_CALL(up(&A->bn_off2, off2)); KS_CALL(up(&A->bn_log2, log2));
-  KS_HIP(hipMalloc(&A->bn_g, sizeof(double) * std::max<long long>(entries, 1)));
-  KS_HIP(hipMemset(A->bn_g, 0, sizeof(double) * std::max<long long>(entries, 1)));
-  KS_CALL(ks_binned_prepare(ks_binned_lds1(cs, wb), ks_binned_lds2(wr)));
+  KS_HIP(upload(&A->bn_col16, p.col16)); KS_HIP(upload(&A->bn_row16, p.row16)); KS_HIP(upload(&A->bn_val, p.val2));
+  KS_HIP(upload(&A->bn_off1, p.off1)); KS_HIP(upload(&A->bn_off2t, p.off2t)); KS_HIP(upload(&A->bn_wseg, p.wseg));
+  KS_HIP(upload(&A->bn_sbase, p.sbase)); KS_HIP(upload(&A->bn_off2, p.off2)); KS_HIP(upload(&A->bn_log2, p.log2));
+  KS_HIP(hipMalloc(&A->bn_g, sizeof(double) * std::max<long long>(p.entries, 1)));
+  KS_HIP(hipMemset(A->bn_g, 0, sizeof(double) * std::max<long long>(p.entries, 1)));
+  KS_CALL(ks_binned_prepare(ks_binned_lds1(g.cs, g.wb), ks_binned_lds2(g.wr)));
   KS_CALL(release_csr(A));
-  A->layout = KS_MAT_LAYOUT_BINNED; A->bn_ns = ns; A->bn_cs = cs; A->bn_wb = wb; A->bn_wr = wr; A->bn_nwin = nwin; A->bn_entries = entries;
+  A->layout = KS_MAT_LAYOUT_BINNED; A->bn_ns = g.ns; A->bn_cs = g.cs; A->bn_wb = g.wb; A->bn_wr = g.wr; A->bn_nwin = p.nwin; A->bn_entries = p.entries;
   } catch (const std::exception &) {                    // out of host memory (or anything else the build throws): the other layouts take the matrix
     hipFree(A->bn_col16); hipFree(A->bn_row16); hipFree(A->bn_val); hipFree(A->bn_g); hipFree(A->bn_off1); hipFree(A->bn_off2t); hipFree(A->bn_wseg); hipFree(A->bn_sbase); hipFree(A->bn_off2); hipFree(A->bn_log2);
     A->bn_col16 = A->bn_row16 = nullptr; A->bn_val = A->bn_g = nullptr; A->bn_off1 = A->bn_off2t = A->bn_wseg = nullptr; A->bn_sbase = nullptr; A->bn_off2 = A->bn_log2 = nullptr;
@@ -801,39 +708,21 @@ static int mat_assemble(ks_ctx ctx, int n_local, int row_start, int n_global, co
   KS_CHECK(rowptr[0] == 0, KS_ERR_ARG_WRONG, "rowptr[0] must be 0");
   KS_HIP(hipSetDevice(ctx->device));
   const long long nnz = rowptr[n_local];
+  // split diag / off-diag on the host (setup path; ks_csr.cpp), before anything is allocated
+  ksc::BlockSplit s;
+  ksc::csr_split_block(n_local, row_start, n_global, rowptr, col, val, s);
+  KS_CHECK(s.status != ksc::SPLIT_ROWPTR, KS_ERR_ARG_WRONG, "rowptr not monotone at row %d", s.bad_row);
+  KS_CHECK(s.status != ksc::SPLIT_COLUMN, KS_ERR_ARG_OUTOFRANGE, "column %d out of range at row %d", s.bad_col, s.bad_row);
+  const std::vector<int> &garray = s.garray;
   ks_mat A = new ks_mat_s(); A->ctx = ctx; A->n = n_local; A->row_start = row_start; A->n_global = n_global; A->nnz = nnz;
-  // split diag / off-diag on the host (setup path)
-  std::vector<int> rp_d(n_local + 1, 0), rp_o(n_local + 1, 0), cd, co; std::vector<double> vd, vo;
-  cd.reserve(nnz); vd.reserve(nnz);
-  for (int r = 0; r < n_local; r++) {
-    KS_CHECK(rowptr[r + 1] >= rowptr[r], KS_ERR_ARG_WRONG, "rowptr not monotone at row %d", r);
-    for (int p = rowptr[r]; p < rowptr[r + 1]; p++) {
-      int c = col[p];
-      if (c < 0 || c >= n_global) { delete A; KS_FAIL(KS_ERR_ARG_OUTOFRANGE, "column %d out of range at row %d", c, r); }
-      if (c >= row_start && c < row_start + n_local) { cd.push_back(c - row_start); vd.push_back(val[p]); }
-      else { co.push_back(c); vo.push_back(val[p]); }
-    }
-    rp_d[r + 1] = (int)cd.size(); rp_o[r + 1] = (int)co.size();
-  }
-  std::vector<int> garray(co);
-  std::sort(garray.begin(), garray.end()); garray.erase(std::unique(garray.begin(), garray.end()), garray.end());
-  for (auto &c : co) c = (int)(std::lower_bound(garray.begin(), garray.end(), c) - garray.begin());
-  A->nnz_d = (long long)cd.size(); A->nnz_o = (long long)co.size();
-  KS_HIP(hipMalloc(&A->d_rowptr, sizeof(int) * (n_local + 1)));
-  KS_HIP(hipMalloc(&A->d_col, sizeof(int) * (cd.size() + CW_PAD)));
-  KS_HIP(hipMalloc(&A->d_val, sizeof(double) * (vd.size() + CW_PAD)));
-  KS_HIP(hipMemcpy(A->d_rowptr, rp_d.data(), sizeof(int) * (n_local + 1), hipMemcpyHostToDevice));
-  KS_HIP(hipMemcpy(A->d_col, cd.data(), sizeof(int) * cd.size(), hipMemcpyHostToDevice));
-  KS_HIP(hipMemcpy(A->d_val, vd.data(), sizeof(double) * vd.size(), hipMemcpyHostToDevice));
+  A->nnz_d = (long long)s.col_d.size(); A->nnz_o = (long long)s.col_o.size();
+  KS_HIP(upload(&A->d_rowptr, s.rp_d));
+  KS_HIP(hipMalloc(&A->d_col, sizeof(int) * (s.col_d.size() + CW_PAD)));
+  KS_HIP(hipMalloc(&A->d_val, sizeof(double) * (s.val_d.size() + CW_PAD)));
+  KS_HIP(hipMemcpy(A->d_col, s.col_d.data(), sizeof(int) * s.col_d.size(), hipMemcpyHostToDevice));
+  KS_HIP(hipMemcpy(A->d_val, s.val_d.data(), sizeof(double) * s.val_d.size(), hipMemcpyHostToDevice));
   A->lanes_per_row = pick_lanes(A->nnz_d, n_local);
-  if (A->nnz_o) {
-    KS_HIP(hipMalloc(&A->o_rowptr, sizeof(int) * (n_local + 1)));
-    KS_HIP(hipMalloc(&A->o_col, sizeof(int) * co.size()));
-    KS_HIP(hipMalloc(&A->o_val, sizeof(double) * vo.size()));
-    KS_HIP(hipMemcpy(A->o_rowptr, rp_o.data(), sizeof(int) * (n_local + 1), hipMemcpyHostToDevice));
-    KS_HIP(hipMemcpy(A->o_col, co.data(), sizeof(int) * co.size(), hipMemcpyHostToDevice));
-    KS_HIP(hipMemcpy(A->o_val, vo.data(), sizeof(double) * vo.size(), hipMemcpyHostToDevice));
-  }
+  if (A->nnz_o) { KS_HIP(upload(&A->o_rowptr, s.rp_o)); KS_HIP(upload(&A->o_col, s.col_o)); KS_HIP(upload(&A->o_val, s.val_o)); }
   A->sharded_transpose = (flags & KS_MAT_SHARDED_TRANSPOSE) && ctx->comm.size > 1 && !local_only;      // (one rank: the flag changes nothing)
   int rc = KS_SUCCESS;
   if (local_only) { if (!garray.empty()) { ks_set_error("a block assembled on its own has a column outside its rows"); rc = KS_ERR_PLIB; } }

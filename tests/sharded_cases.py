@@ -261,3 +261,32 @@ def halo_plan(case):
         nghost.append(len(g))
     nsend = [sum(needs[q].get(p, 0) for q in range(case.world)) for p in range(case.world)]
     return needs, nghost, nsend
+
+
+def forward_plan(c):
+    """What build_halo_plan leaves on every rank, in numpy: the sorted ghost list, the peers (ascending), recv/send counts and offsets per peer, and
+    send_idx - peer after peer, the peer's ghosts inside this rank's rows in ascending order, as local row indices."""
+    world = c.world
+    ghosts = []
+    for p in range(world):
+        r0, r1 = c.range(p)
+        col = c.block(p)[1]
+        ghosts.append(np.unique(col[(col < r0) | (col >= r1)]).astype(np.int32))
+    own = [np.searchsorted(c.starts, g, side="right") - 1 for g in ghosts]
+    plans = []
+    for p in range(world):
+        r0, _ = c.range(p)
+        peers, rcnt, scnt, seg = [], [], [], []
+        for q in range(world):
+            if q == p:
+                continue
+            r = int(np.count_nonzero(own[p] == q))
+            mine = ghosts[q][own[q] == p]
+            if r == 0 and mine.size == 0:
+                continue
+            peers.append(q); rcnt.append(r); scnt.append(int(mine.size)); seg.append(mine - r0)
+        send_idx = np.concatenate(seg).astype(np.int32) if seg else np.zeros(0, np.int32)
+        roff = np.concatenate([[0], np.cumsum(rcnt)])[:-1].astype(int) if peers else np.zeros(0, int)
+        soff = np.concatenate([[0], np.cumsum(scnt)])[:-1].astype(int) if peers else np.zeros(0, int)
+        plans.append({"ghosts": ghosts[p], "peers": peers, "rcnt": rcnt, "scnt": scnt, "roff": roff, "soff": soff, "send_idx": send_idx})
+    return plans

@@ -1,7 +1,8 @@
 """N>1 path on CPU: world_size-2 gloo run of the row-sharded Lanczos expansion.
 
 The GPU path cannot run here, so this test drives the SAME distributed formulation with the oracle's local
-kernels: per-rank row slab, halo exchange of the SpMV boundary entries, local partial dots, allreduce(SUM) of
+kernels: per-rank row slab, halo exchange of the SpMV boundary entries by the plan the product's own planner makes (the diagonal / ghost split and
+the halo functions of slepc_amd/csrc/ks_csr.cpp; the collectives between them are gloo's here), local partial dots, allreduce(SUM) of
 the k+1 coefficients between the reduce and the bookkeeping halves of each CGS pass (bvblas.c:255), replicated
 scalar control flow.  It checks the sharding helpers used by bench.py (slepc_amd.partition) and that the sharded
 run reproduces the single-rank T, beta, pass counts and Ritz values."""
@@ -41,21 +42,39 @@ def _worker(rank, world, port, shape, m, out):
     A = O.laplacian3d(nx, ny, nz, z0, z1 - z0)                 # my rows, GLOBAL column indices
     r0, r1 = z0 * plane, z1 * plane
     n = r1 - r0
-    ghosts = P.ghost_columns(A.col, r0, r1)
+    # the halo plan, by the product's own planner (ks_csr.cpp through its ksc_* hooks): what build_halo_plan computes between its collectives
+    import assembly_hooks as ah
+    hooks = ah.load()
+    N = plane * nz
+    split = ah.split_block(hooks, n, r0, N, A.rowptr, A.col, A.val)
+    assert split["status"] == 0
+    ghosts = split["garray"]
     assert len(ghosts) == plane * ((z0 > 0) + (z1 < nz))       # one plane per neighbour
+    st, need = ah.halo_recv_counts(hooks, ghosts, [a * plane for a, _ in own] + [N], rank)
+    assert st == 0
+    world_needs = [None] * world
+    dist.all_gather_object(world_needs, (need, ghosts))        # the two exchanges of the plan in one: everybody's counts, and the ids behind them
+    plan = ah.halo_peers(hooks, rank, need, np.stack([w[0] for w in world_needs]))
+    ids = np.full(plan["nsend"], -1, np.int32)
+    for q, so, sc in zip(plan["peers"], plan["soff"], plan["scnt"]):      # what q asks of me: its ghost segment for my rank, behind those for lower ranks
+        need_q, ghosts_q = world_needs[q]
+        assert need_q[rank] == sc
+        ids[so:so + sc] = ghosts_q[int(need_q[:rank].sum()):int(need_q[:rank].sum()) + sc]
+    st, send_idx = ah.halo_localize_send_idx(hooks, r0, n, ids)
+    assert st == 0
     eta, deftol = 0.7071, 10 * np.finfo(float).eps
 
     def allreduce(a):
         t = torch.from_numpy(np.ascontiguousarray(a)); dist.all_reduce(t); return t.numpy()
 
     def spmv(xl):
-        # halo: every rank publishes its first and last plane (all_gather keeps the test simple)
+        # halo: every rank ships x[send_idx], segment by segment, to its peers (all_gather keeps the test simple) and places what it gets in its ghosts
         parts = [None] * world
-        dist.all_gather_object(parts, (xl[:plane].copy(), xl[-plane:].copy()))
-        xg = np.zeros(nx * ny * nz)
+        dist.all_gather_object(parts, {int(q): xl[send_idx[so:so + sc]] for q, so, sc in zip(plan["peers"], plan["soff"], plan["scnt"])})
+        xg = np.zeros(N)
         xg[r0:r1] = xl
-        if rank > 0: xg[r0 - plane:r0] = parts[rank - 1][1]
-        if rank < world - 1: xg[r1:r1 + plane] = parts[rank + 1][0]
+        for q, ro, rc in zip(plan["peers"], plan["roff"], plan["rcnt"]):
+            xg[ghosts[ro:ro + rc]] = parts[q][rank]
         return A.mult(xg)
 
     V = np.zeros((n, m + 1)); H = np.zeros((m + 1, m + 1)); passes = 0

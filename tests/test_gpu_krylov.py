@@ -395,6 +395,29 @@ def test_spmv_rejects_bad_input(ctx):
     assert e.value.rc == 63
 
 
+def test_assembly_rejections(ctx):
+    """What ks_mat_create_csr refuses, with its code and the row its message names: a row pointer that goes down (KS_ERR_ARG_WRONG = 62), a column
+    below 0 or at n_global (KS_ERR_ARG_OUTOFRANGE = 63), and on a single rank a column of a row block another rank would own (63, from the halo plan)."""
+    import slepc_amd as ks
+
+    def refused(*a, **k):
+        with pytest.raises(ks.KsError) as e:
+            ks.Mat.from_csr(ctx, *a, **k)
+        return e.value.rc, str(e.value)
+    rc, msg = refused([0, 2, 1, 3], [0, 1, 2], [1.0, 2.0, 3.0])
+    assert rc == 62 and "rowptr not monotone at row 1" in msg
+    for _ in range(10):                                        # the rejection comes before anything is allocated
+        assert refused([0, 2, 1, 3], [0, 1, 2], [1.0, 2.0, 3.0])[0] == 62
+    rc, msg = refused([0, 1, 2, 3], [0, 1, -1], [1.0, 2.0, 3.0])
+    assert rc == 63 and "column -1 out of range at row 2" in msg
+    rc, msg = refused([0, 1, 2], [0, 2], [1.0, 2.0])
+    assert rc == 63 and "column 2 out of range at row 1" in msg
+    rc, msg = refused([0, 1, 3], [5, 2, 4], [1.0, 2.0, 3.0], row_start=4, n_global=3 + 4)      # in range, but columns 2 and 5 are outside rows 4, 5
+    assert rc == 63 and "on a single rank" in msg
+    A = ks.Mat.from_csr(ctx, [0, 1, 3], [5, 4, 4], [1.0, 2.0, 3.0], row_start=4, n_global=7)     # the same block with its own columns only
+    assert np.array_equal(A.mult(np.array([1.0, 10.0])), [10.0, 5.0])
+
+
 # ---- fused Gram-Schmidt -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("refine", [0, 1, 2])
 @pytest.mark.parametrize("n,m", [(7, 3), (600, 12), (5000, 31), (3001, 33)])

@@ -42,35 +42,6 @@ def case(name, world):
     return {"far": lambda: sc.far(world), "islands": sc.islands, "bighalo": lambda: sc.bighalo(world)}[name]()
 
 
-def forward_plan(c):
-    """What build_halo_plan leaves on every rank, in numpy: the sorted ghost list, the peers (ascending), recv/send counts and offsets per peer, and
-    send_idx - peer after peer, the peer's ghosts inside this rank's rows in ascending order, as local row indices."""
-    world = c.world
-    ghosts = []
-    for p in range(world):
-        r0, r1 = c.range(p)
-        col = c.block(p)[1]
-        ghosts.append(np.unique(col[(col < r0) | (col >= r1)]).astype(np.int32))
-    own = [np.searchsorted(c.starts, g, side="right") - 1 for g in ghosts]
-    plans = []
-    for p in range(world):
-        r0, _ = c.range(p)
-        peers, rcnt, scnt, seg = [], [], [], []
-        for q in range(world):
-            if q == p:
-                continue
-            r = int(np.count_nonzero(own[p] == q))
-            mine = ghosts[q][own[q] == p]
-            if r == 0 and mine.size == 0:
-                continue
-            peers.append(q); rcnt.append(r); scnt.append(int(mine.size)); seg.append(mine - r0)
-        send_idx = np.concatenate(seg).astype(np.int32) if seg else np.zeros(0, np.int32)
-        roff = np.concatenate([[0], np.cumsum(rcnt)])[:-1].astype(int) if peers else np.zeros(0, int)
-        soff = np.concatenate([[0], np.cumsum(scnt)])[:-1].astype(int) if peers else np.zeros(0, int)
-        plans.append({"ghosts": ghosts[p], "peers": peers, "rcnt": rcnt, "scnt": scnt, "roff": roff, "soff": soff, "send_idx": send_idx})
-    return plans
-
-
 def build_plan(lib, c, rank, fp):
     rp, col, val = (np.ascontiguousarray(a) for a in c.block(rank))
     r0, r1 = c.range(rank)
@@ -95,7 +66,7 @@ def build_plan(lib, c, rank, fp):
 @pytest.mark.parametrize("name,world", [("far", 4), ("far", 8), ("islands", 4), ("bighalo", 2), ("bighalo", 4)])
 def test_sharded_transpose_plan_and_host_walk(lib, name, world):
     c = case(name, world)
-    fps = forward_plan(c)
+    fps = sc.forward_plan(c)
     needs, nghost, nsend = sc.halo_plan(c)
     x = sc.int_vectors(c.N, 1, seed=100 + c.N % 97)[0]
     ref = (c.int_matrix().T @ x.astype(np.int64)) / float(c.scale)
