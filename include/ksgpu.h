@@ -81,7 +81,7 @@ enum { KS_EPS_LARGEST_MAGNITUDE = 1, KS_EPS_SMALLEST_MAGNITUDE = 2, KS_EPS_LARGE
 typedef int (*ks_eig_compare_fn)(double ar, double ai, double br, double bi, int *res, void *ctx);
 enum { KS_EPS_HEP = 1, KS_EPS_GHEP = 2, KS_EPS_NHEP = 3, KS_EPS_GNHEP = 4 };   /* EPSProblemType, slepceps.h */
 enum { KS_ST_SHIFT = 0, KS_ST_SINVERT = 1, KS_ST_CAYLEY = 2, KS_ST_PRECOND = 3 };   /* STType "shift", "sinvert", "cayley", "precond" (precond.c: K = A - sigma B is only preconditioned, never solved) */
-enum { KS_EPS_KRYLOVSCHUR = 0, KS_EPS_LOBPCG = 1, KS_EPS_GD = 2 };   /* EPSType "krylovschur", "lobpcg", "gd" */
+enum { KS_EPS_KRYLOVSCHUR = 0, KS_EPS_LOBPCG = 1, KS_EPS_GD = 2, KS_EPS_JD = 3 };   /* EPSType "krylovschur", "lobpcg", "gd", "jd" */
 enum { KS_EPS_ERROR_ABSOLUTE = 0, KS_EPS_ERROR_RELATIVE = 1, KS_EPS_ERROR_BACKWARD = 2 };   /* EPSErrorType */
 enum { KS_EPS_RITZ = 0, KS_EPS_HARMONIC = 1, KS_EPS_HARMONIC_RELATIVE, KS_EPS_HARMONIC_RIGHT, KS_EPS_HARMONIC_LARGEST, KS_EPS_REFINED, KS_EPS_REFINED_HARMONIC };  /* EPSExtraction slepceps.h:94-100; Krylov-Schur offers the first two */
 enum { KS_EPS_BALANCE_NONE = 0, KS_EPS_BALANCE_ONESIDE = 1, KS_EPS_BALANCE_TWOSIDE = 2, KS_EPS_BALANCE_USER = 3 };   /* EPSBalance slepceps.h; the two-sided form needs the transposed product (ks_mat_mult_transpose) */
@@ -370,6 +370,25 @@ int ks_bv_block_residual(ks_bv R, ks_bv AX, ks_bv BX, const double *theta, doubl
    not touched. Errors: ncols outside 1..16, or no active column in V: KS_ERR_ARG_OUTOFRANGE; lds < m, AV / BV with fewer than k columns, R with
    fewer than lR + ncols: KS_ERR_ARG_SIZ; R the same BV as V, AV or BV: KS_ERR_ARG_WRONG; different local sizes: KS_ERR_ARG_INCOMP. */
 int ks_bv_ritz_residual(ks_bv R, ks_bv V, ks_bv AV, ks_bv BV, const double *S, int lds, int ncols, const double *theta, double *rnorm, double *xnorm);
+/* The same sweep, which also keeps what it has in registers (dvd_improvex_jd_start, dvdimprovex.c, needs the Ritz vectors of the block and their
+   images under B as columns): X(:, lX + j) = x_j and BX(:, lBX + j) = bx_j (x_j again without BV), each from the first active column of its BV,
+   each optional (NULL). R, rnorm and xnorm have the bits of ks_bv_ritz_residual on the same inputs. Further errors: X or BX the same BV as another
+   argument: KS_ERR_ARG_WRONG; fewer than ncols columns from its first active one: KS_ERR_ARG_SIZ; another local size: KS_ERR_ARG_INCOMP. */
+int ks_bv_ritz_residual_vectors(ks_bv R, ks_bv V, ks_bv AV, ks_bv BV, const double *S, int lds, int ncols, const double *theta, double *rnorm, double *xnorm, ks_bv X, ks_bv BX);
+/* The oblique projector of the Jacobi-Davidson correction equation (dvd_improvex_apply_proj, dvdimprovex.c:220-280, applied to the vector the
+   operator has just produced), fused with the linear combination that forms that vector:
+     t_i = a * u_i;  if (v) t_i += b * v_i;  w_i = s ? s_i * t_i : t_i          (the rounding of the ST's own combinations)
+     h = Z^T w,  c = Minv h,   Z and Y: the k active columns of the two BVs, Minv: k x k on the DEVICE, column-major, ldm >= k
+     w_i <- w_i - sum_j Y(i,j) c_j,  j ascending, one fma each, starting from w_i
+     e given: *dot = e^T w of the result, summed over all ranks (e == w: ||w||^2)
+   All vectors are device arrays of the BVs' local size; v, s, e may be NULL; u == w is allowed. The dot sweep forms and stores w in the same pass, a
+   one-workgroup kernel reduces h and multiplies by Minv, the sum over the ranks runs on the device buffer of c (nothing on one rank), the update
+   sweep reads c from the device: no host wait between them. With dot == NULL the call only enqueues; with a dot the fixed-order sum of the
+   update's partial sums is one more launch and the call waits once. k == 0: the combination and the dot only. More than 64 columns: chunks.
+   Errors: different local sizes or column counts of Y and Z: KS_ERR_ARG_INCOMP; ldm < k: KS_ERR_ARG_SIZ; w or u NULL (Minv with k > 0; e with a
+   dot): KS_ERR_ARG_NULL; w inside the storage of Y or Z: KS_ERR_ARG_WRONG. */
+int ks_bv_oblique_project(ks_bv Y, ks_bv Z, const double *Minv_dev, int ldm, double a, const double *u_dev, double b, const double *v_dev,
+                          const double *s_dev, double *w_dev, const double *e_dev, double *dot);
 
 /* ops->gramschmidt (bvimpl.h:53): ONE Gram-Schmidt pass, the function BVOrthogonalizeGS1 dispatches to (bvorthog.c:134) in place
    of BVOrthogonalizeCGS1 (:91-132) / BVOrthogonalizeMGS1 (:52-85), chosen by the BV's orthogonalization type. The caller
@@ -525,6 +544,31 @@ int ks_eps_gd_get_borth(ks_eps eps, int *borth);          /* EPSGDGetBOrth */
 /* instrumentation of the last GD solve: passes of the main loop, restarts, locking steps, columns a matrix was applied to (A and B), columns
    preconditioned, calls of the fused Ritz-residual sweep */
 int ks_eps_gd_get_stats(ks_eps eps, long long *iterations, long long *restarts, long long *locks, long long *mat_columns, long long *pc_columns, long long *fused_residuals);
+/* KS_EPS_JD: Jacobi-Davidson (src/eps/impls/davidson/jd/jd.c and dvdimprovex.c; ks_jd.hip). The outer loop, the scope, the set-up rules with their
+   KS_ERR_SUP cases and the choice of ST are GD's (above); the expansion vector of a pair (theta_j, u_j) is the approximate solution t of
+       P K^-1 (theta1 A - theta0 B) t = -P K^-1 r_j,    P = I - Y (Zq^T Y)^-1 Zq^T,  Zq = B [X_locked, U],  Y = K^-1 Zq
+   (dvd_improvex_jd_gen, dvdimprovex.c:590-700) with K the ST's preconditioner and (theta0, theta1) = (theta_j, 1) once ||r_j|| < fix |theta_j|, the
+   target pair before (dvd_improvex_jd_lit_const_0). The inner solver is the ST's KSP type on this operator; where the caller has not chosen
+   (ks_st_set_ksp_type, ks_st_set_ksp): BiCGStab, rtol 1e-4, at most 90 iterations (EPSSetDefaultST_JD, jd.c, which picks BiCGStab(l)). Reaching the limit
+   or breaking down is no error: the iterate is the correction. The deviations from the reference are listed at the top of ks_jd.hip. JD keeps its own
+   copy of the settings GD has. */
+int ks_eps_jd_set_blocksize(ks_eps eps, int bs);          /* EPSJDSetBlockSize jd.c; as ks_eps_gd_set_blocksize */
+int ks_eps_jd_get_blocksize(ks_eps eps, int *bs);         /* EPSJDGetBlockSize jd.c */
+int ks_eps_jd_set_restart(ks_eps eps, int minv, int plusk);   /* EPSJDSetRestart jd.c */
+int ks_eps_jd_get_restart(ks_eps eps, int *minv, int *plusk); /* EPSJDGetRestart jd.c */
+int ks_eps_jd_set_initial_size(ks_eps eps, int initialsize);  /* EPSJDSetInitialSize jd.c */
+int ks_eps_jd_get_initial_size(ks_eps eps, int *initialsize); /* EPSJDGetInitialSize jd.c */
+int ks_eps_jd_set_borth(ks_eps eps, int borth);           /* EPSJDSetBOrth jd.c */
+int ks_eps_jd_get_borth(ks_eps eps, int *borth);          /* EPSJDGetBOrth jd.c */
+int ks_eps_jd_set_fix(ks_eps eps, double fix);            /* EPSJDSetFix jd.c: default 0.01; fix <= 0: KS_ERR_ARG_OUTOFRANGE */
+int ks_eps_jd_get_fix(ks_eps eps, double *fix);           /* EPSJDGetFix jd.c */
+int ks_eps_jd_set_const_correction_tol(ks_eps eps, int constant);   /* EPSJDSetConstCorrectionTol jd.c: default on; off: the dynamic tolerance of dvdimprovex.c:603-605 (0.5, halved after each outer iteration that solved a correction, floor 10 eps, 0.5 again after a lock) */
+int ks_eps_jd_get_const_correction_tol(ks_eps eps, int *constant);  /* EPSJDGetConstCorrectionTol jd.c */
+/* instrumentation of the last JD solve: the first five as ks_eps_gd_get_stats (the products and preconditioner applications of the inner solves
+   included), then the correction equations solved (dvd_improvex_jd_gen), their Krylov iterations, and the pairs that took the GD correction instead
+   (dvdimprovex.c:650-655, 683-690) */
+int ks_eps_jd_get_stats(ks_eps eps, long long *iterations, long long *restarts, long long *locks, long long *mat_columns, long long *pc_columns,
+                        long long *inner_solves, long long *inner_iterations, long long *gd_fallbacks);
 int ks_eps_set_track_all(ks_eps eps, int trackall);                          /* EPSSetTrackAll: error estimates of all Ritz pairs at every restart (for monitors) */
 int ks_eps_get_krylovschur(ks_eps eps, double *keep, int *lock);             /* EPSKrylovSchurGetRestart / EPSKrylovSchurGetLocking */
 int ks_eps_set_balance(ks_eps eps, int bal, int its, double cutoff);        /* EPSSetBalance epsopts.c:1050 (non-symmetric problems; EPSBuildBalance_Krylov epsdefault.c:370); its / cutoff 0 keep 5 / 1e-8 */

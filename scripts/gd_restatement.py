@@ -37,8 +37,9 @@ def restart_basis(Q, oldU, size_X, size_plusk):
 
 
 def gd(A, B=None, nev=1, which="largest_magnitude", target=0.0, tol=1e-8, conv="rel", bs=1, pc=None, minv=0, plusk=1, initv=0, ncv=0, mpd=0,
-       defl=None, seed=0, max_it=0):
-    """returns (eigenvalues of the locked pairs, iterations, restarts, locks)"""
+       defl=None, seed=0, max_it=0, correct=None, on_lock=None):
+    """returns (eigenvalues of the locked pairs, iterations, restarts, locks). correct / on_lock: the hooks of the loop that Jacobi-Davidson fills
+    (scripts/jd_restatement.py): the expansion vectors of the block in place of pc(R), and a call when pairs are locked."""
     n = A.shape[0]
     if not ncv:
         ncv = mpd + nev + bs if mpd else (n + nev + bs if n < 10 else max(nev, min(n - bs, max(2 * nev, nev + 15)) + bs))
@@ -113,6 +114,8 @@ def gd(A, B=None, nev=1, which="largest_magnitude", target=0.0, tol=1e-8, conv="
             Y = np.hstack([Y, V[:, :npre]]); eig.extend(w[:npre])
             V, AV, BV = V[:, npre:], AV[:, npre:], BV[:, npre:]
             H = np.diag(w[npre:]); oldU = None; locks += 1
+            if on_lock is not None:
+                on_lock()
         elif m + bs > mpd or nconv + m + bs > ncv:
             mrs = max(0, min(mpd - 1, ncv - nconv - 2))
             so = oldU.shape[0] if oldU is not None else 0
@@ -121,7 +124,10 @@ def gd(A, B=None, nev=1, which="largest_magnitude", target=0.0, tol=1e-8, conv="
             Z = restart_basis(Q, oldU if oldU is not None else np.zeros((0, 0)), size_X, size_plusk)
             V = V @ Z; AV = AV @ Z; BV = BV @ Z; H = Z.T @ H @ Z; oldU = None; restarts += 1
         else:
-            D = pc(R) if pc is not None else R
+            if correct is not None:
+                D = correct(X=X, R=R, theta=w[:nb], locked=Y[:, nc:])
+            else:
+                D = pc(R) if pc is not None else R
             kept = 0
             for j in range(nb):
                 z = orthonormalize(V, D[:, j])

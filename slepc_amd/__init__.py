@@ -32,7 +32,7 @@ WHICH = {"largest_magnitude": 1, "smallest_magnitude": 2, "largest_real": 3, "sm
 BLOCK = {"gs": 0, "chol": 1, "tsqr": 2, "tsqrchol": 3, "svqb": 4}
 SHELL_MULT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
 ST_SHIFT, ST_SINVERT, ST_CAYLEY, ST_PRECOND = 0, 1, 2, 3
-EPS_KRYLOVSCHUR, EPS_LOBPCG, EPS_GD = 0, 1, 2
+EPS_KRYLOVSCHUR, EPS_LOBPCG, EPS_GD, EPS_JD = 0, 1, 2, 3
 PC_JACOBI, PC_BJACOBI, PC_BJACOBI_ILU, PC_NONE = 0, 1, 2, 3
 BV_MATMULT_VECS, BV_MATMULT_MAT, BV_MATMULT_MAT_SAVE = 0, 1, 2
 MATMULT = {"vecs": BV_MATMULT_VECS, "mat": BV_MATMULT_MAT, "mat_save": BV_MATMULT_MAT_SAVE}
@@ -652,6 +652,38 @@ class BV:
         _lib.check(self.ctx.L.ks_bv_ritz_residual(self.h, V.h, AV.h, BV.h if BV is not None else None, _p(flat), lds, ncols, _p(th), _p(rn), _p(xn) if want_xnorm else None))
         return rn[:ncols], (xn[:ncols] if want_xnorm else None)
 
+    def RitzResidualVectors(self, V, AV, BV, S, theta, X=None, BX=None, ncols=None, lds=None, want_xnorm=True):
+        """RitzResidual, which also stores x_j = V S(:,j) into X and B x_j into BX (each from the first active column of its BV, each optional)."""
+        S = np.asarray(S, dtype=np.float64)
+        if S.ndim == 2:
+            S = np.asfortranarray(S); lds = S.shape[0] if lds is None else lds; ncols = S.shape[1] if ncols is None else ncols; flat = S.ravel(order="F")
+        else:
+            flat = np.ascontiguousarray(S)
+        th = _f64(theta); rn = np.zeros(max(ncols, 1)); xn = np.zeros(max(ncols, 1))
+        _lib.check(self.ctx.L.ks_bv_ritz_residual_vectors(self.h, V.h, AV.h, BV.h if BV is not None else None, _p(flat), lds, ncols, _p(th), _p(rn),
+                                                          _p(xn) if want_xnorm else None, X.h if X is not None else None, BX.h if BX is not None else None))
+        return rn[:ncols], (xn[:ncols] if want_xnorm else None)
+
+    def ObliqueProject(self, Z, Minv, a, u_ptr, w_ptr, b=0.0, v_ptr=None, s_ptr=None, e_ptr=None, ldm=None):
+        """w <- (I - Y Minv Z^T) (s .* (a u + b v)) over the active columns of Z and of this BV (self is Y); returns e^T w of the result when e is
+        given, else None (the call then only enqueues). Minv: a host matrix (k x k, staged on the device here); the vectors are device pointers."""
+        k = Z.k - Z.l
+        Mf = np.asfortranarray(np.zeros((max(k, 1), max(k, 1))) if Minv is None else Minv, dtype=np.float64)
+        ldm = Mf.shape[0] if ldm is None else ldm
+        flat = Mf.ravel(order="F")
+        hold = BV(self.ctx, flat.size, 1)
+        hold.set_column(0, flat)
+        dot = C.c_double() if e_ptr is not None else None
+        vp = lambda q: None if q is None else C.c_void_p(q)
+        try:
+            _lib.check(self.ctx.L.ks_bv_oblique_project(self.h, Z.h, C.c_void_p(hold.column_ptr(0)), ldm, float(a), vp(u_ptr), float(b), vp(v_ptr), vp(s_ptr), vp(w_ptr), vp(e_ptr),
+                                                        C.byref(dot) if dot is not None else None))
+            if dot is None:
+                self.ctx.synchronize()           # the staged Minv must outlive the launches that read it
+        finally:
+            hold.destroy()
+        return None if dot is None else dot.value
+
     def SetMatMultMethod(self, method):
         """BVSetMatMultMethod: "vecs" / "mat" / "mat_save" (or the BV_MATMULT_* number)."""
         _lib.check(self.ctx.L.ks_bv_set_matmult_method(self.h, MATMULT.get(method, method)))
@@ -980,11 +1012,11 @@ class EPS:
         _lib.check(self.ctx.L.ks_eps_set_problem_type(self.h, t))
 
     def SetType(self, t):
-        """EPSSetType: "krylovschur" (default), "lobpcg" or "gd"."""
-        _lib.check(self.ctx.L.ks_eps_set_type(self.h, {"krylovschur": EPS_KRYLOVSCHUR, "lobpcg": EPS_LOBPCG, "gd": EPS_GD}.get(t, t)))
+        """EPSSetType: "krylovschur" (default), "lobpcg", "gd" or "jd"."""
+        _lib.check(self.ctx.L.ks_eps_set_type(self.h, {"krylovschur": EPS_KRYLOVSCHUR, "lobpcg": EPS_LOBPCG, "gd": EPS_GD, "jd": EPS_JD}.get(t, t)))
 
     def GetType(self):
-        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_get_type(self.h, C.byref(v))); return {0: "krylovschur", 1: "lobpcg", 2: "gd"}[v.value]
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_get_type(self.h, C.byref(v))); return {0: "krylovschur", 1: "lobpcg", 2: "gd", 3: "jd"}[v.value]
 
     def GDSetBlockSize(self, bs):
         _lib.check(self.ctx.L.ks_eps_gd_set_blocksize(self.h, bs))
@@ -1014,6 +1046,49 @@ class EPS:
         v = [C.c_longlong() for _ in range(6)]
         _lib.check(self.ctx.L.ks_eps_gd_get_stats(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("iterations", "restarts", "locks", "mat_columns", "pc_columns", "fused_residuals"), (x.value for x in v)))
+
+    def JDSetBlockSize(self, bs):
+        _lib.check(self.ctx.L.ks_eps_jd_set_blocksize(self.h, bs))
+
+    def JDGetBlockSize(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_jd_get_blocksize(self.h, C.byref(v))); return v.value
+
+    def JDSetRestart(self, minv=0, plusk=-1):
+        _lib.check(self.ctx.L.ks_eps_jd_set_restart(self.h, minv, plusk))
+
+    def JDGetRestart(self):
+        a, b = C.c_int(), C.c_int(); _lib.check(self.ctx.L.ks_eps_jd_get_restart(self.h, C.byref(a), C.byref(b))); return a.value, b.value
+
+    def JDSetInitialSize(self, initialsize):
+        _lib.check(self.ctx.L.ks_eps_jd_set_initial_size(self.h, initialsize))
+
+    def JDGetInitialSize(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_jd_get_initial_size(self.h, C.byref(v))); return v.value
+
+    def JDSetBOrth(self, borth):
+        _lib.check(self.ctx.L.ks_eps_jd_set_borth(self.h, int(bool(borth))))
+
+    def JDGetBOrth(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_jd_get_borth(self.h, C.byref(v))); return bool(v.value)
+
+    def JDSetFix(self, fix):
+        """EPSJDSetFix: the correction equation takes the Ritz value as its shift once ||r|| < fix |theta| (default 0.01), the target before."""
+        _lib.check(self.ctx.L.ks_eps_jd_set_fix(self.h, float(fix)))
+
+    def JDGetFix(self):
+        v = C.c_double(); _lib.check(self.ctx.L.ks_eps_jd_get_fix(self.h, C.byref(v))); return v.value
+
+    def JDSetConstCorrectionTol(self, constant):
+        """EPSJDSetConstCorrectionTol: a constant inner tolerance (default), or the dynamic one that starts at 0.5 and halves."""
+        _lib.check(self.ctx.L.ks_eps_jd_set_const_correction_tol(self.h, int(bool(constant))))
+
+    def JDGetConstCorrectionTol(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_eps_jd_get_const_correction_tol(self.h, C.byref(v))); return bool(v.value)
+
+    def JDGetStats(self):
+        v = [C.c_longlong() for _ in range(8)]
+        _lib.check(self.ctx.L.ks_eps_jd_get_stats(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("iterations", "restarts", "locks", "mat_columns", "pc_columns", "inner_solves", "inner_iterations", "gd_fallbacks"), (x.value for x in v)))
 
     def LOBPCGSetBlockSize(self, bs):
         _lib.check(self.ctx.L.ks_eps_lobpcg_set_blocksize(self.h, bs))

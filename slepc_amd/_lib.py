@@ -124,6 +124,8 @@ _SIG = {
     "ks_bv_get_matmult_method": [vp, ip],
     "ks_bv_block_residual": [vp, vp, vp, dp, dp],
     "ks_bv_ritz_residual": [vp, vp, vp, vp, dp, C.c_int, C.c_int, dp, dp, dp],
+    "ks_bv_ritz_residual_vectors": [vp, vp, vp, vp, dp, C.c_int, C.c_int, dp, dp, dp, vp, vp],
+    "ks_bv_oblique_project": [vp, vp, vp, C.c_int, C.c_double, vp, C.c_double, vp, vp, vp, vp, dp],
     "ks_bv_gramschmidt_pass": [vp, C.c_int, vp, ip, dp, dp, dp, dp],
     "ks_bv_orthogonalizecolumn": [vp, C.c_int, dp, dp, ip],
     "ks_bv_orthonormalizecolumn": [vp, C.c_int, C.c_int, dp, ip],
@@ -219,6 +221,13 @@ _SIG = {
     "ks_eps_gd_set_initial_size": [vp, C.c_int], "ks_eps_gd_get_initial_size": [vp, ip],
     "ks_eps_gd_set_borth": [vp, C.c_int], "ks_eps_gd_get_borth": [vp, ip],
     "ks_eps_gd_get_stats": [vp, llp, llp, llp, llp, llp, llp],
+    "ks_eps_jd_set_blocksize": [vp, C.c_int], "ks_eps_jd_get_blocksize": [vp, ip],
+    "ks_eps_jd_set_restart": [vp, C.c_int, C.c_int], "ks_eps_jd_get_restart": [vp, ip, ip],
+    "ks_eps_jd_set_initial_size": [vp, C.c_int], "ks_eps_jd_get_initial_size": [vp, ip],
+    "ks_eps_jd_set_borth": [vp, C.c_int], "ks_eps_jd_get_borth": [vp, ip],
+    "ks_eps_jd_set_fix": [vp, C.c_double], "ks_eps_jd_get_fix": [vp, dp],
+    "ks_eps_jd_set_const_correction_tol": [vp, C.c_int], "ks_eps_jd_get_const_correction_tol": [vp, ip],
+    "ks_eps_jd_get_stats": [vp, llp, llp, llp, llp, llp, llp, llp, llp],
     "ks_st_create": [vp, C.POINTER(vp)],
     "ks_st_destroy": [vp],
     "ks_st_set_type": [vp, C.c_int],

@@ -609,6 +609,31 @@ int lu_solve_trans(int n, double *A, int ld, double *b)
   return 0;
 }
 
+// Minv = M^-1 by LU with partial pivoting (lu_factor, then one lu_solve per column of the identity). The projector of the Jacobi-Davidson correction
+// equation needs to know when M = Z^T Y has lost rank numerically: a pivot of modulus at most n eps ||M||_inf reports the matrix singular (return 1,
+// Minv untouched); 0 otherwise. M is not modified.
+int lu_inverse(int n, const double *M, int ldm, double *Minv, int ldi)
+{
+  if (n <= 0) return 0;
+  std::vector<double> F((size_t)n * n), e(n);
+  std::vector<int> piv(n);
+  double nrm = 0.0;
+  for (int i = 0; i < n; i++) {
+    double row = 0.0;
+    for (int j = 0; j < n; j++) { const double v = M[i + (size_t)j * ldm]; F[i + (size_t)j * n] = v; row += fabs(v); }
+    if (!(row <= nrm)) nrm = row;                      // a NaN row makes the norm NaN: every pivot then fails the test below
+  }
+  lu_factor(n, F.data(), n, piv.data());
+  const double thresh = n * 2.220446049250313e-16 * nrm;
+  for (int j = 0; j < n; j++) if (!(fabs(F[j + (size_t)j * n]) > thresh)) return 1;
+  for (int j = 0; j < n; j++) {
+    std::fill(e.begin(), e.end(), 0.0); e[j] = 1.0;
+    lu_solve(n, F.data(), n, piv.data(), e.data(), false);
+    for (int i = 0; i < n; i++) Minv[i + (size_t)j * ldi] = e[i];
+  }
+  return 0;
+}
+
 } // namespace ksd
 
 // ---- C hooks for the CPU unit tests (tests/test_dense_host.py builds this file alone with g++) ----------------
@@ -626,5 +651,6 @@ void ksd_qr_explicit(int M, int n, double *A, int ld, double *R, int ldr, double
 int ksd_lu_solve_trans(int n, double *A, int ld, double *b) { return ksd::lu_solve_trans(n, A, ld, b); }
 int ksd_lu_factor(int n, double *A, int ld, int *piv) { return ksd::lu_factor(n, A, ld, piv); }
 void ksd_lu_solve(int n, const double *A, int ld, const int *piv, double *b, int trans) { ksd::lu_solve(n, A, ld, piv, b, trans != 0); }
+int ksd_lu_inverse(int n, const double *M, int ldm, double *Minv, int ldi) { return ksd::lu_inverse(n, M, ldm, Minv, ldi); }
 }
 #endif

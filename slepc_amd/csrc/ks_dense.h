@@ -46,6 +46,9 @@ int lu_solve_trans(int n, double *A, int ld, double *b);
 // with A^-1 b (trans false) or A^-T b (trans true).
 int lu_factor(int n, double *A, int ld, int *piv);
 void lu_solve(int n, const double *A, int ld, const int *piv, double *b, bool trans);
+// Minv = M^-1 (both n x n, column-major) through those two; M is left alone. Returns 1, with Minv untouched, when a pivot is at most n eps ||M||_inf
+// (numerically singular: the oblique projector of ks_jd.hip then falls back), else 0.
+int lu_inverse(int n, const double *M, int ldm, double *Minv, int ldi);
 
 // Householder QR of the M x n matrix A (column-major, ld; M >= n) with the orthogonal factor formed explicitly (dgeqr2 + dorg2r):
 // R (n x n, upper triangular, ldr) and Q (M x n, ldq) with A = Q R. The combine step of the tall-skinny QR: A is the stack of the

@@ -217,7 +217,7 @@ extern "C" int ks_eps_set_initial_space(ks_eps eps, int n, const double *const *
   KS_CHECK(v_dev && v_dev[0], KS_ERR_ARG_NULL, "NULL argument");
   eps->v0.resize(std::max(eps->A->n, 1));
   KS_HIP(hipSetDevice(eps->ctx->device));
-  if (eps->type == KS_EPS_LOBPCG || eps->type == KS_EPS_GD) {   // a block solver uses all of them (lobpcg.c:133, dvdinitv.c:45): device copies, made only for those solver types
+  if (eps->type == KS_EPS_LOBPCG || eps->type == KS_EPS_GD || eps->type == KS_EPS_JD) {   // a block solver uses all of them (lobpcg.c:133, dvdinitv.c:45): device copies, made only for those solver types
     KS_CALL(ks_bv_create(eps->ctx, eps->A->n, eps->A->n_global, n, 0, &eps->ini));
     for (int i = 0; i < n; i++) { KS_CHECK(v_dev[i], KS_ERR_ARG_NULL, "vector %d is NULL", i); KS_CALL(ks_bv_insert_vec(eps->ini, i, v_dev[i])); }
     eps->nini = n;
@@ -437,7 +437,7 @@ static void sort_eigenvalues(ks_eps eps)
 extern "C" int ks_eps_solve(ks_eps eps)   // EPSSolve epssolve.c:119-208
 {
   KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
-  const ks_eps_ops &ops = eps->type == KS_EPS_LOBPCG ? *ks_lobpcg_ops() : eps->type == KS_EPS_GD ? *ks_gd_ops() : *ks_krylovschur_ops(eps->twosided);
+  const ks_eps_ops &ops = eps->type == KS_EPS_LOBPCG ? *ks_lobpcg_ops() : eps->type == KS_EPS_GD ? *ks_gd_ops() : eps->type == KS_EPS_JD ? *ks_jd_ops() : *ks_krylovschur_ops(eps->twosided);
   KS_CALL(ops.setup(eps));                                             // takes the pass counters (eps->passes0) and allocates the solver's DS
   KS_CALL(ops.solve(eps));
   // ---- EPSSolve epilogue ----
@@ -632,16 +632,16 @@ extern "C" int ks_eps_get_stats(ks_eps eps, long long *steps, long long *passes,
   return KS_SUCCESS;
 }
 
-// EPSSetType epsbasic.c: Krylov-Schur (the default), LOBPCG or GD. LOBPCG and GD make STPRECOND the default of the solver's ST (EPSSetDefaultST_Precond
-// epsdefault.c) unless the caller chose a type; going back to Krylov-Schur undoes that default. The infinite default shift is GD's alone (davidson.c:80)
+// EPSSetType epsbasic.c: Krylov-Schur (the default), LOBPCG, GD or JD. LOBPCG, GD and JD make STPRECOND the default of the solver's ST (EPSSetDefaultST_Precond
+// epsdefault.c) unless the caller chose a type; going back to Krylov-Schur undoes that default. The infinite default shift is GD's and JD's alone (davidson.c:80)
 extern "C" int ks_eps_set_type(ks_eps eps, int type)
 {
   KS_CHECK(eps, KS_ERR_ARG_NULL, "EPS is NULL");
-  KS_CHECK(type == KS_EPS_KRYLOVSCHUR || type == KS_EPS_LOBPCG || type == KS_EPS_GD, KS_ERR_SUP, "only EPSKRYLOVSCHUR, EPSLOBPCG and EPSGD are built");
+  KS_CHECK(type == KS_EPS_KRYLOVSCHUR || type == KS_EPS_LOBPCG || type == KS_EPS_GD || type == KS_EPS_JD, KS_ERR_SUP, "only EPSKRYLOVSCHUR, EPSLOBPCG, EPSGD and EPSJD are built");
   if (type == eps->type) return KS_SUCCESS;
   eps->type = type; eps->solved = false;
   if (eps->st && eps->st->sigma_inf) { eps->st->sigma_inf = false; eps->st->ready = false; }
-  if (type == KS_EPS_LOBPCG || type == KS_EPS_GD) {
+  if (type == KS_EPS_LOBPCG || type == KS_EPS_GD || type == KS_EPS_JD) {
     ks_st st = nullptr;
     KS_CALL(ks_eps_get_st(eps, &st));
     if (!st->type_set) { st->type = KS_ST_PRECOND; st->ready = false; }

@@ -1,10 +1,15 @@
 // The EPS object and what crosses the files of its driver: ks_eps.hip (the object, the generic set-up, ks_eps_solve, results), ks_krylovschur.hip
-// (both Krylov-Schur variants), ks_lobpcg.hip (LOBPCG), ks_gd.hip (Generalized Davidson) and ks_balance.hip (balancing of non-symmetric problems, the driver's only device code).
+// (both Krylov-Schur variants), ks_lobpcg.hip (LOBPCG), ks_gd.hip (Generalized Davidson), ks_jd.hip (Jacobi-Davidson) and ks_balance.hip (balancing of non-symmetric problems, the driver's only device code).
 #pragma once
 #include "ksgpu_internal.h"
 #include "ks_ds.h"
 
 using ksd::KsCompare;
+
+// the settings of EPS_DAVIDSON that GD and JD share (davidson.h: blocksize, minv, plusk, initialsize, ipB; 0 / -1: the default), what the last set-up
+// resolved them to and the counters of the last solve
+struct KsDavidson { int bs = 0, minv = 0, plusk = -1, initv = 0; bool borth = true; int r_bs = 0, r_minv = 0, r_plusk = 0, r_initv = 0;
+                    long long iterations = 0, restarts = 0, locks = 0, mat_columns = 0, pc_columns = 0, fused_residuals = 0; };
 
 struct ks_eps_s {
   ks_ctx ctx = nullptr;
@@ -57,9 +62,12 @@ struct ks_eps_s {
   ks_bv ini = nullptr; int nini = 0;     // EPSSetInitialSpace: all the vectors (a block solver uses every one; the Krylov solvers use v0, the first)
   // KS_EPS_GD (ks_gd.hip): the settings of EPS_DAVIDSON that GD has (davidson.h: blocksize, minv, plusk, initialsize, ipB; 0 / -1: the default), what the
   // last set-up resolved them to, the counters of the last solve and its projected problem
-  struct { int bs = 0, minv = 0, plusk = -1, initv = 0; bool borth = true; int r_bs = 0, r_minv = 0, r_plusk = 0, r_initv = 0;
-           long long iterations = 0, restarts = 0, locks = 0, mat_columns = 0, pc_columns = 0, fused_residuals = 0; } gd;
+  KsDavidson gd;
   ksd::DsGd dsd;
+  // KS_EPS_JD (ks_jd.hip): its own copy of those settings and counters (jd.c keeps them in the same EPS_DAVIDSON, one solver type at a time; here a
+  // change of type leaves the other type's settings alone), then what only JD has (jd.c: fix, const_correction_tol) and the counters of its inner solves
+  KsDavidson jd;
+  struct { double fix = 0.01; bool const_tol = true; long long inner_solves = 0, inner_iterations = 0, gd_fallbacks = 0; } jdx;
 };
 
 // the callbacks of a solve as every solver calls them (ks_eps.hip)
@@ -79,6 +87,7 @@ struct ks_eps_ops { int (*setup)(ks_eps); int (*solve)(ks_eps); int (*compute_ve
 const ks_eps_ops *ks_krylovschur_ops(bool twosided);                              // ks_krylovschur.hip: the one-sided or the two-sided variant
 const ks_eps_ops *ks_lobpcg_ops();                                                // ks_lobpcg.hip
 const ks_eps_ops *ks_gd_ops();                                                    // ks_gd.hip
+const ks_eps_ops *ks_jd_ops();                                                    // ks_jd.hip
 int eps_setup_common(ks_eps eps, int ncv, ks_mat ip);                             // the generic part of EPSSetUp once a solver knows ncv and its inner product (ks_eps.hip)
 int ks_eps_residual_norm(ks_eps eps, double kr, double ki, const double *xr, const double *xi, double xi_sign, double *out, bool trans = false);   // ks_eps.hip
 int ks_eps_schur_vectors(ks_eps eps);                                             // EPSComputeVectors_Schur on first use of an eigenvector (ks_krylovschur.hip)

@@ -151,18 +151,43 @@ int apply_MP(ks_st st, const double *x, double *out, double *tmp, bool tr = fals
   return blocks_apply(st, st->pcwork, out, tr);
 }
 
-// Left-preconditioned restarted GMRES for P y = rhs (KSPGMRES defaults: restart 30, classical Gram-Schmidt); tr: for P^T y = rhs (KSPSolveTranspose),
-// the same iteration with every application of P and M^-1 on its transposed side - one solve never mixes the two
-int gmres_solve(ks_st st, const double *rhs, double *y, bool tr)
+// The ST's own linear system as the KSPs below see it (KsKspOp, ksgpu_internal.h): M^-1 P with the left preconditioner M of the table above; tr: the
+// transposed side of both. The calls and their order are the ones the two solvers made before they took an operator.
+struct StKspOp : KsKspOp {
+  ks_st st; bool tr; double *t1, *t2;
+  StKspOp(ks_st s, bool t) : st(s), tr(t), t1(ks_bv_col(s->W, 1)), t2(ks_bv_col(s->W, 2)) {}
+  int apply(const double *x, double *out) override { return apply_MP(st, x, out, t1, tr); }
+  int residual(const double *rhs, const double *y, double *out) override
+  {
+    if (!y) return pc_lincomb(st, 1.0, rhs, 0.0, nullptr, out, tr);
+    KS_CALL(apply_P(st, nullptr, y, t1, t2, tr));
+    return pc_lincomb(st, 1.0, rhs, -1.0, t1, out, tr);
+  }
+};
+KsKsp st_ksp(ks_st st) { return KsKsp{st->ctx, (long long)st->n, st->K, st->Kb, st->rtol, st->max_it, st->restart, true, &st->solves, &st->its, &st->last_rnorm}; }
+
+} // namespace
+
+// out = M^-1 P x into column jout of K, then *dot = (e, out): the operator application, then the BVDotVec of that one column (one host wait)
+int KsKspOp::apply_dot(const double *x, double *out, ks_bv K, int jout, const double *e, double *dot)
 {
-  ks_ctx ctx = st->ctx; ks_bv K = st->K;
-  const int m = st->restart;
-  const long long n = st->n;
-  double *t1 = ks_bv_col(st->W, 1), *t2 = ks_bv_col(st->W, 2);
+  KS_CALL(apply(x, out));
+  KS_CALL(ks_bv_set_active_columns(K, jout, jout + 1));
+  return ks_bv_dotvec(K, e, dot);
+}
+
+// Left-preconditioned restarted GMRES for P y = rhs (KSPGMRES defaults: restart 30, classical Gram-Schmidt) on the operator M^-1 P and the residual
+// M^-1 (rhs - P y) of `op`; the ST's transposed solves (KSPSolveTranspose) are the same iteration with an operator on the transposed side. k.strict:
+// failure to converge is an error (the ST); otherwise the iterate reached after max_it iterations is the answer (the Jacobi-Davidson correction).
+int ks_ksp_gmres(const KsKsp &k, KsKspOp &op, const double *rhs, double *y)
+{
+  ks_ctx ctx = k.ctx; ks_bv K = k.K;
+  const int m = k.restart;
+  const long long n = k.n;
   std::vector<double> H((size_t)(m + 1) * m, 0.0), g(m + 1, 0.0), cs(m, 0.0), sn(m, 0.0), h(m + 1, 0.0), yc(m, 0.0);
-  st->solves++;
+  (*k.solves)++;
   KS_HIP(hipMemsetAsync(y, 0, sizeof(double) * std::max<long long>(n, 1), ctx->stream));
-  KS_CALL(pc_lincomb(st, 1.0, rhs, 0.0, nullptr, ks_bv_col(K, 0), tr));
+  KS_CALL(op.residual(rhs, nullptr, ks_bv_col(K, 0)));
   double beta = 0.0;
   const bool split = ks_bv_orthonormalize_can_split(K);
   bool k0_normalised = false, applied0 = false;
@@ -171,13 +196,13 @@ int gmres_solve(ks_st st, const double *rhs, double *y, bool tr)
     // the host learns beta while the product runs
     int lin0 = 0, late0 = 0;
     KS_CALL(ks_bv_orthonormalize_enqueue(K, 0));
-    KS_CALL(apply_MP(st, ks_bv_col(K, 0), ks_bv_col(K, 1), t1, tr));
+    KS_CALL(op.apply(ks_bv_col(K, 0), ks_bv_col(K, 1)));
     KS_CALL(ks_bv_orthonormalize_collect(K, 0, nullptr, &beta, &lin0, &late0));
     k0_normalised = true; applied0 = !late0;
   } else KS_CALL(ks_bv_normcolumn(K, 0, KS_NORM_2, &beta));
-  st->last_rnorm = beta;
-  if (beta == 0.0) return KS_SUCCESS;
-  const double tol = std::max(st->rtol * beta, 1e-50);
+  *k.last_rnorm = beta;
+  if (beta == 0.0 || (!k.strict && !std::isfinite(beta))) return KS_SUCCESS;
+  const double tol = std::max(k.rtol * beta, 1e-50);
   int its = 0;
   for (;;) {
     if (!k0_normalised) KS_CALL(ks_bv_scalecolumn(K, 0, 1.0 / beta));
@@ -187,7 +212,7 @@ int gmres_solve(ks_st st, const double *rhs, double *y, bool tr)
     bool applied = applied0;                        // K(:, j+1) = P K(:, j) already enqueued (speculatively, during the previous iteration)
     applied0 = false;
     for (int j = 0; j < m; j++) {
-      if (!applied) KS_CALL(apply_MP(st, ks_bv_col(K, j), ks_bv_col(K, j + 1), t1, tr));
+      if (!applied) KS_CALL(op.apply(ks_bv_col(K, j), ks_bv_col(K, j + 1)));
       applied = false;
       double hn = 0.0; int lindep = 0;
       if (split) {
@@ -195,14 +220,14 @@ int gmres_solve(ks_st st, const double *rhs, double *y, bool tr)
         // is not idle while the host rotates and tests (30 us per iteration in the trace, profiles/r02_config5_kernel_trace_gaps.txt) - but only
         // when the residual history says another iteration is coming: a product wasted on the last iteration costs more than the gaps of a solve.
         const double predicted = (j == 0) ? res : res * std::min(1.0, res / res_before);
-        const bool spec = (j + 1 < m) && (its + 1 < st->max_it) && predicted > 3.0 * tol;
+        const bool spec = (j + 1 < m) && (its + 1 < k.max_it) && predicted > 3.0 * tol;
         int late = 0;
         KS_CALL(ks_bv_orthonormalize_enqueue(K, j + 1));
-        if (spec) KS_CALL(apply_MP(st, ks_bv_col(K, j + 1), ks_bv_col(K, j + 2), t1, tr));
+        if (spec) KS_CALL(op.apply(ks_bv_col(K, j + 1), ks_bv_col(K, j + 2)));
         KS_CALL(ks_bv_orthonormalize_collect(K, j + 1, h.data(), &hn, &lindep, &late));
         applied = spec && !late;                    // a column completed late was multiplied unfinished: apply again
       } else KS_CALL(ks_bv_orthonormalize_coefs(K, j + 1, h.data(), &hn, &lindep));       // the 1/hn scaling rides in the final update; h, hn and the flag arrive in one host wait
-      its++; st->its++;
+      its++; (*k.its)++;
       h[j + 1] = hn;
       for (int i = 0; i < j; i++) { const double t = cs[i] * h[i] + sn[i] * h[i + 1]; h[i + 1] = -sn[i] * h[i] + cs[i] * h[i + 1]; h[i] = t; }
       const double r = hypot(h[j], h[j + 1]);
@@ -211,7 +236,7 @@ int gmres_solve(ks_st st, const double *rhs, double *y, bool tr)
       g[j + 1] = -sn[j] * g[j]; g[j] = cs[j] * g[j];
       for (int i = 0; i <= j; i++) H[(size_t)i + (size_t)j * (m + 1)] = h[i];
       res_before = res; res = fabs(g[j + 1]); jj = j + 1;
-      if (res <= tol || its >= st->max_it || lindep || hn == 0.0) break;
+      if (res <= tol || its >= k.max_it || lindep || hn == 0.0) break;
     }
     for (int i = jj - 1; i >= 0; i--) {                     // back substitution R yc = g
       double t = g[i];
@@ -221,15 +246,15 @@ int gmres_solve(ks_st st, const double *rhs, double *y, bool tr)
     }
     KS_CALL(ks_bv_set_active_columns(K, 0, jj));
     KS_CALL(ks_bv_multvec(K, 1.0, 1.0, y, yc.data()));
-    st->last_rnorm = res;
+    *k.last_rnorm = res;
     if (res <= tol) break;
-    KS_CHECK(its < st->max_it, KS_ERR_NOT_CONVERGED, "KSPSolve has not converged: GMRES reached %d iterations, preconditioned residual %g > %g", its, res, tol);
+    if (!k.strict && its >= k.max_it) break;
+    KS_CHECK(its < k.max_it, KS_ERR_NOT_CONVERGED, "KSPSolve has not converged: GMRES reached %d iterations, preconditioned residual %g > %g", its, res, tol);
     // restart from the true preconditioned residual
-    KS_CALL(apply_P(st, nullptr, y, t1, t2, tr));
-    KS_CALL(pc_lincomb(st, 1.0, rhs, -1.0, t1, ks_bv_col(K, 0), tr));
+    KS_CALL(op.residual(rhs, y, ks_bv_col(K, 0)));
     KS_CALL(ks_bv_normcolumn(K, 0, KS_NORM_2, &beta));
-    st->last_rnorm = beta;
-    if (beta <= tol) break;
+    *k.last_rnorm = beta;
+    if (beta <= tol || (!k.strict && !std::isfinite(beta))) break;
   }
   return KS_SUCCESS;
 }
@@ -237,40 +262,41 @@ int gmres_solve(ks_st st, const double *rhs, double *y, bool tr)
 // Left-preconditioned BiCGStab for P y = rhs (KSPBCGS with PC_LEFT: the iteration runs on D^-1 P, the residual that is tested
 // is the preconditioned one, as for the GMRES above). Two operator applications per iteration, no growing basis: the
 // memory is 7 vectors whatever the iteration count. The dot products of one phase travel in one BVDotVec (one allreduce).
-int bcgs_solve(ks_st st, const double *rhs, double *y, bool tr)
+// Not strict: a breakdown or the iteration limit ends the solve with the iterate it has.
+int ks_ksp_bcgs(const KsKsp &k, KsKspOp &op, const double *rhs, double *y)
 {
-  ks_ctx ctx = st->ctx; ks_bv K = st->Kb;
-  const long long n = st->n;
-  double *t1 = ks_bv_col(st->W, 1);
+  ks_ctx ctx = k.ctx; ks_bv K = k.Kb;
+  const long long n = k.n;
   double *r = ks_bv_col(K, 0), *rh = ks_bv_col(K, 1), *p = ks_bv_col(K, 2), *v = ks_bv_col(K, 3), *s = ks_bv_col(K, 4), *t = ks_bv_col(K, 5);
-  st->solves++;
+  (*k.solves)++;
   KS_HIP(hipMemsetAsync(y, 0, sizeof(double) * std::max<long long>(n, 1), ctx->stream));
-  KS_CALL(pc_lincomb(st, 1.0, rhs, 0.0, nullptr, r, tr));                   // r = D^-1 b (zero initial guess)
+  KS_CALL(op.residual(rhs, nullptr, r));                                    // r = D^-1 b (zero initial guess)
   double beta0 = 0.0;
   KS_CALL(ks_bv_normcolumn(K, 0, KS_NORM_2, &beta0));
-  st->last_rnorm = beta0;
-  if (beta0 == 0.0) return KS_SUCCESS;
-  const double tol = std::max(st->rtol * beta0, 1e-50);
+  *k.last_rnorm = beta0;
+  if (beta0 == 0.0 || (!k.strict && !std::isfinite(beta0))) return KS_SUCCESS;
+  const double tol = std::max(k.rtol * beta0, 1e-50);
   KS_CALL(ksk_copy(ctx, r, rh, n));
   KS_HIP(hipMemsetAsync(p, 0, sizeof(double) * n, ctx->stream));
   KS_HIP(hipMemsetAsync(v, 0, sizeof(double) * n, ctx->stream));
   double rho = 1.0, alpha = 1.0, omega = 1.0, d[2];
   for (int its = 0; ; its++) {
-    KS_CHECK(its < st->max_it, KS_ERR_NOT_CONVERGED, "KSPSolve has not converged: BiCGStab reached %d iterations, preconditioned residual %g > %g", its, st->last_rnorm, tol);
+    if (!k.strict && its >= k.max_it) break;
+    KS_CHECK(its < k.max_it, KS_ERR_NOT_CONVERGED, "KSPSolve has not converged: BiCGStab reached %d iterations, preconditioned residual %g > %g", its, *k.last_rnorm, tol);
     KS_CALL(ks_bv_set_active_columns(K, 0, 1));
     KS_CALL(ks_bv_dotvec(K, rh, d));                                                 // rho' = (rhat, r)
     const double rho_new = d[0];
+    if (!k.strict && (rho_new == 0.0 || omega == 0.0 || !std::isfinite(rho_new))) break;
     KS_CHECK(rho_new != 0.0 && omega != 0.0, KS_ERR_NOT_CONVERGED, "KSPSolve has not converged: BiCGStab breakdown (rho = %g, omega = %g)", rho_new, omega);
     const double bt = (rho_new / rho) * (alpha / omega);
     KS_CALL(lincomb(ctx, n, nullptr, 1.0, p, -omega, v, p));                         // p = r + beta (p - omega v)
     KS_CALL(lincomb(ctx, n, nullptr, bt, p, 1.0, r, p));
-    KS_CALL(apply_MP(st, p, v, t1, tr));                                                // v = D^-1 P p
-    KS_CALL(ks_bv_set_active_columns(K, 3, 4));
-    KS_CALL(ks_bv_dotvec(K, rh, d));                                                 // (rhat, v)
+    KS_CALL(op.apply_dot(p, v, K, 3, rh, d));                                        // v = D^-1 P p, (rhat, v)
+    if (!k.strict && (d[0] == 0.0 || !std::isfinite(d[0]))) break;
     KS_CHECK(d[0] != 0.0, KS_ERR_NOT_CONVERGED, "KSPSolve has not converged: BiCGStab breakdown ((rhat,v) = 0)");
     alpha = rho_new / d[0];
     KS_CALL(lincomb(ctx, n, nullptr, 1.0, r, -alpha, v, s));                         // s = r - alpha v
-    KS_CALL(apply_MP(st, s, t, t1, tr));                                                // t = D^-1 P s
+    KS_CALL(op.apply(s, t));                                                         // t = D^-1 P s
     KS_CALL(ks_bv_set_active_columns(K, 4, 6));
     KS_CALL(ks_bv_dotvec(K, t, d));                                                  // (s,t), (t,t) in one reduction
     omega = d[1] != 0.0 ? d[0] / d[1] : 0.0;
@@ -278,14 +304,18 @@ int bcgs_solve(ks_st st, const double *rhs, double *y, bool tr)
     KS_CALL(lincomb(ctx, n, nullptr, 1.0, y, omega, s, y));
     KS_CALL(lincomb(ctx, n, nullptr, 1.0, s, -omega, t, r));                         // r = s - omega t
     rho = rho_new;
-    st->its++;
+    (*k.its)++;
     double rn = 0.0;
     KS_CALL(ks_bv_normcolumn(K, 0, KS_NORM_2, &rn));
-    st->last_rnorm = rn;
+    *k.last_rnorm = rn;
     if (rn <= tol) break;
   }
   return KS_SUCCESS;
 }
+
+namespace {
+int gmres_solve(ks_st st, const double *rhs, double *y, bool tr) { StKspOp op(st, tr); return ks_ksp_gmres(st_ksp(st), op, rhs, y); }
+int bcgs_solve(ks_st st, const double *rhs, double *y, bool tr) { StKspOp op(st, tr); return ks_ksp_bcgs(st_ksp(st), op, rhs, y); }
 int inner_solve(ks_st st, const double *rhs, double *y, bool tr = false) { return st->ksp_type == KS_KSP_BCGS ? bcgs_solve(st, rhs, y, tr) : gmres_solve(st, rhs, y, tr); }
 
 int st_shell_mult(void *user, const double *x, double *y) { return ks_st_apply_internal((ks_st)user, x, y); }
@@ -529,8 +559,8 @@ extern "C" int ks_st_get_matmode(ks_st st, int *mode) { KS_CHECK(st && mode, KS_
 extern "C" int ks_st_set_ksp(ks_st st, double rtol, int max_it, int restart)   // KSPSetTolerances / KSPGMRESSetRestart on STGetKSP
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  if (rtol > 0.0) st->rtol = rtol;
-  if (max_it > 0) st->max_it = max_it;
+  if (rtol > 0.0) { st->rtol = rtol; st->rtol_set = true; }
+  if (max_it > 0) { st->max_it = max_it; st->max_it_set = true; }
   if (restart > 0 && restart != st->restart) { st->restart = restart; st->ready = false; }   // a basis wider than 64 columns orthogonalises through the host-driven loop
   return KS_SUCCESS;
 }
@@ -539,6 +569,7 @@ extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
   KS_CHECK(type == KS_KSP_GMRES || type == KS_KSP_BCGS, KS_ERR_SUP, "only KSPGMRES and KSPBCGS are built");
   if (st->ksp_type != type) { st->ksp_type = type; st->ready = false; }
+  st->ksp_type_set = true;
   return KS_SUCCESS;
 }
 extern "C" int ks_st_set_pc(ks_st st, int type, int block_size)       // PCSetType (+ PCBJacobiSetLocalBlocks, -sub_pc_type lu | ilu) on the KSP's PC
@@ -608,6 +639,11 @@ int ks_st_pc_apply_multi_internal(ks_st st, int ncols, const double *X, int ldx,
   else hipLaunchKernelGGL(k_diag_apply_multi, dim3(nb, (unsigned)ncols), dim3(256), 0, st->ctx->stream, (long long)st->n, pc_none(st) ? (const double *)nullptr : st->dinv, X, (long long)ldx, Y, (long long)ldy);
   KS_HIP(hipGetLastError());
   return KS_SUCCESS;
+}
+bool ks_st_pc_pointwise(ks_st st, const double **dinv)
+{
+  *dinv = (!pc_none(st) && st->pc_type == KS_PC_JACOBI) ? st->dinv : nullptr;
+  return pc_none(st) || st->pc_type == KS_PC_JACOBI;
 }
 extern "C" int ks_st_pc_apply_multi(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy)
 {

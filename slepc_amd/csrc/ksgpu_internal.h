@@ -290,6 +290,7 @@ struct ks_st_s {
   ks_mat A = nullptr, B = nullptr;            // borrowed
   double rtol = 1e-8; int max_it = 10000, restart = 30;   // KSP: SLEPC_DEFAULT_TOL (stsles.c:407), PETSc defaults
   int ksp_type = KS_KSP_GMRES;                // KSPGMRES (the default of the shell matrix mode) or KSPBCGS
+  bool ksp_type_set = false, rtol_set = false, max_it_set = false;   // chosen by the caller (ks_st_set_ksp_type, ks_st_set_ksp): a solver with KSP defaults of its own (JD) keeps off those
   int gmres_refine = KS_BV_ORTHOG_REFINE_NEVER;   // KSPGMRESSetCGSRefinementType: PETSc's default is classical Gram-Schmidt without refinement
   ks_bv Kb = nullptr;                         // BiCGStab work vectors (7 columns)
   ks_bv K = nullptr, W = nullptr;             // GMRES basis (restart+1 columns), work vectors (3 columns)
@@ -313,6 +314,20 @@ int ks_st_setup_internal(ks_st st);
 int ks_st_apply_internal(ks_st st, const double *x, double *y);
 int ks_st_pc_apply_multi_internal(ks_st st, int ncols, const double *X, int ldx, double *Y, int ldy);   // set-up done, arguments checked by the caller
 void ks_st_backtransform_internal(ks_st st, int n, double *eigr, double *eigi);
+// The two KSPs of the ST (ks_st.hip) on any left-preconditioned operator: the ST's own M^-1 P, or the projected operator of the Jacobi-Davidson
+// correction equation (ks_jd.hip). An operator says how M^-1 P x and the preconditioned residual are formed; the iterations are one copy.
+struct KsKspOp {
+  virtual ~KsKspOp() {}
+  virtual int apply(const double *x, double *out) = 0;                              // out = M^-1 P x (enqueued)
+  virtual int residual(const double *rhs, const double *y, double *out) = 0;        // out = M^-1 (rhs - P y); y NULL: out = M^-1 rhs
+  // out = M^-1 P x, out being column jout of K, and *dot = (e, out) on the host: the application followed by BVDotVec unless the operator has the two in one
+  virtual int apply_dot(const double *x, double *out, ks_bv K, int jout, const double *e, double *dot);
+};
+// K: GMRES basis (restart + 1 columns), Kb: BiCGStab's 7 vectors (the one the type needs); strict: not converging or breaking down is KS_ERR_NOT_CONVERGED
+struct KsKsp { ks_ctx ctx; long long n; ks_bv K, Kb; double rtol; int max_it, restart; bool strict; long long *solves, *its; double *last_rnorm; };
+int ks_ksp_gmres(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);
+int ks_ksp_bcgs(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);
+bool ks_st_pc_pointwise(ks_st st, const double **dinv);   // set-up done. true: no preconditioner (*dinv NULL) or point Jacobi (*dinv its diagonal); false: blocks (ks_st_pc_apply_multi_internal)
 int ksk_lincomb(ks_ctx ctx, long long n, const double *s, double a, const double *u, double b, const double *v, double *out);   // out = s.*(a*u + b*v)   // diagonal of the local diagonal block (MatGetDiagonal)
 
 // ---- BV -----------------------------------------------------------------------------------------
