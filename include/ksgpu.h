@@ -633,8 +633,11 @@ int ks_st_set_matrices(ks_st st, ks_mat A, ks_mat B /* may be NULL */);   /* STS
 #define KS_ST_MATMODE_SHELL 2
 int ks_st_set_matmode(ks_st st, int mode);
 int ks_st_get_matmode(ks_st st, int *mode);
-enum { KS_KSP_GMRES = 0, KS_KSP_BCGS = 1 };
-int ks_st_set_ksp_type(ks_st st, int type);                                /* KSPSetType on STGetKSP: GMRES (restarted, the shell mode's default) or BiCGStab; both with Jacobi on the left */
+/* KS_KSP_PREONLY is KSPPREONLY: the solve is ONE application of the preconditioner - no residual, no convergence test, no Krylov basis - which is
+   exact with KS_PC_LU (the reference's default pair, -st_ksp_type preonly -st_pc_type lu) and allowed with every PC type, as in PETSc.
+   ks_st_get_ksp_stats counts one solve and one iteration per application and leaves last_rnorm alone. */
+enum { KS_KSP_GMRES = 0, KS_KSP_BCGS = 1, KS_KSP_PREONLY = 2 };
+int ks_st_set_ksp_type(ks_st st, int type);                                /* KSPSetType on STGetKSP: GMRES (restarted, the shell mode's default), BiCGStab - both preconditioned on the left - or PREONLY */
 /* KSPGMRESSetCGSRefinementType on STGetKSP, with the BV constants: KS_BV_ORTHOG_REFINE_NEVER (PETSc's default for KSPGMRES: one pass of
    classical Gram-Schmidt, then the norm), _IFNEEDED (PETSc's test is the BV's, eta 0.7071) or _ALWAYS */
 int ks_st_set_gmres_cgs_refinement(ks_st st, int refine);
@@ -653,7 +656,35 @@ int ks_st_set_gmres_cgs_refinement(ks_st st, int refine);
 #define KS_PC_BJACOBI 1
 #define KS_PC_BJACOBI_ILU 2
 #define KS_PC_NONE 3         /* -st_pc_type none: M = I; takes block_size 0 (anything else is KS_ERR_SUP: there is no blocked form of it) */
+/* KS_PC_LU - PCLU (PETSc's built-in sequential sparse LU, the reference's default inner solver with KSPPREONLY: stsles.c, -st_pc_type lu): the whole
+   P = A - sigma B (or B, for a shift with two matrices) is factored WITH fill on the host, Q P Q^T = L U, under a nested dissection ordering Q
+   applied symmetrically and without pivoting (-pc_factor_mat_ordering_type nd, PCLU's default); the application y = Q^T U^-1 L^-1 Q x runs on
+   the device level by level. Takes block_size 0 (anything else is KS_ERR_SUP, as for KS_PC_NONE). At set-up: the matrices must hold their CSR
+   arrays (KS_MAT_KEEP_CSR; KS_ERR_ORDER); more than one rank is KS_ERR_SUP (PETSc's built-in LU is sequential as well); a zero pivot is
+   KS_ERR_MAT_LU_ZRPVT with the original row in the message; factors with more than 2^31 - 1 stored entries, or a failed host or device
+   allocation, are KS_ERR_MEM with nothing left half-built. With ks_st_set_transpose_solves a second plan of the same factors serves
+   y = Q^T L^-T U^-T Q x. The default preconditioner stays point Jacobi. */
+#define KS_PC_LU 4
 int ks_st_set_pc(ks_st st, int type, int block_size);
+/* -pc_factor_mat_ordering_type on the PCLU: KS_ORDERING_ND (the default, as PCLU's: George's automatic nested dissection on rooted level structures
+   of the graph of P + P^T, MATORDERINGND) or KS_ORDERING_NATURAL; any other value is KS_ERR_ARG_OUTOFRANGE. Changing it clears the set-up. */
+#define KS_ORDERING_ND      0
+#define KS_ORDERING_NATURAL 1
+int ks_st_pc_lu_set_ordering(ks_st st, int which);
+int ks_st_pc_lu_get_ordering_type(ks_st st, int *which);
+/* The row permutation of the factorisation (MatGetOrdering / ISGetIndices on the PCLU's ordering): perm_host[i] (n ints, host memory) is the original
+   row eliminated i-th. Runs the set-up if needed; KS_ERR_ORDER when the PC is not KS_PC_LU or the transformation has no solve. */
+int ks_st_pc_lu_get_permutation(ks_st st, int *perm_host);
+/* MatGetInfo on the factor (nz_used, PCFactor's fill) plus this library's schedule. Any pointer may be NULL. n; nnz_l: stored entries of L without its
+   unit diagonal; nnz_u: of U with the diagonal; levels_l, levels_u: levels of the two triangular solves; wide: the threshold in rows from which a
+   level is a launch of its own; wide_launches, narrow_launches: launches of the two kinds per forward application (both triangles); device_bytes:
+   everything the preconditioner holds on the device (the transposed plan included). Runs the set-up if needed; errors as above. */
+int ks_st_pc_lu_get_info(ks_st st, int *n, long long *nnz_l, long long *nnz_u, int *levels_l, int *levels_u, int *wide, int *wide_launches, int *narrow_launches,
+                         long long *device_bytes);
+/* MatGetInertia on the factor: the numbers of negative and positive pivots u_rr; *zero is always 0, a zero pivot having failed the set-up. This is the
+   inertia of P = A - sigma B ONLY WHEN P IS SYMMETRIC (Sylvester's law applied to L D L^T = L U); for a non-symmetric P the counts are just the signs of
+   the pivots. Runs the set-up if needed; errors as above. */
+int ks_st_pc_lu_get_inertia(ks_st st, int *neg, int *zero, int *pos);
 int ks_st_set_ksp(ks_st st, double rtol, int max_it, int restart);        /* KSPSetTolerances / KSPGMRESSetRestart on STGetKSP; 0 keeps */
 int ks_st_setup(ks_st st);                                                /* STSetUp */
 int ks_st_apply(ks_st st, const double *x_dev, double *y_dev);            /* STApply stsolve.c:44 */
@@ -684,12 +715,12 @@ int ks_st_matsolve_transpose(ks_st st, const double *b_dev, double *y_dev);
    Same errors as ks_st_matsolve_transpose. Enqueued on the context's stream, no host wait. */
 int ks_st_pc_apply_transpose(ks_st st, const double *x_dev, double *y_dev);
 /* PCApply on KSPGetPC(STGetKSP) (the KSP of stsles.c:51-58; PCApply itself is PETSc's, external to the reference): y = M^-1 x with the
-   preconditioner of the inner solves, whichever of the three types is set. Runs STSetUp if needed; x == y is KS_ERR_ARG_IDN; a transformation
+   preconditioner of the inner solves, whichever type is set. Runs STSetUp if needed; x == y is KS_ERR_ARG_IDN; a transformation
    without a linear solve (STSHIFT with one matrix) has no preconditioner: KS_ERR_ORDER. Enqueued on the context's stream, no host wait. */
 int ks_st_pc_apply(ks_st st, const double *x_dev, double *y_dev);
 /* KS_ST_PRECOND (STPRECOND, src/sys/classes/st/impls/precond/precond.c): the ST of the preconditioned eigensolvers. ks_st_apply gives y = M^-1 x with the
    preconditioner M built on K = A - sigma B, sigma the shift, or the EPS's target when none was set (precond.c:65); the KSP is preonly, nothing is
-   solved. Default PC: point Jacobi (what the shell matrix mode defaults to, precond.c:30); all four PC types work. ks_st_backtransform leaves values alone.
+   solved. Default PC: point Jacobi (what the shell matrix mode defaults to, precond.c:30); every PC type works, KS_PC_LU being the exact K^-1. ks_st_backtransform leaves values alone.
    PCMatApply on KSPGetPC(STGetKSP): Y(:,j) = M^-1 X(:,j), j < ncols (X(:,j) at X_dev + j*ldx, Y(:,j) at Y_dev + j*ldy), every column bit for bit
    ks_st_pc_apply of that column. Point Jacobi, PCNONE and the dense blocks run their single-vector kernels with the column on the grid; the ILU(0)
    blocks of up to 512 rows keep eight right-hand sides of a block in LDS at once, read every factor entry once for all of them and pay one barrier
@@ -698,7 +729,7 @@ int ks_st_pc_apply(ks_st st, const double *x_dev, double *y_dev);
    Arguments as ks_mat_mult_multi: ncols == 0 does nothing, ldx, ldy >= max(1, n_local) (KS_ERR_ARG_SIZ), X and Y must not overlap
    (KS_ERR_ARG_WRONG). Enqueued, no host wait. */
 int ks_st_pc_apply_multi(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy);
-int ks_st_pc_multi_columns(ks_st st, int *columns);   /* instrumentation: columns of one pass of the above with the PC as set up (ILU blocks: 8 up to block size 512, 1 above; the other types: 65535, one launch) */
+int ks_st_pc_multi_columns(ks_st st, int *columns);   /* instrumentation: columns of one pass of the above with the PC as set up (ILU blocks: 8 up to block size 512, 1 above; KS_PC_LU: 8 - a narrow stage of the schedule keeps eight right-hand sides in one launch, a wide level puts them on the grid; the other types: 65535, one launch) */
 /* STApplyMat stsolve.c:62: Y(:,j) = Op X(:,j). KS_ST_PRECOND: ks_st_pc_apply_multi; the other transformations: ks_st_apply column by column. Same arguments. */
 int ks_st_apply_mat(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy);
 int ks_st_backtransform(ks_st st, int n, double *eigr, double *eigi);     /* STBackTransform stsolve.c:563 */

@@ -30,6 +30,12 @@ def cycle(i):
     d = 1.0 + 0.5 * np.cos(np.arange(Lo.n)) ** 2
     B = ks.Mat.from_csr(ctx, np.arange(Lo.n + 1, dtype=np.int32), np.arange(Lo.n, dtype=np.int32), d)
     e3 = ks.EPS(ctx); e3.SetOperators(L, B); e3.SetProblemType(ks.EPS_GHEP); e3.SetDimensions(3, 16); e3.GetST().SetKSP(rtol=1e-13); e3.Solve()
+    # the LU factors of P = L - sigma B with their transposed plan: set up, applied, set up again by a new shift and a new ordering
+    Lk = ks.Mat.from_csr(ctx, Lo.rowptr, Lo.col, Lo.val, keep_csr=True)
+    Bk = ks.Mat.from_csr(ctx, np.arange(Lo.n + 1, dtype=np.int32), np.arange(Lo.n, dtype=np.int32), d, keep_csr=True)
+    slu = ks.ST(ctx); slu.SetType("sinvert"); slu.SetShift(1.3); slu.SetMatrices(Lk, Bk); slu.SetPC("lu"); slu.SetKSPType("preonly"); slu.SetTransposeSolves(True)
+    slu.Apply(np.ones(Lo.n)); slu.SetShift(2.1 + 0.01 * i); slu.ApplyTranspose(np.ones(Lo.n)); slu.PCLUSetOrdering("natural"); slu.PCApply(np.ones(Lo.n))
+    del slu, Lk, Bk
     V = ks.BV(ctx, 3000, 90); V.set_dense(np.random.default_rng(i).standard_normal((3000, 90)))
     V.SetOrthogBlock(["chol", "svqb", "gs", "tsqr"][i % 4])
     if i % 4 == 3:

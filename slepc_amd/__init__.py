@@ -851,8 +851,37 @@ class ST:
 
     def SetPC(self, t, block_size=0):
         """PCSetType on the ST's KSP: "jacobi" (default), "bjacobi" with blocks of block_size (2..32) consecutive local rows, solved exactly, or
-        "bjacobi-ilu" with blocks of block_size (64..8192) rows, each factored by ILU(0), or "none"."""
-        _lib.check(self.ctx.L.ks_st_set_pc(self.h, {"jacobi": 0, "bjacobi": 1, "bjacobi-ilu": 2, "none": 3}.get(t, t), block_size))
+        "bjacobi-ilu" with blocks of block_size (64..8192) rows, each factored by ILU(0), "none", or "lu": the whole P factored with fill under a
+        nested dissection ordering (PCLU; block_size 0, the matrices need keep_csr, one rank)."""
+        _lib.check(self.ctx.L.ks_st_set_pc(self.h, {"jacobi": 0, "bjacobi": 1, "bjacobi-ilu": 2, "none": 3, "lu": 4}.get(t, t), block_size))
+
+    def PCLUSetOrdering(self, which):
+        """-pc_factor_mat_ordering_type of the PCLU: "nd" (default) or "natural"."""
+        _lib.check(self.ctx.L.ks_st_pc_lu_set_ordering(self.h, {"nd": 0, "natural": 1}.get(which, which)))
+
+    def PCLUGetOrdering(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_st_pc_lu_get_ordering_type(self.h, C.byref(v))); return {0: "nd", 1: "natural"}[v.value]
+
+    def PCLUGetInfo(self):
+        """The factors and their schedule as a dict: n, nnz_l (without the unit diagonal), nnz_u (with the diagonal), levels_l, levels_u, wide (the
+        threshold in rows), wide_launches, narrow_launches (per forward application), device_bytes. Runs the set-up if needed."""
+        n, ll, lu, w, wl, nl = (C.c_int() for _ in range(6)); zl, zu, by = (C.c_longlong() for _ in range(3))
+        _lib.check(self.ctx.L.ks_st_pc_lu_get_info(self.h, C.byref(n), C.byref(zl), C.byref(zu), C.byref(ll), C.byref(lu), C.byref(w), C.byref(wl), C.byref(nl), C.byref(by)))
+        return {"n": n.value, "nnz_l": zl.value, "nnz_u": zu.value, "levels_l": ll.value, "levels_u": lu.value, "wide": w.value,
+                "wide_launches": wl.value, "narrow_launches": nl.value, "device_bytes": by.value}
+
+    def PCLUGetPermutation(self):
+        """perm[i] = the original row eliminated i-th (numpy int32). Runs the set-up if needed."""
+        n = self.PCLUGetInfo()["n"]
+        perm = np.zeros(max(n, 1), dtype=np.int32)
+        _lib.check(self.ctx.L.ks_st_pc_lu_get_permutation(self.h, perm.ctypes.data_as(C.POINTER(C.c_int))))
+        return perm[:n]
+
+    def PCLUGetInertia(self):
+        """(neg, zero, pos): the signs of the pivots - the inertia of P when P is symmetric. zero is always 0 (a zero pivot fails the set-up)."""
+        a, z, b = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self.ctx.L.ks_st_pc_lu_get_inertia(self.h, C.byref(a), C.byref(z), C.byref(b)))
+        return a.value, z.value, b.value
 
     def SetMatMode(self, mode):
         """STSetMatMode: "shell" (default here) or "copy" (P = A - sigma B assembled; the matrices need keep_csr)."""
@@ -862,8 +891,8 @@ class ST:
         v = C.c_int(); _lib.check(self.ctx.L.ks_st_get_matmode(self.h, C.byref(v))); return {0: "copy", 2: "shell"}[v.value]
 
     def SetKSPType(self, t):
-        """KSPSetType on the ST's KSP: "gmres" (default) or "bcgs"."""
-        _lib.check(self.ctx.L.ks_st_set_ksp_type(self.h, {"gmres": 0, "bcgs": 1}.get(t, t)))
+        """KSPSetType on the ST's KSP: "gmres" (default), "bcgs", or "preonly" (one application of the preconditioner: exact with SetPC("lu"))."""
+        _lib.check(self.ctx.L.ks_st_set_ksp_type(self.h, {"gmres": 0, "bcgs": 1, "preonly": 2}.get(t, t)))
 
     def SetUp(self):
         _lib.check(self.ctx.L.ks_st_setup(self.h))

@@ -241,6 +241,11 @@ _SIG = {
     "ks_st_set_matmode": [vp, C.c_int],
     "ks_st_set_pc": [vp, C.c_int, C.c_int],
     "ks_st_set_gmres_cgs_refinement": [vp, C.c_int],
+    "ks_st_pc_lu_set_ordering": [vp, C.c_int],
+    "ks_st_pc_lu_get_ordering_type": [vp, ip],
+    "ks_st_pc_lu_get_permutation": [vp, ip],
+    "ks_st_pc_lu_get_info": [vp, ip, llp, llp, ip, ip, ip, ip, ip, llp],
+    "ks_st_pc_lu_get_inertia": [vp, ip, ip, ip],
     "ks_st_get_matmode": [vp, C.POINTER(C.c_int)],
     "ks_st_setup": [vp],
     "ks_st_apply": [vp, vp, vp],

@@ -1,5 +1,6 @@
 #include "ks_csr.h"
 #include <algorithm>
+#include <functional>
 #include <thread>
 #include <sched.h>
 #include <system_error>
@@ -458,6 +459,274 @@ void ilu0_walk_host(const IluPlan &p, int n, int bs, bool first_scaled, const do
 } // namespace
 void ilu0_apply_host(const IluPlan &p, int n, int bs, const double *in, double *out) { ilu0_walk_host(p, n, bs, false, in, out); }
 void ilu0_apply_transpose_host(const IluPlan &t, int n, int bs, const double *in, double *out) { ilu0_walk_host(t, n, bs, true, in, out); }
+
+// ---- sparse LU with fill (KS_PC_LU) -------------------------------------------------------------------------------------------------------
+namespace {
+// the rows of P sorted by column, repeated entries summed in stored order, the diagonal position always there (0.0 when the row stores none)
+void lu_sorted_rows(int n, const int *rp, const int *col, const double *val, std::vector<int> &srp, std::vector<int> &scol, std::vector<double> &sval)
+{
+  srp.assign((size_t)n + 1, 0); scol.clear(); sval.clear();
+  std::vector<int> idx;
+  for (int r = 0; r < n; r++) {
+    idx.clear();
+    for (int p = rp[r]; p < rp[r + 1]; p++) if (col[p] >= 0 && col[p] < n) idx.push_back(p);
+    std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return col[x] < col[y]; });
+    bool has_diag = false;
+    for (size_t i = 0; i < idx.size(); i++) {
+      const int c = col[idx[i]];
+      if (i > 0 && c == col[idx[i - 1]]) { sval.back() = sval.back() + val[idx[i]]; continue; }
+      if (!has_diag && c > r) { scol.push_back(r); sval.push_back(0.0); has_diag = true; }
+      if (c == r) has_diag = true;
+      scol.push_back(c); sval.push_back(val[idx[i]]);
+    }
+    if (!has_diag) { scol.push_back(r); sval.push_back(0.0); }
+    srp[r + 1] = (int)scol.size();
+  }
+}
+
+// the rooted level structure of `root` inside the nodes with owner[v] == id: order = the nodes level by level, lstart = where the levels start
+struct LevelStructure { std::vector<int> order, lstart; int levels() const { return (int)lstart.size() - 1; } };
+void rooted_levels(int root, int id, const std::vector<int> &xadj, const std::vector<int> &adj, const std::vector<int> &owner, std::vector<int> &stamp, int &tick, LevelStructure &out)
+{
+  out.order.clear(); out.lstart.assign(1, 0);
+  tick++;
+  out.order.push_back(root); stamp[root] = tick;
+  size_t done = 0;
+  while (done < out.order.size()) {
+    const size_t end = out.order.size();
+    out.lstart.push_back((int)end);
+    for (; done < end; done++) {
+      const int v = out.order[done];
+      for (int p = xadj[v]; p < xadj[v + 1]; p++) { const int u = adj[p]; if (owner[u] == id && stamp[u] != tick) { stamp[u] = tick; out.order.push_back(u); } }
+    }
+  }
+}
+
+void nested_dissection(int n, const std::vector<int> &xadj, const std::vector<int> &adj, std::vector<int> &perm)
+{
+  struct Task { bool emit; int id; std::vector<int> nodes; };
+  perm.clear(); perm.reserve((size_t)n);
+  std::vector<int> owner((size_t)n, 0), stamp((size_t)n, 0);
+  int next_id = 1, tick = 0;
+  std::vector<Task> stack, todo;
+  { Task all{false, 0, {}}; all.nodes.resize((size_t)n); for (int i = 0; i < n; i++) all.nodes[i] = i; stack.push_back(std::move(all)); }
+  LevelStructure cur, cand;
+  while (!stack.empty()) {
+    Task t = std::move(stack.back()); stack.pop_back();
+    if (t.emit) { perm.insert(perm.end(), t.nodes.begin(), t.nodes.end()); continue; }
+    todo.clear();
+    for (int v0 : t.nodes) {                                   // ascending: the components come in the order of their smallest nodes
+      if (owner[v0] != t.id) continue;
+      // the component of v0: its level structure from v0, the smallest node, finds it
+      rooted_levels(v0, t.id, xadj, adj, owner, stamp, tick, cur);
+      const int cid = next_id++;
+      std::vector<int> comp(cur.order);
+      std::sort(comp.begin(), comp.end());
+      for (int v : comp) owner[v] = cid;
+      if (comp.size() <= 8) { todo.push_back(Task{true, 0, std::move(comp)}); continue; }
+      for (int round = 0; round < 5; round++) {
+        int best = -1, best_deg = 0;
+        for (int p = cur.lstart[cur.levels() - 1]; p < cur.lstart[cur.levels()]; p++) {
+          const int v = cur.order[p];
+          int deg = 0;
+          for (int q = xadj[v]; q < xadj[v + 1]; q++) deg += owner[adj[q]] == cid;
+          if (best < 0 || deg < best_deg || (deg == best_deg && v < best)) { best = v; best_deg = deg; }
+        }
+        rooted_levels(best, cid, xadj, adj, owner, stamp, tick, cand);
+        if (cand.levels() <= cur.levels()) break;
+        std::swap(cur, cand);
+      }
+      if (cur.levels() < 3) { todo.push_back(Task{true, 0, std::move(comp)}); continue; }
+      const int mid = cur.levels() / 2;
+      std::vector<int> sep(cur.order.begin() + cur.lstart[mid], cur.order.begin() + cur.lstart[mid + 1]), rest;
+      std::sort(sep.begin(), sep.end());
+      for (int v : sep) owner[v] = -1;
+      const int rid = next_id++;
+      rest.reserve(comp.size() - sep.size());
+      for (int v : comp) if (owner[v] == cid) { owner[v] = rid; rest.push_back(v); }
+      todo.push_back(Task{false, rid, std::move(rest)});
+      todo.push_back(Task{true, 0, std::move(sep)});
+    }
+    for (size_t i = todo.size(); i-- > 0;) stack.push_back(std::move(todo[i]));
+  }
+}
+
+struct Tri { std::vector<int> rp, col; std::vector<double> val; };      // the strict part of a triangle by rows, ascending columns
+
+// level sets, level-ordered rows, stages of one triangle (lower: levels ascending from row 0; upper: from the last row), appended to the plan
+void lu_triangle_layout(int n, int t, bool lower, bool scaled, const Tri &T, const std::vector<double> &diag, int wide, LuPlan &out)
+{
+  std::vector<int> level((size_t)n, 0);
+  int nlev = 0;
+  for (int s = 0; s < n; s++) {
+    const int i = lower ? s : n - 1 - s;
+    int lv = 0;
+    for (int p = T.rp[i]; p < T.rp[i + 1]; p++) lv = std::max(lv, level[T.col[p]] + 1);
+    level[i] = lv; nlev = std::max(nlev, lv + 1);
+  }
+  std::vector<int> start((size_t)nlev + 1, 0), where((size_t)nlev, 0);
+  std::vector<long long> entries((size_t)nlev, 0);
+  for (int i = 0; i < n; i++) { start[level[i] + 1]++; entries[level[i]] += T.rp[i + 1] - T.rp[i]; }
+  for (int l = 0; l < nlev; l++) { start[l + 1] += start[l]; where[l] = start[l]; }
+  int *rows = out.rows.data() + (size_t)t * n;
+  for (int i = 0; i < n; i++) rows[where[level[i]]++] = i;
+  for (int p = 0; p < n; p++) {
+    const int i = rows[p];
+    out.col.insert(out.col.end(), T.col.begin() + T.rp[i], T.col.begin() + T.rp[i + 1]);
+    out.val.insert(out.val.end(), T.val.begin() + T.rp[i], T.val.begin() + T.rp[i + 1]);
+    out.rp[(size_t)t * n + p + 1] = (int)out.col.size();
+    if (scaled) out.dinv[p] = 1.0 / diag[i];
+  }
+  const int lev_base = (int)out.lanes.size();
+  for (int l = 0; l < nlev; l++) {
+    const int nl = start[l + 1] - start[l];
+    const bool is_wide = nl >= wide;
+    const double mean = (double)entries[l] / nl;
+    out.lev.push_back(t * n + start[l]);
+    out.lanes.push_back(!is_wide ? 64 : mean <= 2.0 ? 1 : mean <= 16.0 ? 8 : 64);
+    if (out.nstage[t] > 0 && out.stages.back().wide == (int)is_wide) out.stages.back().nlev++;
+    else { out.stages.push_back(LuStage{lev_base + l, 1, (int)is_wide}); out.nstage[t]++; }
+  }
+  out.levels[t] = nlev;
+}
+
+void lu_layout(int n, int wide, int first_scaled, const Tri &first, const Tri &second, const std::vector<double> &diag, LuPlan &out)
+{
+  out.n = n; out.wide = wide; out.first_scaled = first_scaled;
+  out.rows.assign((size_t)2 * n, 0); out.rp.assign((size_t)2 * n + 1, 0); out.dinv.assign((size_t)n, 0.0);
+  out.col.clear(); out.val.clear(); out.lev.clear(); out.lanes.clear(); out.stages.clear();
+  out.col.reserve(first.col.size() + second.col.size()); out.val.reserve(first.col.size() + second.col.size());
+  out.levels[0] = out.levels[1] = out.nstage[0] = out.nstage[1] = 0;
+  if (n > 0) {
+    lu_triangle_layout(n, 0, true, first_scaled != 0, first, diag, wide, out);
+    lu_triangle_layout(n, 1, false, first_scaled == 0, second, diag, wide, out);
+  }
+  out.lev.push_back(2 * n);
+}
+
+// the sum one group of lanes forms for a row: partial sums of the lanes, then the order of the DPP sums (wave_sum, ks_sweeps.cuh; 8 lanes: the two
+// quad steps and the mirror of the half row)
+double lu_row_sum(const double *v, const int *c, int len, int lanes, const double *w)
+{
+  if (lanes == 1) { double acc = 0.0; for (int p = 0; p < len; p++) acc = __builtin_fma(v[p], w[c[p]], acc); return acc; }
+  double part[64];
+  for (int l = 0; l < lanes; l++) { double acc = 0.0; for (int p = l; p < len; p += lanes) acc = __builtin_fma(v[p], w[c[p]], acc); part[l] = acc; }
+  double Q[16];
+  for (int k = 0; k < lanes / 4; k++) { const double a = part[4 * k] + part[4 * k + 1], b = part[4 * k + 2] + part[4 * k + 3]; Q[k] = a + b; }
+  if (lanes == 8) return Q[0] + Q[1];
+  double R[4];
+  for (int j = 0; j < 4; j++) { const double a = Q[4 * j + 3] + Q[4 * j + 2], b = Q[4 * j + 1] + Q[4 * j]; R[j] = a + b; }
+  const double a = R[3] + R[2], b = R[1] + R[0];
+  return a + b;
+}
+
+void lu_walk_host(const LuPlan &p, const double *in, double *out)
+{
+  const int n = p.n;
+  std::vector<double> w((size_t)n, 0.0);
+  const int nlev = p.levels[0] + p.levels[1];
+  for (int l = 0; l < nlev; l++)
+    for (int pos = p.lev[l]; pos < p.lev[l + 1]; pos++) {
+      const int r = p.rows[pos], e0 = p.rp[pos], e1 = p.rp[pos + 1];
+      const bool second = pos >= n, scaled = p.first_scaled ? !second : second;
+      const double acc = lu_row_sum(p.val.data() + e0, p.col.data() + e0, e1 - e0, p.lanes[l], w.data());
+      double t = (second ? w[r] : in[p.perm[r]]) - acc;
+      if (scaled) t = t * p.dinv[pos - (second ? n : 0)];
+      w[r] = t;
+      if (second) out[p.perm[r]] = t;
+    }
+}
+} // namespace
+
+void lu_ordering(int n, const int *rp, const int *col, int ordering, std::vector<int> &perm)
+{
+  if (ordering == LU_ORDERING_NATURAL) { perm.resize((size_t)n); for (int i = 0; i < n; i++) perm[i] = i; return; }
+  // the graph of the pattern of P + P^T without the diagonal: both directions of every entry, sorted, repeated edges removed
+  std::vector<int> xadj((size_t)n + 1, 0), adj, fill;
+  for (int r = 0; r < n; r++) for (int p = rp[r]; p < rp[r + 1]; p++) { const int c = col[p]; if (c >= 0 && c < n && c != r) { xadj[r + 1]++; xadj[c + 1]++; } }
+  for (int r = 0; r < n; r++) xadj[r + 1] += xadj[r];
+  adj.resize((size_t)xadj[n]); fill.assign(xadj.begin(), xadj.end() - 1);
+  for (int r = 0; r < n; r++) for (int p = rp[r]; p < rp[r + 1]; p++) { const int c = col[p]; if (c >= 0 && c < n && c != r) { adj[fill[r]++] = c; adj[fill[c]++] = r; } }
+  std::vector<int> xa((size_t)n + 1, 0), ad; ad.reserve(adj.size());
+  for (int r = 0; r < n; r++) {
+    std::sort(adj.begin() + xadj[r], adj.begin() + xadj[r + 1]);
+    for (int p = xadj[r]; p < xadj[r + 1]; p++) if (p == xadj[r] || adj[p] != adj[p - 1]) ad.push_back(adj[p]);
+    xa[r + 1] = (int)ad.size();
+  }
+  nested_dissection(n, xa, ad, perm);
+}
+
+void csr_lu_plan(int n, const int *rp, const int *col, const double *val, int ordering, int wide, bool keep_factors, LuPlan &out, LuPlan *tr)
+{
+  out = LuPlan(); out.n = n;
+  if (tr) { *tr = LuPlan(); tr->n = n; }
+  std::vector<int> srp, scol; std::vector<double> sval;
+  lu_sorted_rows(n, rp, col, val, srp, scol, sval);
+  lu_ordering(n, srp.data(), scol.data(), ordering, out.perm);
+  std::vector<int> inv((size_t)n, 0);
+  for (int i = 0; i < n; i++) inv[out.perm[i]] = i;
+  // the factors of Q P Q^T row by row: the row's entries scattered into w, the columns left of the diagonal taken ascending from a heap that fill joins
+  Tri L, U;                                                     // U rows start with the pivot here
+  L.rp.assign((size_t)n + 1, 0); U.rp.assign((size_t)n + 1, 0);
+  std::vector<double> w((size_t)n, 0.0), diag((size_t)n, 0.0);
+  std::vector<int> mark((size_t)n, -1), heap, upper;
+  const size_t cap = 2147483647u;
+  for (int i = 0; i < n; i++) {
+    const int orig = out.perm[i];
+    heap.clear(); upper.clear();
+    for (int p = srp[orig]; p < srp[orig + 1]; p++) {
+      const int c = inv[scol[p]];
+      w[c] = sval[p]; mark[c] = i;
+      if (c < i) heap.push_back(c); else upper.push_back(c);
+    }
+    std::make_heap(heap.begin(), heap.end(), std::greater<int>());
+    while (!heap.empty()) {
+      std::pop_heap(heap.begin(), heap.end(), std::greater<int>());
+      const int k = heap.back(); heap.pop_back();
+      const double l = w[k] / U.val[U.rp[k]];
+      L.col.push_back(k); L.val.push_back(l);
+      for (int q = U.rp[k] + 1; q < U.rp[k + 1]; q++) {
+        const int j = U.col[q];
+        const double m = l * U.val[q];
+        if (mark[j] != i) {
+          mark[j] = i; w[j] = 0.0;
+          if (j < i) { heap.push_back(j); std::push_heap(heap.begin(), heap.end(), std::greater<int>()); } else upper.push_back(j);
+        }
+        w[j] = w[j] - m;
+      }
+    }
+    std::sort(upper.begin(), upper.end());
+    for (int j : upper) { U.col.push_back(j); U.val.push_back(w[j]); }
+    L.rp[i + 1] = (int)L.col.size(); U.rp[i + 1] = (int)U.col.size();
+    if (L.col.size() + U.col.size() > cap) { out.status = LU_TOO_LARGE; out.bad_row = orig; return; }
+    out.longest_row = std::max(out.longest_row, (L.rp[i + 1] - L.rp[i]) + (U.rp[i + 1] - U.rp[i]));
+    diag[i] = w[i];
+    if (diag[i] == 0.0) { out.status = LU_ZERO_PIVOT; out.bad_row = orig; return; }
+    if (diag[i] < 0.0) out.neg++; else out.pos++;
+  }
+  out.nnzL = (long long)L.col.size(); out.nnzU = (long long)U.col.size();
+  if (keep_factors) { out.lrp = L.rp; out.lcol = L.col; out.lval = L.val; out.urp = U.rp; out.ucol = U.col; out.uval = U.val; }
+  // the strict part of U
+  Tri Us; Us.rp.assign((size_t)n + 1, 0); Us.col.reserve(U.col.size()); Us.val.reserve(U.col.size());
+  for (int i = 0; i < n; i++) {
+    Us.col.insert(Us.col.end(), U.col.begin() + U.rp[i] + 1, U.col.begin() + U.rp[i + 1]);
+    Us.val.insert(Us.val.end(), U.val.begin() + U.rp[i] + 1, U.val.begin() + U.rp[i + 1]);
+    Us.rp[i + 1] = (int)Us.col.size();
+  }
+  U = Tri();
+  lu_layout(n, wide, 0, L, Us, diag, out);
+  if (tr) {
+    // the transposed triangles of the same factors (the counting sort of csr_transpose: a row lists a column of the factor by ascending original row):
+    // U^T, lower with the pivots, is solved first, L^T, unit upper, second
+    Tri Ut, Lt;
+    csr_transpose(n, n, Us.rp.data(), Us.col.data(), Us.val.data(), Ut.rp, Ut.col, Ut.val);
+    csr_transpose(n, n, L.rp.data(), L.col.data(), L.val.data(), Lt.rp, Lt.col, Lt.val);
+    tr->perm = out.perm; tr->nnzL = out.nnzL; tr->nnzU = out.nnzU; tr->neg = out.neg; tr->pos = out.pos; tr->longest_row = out.longest_row;
+    lu_layout(n, wide, 1, Ut, Lt, diag, *tr);
+  }
+}
+void lu_apply_host(const LuPlan &p, const double *in, double *out) { lu_walk_host(p, in, out); }
+void lu_apply_transpose_host(const LuPlan &t, const double *in, double *out) { lu_walk_host(t, in, out); }
 } // namespace ksc
 
 #ifdef KSD_TEST_HOOKS
@@ -629,6 +898,41 @@ long long ksc_ilu0_blocks_transpose(int n, int row_start, int bs, const int *rp,
   if (in && out_t) ksc::ilu0_apply_transpose_host(t, n, bs, in, out_t);
   if (in && out_f) ksc::ilu0_apply_host(p, n, bs, in, out_f);
   return (long long)t.val.size();
+}
+// test hooks: the ordering alone; and the LU plan. ksc_lu_plan fills info first: status, bad row, entries of L, of U, levels and stages of the two
+// triangles (forward plan: 4..7), pivots < 0 and > 0, longest row, entries of the layout, levels and stages of the transposed plan (12..15); every
+// array may be NULL, else it has room for what a first call reported: perm n; lrp / urp n + 1 with lcol, lval / ucol, uval (the factors by rows, U rows
+// starting with the pivot); rows 2n, prp 2n + 1, pcol / pval, lev levels + 1, lanes levels, dinv n, stages 3 per stage (the forward plan's layout);
+// in -> out_f = the forward host apply, out_t = the transposed one. Returns the status.
+void ksc_lu_ordering(int n, const int *rp, const int *col, int ordering, int *perm)
+{
+  std::vector<int> p;
+  ksc::lu_ordering(n, rp, col, ordering, p);
+  std::copy(p.begin(), p.end(), perm);
+}
+int ksc_lu_plan(int n, const int *rp, const int *col, const double *val, int ordering, int wide, long long *info, int *perm, int *lrp, int *lcol, double *lval,
+                int *urp, int *ucol, double *uval, int *rows, int *prp, int *pcol, double *pval, int *lev, int *lanes, double *dinv, int *stages,
+                const double *in, double *out_f, double *out_t)
+{
+  ksc::LuPlan p, t;
+  ksc::csr_lu_plan(n, rp, col, val, ordering, wide, true, p, &t);
+  for (int i = 0; i < 16; i++) info[i] = 0;
+  info[0] = p.status; info[1] = p.bad_row;
+  if (p.status) return p.status;
+  info[2] = p.nnzL; info[3] = p.nnzU; info[4] = p.levels[0]; info[5] = p.levels[1]; info[6] = p.nstage[0]; info[7] = p.nstage[1];
+  info[8] = p.neg; info[9] = p.pos; info[10] = p.longest_row; info[11] = (long long)p.col.size();
+  info[12] = t.levels[0]; info[13] = t.levels[1]; info[14] = t.nstage[0]; info[15] = t.nstage[1];
+  if (perm) std::copy(p.perm.begin(), p.perm.end(), perm);
+  if (lrp) { std::copy(p.lrp.begin(), p.lrp.end(), lrp); std::copy(p.lcol.begin(), p.lcol.end(), lcol); std::copy(p.lval.begin(), p.lval.end(), lval); }
+  if (urp) { std::copy(p.urp.begin(), p.urp.end(), urp); std::copy(p.ucol.begin(), p.ucol.end(), ucol); std::copy(p.uval.begin(), p.uval.end(), uval); }
+  if (rows) {
+    std::copy(p.rows.begin(), p.rows.end(), rows); std::copy(p.rp.begin(), p.rp.end(), prp); std::copy(p.col.begin(), p.col.end(), pcol); std::copy(p.val.begin(), p.val.end(), pval);
+    std::copy(p.lev.begin(), p.lev.end(), lev); std::copy(p.lanes.begin(), p.lanes.end(), lanes); std::copy(p.dinv.begin(), p.dinv.end(), dinv);
+    for (size_t s = 0; s < p.stages.size(); s++) { stages[3 * s] = p.stages[s].lev0; stages[3 * s + 1] = p.stages[s].nlev; stages[3 * s + 2] = p.stages[s].wide; }
+  }
+  if (in && out_f) ksc::lu_apply_host(p, in, out_f);
+  if (in && out_t) ksc::lu_apply_transpose_host(t, in, out_t);
+  return 0;
 }
 }
 #endif

@@ -1,6 +1,6 @@
 // Host-side planning of the assembly path (no device code, no ks_mat): everything ks_mat.hip decides with index arithmetic on the host - the split of
 // a row block into its diagonal and ghost parts, the halo plan between the ranks, the binned, windowed and ILU(0) layouts, the plan of the transposed
-// product across ranks, MatAXPY on CSR arrays. Plain functions that fill structs of vectors; constants of the device side come in as parameters and a
+// product across ranks, MatAXPY on CSR arrays, the sparse LU with fill of KS_PC_LU (ordering, factors, level schedule; tests/test_lu_host.py). Plain functions that fill structs of vectors; constants of the device side come in as parameters and a
 // refusal is a status in the result. ks_mat.hip calls a planner and uploads what it filled; KSD_TEST_HOOKS exports each of them as a ksc_* C function,
 // and those run on the CPU (tests/test_csr_host.py, test_assembly_host.py, test_sharded_transpose_host.py, test_ilu_host.py, tests/host/assembly_plans.cpp).
 #pragma once
@@ -144,4 +144,47 @@ void csr_ilu0_blocks(int n, int row_start, int bs, const int *rp, const int *col
 // what the kernels compute, on the host, in the same order: out = (LU)^-1 in block by block from the forward plan, out = (LU)^-T in from the transposed one
 void ilu0_apply_host(const IluPlan &p, int n, int bs, const double *in, double *out);
 void ilu0_apply_transpose_host(const IluPlan &t, int n, int bs, const double *in, double *out);
+
+// Sparse LU with fill of a whole square matrix (KS_PC_LU; the kernels that walk the plan: ks_pc_lu.hip): PCLU with PETSc's defaults - a nested
+// dissection ordering applied symmetrically, no pivoting - Q P Q^T = L U, L unit lower triangular. The rows of P are sorted by column and repeated
+// entries summed in stored order, as for the ILU(0) blocks; the diagonal position is always part of the pattern (an absent diagonal entry is a
+// structural zero that fill may make non-zero). Columns outside [0, n) are ignored (one rank owns every row).
+//   ordering   lu_ordering: the graph of the pattern of P + P^T. LU_ORDERING_ND is George's automatic nested dissection on rooted level
+//              structures: per connected component, start from the smallest node; up to five times take as the new root the node of the last
+//              level with the fewest neighbours inside the component (lowest index on ties) while the structure gets deeper; the middle level
+//              (levels / 2) is the separator; what is left is ordered the same way, the separator (ascending) goes last. Components of at most
+//              8 nodes or with fewer than 3 levels are listed ascending. perm[i] = the original row eliminated i-th. Deterministic.
+//   factors    row by row in IKJ order: the pattern of row i is the union of its own entries and the U patterns of the rows k of its L part,
+//              taken ascending (fill included); l_ik = a_ik / u_kk, a_ij -= l_ik u_kj, one rounding per operation. No entry of the pattern is
+//              dropped, whatever its value. u_ii == 0 ends the factorisation: status LU_ZERO_PIVOT, bad_row = the ORIGINAL row.
+//   levels     of the two triangles as for the ILU(0) blocks: a row's level is one more than the largest level among the rows it reads.
+//   layout     the rows of the triangle solved first at positions [0, n) and of the one solved second at [n, 2n), in level order (ascending row
+//              inside a level); rp (2n + 1) points into col / val, where a row's off-diagonal entries are contiguous with ascending column
+//              (permuted numbering). lev (levels + 1) are the positions where the levels start, the first triangle's levels first.
+//              dinv is 1 / u_rr in the level order of the triangle that carries the pivots (first_scaled: the first one - the transposed plan).
+//   stages     the levels of each triangle cut in order into runs: a WIDE stage is a run of levels with at least `wide` rows each (one launch
+//              per level, lanes[level] = 1, 8 or 64 lanes per row by the level's mean row length), a NARROW stage a maximal run of levels with
+//              fewer (one launch of one workgroup, a wave of 64 lanes per row).
+constexpr int LU_ORDERING_ND = 0, LU_ORDERING_NATURAL = 1;
+constexpr int LU_ZERO_PIVOT = 1, LU_TOO_LARGE = 2;        // LU_TOO_LARGE: more than 2^31 - 1 stored entries in the factors
+struct LuStage { int lev0, nlev, wide; };
+struct LuPlan {
+  int status = 0, bad_row = -1;
+  int n = 0, longest_row = 0;                     // longest_row: most entries in one row of L + U, diagonal included
+  long long nnzL = 0, nnzU = 0;                   // stored entries of L (without the unit diagonal) and of U (with the diagonal)
+  int levels[2] = {0, 0}, nstage[2] = {0, 0};     // of the triangle solved first and of the one solved second
+  int first_scaled = 0;                           // 0: L then U (forward), 1: U^T then L^T (transposed)
+  int wide = 0, neg = 0, pos = 0;                 // the threshold the stages were cut with; signs of the pivots u_rr
+  std::vector<int> perm, rows, rp, col, lev, lanes;
+  std::vector<double> val, dinv;
+  std::vector<LuStage> stages;
+  std::vector<int> lrp, lcol, urp, ucol; std::vector<double> lval, uval;      // the factors by rows in permuted numbering (U rows start with the pivot), kept only on request
+};
+void lu_ordering(int n, const int *rp, const int *col, int ordering, std::vector<int> &perm);
+// tr (optional): a second plan of the SAME factors for y = Q^T L^-T U^-T Q x, made the way csr_ilu0_blocks makes its transposed plan
+void csr_lu_plan(int n, const int *rp, const int *col, const double *val, int ordering, int wide, bool keep_factors, LuPlan &out, LuPlan *tr = nullptr);
+// what the kernels compute, in their summation order: lane l of a row's group takes entries l, l + lanes, ... ascending by fma, the partial sums are
+// combined in the fixed order of the wave sums (ks_sweeps.cuh). out = Q^T U^-1 L^-1 Q in from the forward plan, Q^T L^-T U^-T Q in from the transposed
+void lu_apply_host(const LuPlan &p, const double *in, double *out);
+void lu_apply_transpose_host(const LuPlan &t, const double *in, double *out);
 }

@@ -297,6 +297,7 @@ struct Jd : Gd {
     ksp_type = st->ksp_type_set ? st->ksp_type : KS_KSP_BCGS;
     rtol = st->rtol_set ? st->rtol : 1e-4; max_it = st->max_it_set ? st->max_it : 90; restart = st->restart;
     if (ksp_type == KS_KSP_BCGS) KS_CALL(make(7, &Kb));
+    else if (ksp_type == KS_KSP_PREONLY) {}      // the preconditioned, projected right-hand side is the correction: no vectors
     else { KS_CALL(make(restart + 1, &Kg)); KS_CALL(ks_bv_set_orthogonalization(Kg, KS_BV_ORTHOG_CGS, st->gmres_refine, 0.7071)); }
     M.assign((size_t)ldM * ldM, 0.0); Minv.assign((size_t)ldM * ldM, 0.0);
     KS_HIP(hipMalloc(&Minv_dev, sizeof(double) * (size_t)ldM * ldM));
@@ -379,7 +380,7 @@ int Jd::correction(int nb, const double *theta, const double *rnorm, int base)
       else { KS_CALL(op.pc(rj, rhs)); KS_CALL(op.project(-1.0, rhs, 0.0, nullptr, nullptr, rhs, nullptr, nullptr)); }
       if (op.pointwise && op.dinv) cfg->pc_columns++;
       KsKsp ksp{ctx, (long long)n, Kg, Kb, tol, max_it, restart, false, &solves, &eps->jdx.inner_iterations, &last_rnorm};
-      KS_CALL(ksp_type == KS_KSP_BCGS ? ks_ksp_bcgs(ksp, op, rhs, dst) : ks_ksp_gmres(ksp, op, rhs, dst));
+      KS_CALL(ksp_type == KS_KSP_BCGS ? ks_ksp_bcgs(ksp, op, rhs, dst) : ksp_type == KS_KSP_PREONLY ? ks_ksp_preonly(ksp, op, rhs, dst) : ks_ksp_gmres(ksp, op, rhs, dst));
       eps->jdx.inner_solves++; solved_one = true;
       double nrm = 0.0;
       KS_CALL(ks_bv_normvec(Wk, dst, KS_NORM_2, &nrm));

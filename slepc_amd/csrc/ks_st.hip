@@ -130,9 +130,11 @@ int bjacobi_apply(ks_st st, const double *in, double *out, bool tr = false)
   KS_HIP(hipGetLastError());
   return KS_SUCCESS;
 }
-// out = M^-1 in for the block preconditioners: the dense inverses, or the ILU(0) factors (k_bjacobi_ilu_apply, ks_pc.hip)
+// out = M^-1 in for the preconditioners that are not pointwise: the dense inverses, the ILU(0) factors (k_bjacobi_ilu_apply, ks_pc.hip), or the LU
+// factors of the whole P (ks_pc_lu.hip)
 int blocks_apply(ks_st st, const double *in, double *out, bool tr = false)
 {
+  if (st->pc_type == KS_PC_LU) return tr ? ks_pc_lu_apply_transpose(st->ctx, st->lu, in, out) : ks_pc_lu_apply(st->ctx, st->lu, in, out);
   if (st->pc_type == KS_PC_BJACOBI_ILU) return tr ? ks_pc_ilu_apply_transpose(st->ctx, st->ilu, in, out) : ks_pc_ilu_apply(st->ctx, st->ilu, in, out);
   return bjacobi_apply(st, in, out, tr);
 }
@@ -140,6 +142,7 @@ int blocks_apply(ks_st st, const double *in, double *out, bool tr = false)
 int pc_lincomb(ks_st st, double a, const double *u, double b, const double *v, double *out, bool tr = false)
 {
   if (st->pc_type == KS_PC_JACOBI || pc_none(st)) return lincomb(st->ctx, st->n, pc_none(st) ? nullptr : st->dinv, a, u, b, v, out);
+  if (st->pc_type == KS_PC_LU && a == 1.0 && (b == 0.0 || !v) && u != out) return blocks_apply(st, u, out, tr);      // the factors read u through their permutation: no copy
   KS_CALL(lincomb(st->ctx, st->n, nullptr, a, u, b, v, st->pcwork));
   return blocks_apply(st, st->pcwork, out, tr);
 }
@@ -313,10 +316,23 @@ int ks_ksp_bcgs(const KsKsp &k, KsKspOp &op, const double *rhs, double *y)
   return KS_SUCCESS;
 }
 
+// KSPPREONLY: y = M^-1 rhs - one application of the preconditioner (the operator's residual with a zero iterate), no residual norm, no convergence
+// test. One solve and one iteration are counted; last_rnorm is left alone.
+int ks_ksp_preonly(const KsKsp &k, KsKspOp &op, const double *rhs, double *y)
+{
+  (*k.solves)++; (*k.its)++;
+  return op.residual(rhs, nullptr, y);
+}
+
 namespace {
 int gmres_solve(ks_st st, const double *rhs, double *y, bool tr) { StKspOp op(st, tr); return ks_ksp_gmres(st_ksp(st), op, rhs, y); }
 int bcgs_solve(ks_st st, const double *rhs, double *y, bool tr) { StKspOp op(st, tr); return ks_ksp_bcgs(st_ksp(st), op, rhs, y); }
-int inner_solve(ks_st st, const double *rhs, double *y, bool tr = false) { return st->ksp_type == KS_KSP_BCGS ? bcgs_solve(st, rhs, y, tr) : gmres_solve(st, rhs, y, tr); }
+int preonly_solve(ks_st st, const double *rhs, double *y, bool tr) { StKspOp op(st, tr); return ks_ksp_preonly(st_ksp(st), op, rhs, y); }
+int inner_solve(ks_st st, const double *rhs, double *y, bool tr = false)
+{
+  if (st->ksp_type == KS_KSP_PREONLY) return preonly_solve(st, rhs, y, tr);
+  return st->ksp_type == KS_KSP_BCGS ? bcgs_solve(st, rhs, y, tr) : gmres_solve(st, rhs, y, tr);
+}
 
 int st_shell_mult(void *user, const double *x, double *y) { return ks_st_apply_internal((ks_st)user, x, y); }
 int st_shell_mult_transpose(void *user, const double *x, double *y) { return ks_st_apply_transpose_internal((ks_st)user, x, y); }
@@ -404,6 +420,23 @@ static int bjacobi_ilu_setup(ks_st st)
   return KS_SUCCESS;
 }
 
+// PCLU (PCSetUp_LU: MatGetOrdering, MatLUFactorSymbolic / Numeric): the whole P from the same arrays the blocks come from, ordered and factored with fill on
+// the host (ksc::csr_lu_plan), uploaded once per set-up (ks_pc_lu.hip)
+static int lu_setup(ks_st st)
+{
+  KS_CHECK(st->ctx->comm.size == 1, KS_ERR_SUP, "KS_PC_LU runs on one rank (PETSc's built-in LU is sequential as well)");
+  std::vector<int> rp, col; std::vector<double> val;
+  const int *prp; const int *pcol; const double *pval;
+  KS_CALL(pc_block_source(st, rp, col, val, &prp, &pcol, &pval));
+  KS_CALL(ks_pc_lu_build(st->ctx, st->n, prp, pcol, pval, st->lu_ordering, st->tsolves, &st->lu));
+  if (st->pcwork) { hipFree(st->pcwork); st->pcwork = nullptr; }
+  if (hipMalloc(&st->pcwork, sizeof(double) * std::max(st->n, 1)) != hipSuccess) {
+    (void)hipGetLastError(); st->pcwork = nullptr; ks_pc_lu_free(st->lu); st->lu = nullptr;
+    KS_FAIL(KS_ERR_MEM, "LU set-up: no device memory for a work vector of %d rows", st->n);
+  }
+  return KS_SUCCESS;
+}
+
 bool ks_st_is_plain(ks_st st) { return !st || (st->type == KS_ST_SHIFT && st->sigma == 0.0 && !st->B); }
 
 int ks_st_setup_internal(ks_st st)
@@ -421,6 +454,7 @@ int ks_st_setup_internal(ks_st st)
   }
   if (st->Pmat) { ks_mat_destroy(st->Pmat); st->Pmat = nullptr; }           // the assembled P of an earlier shift / type / mode
   if (st->ilu) { ks_pc_ilu_free(st->ilu); st->ilu = nullptr; }              // and its ILU(0) blocks
+  if (st->lu) { ks_pc_lu_free(st->lu); st->lu = nullptr; }                  // or its LU factors
   const bool need_solve = (st->type == KS_ST_SINVERT) || (st->type == KS_ST_CAYLEY) || (st->type == KS_ST_SHIFT && B);
   // STPRECOND (precond.c:36-110): K = A - sigma B is only preconditioned, the KSP is preonly - the preconditioner is built, no Krylov basis
   const bool precond = st->type == KS_ST_PRECOND;
@@ -439,8 +473,9 @@ int ks_st_setup_internal(ks_st st)
   if (need_solve || precond) {
     if (st->K && !need_solve) { ks_bv_destroy(st->K); st->K = nullptr; }
     if (st->K) { int km = 0; ks_bv_get_sizes(st->K, nullptr, nullptr, &km, nullptr); if (km != st->restart + 1) { ks_bv_destroy(st->K); st->K = nullptr; } }
-    if (need_solve && !st->K) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, st->restart + 1, 0, &st->K)); st->K->row_start = A->row_start; }
-    if (need_solve) KS_CALL(ks_bv_set_orthogonalization(st->K, KS_BV_ORTHOG_CGS, st->gmres_refine, 0.7071));      // KSPGMRESClassicalGramSchmidtOrthogonalization + refinement type
+    if (st->K && st->ksp_type == KS_KSP_PREONLY) { ks_bv_destroy(st->K); st->K = nullptr; }      // KSPPREONLY keeps no basis
+    if (need_solve && !st->K && st->ksp_type != KS_KSP_PREONLY) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, st->restart + 1, 0, &st->K)); st->K->row_start = A->row_start; }
+    if (need_solve && st->K) KS_CALL(ks_bv_set_orthogonalization(st->K, KS_BV_ORTHOG_CGS, st->gmres_refine, 0.7071));      // KSPGMRESClassicalGramSchmidtOrthogonalization + refinement type
     if (need_solve && st->ksp_type == KS_KSP_BCGS && !st->Kb) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 7, 0, &st->Kb)); st->Kb->row_start = A->row_start; }
     if (!st->dinv) KS_HIP(hipMalloc(&st->dinv, sizeof(double) * std::max(A->n, 1)));
     // Jacobi: diag(P)
@@ -464,6 +499,7 @@ int ks_st_setup_internal(ks_st st)
     KS_HIP(hipGetLastError());
     if (st->pc_type == KS_PC_BJACOBI && !st->pc_identity) KS_CALL(bjacobi_setup(st));
     if (st->pc_type == KS_PC_BJACOBI_ILU && !st->pc_identity) KS_CALL(bjacobi_ilu_setup(st));
+    if (st->pc_type == KS_PC_LU && !st->pc_identity) KS_CALL(lu_setup(st));
   }
   if (!st->op) KS_CALL(ks_mat_create_shell(ctx, A->n, A->row_start, A->n_global, st_shell_mult, st, &st->op));
   st->op->n = A->n; st->op->row_start = A->row_start; st->op->n_global = A->n_global;
@@ -514,6 +550,7 @@ extern "C" int ks_st_destroy(ks_st st)
   if (st->binv) hipFree(st->binv);
   if (st->pcwork) hipFree(st->pcwork);
   ks_pc_ilu_free(st->ilu);
+  ks_pc_lu_free(st->lu);
   delete st;
   return KS_SUCCESS;
 }
@@ -567,7 +604,7 @@ extern "C" int ks_st_set_ksp(ks_st st, double rtol, int max_it, int restart)   /
 extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType on STGetKSP: KSPGMRES (default) or KSPBCGS
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  KS_CHECK(type == KS_KSP_GMRES || type == KS_KSP_BCGS, KS_ERR_SUP, "only KSPGMRES and KSPBCGS are built");
+  KS_CHECK(type == KS_KSP_GMRES || type == KS_KSP_BCGS || type == KS_KSP_PREONLY, KS_ERR_SUP, "only KSPGMRES, KSPBCGS and KSPPREONLY are built");
   if (st->ksp_type != type) { st->ksp_type = type; st->ready = false; }
   st->ksp_type_set = true;
   return KS_SUCCESS;
@@ -575,12 +612,54 @@ extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType
 extern "C" int ks_st_set_pc(ks_st st, int type, int block_size)       // PCSetType (+ PCBJacobiSetLocalBlocks, -sub_pc_type lu | ilu) on the KSP's PC
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  KS_CHECK(type == KS_PC_JACOBI || type == KS_PC_BJACOBI || type == KS_PC_BJACOBI_ILU || type == KS_PC_NONE, KS_ERR_SUP, "only PCNONE, PCJACOBI and PCBJACOBI (sub-solves: LU on dense blocks, or ILU(0)) are built");
+  KS_CHECK(type == KS_PC_JACOBI || type == KS_PC_BJACOBI || type == KS_PC_BJACOBI_ILU || type == KS_PC_NONE || type == KS_PC_LU, KS_ERR_SUP, "only PCNONE, PCJACOBI, PCBJACOBI (sub-solves: LU on dense blocks, or ILU(0)) and PCLU are built");
+  KS_CHECK(type != KS_PC_LU || block_size == 0, KS_ERR_SUP, "PCLU factors the whole matrix: a block size (%d) with it names no preconditioner this build has", block_size);
   KS_CHECK(type != KS_PC_NONE || block_size == 0, KS_ERR_SUP, "PCNONE has no blocks: a block size (%d) with it names no preconditioner this build has", block_size);
   KS_CHECK(type != KS_PC_BJACOBI || (block_size >= 2 && block_size <= 32), KS_ERR_ARG_OUTOFRANGE, "block size %d (2..32)", block_size);
   KS_CHECK(type != KS_PC_BJACOBI_ILU || (block_size >= 64 && block_size <= ksc::ILU_BS_MAX), KS_ERR_ARG_OUTOFRANGE, "block size %d (64..%d)", block_size, ksc::ILU_BS_MAX);
   if (type == KS_PC_JACOBI || type == KS_PC_NONE) block_size = 0;
   if (st->pc_type != type || st->pc_bs != block_size) { st->pc_type = type; st->pc_bs = block_size; st->ready = false; }
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_lu_set_ordering(ks_st st, int which)          // PCFactorSetMatOrderingType on the PCLU
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  KS_CHECK(which == KS_ORDERING_ND || which == KS_ORDERING_NATURAL, KS_ERR_ARG_OUTOFRANGE, "unknown ordering %d (KS_ORDERING_ND, KS_ORDERING_NATURAL)", which);
+  if (st->lu_ordering != which) { st->lu_ordering = which; st->ready = false; }
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_lu_get_ordering_type(ks_st st, int *which) { KS_CHECK(st && which, KS_ERR_ARG_NULL, "NULL argument"); *which = st->lu_ordering; return KS_SUCCESS; }
+// the set-up behind the three queries of the factors
+static int lu_query(ks_st st, KsLuInfo *info)
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  KS_CHECK(st->A, KS_ERR_ORDER, "STSetMatrices must be called first");
+  KS_CHECK(st->pc_type == KS_PC_LU, KS_ERR_ORDER, "the preconditioner is not KS_PC_LU");
+  KS_HIP(hipSetDevice(st->ctx->device));
+  if (!st->ready) KS_CALL(ks_st_setup_internal(st));
+  KS_CHECK(st->lu, KS_ERR_ORDER, "this transformation has no linear solve, so no factors (STSHIFT with one matrix, or STPRECOND without a matrix to precondition)");
+  ks_pc_lu_info(st->lu, info);
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_lu_get_permutation(ks_st st, int *perm_host)
+{
+  KS_CHECK(perm_host, KS_ERR_ARG_NULL, "NULL argument");
+  KsLuInfo i; KS_CALL(lu_query(st, &i));
+  std::copy(i.perm, i.perm + i.n, perm_host);
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_lu_get_info(ks_st st, int *n, long long *nnz_l, long long *nnz_u, int *levels_l, int *levels_u, int *wide, int *wide_launches, int *narrow_launches, long long *device_bytes)
+{
+  KsLuInfo i; KS_CALL(lu_query(st, &i));
+  if (n) *n = i.n; if (nnz_l) *nnz_l = i.nnzL; if (nnz_u) *nnz_u = i.nnzU; if (levels_l) *levels_l = i.levelsL; if (levels_u) *levels_u = i.levelsU;
+  if (wide) *wide = i.wide; if (wide_launches) *wide_launches = i.wide_launches; if (narrow_launches) *narrow_launches = i.narrow_launches;
+  if (device_bytes) *device_bytes = i.bytes + (long long)sizeof(double) * std::max(i.n, 1);      // the ST's own work vector with it
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_lu_get_inertia(ks_st st, int *neg, int *zero, int *pos)      // MatGetInertia on the factor
+{
+  KsLuInfo i; KS_CALL(lu_query(st, &i));
+  if (neg) *neg = i.neg; if (zero) *zero = 0; if (pos) *pos = i.pos;
   return KS_SUCCESS;
 }
 extern "C" int ks_st_set_gmres_cgs_refinement(ks_st st, int refine)   // KSPGMRESSetCGSRefinementType on STGetKSP
@@ -634,6 +713,7 @@ int ks_st_pc_apply_multi_internal(ks_st st, int ncols, const double *X, int ldx,
 {
   if (ncols <= 0 || st->n == 0) return KS_SUCCESS;
   if (st->pc_type == KS_PC_BJACOBI_ILU && !st->pc_identity) return ks_pc_ilu_apply_multi(st->ctx, st->ilu, ncols, X, ldx, Y, ldy);
+  if (st->pc_type == KS_PC_LU && !st->pc_identity) return ks_pc_lu_apply_multi(st->ctx, st->lu, ncols, X, ldx, Y, ldy);
   const unsigned nb = (unsigned)std::min<long long>(((long long)st->n + 255) / 256, (long long)st->ctx->num_cu * 16);
   if (st->pc_type == KS_PC_BJACOBI && !st->pc_identity) hipLaunchKernelGGL(k_bjacobi_apply, dim3(nb, (unsigned)ncols), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_bs, st->binv, X, (long long)ldx, Y, (long long)ldy);
   else hipLaunchKernelGGL(k_diag_apply_multi, dim3(nb, (unsigned)ncols), dim3(256), 0, st->ctx->stream, (long long)st->n, pc_none(st) ? (const double *)nullptr : st->dinv, X, (long long)ldx, Y, (long long)ldy);
@@ -659,6 +739,7 @@ extern "C" int ks_st_pc_multi_columns(ks_st st, int *columns)      // instrument
   KS_CHECK(st->A, KS_ERR_ORDER, "STSetMatrices must be called first");
   KS_HIP(hipSetDevice(st->ctx->device));
   if (!st->ready) KS_CALL(ks_st_setup_internal(st));
+  if (st->pc_type == KS_PC_LU && st->lu) { *columns = ks_pc_lu_multi_columns(); return KS_SUCCESS; }
   *columns = (st->pc_type == KS_PC_BJACOBI_ILU && st->ilu) ? std::max(1, ks_pc_ilu_multi_columns(st->ctx, st->ilu)) : 65535;      // the other types take the whole block in one launch (grid.y)
   return KS_SUCCESS;
 }

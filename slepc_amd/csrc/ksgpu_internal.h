@@ -277,6 +277,21 @@ int ks_pc_ilu_apply_multi(ks_ctx ctx, const KsIlu *p, int ncols, const double *X
 int ks_pc_ilu_multi_columns(ks_ctx ctx, const KsIlu *p);   // columns of a pass of the above (0: one at a time)
 void ks_pc_ilu_free(KsIlu *p);
 
+// ---- sparse LU with fill (ks_pc_lu.hip): Q P Q^T = L U from CSR arrays of the whole matrix (one rank), y = Q^T U^-1 L^-1 Q x -------------------
+// A level of the triangular solves with at least this many rows is a launch of its own, a run of levels with fewer one launch of a single workgroup
+// (where the value comes from). ks_st_pc_lu_get_info reports the value a set-up used.
+constexpr int KS_LU_WIDE = 8;
+struct KsLu;
+struct KsLuInfo { int n, levelsL, levelsU, wide, wide_launches, narrow_launches, neg, pos; long long nnzL, nnzU, bytes; const int *perm; };
+int ks_pc_lu_wide_threshold();
+int ks_pc_lu_build(ks_ctx ctx, int n, const int *rp, const int *col, const double *val, int ordering, bool transpose, KsLu **out);   // KS_ERR_MAT_LU_ZRPVT, KS_ERR_MEM: nothing is left allocated
+int ks_pc_lu_apply(ks_ctx ctx, const KsLu *p, const double *in, double *out);                 // enqueued; in != out
+int ks_pc_lu_apply_transpose(ks_ctx ctx, const KsLu *p, const double *in, double *out);       // needs the transposed plan
+int ks_pc_lu_apply_multi(ks_ctx ctx, const KsLu *p, int ncols, const double *X, long long ldx, double *Y, long long ldy);   // every column the bits of ks_pc_lu_apply
+int ks_pc_lu_multi_columns();
+void ks_pc_lu_info(const KsLu *p, KsLuInfo *out);     // perm: host array of the plan, valid while it lives
+void ks_pc_lu_free(KsLu *p);
+
 // ---- ST: spectral transformation (ks_st.hip) ----------------------------------------------------
 struct ks_st_s {
   ks_ctx ctx = nullptr;
@@ -289,7 +304,7 @@ struct ks_st_s {
   ks_mat bil = nullptr;                       // STCAYLEY: shell matrix A + nu B, the bilinear form of symmetric problems (cayley.c:70-77)
   ks_mat A = nullptr, B = nullptr;            // borrowed
   double rtol = 1e-8; int max_it = 10000, restart = 30;   // KSP: SLEPC_DEFAULT_TOL (stsles.c:407), PETSc defaults
-  int ksp_type = KS_KSP_GMRES;                // KSPGMRES (the default of the shell matrix mode) or KSPBCGS
+  int ksp_type = KS_KSP_GMRES;                // KSPGMRES (the default of the shell matrix mode), KSPBCGS or KSPPREONLY
   bool ksp_type_set = false, rtol_set = false, max_it_set = false;   // chosen by the caller (ks_st_set_ksp_type, ks_st_set_ksp): a solver with KSP defaults of its own (JD) keeps off those
   int gmres_refine = KS_BV_ORTHOG_REFINE_NEVER;   // KSPGMRESSetCGSRefinementType: PETSc's default is classical Gram-Schmidt without refinement
   ks_bv Kb = nullptr;                         // BiCGStab work vectors (7 columns)
@@ -299,6 +314,8 @@ struct ks_st_s {
   double *binv = nullptr;                     // block Jacobi: row i holds the pc_bs coefficients of row i of its block's inverse (n x pc_bs, zero beyond a short last block)
   double *pcwork = nullptr;                   // block Jacobi: the vector the blocks are applied to (n)
   KsIlu *ilu = nullptr;                       // KS_PC_BJACOBI_ILU: the blocks' factors on the device (owned)
+  KsLu *lu = nullptr;                         // KS_PC_LU: the factors of P on the device (owned)
+  int lu_ordering = KS_ORDERING_ND;           // ks_st_pc_lu_set_ordering
   int matmode = KS_ST_MATMODE_SHELL;          // STSetMatMode: how P = A - sigma B exists (shell: applied term by term; copy: assembled, stsolve.c:603-631)
   ks_mat Pmat = nullptr;                      // ST_MATMODE_COPY: the assembled P (owned)
   ks_mat op = nullptr;                        // shell matrix whose MatMult is STApply
@@ -327,6 +344,7 @@ struct KsKspOp {
 struct KsKsp { ks_ctx ctx; long long n; ks_bv K, Kb; double rtol; int max_it, restart; bool strict; long long *solves, *its; double *last_rnorm; };
 int ks_ksp_gmres(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);
 int ks_ksp_bcgs(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);
+int ks_ksp_preonly(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);     // KSPPREONLY: y = M^-1 rhs, one application, no residual, no test; K and Kb are not used
 bool ks_st_pc_pointwise(ks_st st, const double **dinv);   // set-up done. true: no preconditioner (*dinv NULL) or point Jacobi (*dinv its diagonal); false: blocks (ks_st_pc_apply_multi_internal)
 int ksk_lincomb(ks_ctx ctx, long long n, const double *s, double a, const double *u, double b, const double *v, double *out);   // out = s.*(a*u + b*v)   // diagonal of the local diagonal block (MatGetDiagonal)
 
