@@ -665,7 +665,46 @@ int ks_st_set_gmres_cgs_refinement(ks_st st, int refine);
    allocation, are KS_ERR_MEM with nothing left half-built. With ks_st_set_transpose_solves a second plan of the same factors serves
    y = Q^T L^-T U^-T Q x. The default preconditioner stays point Jacobi. */
 #define KS_PC_LU 4
+/* KS_PC_AMG - smoothed-aggregation algebraic multigrid (PCGAMG with -pc_gamg_type agg, -st_pc_type gamg; written from the algorithm's description): a
+   hierarchy of P = A - sigma B (or B) made on the host - a symmetrised strength graph with threshold theta, aggregates in three ascending passes,
+   the prolongator (I - 4/(3 rho) D^-1 A) T of the piecewise constant T, R = P^T, Galerkin operators R A P, the last level (at most coarse_limit
+   rows, or the max_levels-th, or one that no longer coarsens) factored like KS_PC_LU - and on the device one V(nu, nu) cycle per application with
+   nu Chebyshev steps on D^-1 A over [0.1 rho, rho], rho being Gershgorin's bound. The cycle is symmetric for a symmetric P. Takes block_size 0
+   (anything else is KS_ERR_SUP). At set-up: the matrices must hold their CSR arrays (KS_MAT_KEEP_CSR; KS_ERR_ORDER); more than one rank, or
+   ks_st_set_transpose_solves, is KS_ERR_SUP (ks_st_pc_apply_transpose too); a row of any level without a stored diagonal entry, or with a zero
+   one, is KS_ERR_ARG_WRONGSTATE with the row in the message; a zero pivot of the last level KS_ERR_MAT_LU_ZRPVT; a product with more than
+   2^31 - 1 entries KS_ERR_ARG_OUTOFRANGE, a failed allocation KS_ERR_MEM, with nothing left half-built. The default stays point Jacobi. */
+#define KS_PC_AMG 5
 int ks_st_set_pc(ks_st st, int type, int block_size);
+/* The options of KS_PC_AMG; every setter clears the set-up, a value out of range is KS_ERR_ARG_OUTOFRANGE.
+   threshold: theta of the strength test |a_ij| >= theta sqrt(|a_ii a_jj|), 0 <= theta < 1, default 0 (-pc_gamg_threshold).
+   smoother: Chebyshev steps nu before and after the coarse correction, 1..4, default 2 (-mg_levels_ksp_max_it).
+   coarse: a level with at most coarse_limit (>= 1, default 200) rows is solved directly (-pc_gamg_coarse_eq_limit); at most max_levels levels,
+   1..16, default 10 (-pc_mg_levels).
+   prolongator smoothing: on by default (-pc_gamg_agg_nsmooths 1); off: the plain aggregation prolongator T. */
+int ks_st_pc_amg_set_threshold(ks_st st, double theta);
+int ks_st_pc_amg_get_threshold(ks_st st, double *theta);
+int ks_st_pc_amg_set_smoother(ks_st st, int degree);
+int ks_st_pc_amg_get_smoother(ks_st st, int *degree);
+int ks_st_pc_amg_set_coarse(ks_st st, int coarse_limit, int max_levels);
+int ks_st_pc_amg_get_coarse(ks_st st, int *coarse_limit, int *max_levels);
+int ks_st_pc_amg_set_prolongator_smoothing(ks_st st, int on);
+int ks_st_pc_amg_get_prolongator_smoothing(ks_st st, int *on);
+/* The hierarchy. Any pointer may be NULL. levels; rows, nnz, rho: per level, arrays of 16 (rho of the last level is 0: it is not smoothed);
+   complexity: stored entries of all the operators over those of the first; device_bytes: everything the preconditioner holds on the device;
+   launches: per application of one vector, a matrix product counted as one. Runs the set-up if needed; KS_ERR_ORDER when the PC is not KS_PC_AMG
+   or the transformation has no solve. */
+int ks_st_pc_amg_get_info(ks_st st, int *levels, int *rows, long long *nnz, double *rho, double *complexity, long long *device_bytes, int *launches);
+/* One level on the host, in two steps: with the arrays NULL only n, n_coarse (0 on the last level) and the stored entries of the level's operator
+   and of its prolongator are returned; then arp (n + 1), acol, aval (nnz_a), prp (n + 1), pcol, pval (nnz_p) and agg (n: the aggregate of a row, -1
+   outside every aggregate) are filled - the A group, the P group and agg each only when given; on the last level prp is all 0 and agg all -1. */
+int ks_st_pc_amg_get_level(ks_st st, int level, int *n, int *n_coarse, long long *nnz_a, long long *nnz_p, int *arp, int *acol, double *aval,
+                           int *prp, int *pcol, double *pval, int *agg);
+/* Test hook (KSD_TEST_HOOKS): one transfer kernel of KS_PC_AMG on a rectangular CSR matrix M given in host arrays (nrows x ncols, nvec vectors,
+   column-major). restriction != 0: out = M (u - v), u and v ncols x nvec; else out = v + M u, u ncols x nvec, v nrows x nvec. lanes: lanes per
+   row, 1, 8 or 64, 0 = the library's choice. All arrays in host memory. */
+int ks_pc_amg_test_transfer(ks_ctx ctx, int restriction, int lanes, int nrows, int ncols, const int *rp, const int *col, const double *val,
+                            int nvec, const double *u_host, const double *v_host, double *out_host);
 /* -pc_factor_mat_ordering_type on the PCLU: KS_ORDERING_ND (the default, as PCLU's: George's automatic nested dissection on rooted level structures
    of the graph of P + P^T, MATORDERINGND) or KS_ORDERING_NATURAL; any other value is KS_ERR_ARG_OUTOFRANGE. Changing it clears the set-up. */
 #define KS_ORDERING_ND      0
@@ -729,7 +768,7 @@ int ks_st_pc_apply(ks_st st, const double *x_dev, double *y_dev);
    Arguments as ks_mat_mult_multi: ncols == 0 does nothing, ldx, ldy >= max(1, n_local) (KS_ERR_ARG_SIZ), X and Y must not overlap
    (KS_ERR_ARG_WRONG). Enqueued, no host wait. */
 int ks_st_pc_apply_multi(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy);
-int ks_st_pc_multi_columns(ks_st st, int *columns);   /* instrumentation: columns of one pass of the above with the PC as set up (ILU blocks: 8 up to block size 512, 1 above; KS_PC_LU: 8 - a narrow stage of the schedule keeps eight right-hand sides in one launch, a wide level puts them on the grid; the other types: 65535, one launch) */
+int ks_st_pc_multi_columns(ks_st st, int *columns);   /* instrumentation: columns of one pass of the above with the PC as set up (ILU blocks: 8 up to block size 512, 1 above; KS_PC_LU: 8 - a narrow stage of the schedule keeps eight right-hand sides in one launch, a wide level puts them on the grid; KS_PC_AMG: 8 - the level operators' block product and the work vectors of the cycle; the other types: 65535, one launch) */
 /* STApplyMat stsolve.c:62: Y(:,j) = Op X(:,j). KS_ST_PRECOND: ks_st_pc_apply_multi; the other transformations: ks_st_apply column by column. Same arguments. */
 int ks_st_apply_mat(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy);
 int ks_st_backtransform(ks_st st, int n, double *eigr, double *eigi);     /* STBackTransform stsolve.c:563 */

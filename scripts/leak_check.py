@@ -35,6 +35,10 @@ def cycle(i):
     Bk = ks.Mat.from_csr(ctx, np.arange(Lo.n + 1, dtype=np.int32), np.arange(Lo.n, dtype=np.int32), d, keep_csr=True)
     slu = ks.ST(ctx); slu.SetType("sinvert"); slu.SetShift(1.3); slu.SetMatrices(Lk, Bk); slu.SetPC("lu"); slu.SetKSPType("preonly"); slu.SetTransposeSolves(True)
     slu.Apply(np.ones(Lo.n)); slu.SetShift(2.1 + 0.01 * i); slu.ApplyTranspose(np.ones(Lo.n)); slu.PCLUSetOrdering("natural"); slu.PCApply(np.ones(Lo.n))
+    # the multigrid hierarchy of the same P: set up, applied to one and to nine vectors, set up again by a new shift and by new options
+    samg = ks.ST(ctx); samg.SetType("sinvert"); samg.SetShift(-0.3); samg.SetMatrices(Lk, Bk); samg.SetPC("amg"); samg.PCAMGSetCoarse(8, 10)
+    samg.Apply(np.ones(Lo.n)); samg.SetShift(-0.2 - 0.01 * i); samg.PCApplyMulti(np.ones((Lo.n, 9))); samg.PCAMGSetSmoother(3); samg.PCAMGSetProlongatorSmoothing(False); samg.PCApply(np.ones(Lo.n))
+    del samg
     del slu, Lk, Bk
     V = ks.BV(ctx, 3000, 90); V.set_dense(np.random.default_rng(i).standard_normal((3000, 90)))
     V.SetOrthogBlock(["chol", "svqb", "gs", "tsqr"][i % 4])

@@ -852,8 +852,62 @@ class ST:
     def SetPC(self, t, block_size=0):
         """PCSetType on the ST's KSP: "jacobi" (default), "bjacobi" with blocks of block_size (2..32) consecutive local rows, solved exactly, or
         "bjacobi-ilu" with blocks of block_size (64..8192) rows, each factored by ILU(0), "none", or "lu": the whole P factored with fill under a
-        nested dissection ordering (PCLU; block_size 0, the matrices need keep_csr, one rank)."""
-        _lib.check(self.ctx.L.ks_st_set_pc(self.h, {"jacobi": 0, "bjacobi": 1, "bjacobi-ilu": 2, "none": 3, "lu": 4}.get(t, t), block_size))
+        nested dissection ordering (PCLU; block_size 0, the matrices need keep_csr, one rank), or "amg" ("gamg"): smoothed-aggregation multigrid,
+        one V-cycle with Chebyshev smoothing per application (same conditions as "lu")."""
+        _lib.check(self.ctx.L.ks_st_set_pc(self.h, {"jacobi": 0, "bjacobi": 1, "bjacobi-ilu": 2, "none": 3, "lu": 4, "amg": 5, "gamg": 5}.get(t, t), block_size))
+
+    def PCAMGSetThreshold(self, theta):
+        """-pc_gamg_threshold: an entry is strong when |a_ij| >= theta sqrt(|a_ii a_jj|); 0 <= theta < 1, default 0."""
+        _lib.check(self.ctx.L.ks_st_pc_amg_set_threshold(self.h, float(theta)))
+
+    def PCAMGGetThreshold(self):
+        v = C.c_double(); _lib.check(self.ctx.L.ks_st_pc_amg_get_threshold(self.h, C.byref(v))); return v.value
+
+    def PCAMGSetSmoother(self, degree):
+        """Chebyshev steps before and after the coarse correction (1..4, default 2)."""
+        _lib.check(self.ctx.L.ks_st_pc_amg_set_smoother(self.h, int(degree)))
+
+    def PCAMGGetSmoother(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_st_pc_amg_get_smoother(self.h, C.byref(v))); return v.value
+
+    def PCAMGSetCoarse(self, coarse_limit=200, max_levels=10):
+        """A level of at most coarse_limit rows is solved directly; at most max_levels (1..16) levels."""
+        _lib.check(self.ctx.L.ks_st_pc_amg_set_coarse(self.h, int(coarse_limit), int(max_levels)))
+
+    def PCAMGGetCoarse(self):
+        a, b = C.c_int(), C.c_int(); _lib.check(self.ctx.L.ks_st_pc_amg_get_coarse(self.h, C.byref(a), C.byref(b))); return a.value, b.value
+
+    def PCAMGSetProlongatorSmoothing(self, on):
+        _lib.check(self.ctx.L.ks_st_pc_amg_set_prolongator_smoothing(self.h, 1 if on else 0))
+
+    def PCAMGGetProlongatorSmoothing(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_st_pc_amg_get_prolongator_smoothing(self.h, C.byref(v))); return bool(v.value)
+
+    def PCAMGGetInfo(self):
+        """The hierarchy as a dict: levels, rows, nnz, rho (lists, one entry per level), complexity (operator complexity), device_bytes, launches (per
+        application of one vector, a product counted as one). Runs the set-up if needed."""
+        nl, la = C.c_int(), C.c_int(); cx = C.c_double(); by = C.c_longlong()
+        rows = (C.c_int * 16)(); nnz = (C.c_longlong * 16)(); rho = (C.c_double * 16)()
+        _lib.check(self.ctx.L.ks_st_pc_amg_get_info(self.h, C.byref(nl), rows, nnz, rho, C.byref(cx), C.byref(by), C.byref(la)))
+        k = nl.value
+        return {"levels": k, "rows": list(rows[:k]), "nnz": list(nnz[:k]), "rho": list(rho[:k]), "complexity": cx.value, "device_bytes": by.value, "launches": la.value}
+
+    def PCAMGGetLevel(self, level):
+        """One level on the host: (A, P, agg) - the level's operator and its prolongator as scipy CSR matrices with the library's stored pattern, and the
+        aggregate of every row (-1 outside every aggregate). On the last level P has no columns and agg is all -1."""
+        import scipy.sparse as sp
+        ipc, dpc = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        n, nc = C.c_int(), C.c_int(); za, zp = C.c_longlong(), C.c_longlong()
+        _lib.check(self.ctx.L.ks_st_pc_amg_get_level(self.h, int(level), C.byref(n), C.byref(nc), C.byref(za), C.byref(zp), None, None, None, None, None, None, None))
+        arp = np.zeros(n.value + 1, np.int32); acol = np.zeros(max(za.value, 1), np.int32); aval = np.zeros(max(za.value, 1))
+        prp = np.zeros(n.value + 1, np.int32); pcol = np.zeros(max(zp.value, 1), np.int32); pval = np.zeros(max(zp.value, 1)); agg = np.zeros(max(n.value, 1), np.int32)
+        _lib.check(self.ctx.L.ks_st_pc_amg_get_level(self.h, int(level), None, None, None, None, arp.ctypes.data_as(ipc), acol.ctypes.data_as(ipc), aval.ctypes.data_as(dpc),
+                                                     prp.ctypes.data_as(ipc), pcol.ctypes.data_as(ipc), pval.ctypes.data_as(dpc), agg.ctypes.data_as(ipc)))
+
+        def csr(val, col, rp, shape):
+            M = sp.csr_matrix(shape, dtype=np.float64); M.data, M.indices, M.indptr = val, col, rp      # the stored pattern as it is, explicit zeros included
+            return M
+        return csr(aval[:za.value], acol[:za.value], arp, (n.value, n.value)), csr(pval[:zp.value], pcol[:zp.value], prp, (n.value, nc.value)), agg[:n.value]
 
     def PCLUSetOrdering(self, which):
         """-pc_factor_mat_ordering_type of the PCLU: "nd" (default) or "natural"."""

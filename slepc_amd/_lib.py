@@ -246,6 +246,17 @@ _SIG = {
     "ks_st_pc_lu_get_permutation": [vp, ip],
     "ks_st_pc_lu_get_info": [vp, ip, llp, llp, ip, ip, ip, ip, ip, llp],
     "ks_st_pc_lu_get_inertia": [vp, ip, ip, ip],
+    "ks_st_pc_amg_set_threshold": [vp, C.c_double],
+    "ks_st_pc_amg_get_threshold": [vp, dp],
+    "ks_st_pc_amg_set_smoother": [vp, C.c_int],
+    "ks_st_pc_amg_get_smoother": [vp, ip],
+    "ks_st_pc_amg_set_coarse": [vp, C.c_int, C.c_int],
+    "ks_st_pc_amg_get_coarse": [vp, ip, ip],
+    "ks_st_pc_amg_set_prolongator_smoothing": [vp, C.c_int],
+    "ks_st_pc_amg_get_prolongator_smoothing": [vp, ip],
+    "ks_st_pc_amg_get_info": [vp, ip, ip, llp, dp, dp, llp, ip],
+    "ks_st_pc_amg_get_level": [vp, C.c_int, ip, ip, llp, llp, ip, ip, dp, ip, ip, dp, ip],
+    "ks_pc_amg_test_transfer": [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, dp, C.c_int, dp, dp, dp],
     "ks_st_get_matmode": [vp, C.POINTER(C.c_int)],
     "ks_st_setup": [vp],
     "ks_st_apply": [vp, vp, vp],

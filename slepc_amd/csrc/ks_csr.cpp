@@ -1,5 +1,6 @@
 #include "ks_csr.h"
 #include <algorithm>
+#include <cmath>
 #include <functional>
 #include <thread>
 #include <sched.h>
@@ -727,6 +728,173 @@ void csr_lu_plan(int n, const int *rp, const int *col, const double *val, int or
 }
 void lu_apply_host(const LuPlan &p, const double *in, double *out) { lu_walk_host(p, in, out); }
 void lu_apply_transpose_host(const LuPlan &t, const double *in, double *out) { lu_walk_host(t, in, out); }
+
+// ---- smoothed-aggregation multigrid (KS_PC_AMG) ---------------------------------------------------------------------------------------------
+namespace {
+struct Csr { std::vector<int> rp, col; std::vector<double> val; };
+constexpr size_t AMG_CAP = 2147483647u;
+
+// the rows sorted by column, repeated entries summed in stored order; nothing is added (a missing diagonal is the set-up's error to report)
+void amg_sorted_rows(int n, const int *rp, const int *col, const double *val, Csr &out)
+{
+  out.rp.assign((size_t)n + 1, 0); out.col.clear(); out.val.clear();
+  std::vector<int> idx;
+  for (int r = 0; r < n; r++) {
+    idx.clear();
+    for (int p = rp[r]; p < rp[r + 1]; p++) if (col[p] >= 0 && col[p] < n) idx.push_back(p);
+    std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return col[x] < col[y]; });
+    for (size_t i = 0; i < idx.size(); i++) {
+      if (i > 0 && col[idx[i]] == col[idx[i - 1]]) { out.val.back() = out.val.back() + val[idx[i]]; continue; }
+      out.col.push_back(col[idx[i]]); out.val.push_back(val[idx[i]]);
+    }
+    out.rp[r + 1] = (int)out.col.size();
+  }
+}
+
+// C = A B row by row, A with na rows, B with nb columns: the entries of A's row ascending, for each the row of B ascending, one fma per pair; false: too many entries
+bool amg_product(int na, int nb, const std::vector<int> &arp, const std::vector<int> &acol, const std::vector<double> &aval,
+                 const std::vector<int> &brp, const std::vector<int> &bcol, const std::vector<double> &bval, Csr &C)
+{
+  C.rp.assign((size_t)na + 1, 0); C.col.clear(); C.val.clear();
+  std::vector<int> mark((size_t)nb, -1), cols;
+  std::vector<double> acc((size_t)nb, 0.0);
+  for (int i = 0; i < na; i++) {
+    cols.clear();
+    for (int p = arp[i]; p < arp[i + 1]; p++) {
+      const int k = acol[p]; const double a = aval[p];
+      for (int q = brp[k]; q < brp[k + 1]; q++) {
+        const int j = bcol[q];
+        if (mark[j] != i) { mark[j] = i; acc[j] = 0.0; cols.push_back(j); }
+        acc[j] = __builtin_fma(a, bval[q], acc[j]);
+      }
+    }
+    std::sort(cols.begin(), cols.end());
+    if (C.col.size() + cols.size() > AMG_CAP) return false;
+    for (int j : cols) { C.col.push_back(j); C.val.push_back(acc[j]); }
+    C.rp[i + 1] = (int)C.col.size();
+  }
+  return true;
+}
+
+// the symmetrised strength graph: xadj / adj / w, a row's neighbours ascending, each once with the larger of the two weights
+void amg_strength(const AmgLevel &L, const std::vector<double> &d, double theta, std::vector<int> &xadj, std::vector<int> &adj, std::vector<double> &w)
+{
+  const int n = L.n;
+  auto strong = [&](int i, int p) { const int j = L.col[p]; const double a = std::fabs(L.val[p]); return j != i && L.val[p] != 0.0 && a >= theta * std::sqrt(std::fabs(d[i] * d[j])); };
+  std::vector<size_t> start((size_t)n + 1, 0);
+  for (int i = 0; i < n; i++) for (int p = L.rp[i]; p < L.rp[i + 1]; p++) if (strong(i, p)) { start[i + 1]++; start[L.col[p] + 1]++; }
+  for (int i = 0; i < n; i++) start[i + 1] += start[i];
+  std::vector<std::pair<int, double>> e(start[n]);
+  std::vector<size_t> fill(start.begin(), start.end() - 1);
+  for (int i = 0; i < n; i++) for (int p = L.rp[i]; p < L.rp[i + 1]; p++) if (strong(i, p)) {
+    const int j = L.col[p]; const double a = std::fabs(L.val[p]);
+    e[fill[i]++] = {j, a}; e[fill[j]++] = {i, a};
+  }
+  xadj.assign((size_t)n + 1, 0); adj.clear(); w.clear();
+  for (int i = 0; i < n; i++) {
+    std::sort(e.begin() + start[i], e.begin() + start[i + 1]);        // by neighbour, then by weight: the last of a run is the larger
+    for (size_t p = start[i]; p < start[i + 1]; p++) {
+      if (p + 1 < start[i + 1] && e[p + 1].first == e[p].first) continue;
+      adj.push_back(e[p].first); w.push_back(e[p].second);
+    }
+    xadj[i + 1] = (int)adj.size();
+  }
+}
+
+int amg_aggregate(int n, const std::vector<int> &xadj, const std::vector<int> &adj, const std::vector<double> &w, std::vector<int> &agg)
+{
+  agg.assign((size_t)n, -1);
+  int nagg = 0;
+  for (int i = 0; i < n; i++) {                                       // pass 1
+    if (agg[i] >= 0 || xadj[i] == xadj[i + 1]) continue;
+    bool free_ = true;
+    for (int p = xadj[i]; p < xadj[i + 1] && free_; p++) free_ = agg[adj[p]] < 0;
+    if (!free_) continue;
+    agg[i] = nagg;
+    for (int p = xadj[i]; p < xadj[i + 1]; p++) agg[adj[p]] = nagg;
+    nagg++;
+  }
+  const std::vector<int> after1(agg);
+  for (int i = 0; i < n; i++) {                                       // pass 2: against the state pass 1 left
+    if (after1[i] >= 0) continue;
+    int best = -1;
+    for (int p = xadj[i]; p < xadj[i + 1]; p++) if (after1[adj[p]] >= 0 && (best < 0 || w[p] > w[best])) best = p;
+    if (best >= 0) agg[i] = after1[adj[best]];
+  }
+  for (int i = 0; i < n; i++) {                                       // pass 3
+    if (agg[i] >= 0 || xadj[i] == xadj[i + 1]) continue;
+    agg[i] = nagg;
+    for (int p = xadj[i]; p < xadj[i + 1]; p++) if (agg[adj[p]] < 0) agg[adj[p]] = nagg;
+    nagg++;
+  }
+  return nagg;
+}
+} // namespace
+
+void amg_plan(int n, const int *rp, const int *col, const double *val, const AmgOptions &opt, AmgPlan &out)
+{
+  out = AmgPlan();
+  const int max_levels = std::max(1, std::min(opt.max_levels, AMG_MAX_LEVELS));
+  out.levels.reserve((size_t)max_levels);
+  out.levels.emplace_back();
+  { Csr A0; amg_sorted_rows(n, rp, col, val, A0); AmgLevel &L = out.levels.back(); L.n = n; L.rp.swap(A0.rp); L.col.swap(A0.col); L.val.swap(A0.val); }
+  std::vector<int> xadj, adj, size, mark, cols;
+  std::vector<double> w, d, t, acc;
+  while (out.levels.back().n > opt.coarse_limit && (int)out.levels.size() < max_levels) {
+    AmgLevel &L = out.levels.back();
+    const int nl = L.n, lev = (int)out.levels.size() - 1;
+    d.assign((size_t)nl, 0.0);
+    double rho = 0.0;
+    for (int i = 0; i < nl; i++) {
+      double sum = 0.0; bool stored = false;
+      for (int p = L.rp[i]; p < L.rp[i + 1]; p++) { sum = sum + std::fabs(L.val[p]); if (L.col[p] == i) { d[i] = L.val[p]; stored = true; } }
+      if (!stored || d[i] == 0.0) { out.status = AMG_NO_DIAGONAL; out.bad_level = lev; out.bad_row = i; return; }
+      rho = std::max(rho, sum / std::fabs(d[i]));
+    }
+    amg_strength(L, d, opt.theta, xadj, adj, w);
+    std::vector<int> agg;
+    const int nagg = amg_aggregate(nl, xadj, adj, w, agg);
+    if (nagg == 0 || (double)nagg > opt.stall * (double)nl) break;
+    size.assign((size_t)nagg, 0);
+    for (int i = 0; i < nl; i++) if (agg[i] >= 0) size[agg[i]]++;
+    t.assign((size_t)nl, 0.0);
+    for (int i = 0; i < nl; i++) if (agg[i] >= 0) t[i] = 1.0 / std::sqrt((double)size[agg[i]]);
+    L.rho = rho; L.nagg = nagg;
+    L.dinv.resize((size_t)nl);
+    for (int i = 0; i < nl; i++) L.dinv[i] = 1.0 / d[i];
+    L.prp.assign((size_t)nl + 1, 0);
+    if (!opt.smooth) {
+      for (int i = 0; i < nl; i++) { if (agg[i] >= 0) { L.pcol.push_back(agg[i]); L.pval.push_back(t[i]); } L.prp[i + 1] = (int)L.pcol.size(); }
+    } else {
+      const double omega = 4.0 / (3.0 * rho);
+      mark.assign((size_t)nagg, -1); acc.assign((size_t)nagg, 0.0);
+      for (int i = 0; i < nl; i++) {
+        cols.clear();
+        if (agg[i] >= 0) { mark[agg[i]] = i; acc[agg[i]] = 0.0; cols.push_back(agg[i]); }
+        for (int p = L.rp[i]; p < L.rp[i + 1]; p++) {
+          const int c = agg[L.col[p]];
+          if (c < 0) continue;
+          if (mark[c] != i) { mark[c] = i; acc[c] = 0.0; cols.push_back(c); }
+          acc[c] = __builtin_fma(L.val[p], t[L.col[p]], acc[c]);
+        }
+        std::sort(cols.begin(), cols.end());
+        if (L.pcol.size() + cols.size() > AMG_CAP) { out.status = AMG_TOO_LARGE; out.bad_level = lev; out.bad_row = i; return; }
+        const double s = omega / d[i];
+        for (int c : cols) { const double sm = s * acc[c]; L.pcol.push_back(c); L.pval.push_back((c == agg[i] ? t[i] : 0.0) - sm); }
+        L.prp[i + 1] = (int)L.pcol.size();
+      }
+    }
+    L.agg.swap(agg);
+    csr_transpose(nl, nagg, L.prp.data(), L.pcol.data(), L.pval.data(), L.rrp, L.rcol, L.rval);
+    Csr AP, Ac;
+    if (!amg_product(nl, nagg, L.rp, L.col, L.val, L.prp, L.pcol, L.pval, AP) || !amg_product(nagg, nagg, L.rrp, L.rcol, L.rval, AP.rp, AP.col, AP.val, Ac)) {
+      out.status = AMG_TOO_LARGE; out.bad_level = lev; return;
+    }
+    out.levels.emplace_back();                                      // (reserved above: L stays valid)
+    AmgLevel &Lc = out.levels.back();
+    Lc.n = nagg; Lc.rp.swap(Ac.rp); Lc.col.swap(Ac.col); Lc.val.swap(Ac.val);
+  }
+}
 } // namespace ksc
 
 #ifdef KSD_TEST_HOOKS
@@ -932,6 +1100,32 @@ int ksc_lu_plan(int n, const int *rp, const int *col, const double *val, int ord
   }
   if (in && out_f) ksc::lu_apply_host(p, in, out_f);
   if (in && out_t) ksc::lu_apply_transpose_host(t, in, out_t);
+  return 0;
+}
+// test hook: the AMG hierarchy. info: status, bad row, bad level, levels, then four per level: rows, entries of the operator, entries of P, aggregates
+// (room for 4 + 4 * 16); rho: one per level (16). level >= 0: that level's operator (arp rows + 1, acol / aval), and - every level but the last - its
+// P (prp rows + 1, pcol / pval) and aggregate index (agg rows; the last level: -1 everywhere) into arrays sized by a first call. Returns the status.
+int ksc_amg_plan(int n, const int *rp, const int *col, const double *val, double theta, int coarse_limit, int max_levels, int smooth, double stall, long long *info,
+                 double *rho, int level, int *arp, int *acol, double *aval, int *prp, int *pcol, double *pval, int *agg)
+{
+  ksc::AmgOptions opt; opt.theta = theta; opt.coarse_limit = coarse_limit; opt.max_levels = max_levels; opt.smooth = smooth != 0; opt.stall = stall;
+  ksc::AmgPlan p;
+  ksc::amg_plan(n, rp, col, val, opt, p);
+  for (int i = 0; i < 4 + 4 * ksc::AMG_MAX_LEVELS; i++) info[i] = 0;
+  info[0] = p.status; info[1] = p.bad_row; info[2] = p.bad_level;
+  if (p.status) return p.status;
+  info[3] = (long long)p.levels.size();
+  for (size_t l = 0; l < p.levels.size(); l++) {
+    const ksc::AmgLevel &L = p.levels[l];
+    info[4 + 4 * l] = L.n; info[5 + 4 * l] = (long long)L.col.size(); info[6 + 4 * l] = (long long)L.pcol.size(); info[7 + 4 * l] = L.nagg;
+    rho[l] = L.rho;
+  }
+  if (level >= 0 && level < (int)p.levels.size()) {
+    const ksc::AmgLevel &L = p.levels[level];
+    std::copy(L.rp.begin(), L.rp.end(), arp); std::copy(L.col.begin(), L.col.end(), acol); std::copy(L.val.begin(), L.val.end(), aval);
+    if (L.agg.empty()) { std::fill(prp, prp + L.n + 1, 0); std::fill(agg, agg + L.n, -1); }
+    else { std::copy(L.prp.begin(), L.prp.end(), prp); std::copy(L.pcol.begin(), L.pcol.end(), pcol); std::copy(L.pval.begin(), L.pval.end(), pval); std::copy(L.agg.begin(), L.agg.end(), agg); }
+  }
   return 0;
 }
 }

@@ -1,6 +1,6 @@
 // Host-side planning of the assembly path (no device code, no ks_mat): everything ks_mat.hip decides with index arithmetic on the host - the split of
 // a row block into its diagonal and ghost parts, the halo plan between the ranks, the binned, windowed and ILU(0) layouts, the plan of the transposed
-// product across ranks, MatAXPY on CSR arrays, the sparse LU with fill of KS_PC_LU (ordering, factors, level schedule; tests/test_lu_host.py). Plain functions that fill structs of vectors; constants of the device side come in as parameters and a
+// product across ranks, MatAXPY on CSR arrays, the sparse LU with fill of KS_PC_LU (ordering, factors, level schedule; tests/test_lu_host.py), the multigrid hierarchy of KS_PC_AMG (tests/test_amg_host.py). Plain functions that fill structs of vectors; constants of the device side come in as parameters and a
 // refusal is a status in the result. ks_mat.hip calls a planner and uploads what it filled; KSD_TEST_HOOKS exports each of them as a ksc_* C function,
 // and those run on the CPU (tests/test_csr_host.py, test_assembly_host.py, test_sharded_transpose_host.py, test_ilu_host.py, tests/host/assembly_plans.cpp).
 #pragma once
@@ -187,4 +187,36 @@ void csr_lu_plan(int n, const int *rp, const int *col, const double *val, int or
 // combined in the fixed order of the wave sums (ks_sweeps.cuh). out = Q^T U^-1 L^-1 Q in from the forward plan, Q^T L^-T U^-T Q in from the transposed
 void lu_apply_host(const LuPlan &p, const double *in, double *out);
 void lu_apply_transpose_host(const LuPlan &t, const double *in, double *out);
+
+// The hierarchy of the smoothed-aggregation multigrid preconditioner (KS_PC_AMG; the kernels that walk it: ks_pc_amg.hip). Level 0 is P itself, its
+// rows sorted by column and repeated entries summed in stored order (columns outside [0, n) ignored: one rank owns every row); explicit zeros stay
+// entries. A level that has at most coarse_limit rows, or is the max_levels-th, is the last. Otherwise, in order:
+//   diagonal   d_i = a_ii; a row that stores none, or a zero, ends the plan: status AMG_NO_DIAGONAL with the level and the row.
+//              rho = max_i (sum_j |a_ij|) / |a_ii|: Gershgorin's bound of the spectral radius of D^-1 A, never an underestimate.
+//   strength   the graph with an edge i - j (i != j) when a_ij != 0 and |a_ij| >= theta sqrt(|a_ii a_jj|) or the same holds for a_ji; the edge's
+//              weight is max(|a_ij|, |a_ji|), an entry that is not stored counting as 0.
+//   aggregates three passes, every loop ascending. 1: an unaggregated node with neighbours, none of them aggregated, founds an aggregate with all
+//              of them. 2: a node still outside joins the aggregate of the neighbour with the largest weight among those pass 1 aggregated (what
+//              pass 2 assigns is not looked at; ties: the lowest column). 3: a node still outside that has neighbours founds an aggregate with
+//              the neighbours still outside. A node without neighbours stays outside (agg = -1): its row of the prolongator is empty.
+//              No aggregate at all, or more than `stall` times the rows, makes this level the last.
+//   transfer   T has one column per aggregate with the entries 1 / sqrt(size). The prolongator is T, or smoothed P = (I - (4 / (3 rho)) D^-1 A) T:
+//              row i sums a_ij t_j by fma in ascending j into its aggregates' columns, then p_ic = t_ic - ((4 / (3 rho)) / d_i) sum_c. The
+//              pattern is that of A T joined with T's; nothing is dropped. R = P^T by the counting sort of csr_transpose.
+//   Galerkin   A_c = R (A P), both products row by row (Gustavson): the entries of the left row ascending, for each the right row ascending,
+//              acc[col] = fma(left, right, acc[col]); a row's columns come out ascending. Nothing is dropped.
+// status AMG_TOO_LARGE: a product with more than 2^31 - 1 entries. Deterministic; allocation failures are exceptions of the vectors.
+constexpr int AMG_NO_DIAGONAL = 1, AMG_TOO_LARGE = 2;
+constexpr int AMG_MAX_LEVELS = 16;
+struct AmgOptions { double theta = 0.0; int coarse_limit = 200, max_levels = 10; bool smooth = true; double stall = 0.8; };
+struct AmgLevel {
+  int n = 0, nagg = 0; double rho = 0.0;                      // rho, dinv, agg and the transfers: every level but the last
+  std::vector<int> rp, col; std::vector<double> val;          // the level's operator
+  std::vector<double> dinv;                                   // 1 / a_ii
+  std::vector<int> agg;                                       // the aggregate of a row, -1: none
+  std::vector<int> prp, pcol; std::vector<double> pval;       // P: n x nagg
+  std::vector<int> rrp, rcol; std::vector<double> rval;       // R: nagg x n
+};
+struct AmgPlan { int status = 0, bad_level = -1, bad_row = -1; std::vector<AmgLevel> levels; };
+void amg_plan(int n, const int *rp, const int *col, const double *val, const AmgOptions &opt, AmgPlan &out);
 }

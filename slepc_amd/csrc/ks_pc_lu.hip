@@ -40,16 +40,7 @@ constexpr int LU_MULTI_COLUMNS = 8;
 
 struct LuDev { const int *rows, *rp, *col, *lev, *perm; const double *val, *dinv; int n, first_scaled; };
 
-// the sum over a group of LANES consecutive lanes, in every lane of the group (8) or of the wave (64); every lane of the wave takes part
-template <int LANES> __device__ __forceinline__ double group_sum(double v)
-{
-  if (LANES == 1) return v;
-  if (LANES == 64) return ksk::wave_sum(v);
-  v += ksk::dpp_mov<0xb1>(v);        // quad_perm [1,0,3,2]
-  v += ksk::dpp_mov<0x4e>(v);        // quad_perm [2,3,0,1]
-  v += ksk::dpp_mov<0x141>(v);       // row_half_mirror: lane l of a half row reads lane 7 - l, the other quad
-  return v;
-}
+using ksk::group_sum;      // the sum over the 1, 8 or 64 lanes of a row (ks_sweeps.cuh)
 
 // what a finished row does with its sum: the first triangle reads its right-hand side through the permutation, the second one writes the result through it
 __device__ __forceinline__ void lu_finish_row(const LuDev &d, int pos, int r, double acc, const double *__restrict__ in, double *__restrict__ w, double *__restrict__ out)

@@ -131,10 +131,14 @@ int bjacobi_apply(ks_st st, const double *in, double *out, bool tr = false)
   return KS_SUCCESS;
 }
 // out = M^-1 in for the preconditioners that are not pointwise: the dense inverses, the ILU(0) factors (k_bjacobi_ilu_apply, ks_pc.hip), or the LU
-// factors of the whole P (ks_pc_lu.hip)
+// factors of the whole P (ks_pc_lu.hip), or the multigrid cycle on P (ks_pc_amg.hip)
 int blocks_apply(ks_st st, const double *in, double *out, bool tr = false)
 {
   if (st->pc_type == KS_PC_LU) return tr ? ks_pc_lu_apply_transpose(st->ctx, st->lu, in, out) : ks_pc_lu_apply(st->ctx, st->lu, in, out);
+  if (st->pc_type == KS_PC_AMG) {
+    KS_CHECK(!tr, KS_ERR_SUP, "KS_PC_AMG has no transposed cycle");
+    return ks_pc_amg_apply(st->ctx, st->amg, in, out);
+  }
   if (st->pc_type == KS_PC_BJACOBI_ILU) return tr ? ks_pc_ilu_apply_transpose(st->ctx, st->ilu, in, out) : ks_pc_ilu_apply(st->ctx, st->ilu, in, out);
   return bjacobi_apply(st, in, out, tr);
 }
@@ -142,7 +146,7 @@ int blocks_apply(ks_st st, const double *in, double *out, bool tr = false)
 int pc_lincomb(ks_st st, double a, const double *u, double b, const double *v, double *out, bool tr = false)
 {
   if (st->pc_type == KS_PC_JACOBI || pc_none(st)) return lincomb(st->ctx, st->n, pc_none(st) ? nullptr : st->dinv, a, u, b, v, out);
-  if (st->pc_type == KS_PC_LU && a == 1.0 && (b == 0.0 || !v) && u != out) return blocks_apply(st, u, out, tr);      // the factors read u through their permutation: no copy
+  if ((st->pc_type == KS_PC_LU || st->pc_type == KS_PC_AMG) && a == 1.0 && (b == 0.0 || !v) && u != out) return blocks_apply(st, u, out, tr);      // the factors read u through their permutation, the cycle only reads it: no copy
   KS_CALL(lincomb(st->ctx, st->n, nullptr, a, u, b, v, st->pcwork));
   return blocks_apply(st, st->pcwork, out, tr);
 }
@@ -437,6 +441,23 @@ static int lu_setup(ks_st st)
   return KS_SUCCESS;
 }
 
+// PCGAMG with smoothed aggregation: the hierarchy of the whole P from the same arrays, made on the host (ksc::amg_plan), uploaded once per set-up (ks_pc_amg.hip)
+static int amg_setup(ks_st st)
+{
+  KS_CHECK(st->ctx->comm.size == 1, KS_ERR_SUP, "KS_PC_AMG runs on one rank (the aggregation of a row-sharded matrix is not built)");
+  KS_CHECK(!st->tsolves, KS_ERR_SUP, "KS_PC_AMG has no transposed cycle: ks_st_set_transpose_solves cannot be on with it");
+  std::vector<int> rp, col; std::vector<double> val;
+  const int *prp; const int *pcol; const double *pval;
+  KS_CALL(pc_block_source(st, rp, col, val, &prp, &pcol, &pval));
+  KS_CALL(ks_pc_amg_build(st->ctx, st->n, prp, pcol, pval, st->amg_opt, &st->amg));
+  if (st->pcwork) { hipFree(st->pcwork); st->pcwork = nullptr; }
+  if (hipMalloc(&st->pcwork, sizeof(double) * std::max(st->n, 1)) != hipSuccess) {
+    (void)hipGetLastError(); st->pcwork = nullptr; ks_pc_amg_free(st->amg); st->amg = nullptr;
+    KS_FAIL(KS_ERR_MEM, "AMG set-up: no device memory for a work vector of %d rows", st->n);
+  }
+  return KS_SUCCESS;
+}
+
 bool ks_st_is_plain(ks_st st) { return !st || (st->type == KS_ST_SHIFT && st->sigma == 0.0 && !st->B); }
 
 int ks_st_setup_internal(ks_st st)
@@ -455,6 +476,7 @@ int ks_st_setup_internal(ks_st st)
   if (st->Pmat) { ks_mat_destroy(st->Pmat); st->Pmat = nullptr; }           // the assembled P of an earlier shift / type / mode
   if (st->ilu) { ks_pc_ilu_free(st->ilu); st->ilu = nullptr; }              // and its ILU(0) blocks
   if (st->lu) { ks_pc_lu_free(st->lu); st->lu = nullptr; }                  // or its LU factors
+  if (st->amg) { ks_pc_amg_free(st->amg); st->amg = nullptr; }              // or its multigrid hierarchy
   const bool need_solve = (st->type == KS_ST_SINVERT) || (st->type == KS_ST_CAYLEY) || (st->type == KS_ST_SHIFT && B);
   // STPRECOND (precond.c:36-110): K = A - sigma B is only preconditioned, the KSP is preonly - the preconditioner is built, no Krylov basis
   const bool precond = st->type == KS_ST_PRECOND;
@@ -500,6 +522,7 @@ int ks_st_setup_internal(ks_st st)
     if (st->pc_type == KS_PC_BJACOBI && !st->pc_identity) KS_CALL(bjacobi_setup(st));
     if (st->pc_type == KS_PC_BJACOBI_ILU && !st->pc_identity) KS_CALL(bjacobi_ilu_setup(st));
     if (st->pc_type == KS_PC_LU && !st->pc_identity) KS_CALL(lu_setup(st));
+    if (st->pc_type == KS_PC_AMG && !st->pc_identity) KS_CALL(amg_setup(st));
   }
   if (!st->op) KS_CALL(ks_mat_create_shell(ctx, A->n, A->row_start, A->n_global, st_shell_mult, st, &st->op));
   st->op->n = A->n; st->op->row_start = A->row_start; st->op->n_global = A->n_global;
@@ -551,6 +574,7 @@ extern "C" int ks_st_destroy(ks_st st)
   if (st->pcwork) hipFree(st->pcwork);
   ks_pc_ilu_free(st->ilu);
   ks_pc_lu_free(st->lu);
+  ks_pc_amg_free(st->amg);
   delete st;
   return KS_SUCCESS;
 }
@@ -612,7 +636,8 @@ extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType
 extern "C" int ks_st_set_pc(ks_st st, int type, int block_size)       // PCSetType (+ PCBJacobiSetLocalBlocks, -sub_pc_type lu | ilu) on the KSP's PC
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  KS_CHECK(type == KS_PC_JACOBI || type == KS_PC_BJACOBI || type == KS_PC_BJACOBI_ILU || type == KS_PC_NONE || type == KS_PC_LU, KS_ERR_SUP, "only PCNONE, PCJACOBI, PCBJACOBI (sub-solves: LU on dense blocks, or ILU(0)) and PCLU are built");
+  KS_CHECK(type == KS_PC_JACOBI || type == KS_PC_BJACOBI || type == KS_PC_BJACOBI_ILU || type == KS_PC_NONE || type == KS_PC_LU || type == KS_PC_AMG, KS_ERR_SUP, "only PCNONE, PCJACOBI, PCBJACOBI (sub-solves: LU on dense blocks, or ILU(0)), PCLU and PCGAMG are built");
+  KS_CHECK(type != KS_PC_AMG || block_size == 0, KS_ERR_SUP, "PCGAMG works on the whole matrix: a block size (%d) with it names no preconditioner this build has", block_size);
   KS_CHECK(type != KS_PC_LU || block_size == 0, KS_ERR_SUP, "PCLU factors the whole matrix: a block size (%d) with it names no preconditioner this build has", block_size);
   KS_CHECK(type != KS_PC_NONE || block_size == 0, KS_ERR_SUP, "PCNONE has no blocks: a block size (%d) with it names no preconditioner this build has", block_size);
   KS_CHECK(type != KS_PC_BJACOBI || (block_size >= 2 && block_size <= 32), KS_ERR_ARG_OUTOFRANGE, "block size %d (2..32)", block_size);
@@ -660,6 +685,77 @@ extern "C" int ks_st_pc_lu_get_inertia(ks_st st, int *neg, int *zero, int *pos) 
 {
   KsLuInfo i; KS_CALL(lu_query(st, &i));
   if (neg) *neg = i.neg; if (zero) *zero = 0; if (pos) *pos = i.pos;
+  return KS_SUCCESS;
+}
+// KS_PC_AMG: its options (each clears the set-up) and the two queries of the hierarchy
+extern "C" int ks_st_pc_amg_set_threshold(ks_st st, double theta)           // -pc_gamg_threshold
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  KS_CHECK(theta >= 0.0 && theta < 1.0, KS_ERR_ARG_OUTOFRANGE, "strength threshold %g (0 <= theta < 1)", theta);
+  if (st->amg_opt.theta != theta) { st->amg_opt.theta = theta; st->ready = false; }
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_amg_get_threshold(ks_st st, double *theta) { KS_CHECK(st && theta, KS_ERR_ARG_NULL, "NULL argument"); *theta = st->amg_opt.theta; return KS_SUCCESS; }
+extern "C" int ks_st_pc_amg_set_smoother(ks_st st, int degree)
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  KS_CHECK(degree >= 1 && degree <= 4, KS_ERR_ARG_OUTOFRANGE, "Chebyshev degree %d (1..4)", degree);
+  if (st->amg_opt.degree != degree) { st->amg_opt.degree = degree; st->ready = false; }
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_amg_get_smoother(ks_st st, int *degree) { KS_CHECK(st && degree, KS_ERR_ARG_NULL, "NULL argument"); *degree = st->amg_opt.degree; return KS_SUCCESS; }
+extern "C" int ks_st_pc_amg_set_coarse(ks_st st, int coarse_limit, int max_levels)
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  KS_CHECK(coarse_limit >= 1, KS_ERR_ARG_OUTOFRANGE, "coarse limit %d (at least 1 row)", coarse_limit);
+  KS_CHECK(max_levels >= 1 && max_levels <= KS_AMG_MAX_LEVELS, KS_ERR_ARG_OUTOFRANGE, "levels %d (1..%d)", max_levels, KS_AMG_MAX_LEVELS);
+  if (st->amg_opt.coarse_limit != coarse_limit || st->amg_opt.max_levels != max_levels) { st->amg_opt.coarse_limit = coarse_limit; st->amg_opt.max_levels = max_levels; st->ready = false; }
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_amg_get_coarse(ks_st st, int *coarse_limit, int *max_levels)
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  if (coarse_limit) *coarse_limit = st->amg_opt.coarse_limit; if (max_levels) *max_levels = st->amg_opt.max_levels;
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_amg_set_prolongator_smoothing(ks_st st, int on)
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  if (st->amg_opt.smooth != (on != 0)) { st->amg_opt.smooth = on != 0; st->ready = false; }
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_amg_get_prolongator_smoothing(ks_st st, int *on) { KS_CHECK(st && on, KS_ERR_ARG_NULL, "NULL argument"); *on = st->amg_opt.smooth ? 1 : 0; return KS_SUCCESS; }
+static int amg_query(ks_st st)
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  KS_CHECK(st->A, KS_ERR_ORDER, "STSetMatrices must be called first");
+  KS_CHECK(st->pc_type == KS_PC_AMG, KS_ERR_ORDER, "the preconditioner is not KS_PC_AMG");
+  KS_HIP(hipSetDevice(st->ctx->device));
+  if (!st->ready) KS_CALL(ks_st_setup_internal(st));
+  KS_CHECK(st->amg, KS_ERR_ORDER, "this transformation has no linear solve, so no hierarchy (STSHIFT with one matrix, or STPRECOND without a matrix to precondition)");
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_amg_get_info(ks_st st, int *levels, int *rows, long long *nnz, double *rho, double *complexity, long long *device_bytes, int *launches)
+{
+  KS_CALL(amg_query(st));
+  KsAmgInfo i; ks_pc_amg_info(st->amg, &i);
+  if (levels) *levels = i.levels;
+  for (int l = 0; l < KS_AMG_MAX_LEVELS; l++) { if (rows) rows[l] = i.rows[l]; if (nnz) nnz[l] = i.nnz[l]; if (rho) rho[l] = i.rho[l]; }
+  if (complexity) *complexity = i.complexity; if (launches) *launches = i.launches;
+  if (device_bytes) *device_bytes = i.bytes + (long long)sizeof(double) * std::max(st->n, 1);      // the ST's own work vector with it
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_amg_get_level(ks_st st, int level, int *n, int *n_coarse, long long *nnz_a, long long *nnz_p, int *arp, int *acol, double *aval,
+                                      int *prp, int *pcol, double *pval, int *agg)
+{
+  KS_CALL(amg_query(st));
+  int nl = 0, nc = 0; const int *hrp, *hcol, *hprp, *hpcol, *hagg; const double *hval, *hpval;
+  KS_CALL(ks_pc_amg_level(st->amg, level, &nl, &nc, &hrp, &hcol, &hval, &hprp, &hpcol, &hpval, &hagg));
+  const long long za = hrp[nl], zp = hprp ? hprp[nl] : 0;
+  if (n) *n = nl; if (n_coarse) *n_coarse = nc; if (nnz_a) *nnz_a = za; if (nnz_p) *nnz_p = zp;
+  if (arp && acol && aval) { std::copy(hrp, hrp + nl + 1, arp); std::copy(hcol, hcol + za, acol); std::copy(hval, hval + za, aval); }
+  if (prp && pcol && pval) { if (hprp) { std::copy(hprp, hprp + nl + 1, prp); std::copy(hpcol, hpcol + zp, pcol); std::copy(hpval, hpval + zp, pval); } else std::fill(prp, prp + nl + 1, 0); }
+  if (agg) { if (hagg) std::copy(hagg, hagg + nl, agg); else std::fill(agg, agg + nl, -1); }
   return KS_SUCCESS;
 }
 extern "C" int ks_st_set_gmres_cgs_refinement(ks_st st, int refine)   // KSPGMRESSetCGSRefinementType on STGetKSP
@@ -714,6 +810,7 @@ int ks_st_pc_apply_multi_internal(ks_st st, int ncols, const double *X, int ldx,
   if (ncols <= 0 || st->n == 0) return KS_SUCCESS;
   if (st->pc_type == KS_PC_BJACOBI_ILU && !st->pc_identity) return ks_pc_ilu_apply_multi(st->ctx, st->ilu, ncols, X, ldx, Y, ldy);
   if (st->pc_type == KS_PC_LU && !st->pc_identity) return ks_pc_lu_apply_multi(st->ctx, st->lu, ncols, X, ldx, Y, ldy);
+  if (st->pc_type == KS_PC_AMG && !st->pc_identity) return ks_pc_amg_apply_multi(st->ctx, st->amg, ncols, X, ldx, Y, ldy);
   const unsigned nb = (unsigned)std::min<long long>(((long long)st->n + 255) / 256, (long long)st->ctx->num_cu * 16);
   if (st->pc_type == KS_PC_BJACOBI && !st->pc_identity) hipLaunchKernelGGL(k_bjacobi_apply, dim3(nb, (unsigned)ncols), dim3(256), 0, st->ctx->stream, (long long)st->n, st->pc_bs, st->binv, X, (long long)ldx, Y, (long long)ldy);
   else hipLaunchKernelGGL(k_diag_apply_multi, dim3(nb, (unsigned)ncols), dim3(256), 0, st->ctx->stream, (long long)st->n, pc_none(st) ? (const double *)nullptr : st->dinv, X, (long long)ldx, Y, (long long)ldy);
@@ -740,6 +837,7 @@ extern "C" int ks_st_pc_multi_columns(ks_st st, int *columns)      // instrument
   KS_HIP(hipSetDevice(st->ctx->device));
   if (!st->ready) KS_CALL(ks_st_setup_internal(st));
   if (st->pc_type == KS_PC_LU && st->lu) { *columns = ks_pc_lu_multi_columns(); return KS_SUCCESS; }
+  if (st->pc_type == KS_PC_AMG && st->amg) { *columns = ks_pc_amg_multi_columns(); return KS_SUCCESS; }
   *columns = (st->pc_type == KS_PC_BJACOBI_ILU && st->ilu) ? std::max(1, ks_pc_ilu_multi_columns(st->ctx, st->ilu)) : 65535;      // the other types take the whole block in one launch (grid.y)
   return KS_SUCCESS;
 }

@@ -56,6 +56,18 @@ __device__ __forceinline__ double wave_sum(double v)
   v += dpp_mov<0x143>(v);      // row_bcast 31: rows 2, 3 add lane 31 (rows 0 + 1); lane 63 = all four rows
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
+// the sum over a group of LANES consecutive lanes, in every lane of the group (8) or of the wave (64); every lane of the wave takes part
+// (the row sums of the triangular solves, ks_pc_lu.hip, and of the multigrid transfers, ks_pc_amg.hip)
+template <int LANES> __device__ __forceinline__ double group_sum(double v)
+{
+  static_assert(LANES == 1 || LANES == 8 || LANES == 64, "1, 8 or 64 lanes per row");
+  if (LANES == 1) return v;
+  if (LANES == 64) return wave_sum(v);
+  v += dpp_mov<0xb1>(v);        // quad_perm [1,0,3,2]
+  v += dpp_mov<0x4e>(v);        // quad_perm [2,3,0,1]
+  v += dpp_mov<0x141>(v);       // row_half_mirror: lane l of a half row reads lane 7 - l, the other quad
+  return v;
+}
 
 // Block-combine KT per-thread accumulators and write them to partials[i*gridDim.x + blockIdx.x], i<ncols.
 template <int KT>

@@ -292,6 +292,20 @@ int ks_pc_lu_multi_columns();
 void ks_pc_lu_info(const KsLu *p, KsLuInfo *out);     // perm: host array of the plan, valid while it lives
 void ks_pc_lu_free(KsLu *p);
 
+// ---- smoothed-aggregation multigrid (ks_pc_amg.hip): the hierarchy of ksc::amg_plan from CSR arrays of the whole matrix (one rank), y = one V-cycle on x ----
+struct KsAmg;
+struct KsAmgOptions { double theta = 0.0; int degree = 2, coarse_limit = 200, max_levels = 10; bool smooth = true; };
+constexpr int KS_AMG_MAX_LEVELS = 16;
+struct KsAmgInfo { int levels; int rows[KS_AMG_MAX_LEVELS]; long long nnz[KS_AMG_MAX_LEVELS]; double rho[KS_AMG_MAX_LEVELS]; double complexity; long long bytes; int launches; };
+int ks_pc_amg_build(ks_ctx ctx, int n, const int *rp, const int *col, const double *val, const KsAmgOptions &opt, KsAmg **out);   // KS_ERR_ARG_WRONGSTATE, KS_ERR_MAT_LU_ZRPVT, KS_ERR_MEM, KS_ERR_ARG_OUTOFRANGE: nothing is left allocated
+int ks_pc_amg_apply(ks_ctx ctx, const KsAmg *p, const double *in, double *out);                 // enqueued; in != out
+int ks_pc_amg_apply_multi(ks_ctx ctx, const KsAmg *p, int ncols, const double *X, long long ldx, double *Y, long long ldy);   // passes of eight columns; every column the bits of ks_pc_amg_apply
+int ks_pc_amg_multi_columns();
+void ks_pc_amg_info(const KsAmg *p, KsAmgInfo *out);
+// one level on the host (arrays of the plan, valid while it lives): its operator, and - every level but the last, else NULL - its prolongator and aggregate index
+int ks_pc_amg_level(const KsAmg *p, int level, int *n, int *nagg, const int **arp, const int **acol, const double **aval, const int **prp, const int **pcol, const double **pval, const int **agg);
+void ks_pc_amg_free(KsAmg *p);
+
 // ---- ST: spectral transformation (ks_st.hip) ----------------------------------------------------
 struct ks_st_s {
   ks_ctx ctx = nullptr;
@@ -316,6 +330,8 @@ struct ks_st_s {
   KsIlu *ilu = nullptr;                       // KS_PC_BJACOBI_ILU: the blocks' factors on the device (owned)
   KsLu *lu = nullptr;                         // KS_PC_LU: the factors of P on the device (owned)
   int lu_ordering = KS_ORDERING_ND;           // ks_st_pc_lu_set_ordering
+  KsAmg *amg = nullptr;                       // KS_PC_AMG: the multigrid hierarchy of P on the device (owned)
+  KsAmgOptions amg_opt;                       // ks_st_pc_amg_set_*
   int matmode = KS_ST_MATMODE_SHELL;          // STSetMatMode: how P = A - sigma B exists (shell: applied term by term; copy: assembled, stsolve.c:603-631)
   ks_mat Pmat = nullptr;                      // ST_MATMODE_COPY: the assembled P (owned)
   ks_mat op = nullptr;                        // shell matrix whose MatMult is STApply
