@@ -106,7 +106,8 @@ int ks_ctx_synchronize(ks_ctx ctx);
  * dictionary layout's 2-byte codes per entry, never its row-pattern form) at matrix assembly; the others per call. */
 enum { KS_DEBUG_NO_FUSED_GS = 0, KS_DEBUG_NO_MFMA = 1, KS_DEBUG_NO_SPMV_DOT = 2, KS_DEBUG_FORCE_MULTI = 3, KS_DEBUG_HALO_OVERLAP = 4, KS_DEBUG_ONESHOT_SEQ0 = 5,
        KS_DEBUG_NO_DICT_PATTERNS = 6, KS_DEBUG_NO_RESTART_FUSION = 7 /* the final update of a run's last column, the restart product and the copy as the launches of their own */,
-       KS_DEBUG_NO_DICT_PAIRS = 8 /* read at launch: the dictionary product one row per lane also where the matrix has the pair form */ };
+       KS_DEBUG_NO_DICT_PAIRS = 8 /* read at launch: the dictionary product one row per lane also where the matrix has the pair form */,
+       KS_DEBUG_NO_STEP_FORWARD = 9 /* read at enqueue: the final update of a Krylov step, the next product and the next dot sweep as the launches of their own */ };
 int ks_ctx_set_debug(ks_ctx ctx, int key, long long value);
 int ks_ctx_sync_count(ks_ctx ctx, long long *count);   /* instrumentation: host waits on the context's stream made by the library so far */
 int ks_ctx_device_info(ks_ctx ctx, char *arch, int arch_len, int *num_cu, size_t *mem_total);
@@ -322,6 +323,17 @@ int ks_bv_multinplace_trans(ks_bv V, const double *Q, int ldq, int s, int e);   
 int ks_bv_restart(ks_bv V, const double *Q, int ldq, int s, int e, int src, int dst);
 int ks_bv_set_defer_final(ks_bv bv, int on);
 int ks_bv_restart_stats(ks_bv bv, int *pending, long long *flushes, long long *fused);
+/* Forward form of the final update (an enqueued Krylov run on one rank, pair-form dictionary matrix of at most five bases, basis streaming from HBM):
+   the launch that stores column j + 1 also forms y = A v_{j+1} and the first dots of the next step; the ordinary product and dot sweep stay enqueued
+   behind it and run only if the device did not take the form (a column that left the two-pass program) or a bounded wait inside it gave up.
+   ks_bv_step_forward_stats (waits for the stream): launches whose bookkeeping took the form, those that completed, those that gave up, fallback
+   products that ran. ks_bv_step_forward_info: forward launches enqueued so far and why the last column asked about was refused ("" if it was not).
+   Test hooks (KSD_TEST_HOOKS) ks_bv_step_forward_hooks: force != 0 drops the size conditions (16 tiles per CU, basis not cache-resident); grid > 0
+   forces the number of workgroups; budget >= 0 replaces the wall-time budget of a wait (ticks of 10 ns; 0: every wait gives up);
+   abort_wg >= 0 makes that workgroup give up at its first wait; lag_odd != 0 makes odd workgroups sleep before they publish a tile. */
+int ks_bv_step_forward_stats(ks_bv bv, long long *taken, long long *completed, long long *aborted, long long *fell_back);
+int ks_bv_step_forward_info(ks_bv bv, long long *enqueued, char *why, int why_len);
+int ks_bv_step_forward_hooks(ks_bv bv, int force, int grid, long long budget, int abort_wg, int lag_odd);
 int ks_bv_dot(ks_bv X, ks_bv Y, double *M, int ldm);                                             /* ops->dot: M = Y^H X (+allreduce) */
 int ks_bv_dotvec(ks_bv X, const double *y_dev, double *m);                                       /* ops->dotvec; m NULL -> buffer */
 int ks_bv_dotvec_local(ks_bv X, const double *y_dev, double *m);                                 /* ops->dotvec_local (no reduction) */

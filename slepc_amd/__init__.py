@@ -118,7 +118,7 @@ class Context:
     def synchronize(self):
         _lib.check(self.L.ks_ctx_synchronize(self.h))
 
-    DEBUG_KEYS = {"no_fused_gs": 0, "no_mfma": 1, "no_spmv_dot": 2, "force_multi": 3, "halo_overlap": 4, "oneshot_seq0": 5, "no_dict_patterns": 6, "no_restart_fusion": 7, "no_dict_pairs": 8}
+    DEBUG_KEYS = {"no_fused_gs": 0, "no_mfma": 1, "no_spmv_dot": 2, "force_multi": 3, "halo_overlap": 4, "oneshot_seq0": 5, "no_dict_patterns": 6, "no_restart_fusion": 7, "no_dict_pairs": 8, "no_step_forward": 9}
 
     def set_debug(self, key, value=1):
         """Test hooks (ks_ctx_set_debug): run the path a fast one replaces, or the multi-rank path on one rank."""
@@ -579,6 +579,17 @@ class BV:
         p = C.c_int(); fl = C.c_longlong(); fu = C.c_longlong()
         _lib.check(self.ctx.L.ks_bv_restart_stats(self.h, C.byref(p), C.byref(fl), C.byref(fu)))
         return {"pending": bool(p.value), "flushes": fl.value, "fused": fu.value}
+
+    def step_forward_stats(self):
+        """Forward form of the final update (final update, next product and next dots in one launch): what the device did with the launches enqueued so far."""
+        t = C.c_longlong(); c = C.c_longlong(); a = C.c_longlong(); f = C.c_longlong(); e = C.c_longlong(); why = C.create_string_buffer(160)
+        _lib.check(self.ctx.L.ks_bv_step_forward_stats(self.h, C.byref(t), C.byref(c), C.byref(a), C.byref(f)))
+        _lib.check(self.ctx.L.ks_bv_step_forward_info(self.h, C.byref(e), why, 160))
+        return {"enqueued": e.value, "taken": t.value, "completed": c.value, "aborted": a.value, "fell_back": f.value, "refused": why.value.decode()}
+
+    def step_forward_hooks(self, force=False, grid=0, budget=-1, abort_wg=-1, lag_odd=False):
+        """Test hooks of the forward form (ks_bv_step_forward_hooks)."""
+        _lib.check(self.ctx.L.ks_bv_step_forward_hooks(self.h, int(bool(force)), int(grid), int(budget), int(abort_wg), int(bool(lag_odd))))
 
     def Dot(self, Y, M):
         assert M.flags.f_contiguous and M.dtype == np.float64

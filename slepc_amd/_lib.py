@@ -102,6 +102,9 @@ _SIG = {
     "ks_bv_restart": [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "ks_bv_set_defer_final": [vp, C.c_int],
     "ks_bv_restart_stats": [vp, ip, llp, llp],
+    "ks_bv_step_forward_stats": [vp, llp, llp, llp, llp],
+    "ks_bv_step_forward_info": [vp, llp, C.c_char_p, C.c_int],
+    "ks_bv_step_forward_hooks": [vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int],
     "ks_bv_dot": [vp, vp, dp, C.c_int],
     "ks_bv_dotvec": [vp, vp, dp],
     "ks_bv_dotvec_local": [vp, vp, dp],

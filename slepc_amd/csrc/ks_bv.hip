@@ -152,14 +152,17 @@ int ksk_dot(ks_bv bv, const double *A, int lda, int ncols, const double *y, bool
   const KsGsState *g = gate ? bv->gs : nullptr;
   bv->spec.valid = false;                                       // the partials a chained Gram-Schmidt pass would have read are rewritten
   const int plain = ks_basis_is_cache_resident((size_t)(bv->nc + bv->m), (size_t)bv->ld);
+  // behind a forward final update (bv->fwd.gate, set by the enqueue around this call) the sweep is the fallback: in the common case it returns at once. It
+  // takes and toggles the direction like any sweep: the forward launch ran in this direction and left the sums this sweep would leave
+  unsigned *const fctl = bv->fwd.gate.ctl; const unsigned fepoch = bv->fwd.gate.epoch;
   const int rev = bv->sweep_dir; bv->sweep_dir ^= 1;            // snake over the basis with the sweeps before and after (ks_gs.hip launch_update)
-  KsProfScope ps(ctx, KS_K_DOT, 8.0 * bv->n * (ncols + (y >= A && y < A + (size_t)ncols * lda ? 0 : 1)), ks_kt_for(ncols));
+  KsProfScope ps(ctx, KS_K_DOT, fctl ? 0.0 : 8.0 * bv->n * (ncols + (y >= A && y < A + (size_t)ncols * lda ? 0 : 1)), ks_kt_for(ncols));
 #define LAUNCH_DOT(KT)                                                                                                                        \
   do {                                                                                                                                        \
     if (v2) { grid = ks_sweep_grid_for(ctx, bv->n, 2, (const void *)k_dot_sweep<KT, 2>, dot_per_cu); bv->last_grid = grid;                                \
-      hipLaunchKernelGGL((k_dot_sweep<KT, 2>), dim3(grid), dim3(SW_BLOCK), 0, ctx->stream, A, (long long)lda, bv->n, ncols, y, bv->partials, g, &bv->gs->pgrid, rev, plain); } \
+      hipLaunchKernelGGL((k_dot_sweep<KT, 2>), dim3(grid), dim3(SW_BLOCK), 0, ctx->stream, A, (long long)lda, bv->n, ncols, y, bv->partials, g, &bv->gs->pgrid, rev, plain, fctl, fepoch); } \
     else { grid = ks_sweep_grid_for(ctx, bv->n, 1, (const void *)k_dot_sweep<KT, 1>, dot_per_cu); bv->last_grid = grid;                                   \
-      hipLaunchKernelGGL((k_dot_sweep<KT, 1>), dim3(grid), dim3(SW_BLOCK), 0, ctx->stream, A, (long long)lda, bv->n, ncols, y, bv->partials, g, &bv->gs->pgrid, rev, plain); }   \
+      hipLaunchKernelGGL((k_dot_sweep<KT, 1>), dim3(grid), dim3(SW_BLOCK), 0, ctx->stream, A, (long long)lda, bv->n, ncols, y, bv->partials, g, &bv->gs->pgrid, rev, plain, fctl, fepoch); }   \
   } while (0)
   KS_KT_DISPATCH(ncols, LAUNCH_DOT);
 #undef LAUNCH_DOT
@@ -296,7 +299,7 @@ extern "C" int ks_bv_destroy(ks_bv bv)
   if (!bv) return KS_SUCCESS;
   hipSetDevice(bv->ctx->device);
   ks_sync(bv->ctx);
-  hipFree(bv->array); hipFree(bv->own_buffer ? bv->buffer : bv->buffer_own); hipFree(bv->partials_base); hipFree(bv->coef); hipFree(bv->hc); hipFree(bv->cred); hipFree(bv->cw); hipFree(bv->gs_base); hipFree(bv->recs); hipFree(bv->panel); hipFree(bv->Bx); hipFree(bv->pend);
+  hipFree(bv->array); hipFree(bv->own_buffer ? bv->buffer : bv->buffer_own); hipFree(bv->partials_base); hipFree(bv->coef); hipFree(bv->hc); hipFree(bv->cred); hipFree(bv->cw); hipFree(bv->gs_base); hipFree(bv->recs); hipFree(bv->panel); hipFree(bv->Bx); hipFree(bv->pend); hipFree(bv->fwd.flags); hipFree(bv->fwd.ctl);
   delete bv;
   return KS_SUCCESS;
 }

@@ -205,6 +205,7 @@ extern "C" int ks_ctx_set_debug(ks_ctx ctx, int key, long long value)
     case KS_DEBUG_NO_DICT_PATTERNS: ctx->dbg.no_dict_patterns = value != 0; break;
     case KS_DEBUG_NO_RESTART_FUSION: ctx->dbg.no_restart_fusion = value != 0; break;
     case KS_DEBUG_NO_DICT_PAIRS: ctx->dbg.no_dict_pairs = value != 0; break;
+    case KS_DEBUG_NO_STEP_FORWARD: ctx->dbg.no_step_forward = value != 0; break;
     default: KS_FAIL(KS_ERR_ARG_OUTOFRANGE, "unknown debug key %d", key);
   }
   return KS_SUCCESS;
@@ -339,7 +340,7 @@ void ks_prof_resolve_gs(ks_ctx ctx, const KsStepRec *recs, int col0, int col1)
     if (p.kclass == KS_K_UPD_FUSED || p.kclass == KS_K_UPD) {
       if (p.tag_slot > passes) { p.kclass = KS_K_NOOP; p.bytes = 0.0; p.hbm = 0.0; }
       else if (p.tag_slot < passes || expl) { p.kclass = KS_K_UPD_FUSED; p.hbm = 8.0 * n * (k + (expl ? 2 : 1)); p.bytes = 8.0 * n * (k + 2) + 8.0 * n * (k + 1); }   // a fused pass that is not followed by an explicit norm keeps its result in registers: no write
-      else { p.kclass = KS_K_UPD; p.hbm = 8.0 * n * (k + 2); p.bytes = p.hbm; }
+      else { p.kclass = KS_K_UPD; p.hbm = 8.0 * n * (k + 2) + p.tag_extra; p.bytes = p.hbm; }      // tag_extra: the product and the stored y of the forward form
     } else if (p.kclass == KS_K_GSFIN) {
       if (p.tag_slot > passes + (expl ? 1 : 0)) { p.kclass = KS_K_NOOP; p.bytes = 0.0; p.hbm = 0.0; }
     } else if (p.kclass == KS_K_SCALE) {

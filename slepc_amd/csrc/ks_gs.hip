@@ -21,6 +21,7 @@
 // Multi-rank: the reduce and bookkeeping halves are split around an allreduce of k+1 doubles
 // (bvblas.c:255 MPIU_Allreduce) on the same stream.
 #include "ks_sweeps.cuh"
+#include "ks_rows.cuh"
 #include "ks_oneshot.cuh"
 #include <algorithm>
 
@@ -491,6 +492,277 @@ __global__ __launch_bounds__(SW_BLOCK) void k_gs_update(const double *V, long lo
   }
 }
 
+// ---- forward form of the final update ------------------------------------------------------------------------------------------
+// Slot 2 of column c of an enqueued Krylov run, when the next step's product is a pair-form dictionary product: besides the final update of v = V(:,c)
+// the launch forms y = A v into column c + 1 and the k + 2 dots of the next step's first sweep, so that the step reads the basis twice instead of three
+// times. One workgroup per CU; tile q of 512 rows goes through
+//   C-phase  (round i):     today's final update of the tile, arithmetic unchanged; the panel V(r,0:k) and the new rows stay in registers; the tile is
+//                           stored with the 16-byte write-through store and PUBLISHED: every wave s_waitcnt vmcnt(0), workgroup barrier, one lane
+//                           stores the tile's flag (relaxed, agent scope) with the launch's epoch;
+//   A-phase  (round i + 1): wave 0 polls the flags of the tiles that hold the tile's neighbour rows (relaxed agent-scope loads, s_sleep between polls,
+//                           a wall-time budget), a barrier lets the other waves through, then the pair walk of ks_dict_pairs.h with EVERY load of v a
+//                           buffer_load sc1 (the centre pair comes from the registers), y stored, dots accumulated from the registers.
+// A workgroup runs C(i) before A(i - 1). No C-phase waits; an A-phase waits for C-phases of its own or an earlier round's tiles or the next round's (the
+// far neighbours are less than a grid of tiles away: eligibility), which every workgroup runs before its own A-phase of the round before: the wait graph
+// descends in the round index and cannot close. A wait that runs out of budget sets the abort word; every workgroup that sees it skips its remaining
+// A-phases and still completes every C-phase; the ordinary product and dot sweep enqueued behind this launch run iff the form was not taken or gave up.
+// Column c held y of the step before: other CUs read it with plain loads in the sweeps before this launch, so no plain or scalar load of it may stand
+// in an A-phase (the C-phase reads the tile's own rows, which nobody has stored in this launch yet).
+struct FwdArgs {
+  double *y;                                   // column c + 1
+  const unsigned char *rowpat; const unsigned short *pats; const double *dval; const int *doff; int npat, w;
+  ksp::PairArgs pa; const double *pcoef; const unsigned *pmask;
+  unsigned *flags, *ctl; unsigned epoch;
+  unsigned long long budget;                   // wall_clock64 ticks (10 ns) one wait may take
+  int abort_wg, lag_odd;                       // test hooks: this workgroup gives up at its first wait; odd workgroups sleep before they publish
+};
+// the walk's lane with every load of x an sc1 load (ksr::PairLane with aux = sc1) and the lane's own pair from registers: i - own is the base's offset, the
+// same in every lane, so the branch is uniform and no select stands behind a load
+struct FwdLane {
+  __amdgpu_buffer_rsrc_t rs; long long n, own; ksp::D2 c;
+  __device__ __forceinline__ FwdLane(const double *x, long long n_, long long own_, ksp::D2 c_) : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(x), 0, (int)(unsigned)(n_ * 8), 0x00020000)), n(n_), own(own_), c(c_) {}
+  __device__ __forceinline__ unsigned off(long long i, bool want = true) const { return want && (unsigned long long)i < (unsigned long long)n ? (unsigned)(i * 8) : ksr::PAIR_OOB_OFFSET; }
+  __device__ __forceinline__ int lane() const { return threadIdx.x & 63; }
+  __device__ __forceinline__ ksp::D2 pair(long long i) const
+  {
+    if (__builtin_amdgcn_readfirstlane((int)(i == own))) return c;
+    ksp::D2 v; const auto t = __builtin_amdgcn_raw_buffer_load_b128(rs, off(i), 0, 16); __builtin_memcpy(&v, &t, 16); return v;
+  }
+  __device__ __forceinline__ double one(long long i, bool want) const { double v; const auto t = __builtin_amdgcn_raw_buffer_load_b64(rs, off(i, want), 0, 16); __builtin_memcpy(&v, &t, 8); return v; }
+  __device__ __forceinline__ double up(double v, long long) const { return __shfl_up(v, 1); }
+  __device__ __forceinline__ double down(double v, long long) const { return __shfl_down(v, 1); }
+};
+// the last row of an odd n (ksp::dict_row_from_tables with x read by agent-scope loads: same entries, same chain)
+__device__ __forceinline__ double fwd_last_row(const FwdArgs &f, long long r, const double *x)
+{
+  const int p = f.rowpat[r];
+  double acc = 0.0;
+#pragma unroll 1
+  for (int e = 0; e < f.w; e++) {
+    const unsigned code = f.pats[p * f.w + e], oc = code & 0xffu, vc = code >> 8;
+    const bool ok = vc != 255u;
+    acc = fma(ok ? f.dval[vc] : 0.0, ok ? __hip_atomic_load(x + r + f.doff[oc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0, acc);
+  }
+  return acc;
+}
+
+// amdgpu_waves_per_eu(1, 1): one workgroup of four waves per CU also where a narrow panel would leave registers for two (the hand-off's measured form)
+// S: the dots leave the launch as the partials of a dot sweep of S x gridDim.x workgroups in the same direction would - tile t0 of that sweep belongs to its
+// workgroup t0 mod (S gridDim.x), which is this launch's workgroup blockIdx.x in a round of parity (t0 / gridDim.x) mod S: S sets of accumulators, the
+// same products added in the same order, the same wave and block combine, so the next step starts from the bits the three launches leave.
+// rev: direction of the forward sweep (the replaced dot sweep's); rev_upd: the replaced update's, for a column that takes the generic form.
+template <int KT, int S>
+__global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_gs_update_fwd(const double *V, long long ld, int n, int k, double *v, double *__restrict__ partials, int rev, int rev_upd, FoldArgs fa, FwdArgs f)
+{
+  __shared__ double c_lds[KS_MAX_COLS + 8];
+  __shared__ double spend[3 * KS_PSTRIDE];
+  __shared__ KsGsState s_sh;
+  __shared__ BookPlan plan_sh;
+  __shared__ int go_sh, fwd_sh, poll_sh;
+  // ---- prologue: the slot's bookkeeping, as k_gs_update's folded form; workgroup 0 writes the state and says whether the A-phases run ----
+  const GsArgs &a = fa.a;
+  if (threadIdx.x == 0) {
+    KsGsState s = *fa.st_in;
+    int go = 1;
+    if (!s.active || (a.slot > 1 && !s.expl && !s.more_)) { go = 0; s.do_update = 0; }
+    s_sh = s; go_sh = go;
+  }
+  __syncthreads();
+  if (!go_sh) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *fa.st_out = s_sh;
+    return;
+  }
+  const int ncols = a.k + 1;
+  reduce_partials_to_lds(fa.partials_in, s_sh.pgrid, ncols, c_lds);
+  if (threadIdx.x == 0) {
+    KsGsState s = s_sh;
+    gs_bookkeep(a, c_lds, &s, &plan_sh);
+    // the plain two-pass state: this update is the column's final, scaled store and the run goes on
+    const int fwd = s.do_update && s.store_now && !s.fuse_dot && s.npend == 2 && s.active && !s.lindep && !s.err && !s.more_ && !s.expl && s.halt_col < 0;
+    if (s.do_update && (s.fuse_dot || fwd)) s.pgrid = fwd ? S * gridDim.x : gridDim.x;
+    s_sh = s; fwd_sh = fwd;
+  }
+  __syncthreads();
+  for (int p = 0; p < s_sh.npend; p++)
+    if ((int)threadIdx.x < a.k) spend[p * KS_PSTRIDE + threadIdx.x] = (p == plan_sh.pslot) ? c_lds[threadIdx.x] : fa.pend[(size_t)p * KS_PSTRIDE + threadIdx.x];
+  if (blockIdx.x == 0) {
+    apply_plan(a, plan_sh, c_lds, fa.buffer, fa.pend);
+    if ((int)threadIdx.x < ncols && !(a.col == 0 && (int)threadIdx.x <= a.k)) fa.buffer[threadIdx.x] = c_lds[threadIdx.x];
+    if (threadIdx.x == 0) {
+      *fa.st_out = s_sh; if (plan_sh.set_rec) fa.recs[a.col] = plan_sh.rec;
+      if (fwd_sh) { f.ctl[KS_FWD_TAKEN] = f.epoch; atomicAdd(f.ctl + KS_FWD_NTAKEN, 1u); }      // read by the launches behind this one
+    }
+  }
+  __syncthreads();
+  if (!s_sh.do_update) return;
+  const bool fuse = s_sh.fuse_dot != 0, scal = s_sh.scale_now != 0, store = s_sh.store_now != 0; const int npend = s_sh.npend; const double alpha = s_sh.alpha;
+  if (!fwd_sh) {
+    // a column that has left the optimistic program (a third pass, an explicit norm): the update kernel's generic form
+    double acc[KT + 1];
+#pragma unroll
+    for (int i = 0; i <= KT; i++) acc[i] = 0.0;
+    upd_tiles<KT, 2, 0, -1, false>(V, ld, n, k, v, spend, npend, fuse, scal, store, alpha, rev_upd, acc);
+    if (!fuse) return;
+    __shared__ double red[SW_WAVES][KT + 1];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i <= KT; i++) { const double s = wave_sum(acc[i]); if (lane == 0) red[w][i] = s; }
+    __syncthreads();
+    if ((int)threadIdx.x <= k) {
+      const int src = ((int)threadIdx.x == k) ? KT : (int)threadIdx.x;
+      double s = red[0][src];
+#pragma unroll
+      for (int ww = 1; ww < SW_WAVES; ww++) s += red[ww][src];
+      partials[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
+    }
+    return;
+  }
+  // ---- the forward sweep ----
+  double *sc = reinterpret_cast<double *>(ksr::dict_pat_lds); unsigned *sm = reinterpret_cast<unsigned *>(sc + f.npat * 3 * f.pa.nb);
+  for (int i = threadIdx.x; i < f.npat * 3 * f.pa.nb; i += SW_BLOCK) sc[i] = f.pcoef[i];
+  for (int i = threadIdx.x; i < f.npat; i += SW_BLOCK) sm[i] = f.pmask[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long tile = 2LL * SW_BLOCK, ntiles = ((long long)n + tile - 1) / tile;
+  double acc[S][KT + 2];
+#pragma unroll
+  for (int q = 0; q < S; q++)
+#pragma unroll
+    for (int i = 0; i < KT + 2; i++) acc[q][i] = 0.0;
+  int rset = 0, pset = 0;                                  // accumulator set of this round's tile and of the tile whose A-phase is still to come
+  ks_d2v pv[KT]; ks_d2v ps = {0.0, 0.0};                 // panel and new rows of the tile whose A-phase is still to come
+#pragma unroll
+  for (int i = 0; i < KT; i++) pv[i] = ks_d2v{0.0, 0.0};
+  long long pt = -1;
+  bool dead = false;                                       // uniform: this workgroup has seen the abort word
+  for (long long t0 = blockIdx.x;; t0 += gridDim.x) {
+    const bool has = t0 < ntiles;
+    const long long t = rev ? ntiles - 1 - t0 : t0;
+    ks_d2v cv[KT]; ks_d2v cs = {0.0, 0.0};
+#pragma unroll
+    for (int i = 0; i < KT; i++) cv[i] = ks_d2v{0.0, 0.0};
+    if (has) {
+      // ---- C-phase: upd_tiles<KT, 2, 2, 0, false>'s tile, the coefficients read from LDS as they are used ----
+      const long long r = t * tile + 2LL * threadIdx.x;
+      if (r + 1 < n) {
+        cs = *reinterpret_cast<const ks_d2v *>(v + r);
+#pragma unroll
+        for (int i = 0; i < KT; i++) { const int ii = i < k ? i : k - 1; cv[i] = __builtin_nontemporal_load(reinterpret_cast<const ks_d2v *>(V + (long long)ii * ld + r)); }
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+          for (int i = 0; i < KT; i++) { const double c = (i < k) ? -spend[p * KS_PSTRIDE + i] : 0.0; cs.x = fma(c, cv[i].x, cs.x); cs.y = fma(c, cv[i].y, cs.y); }
+        if (scal) { cs.x *= alpha; cs.y *= alpha; }
+        asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(reinterpret_cast<ks_d2v *>(v + r)), "v"(cs) : "memory");
+      } else if (r < n) {                                  // odd n: the last row on its own, stored by an 8-byte agent-scope (sc1) store
+        double s1 = v[r];
+#pragma unroll
+        for (int i = 0; i < KT; i++) { const int ii = i < k ? i : k - 1; cv[i].x = V[(long long)ii * ld + r]; }
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+          for (int i = 0; i < KT; i++) s1 = fma((i < k) ? -spend[p * KS_PSTRIDE + i] : 0.0, cv[i].x, s1);
+        if (scal) s1 *= alpha;
+        cs.x = s1;
+        __hip_atomic_store(v + r, s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      if (f.lag_odd && (blockIdx.x & 1)) for (int q = 0; q < 8; q++) __builtin_amdgcn_s_sleep(127);
+    }
+    // ---- publish ----
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave
+    __syncthreads();
+    if (has && threadIdx.x == 0) __hip_atomic_store(f.flags + t, f.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // ---- A-phase of the tile of the round before ----
+    if (pt >= 0 && !dead) {
+      if (w == 0) {
+        // lane 3 kb + wh polls the wh-th tile that holds rows of base kb's window [r0 + b - d, r0 + 511 + b + d] (d = 1 for a base with neighbours);
+        // lane 63 reads the abort word
+        const int kb = lane / 3, wh = lane % 3;
+        long long tl = -1;
+        int b = 0; bool isb = false;
+#pragma unroll
+        for (int q = 0; q < 5; q++) if (q == kb && q < f.pa.nb) { b = f.pa.base[q]; isb = true; }
+        if (isb) {
+          const int d = (int)(f.pa.dmask >> kb & 1u);
+          long long lo = pt * tile + b - d, hi = pt * tile + (tile - 1) + b + d;
+          if (lo < 0) lo = 0;
+          if (hi > (long long)n - 1) hi = (long long)n - 1;
+          if (lo <= hi && (lo >> 9) + wh <= (hi >> 9)) tl = (lo >> 9) + wh;
+        }
+        if (tl == pt) tl = -1;                             // the workgroup's own tile: stored, drained and behind the barrier above
+        int res;
+        const long long tstart = wall_clock64();
+        for (;;) {
+          unsigned fl = f.epoch, ab = 0;
+          if (tl >= 0) fl = __hip_atomic_load(f.flags + tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (lane == 63) ab = __hip_atomic_load(f.ctl + KS_FWD_ABORT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (__any(lane == 63 && ab == f.epoch)) { res = 0; break; }
+          if (__all(fl == f.epoch) && (int)blockIdx.x != f.abort_wg && f.budget != 0) { res = 1; break; }      // (a budget of 0, a test hook: every wait gives up)
+          if ((int)blockIdx.x == f.abort_wg || (unsigned long long)(wall_clock64() - tstart) >= f.budget) {
+            if (lane == 0 && __hip_atomic_exchange(f.ctl + KS_FWD_ABORT, f.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != f.epoch) atomicAdd(f.ctl + KS_FWD_NABORT, 1u);
+            res = 0; break;
+          }
+          __builtin_amdgcn_s_sleep(8);
+        }
+        if (lane == 0) poll_sh = res;
+      }
+      __syncthreads();                                     // the other waves load v only behind this barrier
+      if (poll_sh) {
+        const long long r = pt * tile + 2LL * threadIdx.x;
+        const FwdLane ln(v, n, r, ksp::D2{ps.x, ps.y});
+        int p0, p1;
+        ksr::pair_patterns(f.rowpat, r, n, p0, p1);
+        double y0, y1;
+        ksp::dict_pair_walk<5>(f.pa, sc, sm, p0, p1, r, ln, y0, y1);
+        if (r + 1 < n) {
+          __builtin_nontemporal_store(ks_d2v{y0, y1}, reinterpret_cast<ks_d2v *>(f.y + r));
+#pragma unroll
+          for (int q = 0; q < S; q++)
+            if (q == pset) {
+#pragma unroll
+              for (int i = 0; i < KT; i++) { acc[q][i] = fma(pv[i].x, y0, acc[q][i]); acc[q][i] = fma(pv[i].y, y1, acc[q][i]); }
+              acc[q][KT] = fma(ps.x, y0, acc[q][KT]); acc[q][KT] = fma(ps.y, y1, acc[q][KT]);
+              acc[q][KT + 1] = fma(y0, y0, acc[q][KT + 1]); acc[q][KT + 1] = fma(y1, y1, acc[q][KT + 1]);
+            }
+        } else if (r < n) {
+          const double yl = fwd_last_row(f, r, v);
+          __builtin_nontemporal_store(yl, f.y + r);
+#pragma unroll
+          for (int q = 0; q < S; q++)
+            if (q == pset) {
+#pragma unroll
+              for (int i = 0; i < KT; i++) acc[q][i] = fma(pv[i].x, yl, acc[q][i]);
+              acc[q][KT] = fma(ps.x, yl, acc[q][KT]);
+              acc[q][KT + 1] = fma(yl, yl, acc[q][KT + 1]);
+            }
+        }
+      } else dead = true;
+    }
+    if (!has) break;
+#pragma unroll
+    for (int i = 0; i < KT; i++) pv[i] = cv[i];
+    ps = cs; pt = t; pset = rset; rset = rset + 1 == S ? 0 : rset + 1;
+  }
+  if (dead) return;                                        // the dot sweep behind this launch rewrites every partial
+  // block combine, set by set, as block_write_partials does it for the sweep's workgroup blockIdx.x + q gridDim.x: partial index i < k <- acc[i] (y against
+  // column i), k <- acc[KT] (against the new column), k + 1 <- acc[KT + 1] (the self dot)
+  __shared__ double red2[SW_WAVES][KT + 2];
+#pragma unroll
+  for (int q = 0; q < S; q++) {
+    if (q) __syncthreads();
+#pragma unroll
+    for (int i = 0; i < KT + 2; i++) { const double s = wave_sum(acc[q][i]); if (lane == 0) red2[w][i] = s; }
+    __syncthreads();
+    if ((int)threadIdx.x <= k + 1) {
+      const int src = ((int)threadIdx.x >= k) ? KT + ((int)threadIdx.x - k) : (int)threadIdx.x;
+      double s = red2[0][src];
+#pragma unroll
+      for (int ww = 1; ww < SW_WAVES; ww++) s += red2[ww][src];
+      partials[(size_t)threadIdx.x * (S * gridDim.x) + blockIdx.x + q * gridDim.x] = s;
+    }
+  }
+}
+
 __global__ void k_scale_if(double *__restrict__ x, int n, const KsGsState *__restrict__ st)
 {
   if (!st->pending_scale) return;
@@ -586,6 +858,108 @@ int launch_update(ks_bv bv, int col, double *v, int slot, const GsArgs *fold = n
   return KS_SUCCESS;
 }
 
+// ---- forward form: eligibility and launch ---------------------------------------------------------------------------------------------------------
+// Decided on the host at enqueue; anything else takes the ordinary launches untouched. *grid: workgroups of the launch (one per CU).
+bool fwd_eligible(ks_bv bv, ks_mat A, int col, int *grid)
+{
+  ks_ctx ctx = bv->ctx;
+  auto no = [&](const char *why) { bv->fwd.why = why; return false; };
+  if (ctx->dbg.no_step_forward) return no("switched off (KS_DEBUG_NO_STEP_FORWARD)");
+  if (ks_is_multi(ctx)) return no("more than one rank");
+  if (bv->matrix) return no("a B-inner product");
+  if (!A || A->shell_mult || A->sht || A->n_orows > 0 || A->n != bv->n) return no("not an assembled one-rank matrix of the basis' size");
+  if (A->layout != KS_MAT_LAYOUT_DICT || !A->dc_rowpat || !A->pr_ok || ctx->dbg.no_dict_pairs) return no("the matrix has no pair-form dictionary product");
+  if (A->pr_args.nb > 5) return no("more than five bases");
+  if (!ksr::pair_fits32(A->n)) return no("rows beyond a 32-bit buffer offset");
+  if (bv->orthog_ref == KS_BV_ORTHOG_REFINE_NEVER) return no("no two-pass program");
+  const int k = bv->nc + col;
+  if (k < 1 || k + 1 > 32 || col + 1 >= bv->m) return no("column count");
+  if (bv->ld % 2 || !aligned16(ks_bv_col(bv, -bv->nc))) return no("odd leading dimension or unaligned columns");
+  const long long ntiles = ((long long)bv->n + 511) / 512;
+  const int g = bv->fwd.force_grid > 0 ? bv->fwd.force_grid : ctx->num_cu;
+  long long far = 0;
+  for (int q = 0; q < A->pr_args.nb; q++) far = std::max<long long>(far, std::llabs((long long)A->pr_args.base[q]));
+  if ((far + 511) / 512 + 2 > g) return no("the far neighbours are more than one round away");
+  if (!bv->fwd.force) {
+    if (ntiles < 16LL * ctx->num_cu) return no("fewer than 16 tiles per CU");
+    if (ks_basis_is_cache_resident((size_t)(bv->nc + bv->m), (size_t)bv->ld)) return no("the basis is resident in the Infinity Cache");
+  }
+  if (g > KS_MAX_BLOCKS) return no("grid");
+  bv->fwd.why = "";
+  *grid = g;
+  return true;
+}
+
+// One wait's budget: the guide prices a loaded flag hand-off at about 5.5 us (handoff-1to1 L->L 2.9 us x 1.9 for the separate flag) and a producer is at
+// most one round (a few us) behind its consumer; 1 ms of wall time is some 180 such hops and twice the whole launch. Ticks of wall_clock64 (10 ns).
+constexpr long long FWD_BUDGET_TICKS = 100000;
+
+int launch_update_fwd(ks_bv bv, ks_mat A, int col, double *v, const GsArgs &a, int grid)
+{
+  ks_ctx ctx = bv->ctx;
+  const int k = bv->nc + col;
+  const double *V = ks_bv_col(bv, -bv->nc);
+  const size_t ntiles = ((size_t)bv->n + 511) / 512;
+  if (!bv->fwd.ctl) {
+    KS_HIP(hipMalloc(&bv->fwd.ctl, KS_FWD_WORDS * sizeof(unsigned)));
+    KS_HIP(hipMemsetAsync(bv->fwd.ctl, 0, KS_FWD_WORDS * sizeof(unsigned), ctx->stream));
+  }
+  bool fresh = false;
+  if (bv->fwd.nflags < ntiles) {
+    if (bv->fwd.flags) { KS_HIP(ks_sync(ctx)); KS_HIP(hipFree(bv->fwd.flags)); bv->fwd.flags = nullptr; }
+    KS_HIP(hipMalloc(&bv->fwd.flags, ntiles * sizeof(unsigned)));
+    bv->fwd.nflags = ntiles; fresh = true;
+  }
+  if (++bv->fwd.epoch == 0) {      // epochs only grow, so a flag of an earlier launch never matches; after 2^32 launches start over: flags, TAKEN and ABORT words
+    bv->fwd.epoch = 1; fresh = true;
+    static_assert(KS_FWD_TAKEN == 0 && KS_FWD_ABORT == 1, "the two epoch words lead the control block");
+    KS_HIP(hipMemsetAsync(bv->fwd.ctl, 0, 2 * sizeof(unsigned), ctx->stream));
+  }
+  if (fresh) KS_HIP(hipMemsetAsync(bv->fwd.flags, 0, bv->fwd.nflags * sizeof(unsigned), ctx->stream));
+  // Directions: the launch stands for a final update and, behind it, a dot sweep, each of which takes the BV's direction and toggles it. The forward sweep
+  // runs in the DOT SWEEP's direction (the order of its sums); the gated dot sweep behind this launch does the second toggle, so every other sweep of the
+  // run keeps the direction it has without this form.
+  const int rev_upd = bv->sweep_dir; bv->sweep_dir ^= 1;
+  const int rev = bv->sweep_dir;
+  // the grid the replaced dot sweep would have (ksk_dot): S sets of accumulators when it is S times this launch's
+  const int ncols_dot = k + 2;
+  const int gdot = ks_sweep_grid_for(ctx, bv->n, 2, nullptr, std::max(1, std::min(4, (30 + ncols_dot - 1) / ncols_dot)));
+  const int sets_kt = k + 2 <= 9 ? 4 : (k + 2 <= 14 ? 3 : (k + 2 <= 29 ? 2 : 1));      // the sets compiled for this column count: what that grid is on a full-size problem
+  const int sets = gdot == sets_kt * grid ? sets_kt : 1;                                 // anything else (a grid forced by the test hook): the launch's own grid, other last bits
+  // compulsory bytes beyond the final update's 8 n (k + 2): the stored y and the row patterns (the neighbour rows of v come from the caches)
+  const double extra = 9.0 * bv->n;
+  KsProfScope ps(ctx, KS_K_UPD_FUSED, 8.0 * bv->n * (k + 2) + extra, ks_kt_for(k));
+  ps.tag(col, 2, k, bv->n, extra);
+  FoldArgs fa; memset(&fa, 0, sizeof(fa));
+  fa.a = a; fa.cred = nullptr; fa.partials_in = bv->partials; fa.st_in = bv->gs; fa.st_out = bv->gs_alt; fa.buffer = bv->buffer; fa.pend = bv->pend; fa.recs = bv->recs;
+  FwdArgs f;
+  f.y = ks_bv_col(bv, col + 1);
+  f.rowpat = A->dc_rowpat; f.pats = A->dc_pats; f.dval = A->dc_val; f.doff = A->dc_off; f.npat = A->dict_npat; f.w = A->dict_w;
+  f.pa = A->pr_args; f.pcoef = A->pr_coef; f.pmask = A->pr_mask;
+  f.flags = bv->fwd.flags; f.ctl = bv->fwd.ctl; f.epoch = bv->fwd.epoch;
+  f.budget = (unsigned long long)(bv->fwd.budget >= 0 ? bv->fwd.budget : FWD_BUDGET_TICKS);
+  f.abort_wg = bv->fwd.abort_wg; f.lag_odd = bv->fwd.lag_odd;
+  bv->spec.valid = false;
+  bv->last_grid = sets * grid;
+  const size_t lds = ksr::dict_pair_lds_bytes(A);
+#define LAUNCH_FWD_S(KT, S) hipLaunchKernelGGL((k_gs_update_fwd<KT, S>), dim3(grid), dim3(SW_BLOCK), lds, ctx->stream, V, (long long)bv->ld, bv->n, k, v, bv->partials_alt, rev, rev_upd, fa, f)
+#define LAUNCH_FWD(KT) do { constexpr int SK = KT + 2 <= 9 ? 4 : (KT + 2 <= 14 ? 3 : (KT + 2 <= 29 ? 2 : 1)); if (sets == SK) LAUNCH_FWD_S(KT, SK); else LAUNCH_FWD_S(KT, 1); } while (0)
+  switch (k) {
+    KS_KT_CASE(1, LAUNCH_FWD) KS_KT_CASE(2, LAUNCH_FWD) KS_KT_CASE(3, LAUNCH_FWD) KS_KT_CASE(4, LAUNCH_FWD) KS_KT_CASE(5, LAUNCH_FWD) KS_KT_CASE(6, LAUNCH_FWD) KS_KT_CASE(7, LAUNCH_FWD) KS_KT_CASE(8, LAUNCH_FWD)
+    KS_KT_CASE(9, LAUNCH_FWD) KS_KT_CASE(10, LAUNCH_FWD) KS_KT_CASE(11, LAUNCH_FWD) KS_KT_CASE(12, LAUNCH_FWD) KS_KT_CASE(13, LAUNCH_FWD) KS_KT_CASE(14, LAUNCH_FWD) KS_KT_CASE(15, LAUNCH_FWD) KS_KT_CASE(16, LAUNCH_FWD)
+    KS_KT_CASE(17, LAUNCH_FWD) KS_KT_CASE(18, LAUNCH_FWD) KS_KT_CASE(19, LAUNCH_FWD) KS_KT_CASE(20, LAUNCH_FWD) KS_KT_CASE(21, LAUNCH_FWD) KS_KT_CASE(22, LAUNCH_FWD) KS_KT_CASE(23, LAUNCH_FWD) KS_KT_CASE(24, LAUNCH_FWD)
+    KS_KT_CASE(25, LAUNCH_FWD) KS_KT_CASE(26, LAUNCH_FWD) KS_KT_CASE(27, LAUNCH_FWD) KS_KT_CASE(28, LAUNCH_FWD) KS_KT_CASE(29, LAUNCH_FWD) KS_KT_CASE(30, LAUNCH_FWD) KS_KT_CASE(31, LAUNCH_FWD)
+    default: KS_FAIL(KS_ERR_PLIB, "forward update with %d columns", k);
+  }
+#undef LAUNCH_FWD
+#undef LAUNCH_FWD_S
+  KS_HIP(hipGetLastError());
+  std::swap(bv->gs, bv->gs_alt); std::swap(bv->partials, bv->partials_alt);
+  bv->fwd.next.ctl = bv->fwd.ctl; bv->fwd.next.epoch = bv->fwd.epoch;      // the product and the dot sweep of the next step run only if this launch did not leave them
+  bv->fwd.enqueued++;
+  return KS_SUCCESS;
+}
+
 // Slot programs of one column (no host sync inside):
 //   optimistic:  dot, [finish p, update p] for p = 1..2              (IFNEEDED / ALWAYS: the common CGS2 case)
 //   completion:  [finish p, update p] for the remaining passes, the explicit-norm resolution slot and the
@@ -646,7 +1020,7 @@ int enqueue_scale_if(ks_bv bv, int j, bool clear)
   return KS_SUCCESS;
 }
 
-int enqueue_gs_slots(ks_bv bv, int j, int normalize, int krylov, int first, int last, bool halt_at_last, bool resolution_and_scale, bool defer_last = false)
+int enqueue_gs_slots(ks_bv bv, int j, int normalize, int krylov, int first, int last, bool halt_at_last, bool resolution_and_scale, bool defer_last = false, ks_mat fwdA = nullptr)
 {
   ks_ctx ctx = bv->ctx;
   const bool bmat = bv->matrix != nullptr;
@@ -674,6 +1048,8 @@ int enqueue_gs_slots(ks_bv bv, int j, int normalize, int krylov, int first, int 
     }
     if (bmat) KS_CALL(enqueue_dots(bv, j, krylov));          // every pass takes its dots with B v afresh (a pass that turns out not to be needed gates itself off in the bookkeeping)
     if (multi) KS_CALL(launch_reduce_allreduce(bv, a));      // ranks: block partials -> buffer[0..k], summed over the ranks (bvblas.c:255)
+    int fgrid = 0;
+    if (fwdA && p == 2 && p == last && normalize && krylov && fwd_eligible(bv, fwdA, j, &fgrid)) { KS_CALL(launch_update_fwd(bv, fwdA, j, v, a, fgrid)); continue; }      // final update, next product and next dots in one launch
     if (fold) KS_CALL(launch_update(bv, j, v, p, &a));       // the update kernel runs the slot's bookkeeping in its prologue
     else { KS_CALL(launch_finish(bv, a)); KS_CALL(launch_update(bv, j, v, p)); }
   }
@@ -690,14 +1066,14 @@ int enqueue_gs_slots(ks_bv bv, int j, int normalize, int krylov, int first, int 
 }
 
 // Optimistic program of column j (against columns 0..j-1).
-int enqueue_fused_gs(ks_bv bv, int j, int normalize, int krylov, bool dots_done = false, bool defer_last = false)
+int enqueue_fused_gs(ks_bv bv, int j, int normalize, int krylov, bool dots_done = false, bool defer_last = false, ks_mat fwdA = nullptr)
 {
   KS_CHECK(bv->nc + j + 1 <= 8000, KS_ERR_SUP, "device-resident Gram-Schmidt supports at most 8000 columns");
   if (!dots_done && !bv->matrix && bv->nc + j + 1 <= KS_MAX_COLS) KS_CALL(enqueue_dots(bv, j, krylov));      // with a matrix, or more than 64 coefficients, every slot starts with its own dots
   const int ns = spec_slots(bv), nt = total_slots(bv);
   const bool whole = (ns >= nt) && bv->orthog_ref == KS_BV_ORTHOG_REFINE_NEVER;
   if (whole) return enqueue_gs_slots(bv, j, normalize, krylov, 1, nt, false, true);
-  return enqueue_gs_slots(bv, j, normalize, krylov, 1, ns, true, false, defer_last && ns == 2);
+  return enqueue_gs_slots(bv, j, normalize, krylov, 1, ns, true, false, defer_last && ns == 2, ns == 2 ? fwdA : nullptr);
 }
 
 // Completion program of the column the device flagged: remaining passes + resolution + scaling.
@@ -1336,13 +1712,21 @@ static int krylov_run(ks_bv V, ks_mat A, int k, int *m, double *beta, int *break
     // the final update of the run's last column may wait for the restart product (ks_bv_set_defer_final): one rank, a basis the fused restart kernel takes
     const bool defer = V->defer.want && !ctx->dbg.no_restart_fusion && !ks_is_multi(ctx) && !V->matrix && V->nc + m0 <= 32 && V->ld % 2 == 0 && aligned16(ks_bv_col(V, -V->nc));
     while (j0 < m0 && !lin) {
+      V->fwd.next = KsFwdGate(); V->fwd.gate = KsFwdGate();      // a run that failed between a forward launch and the step behind it must not gate this run's first product
       KS_CALL(begin_run(V));
       for (int j = j0; j < m0; j++) {
         bool dots_done = false;                                                      // the product inside the first dot sweep where that pays (small problems)
-        KS_CALL(ks_mat_mult_dot_fused(A, V, ks_bv_col(V, j), j + 1, true, &dots_done));
-        if (!dots_done) KS_CALL(ks_mat_mult_internal(A, ks_bv_col(V, j), ks_bv_col(V, j + 1)));    // BVMatMultColumn (not gated: harmless after a halt)
-        KS_CALL(enqueue_fused_gs(V, j + 1, 1, 1, dots_done, defer && j == m0 - 1));
+        // a forward final update of column j (enqueued by the step before) has left this step's product and first dots: both are still enqueued,
+        // gated on that launch's words, and run only if it did not take the form or gave up
+        const KsFwdGate gate = V->fwd.next; V->fwd.next = KsFwdGate();
+        if (!gate.ctl) KS_CALL(ks_mat_mult_dot_fused(A, V, ks_bv_col(V, j), j + 1, true, &dots_done));
+        if (!dots_done) KS_CALL(ks_mat_mult_internal(A, ks_bv_col(V, j), ks_bv_col(V, j + 1), nullptr, &gate));    // BVMatMultColumn (not gated on the run: harmless after a halt)
+        V->fwd.gate = gate;                                                          // read by the dot sweep of enqueue_fused_gs
+        const int rcg = enqueue_fused_gs(V, j + 1, 1, 1, dots_done, defer && j == m0 - 1, j + 1 < m0 ? A : nullptr);
+        V->fwd.gate = KsFwdGate();
+        KS_CALL(rcg);
       }
+      V->fwd.next = KsFwdGate();
       KsGsState st; std::vector<KsStepRec> recs(m0 - j0);
       buf.resize((size_t)V->m * (V->nc + V->m));
       KS_CALL(fetch_state(V, &st, recs.data(), j0 + 1, m0, buf.data(), buf.size()));          // the coefficient buffer travels with the state (VecGetArrayRead(buf) bvkrylov.c:103,215)
@@ -1439,6 +1823,39 @@ extern "C" int ks_bv_matlanczos(ks_bv V, ks_mat A, double *T, int ldt, int k, in
   }
   return KS_SUCCESS;
 }
+
+// ---- forward form of the final update: counters and test hooks --------------------------------------------------------------------------------------
+extern "C" int ks_bv_step_forward_stats(ks_bv bv, long long *taken, long long *completed, long long *aborted, long long *fell_back)
+{
+  KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
+  unsigned w[KS_FWD_WORDS] = {0};
+  if (bv->fwd.ctl) {
+    KS_HIP(hipSetDevice(bv->ctx->device));
+    KS_HIP(hipMemcpyAsync(w, bv->fwd.ctl, sizeof(w), hipMemcpyDeviceToHost, bv->ctx->stream));
+    KS_HIP(ks_sync(bv->ctx));
+  }
+  if (taken) *taken = w[KS_FWD_NTAKEN];
+  if (completed) *completed = (long long)w[KS_FWD_NTAKEN] - (long long)w[KS_FWD_NABORT];
+  if (aborted) *aborted = w[KS_FWD_NABORT];
+  if (fell_back) *fell_back = w[KS_FWD_NFALLBACK];
+  return KS_SUCCESS;
+}
+extern "C" int ks_bv_step_forward_info(ks_bv bv, long long *enqueued, char *why, int why_len)
+{
+  KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
+  if (enqueued) *enqueued = bv->fwd.enqueued;
+  if (why && why_len > 0) snprintf(why, why_len, "%s", bv->fwd.why ? bv->fwd.why : "");
+  return KS_SUCCESS;
+}
+#ifdef KSD_TEST_HOOKS
+extern "C" int ks_bv_step_forward_hooks(ks_bv bv, int force, int grid, long long budget, int abort_wg, int lag_odd)
+{
+  KS_CHECK(bv, KS_ERR_ARG_NULL, "BV is NULL");
+  KS_CHECK(grid >= 0 && grid <= KS_MAX_BLOCKS, KS_ERR_ARG_OUTOFRANGE, "forced grid %d", grid);
+  bv->fwd.force = force != 0; bv->fwd.force_grid = grid; bv->fwd.budget = budget; bv->fwd.abort_wg = abort_wg; bv->fwd.lag_odd = lag_odd != 0;
+  return KS_SUCCESS;
+}
+#endif
 
 // ---- deferred final update ----------------------------------------------------------------------------
 extern "C" int ks_bv_set_defer_final(ks_bv bv, int on)

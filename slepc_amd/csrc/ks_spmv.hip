@@ -419,9 +419,15 @@ template <int W, int NBT = 0>
 __global__ __launch_bounds__(SPMV_BLOCK) void k_spmv_dict(int nrows, const uint4 *__restrict__ codes, const unsigned char *__restrict__ rowpat, const uint4 *__restrict__ pats, int npat,
                                                           const double *__restrict__ dval, int nval, const int *__restrict__ doff, int noff,
                                                           const double *__restrict__ x, double *__restrict__ y, int xcd_remap,
-                                                          ksp::PairArgs pa = ksp::PairArgs(), const double *__restrict__ pcoef = nullptr, const unsigned *__restrict__ pmask = nullptr)
+                                                          ksp::PairArgs pa = ksp::PairArgs(), const double *__restrict__ pcoef = nullptr, const unsigned *__restrict__ pmask = nullptr,
+                                                          unsigned *fctl = nullptr, unsigned fepoch = 0)
 {
   if constexpr (NBT > 0) {
+    // the fallback behind a forward final update (ks_gs.hip): nothing to do when that launch formed this product itself and no wait of it gave up
+    if (fctl) {
+      if (fctl[KS_FWD_TAKEN] == fepoch && fctl[KS_FWD_ABORT] != fepoch) return;
+      if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(fctl + KS_FWD_NFALLBACK, 1u);
+    }
     KS_PAIR_LDS_FILL(SPMV_BLOCK, pa, pcoef, pmask, npat, sc, sm);
     const RowGroups rg = row_groups_xcd(nrows, 2 * SPMV_BLOCK, xcd_remap);
     const PairLane ln(x, nrows);
@@ -848,7 +854,7 @@ static int spmv_variant(ks_mat A)
 
 // tail (the transposed view of a row-sharded matrix, mult_sharded_transpose): behind the diagonal block's product the main stream waits for the
 // reverse exchange (tail_overlap: it ran on the halo stream) and adds what the other ranks sent - where the forward product runs its off-diagonal rows
-static int mult_assembled(ks_mat A, const double *x, double *y, const double *rowscale, const ks_mat_s::ShT *tail, bool tail_overlap)
+static int mult_assembled(ks_mat A, const double *x, double *y, const double *rowscale, const ks_mat_s::ShT *tail, bool tail_overlap, const KsFwdGate *gate = nullptr)
 {
   ks_ctx ctx = A->ctx;
   const bool multi = ctx->comm.size > 1 && (A->nsend > 0 || A->nghost > 0);
@@ -878,7 +884,8 @@ static int mult_assembled(ks_mat A, const double *x, double *y, const double *ro
     const double csr_bytes = 12.0 * A->nnz + 4.0 * (A->n + 1) + 16.0 * A->n;                    // what the CSR algorithm moves
     const int variant = spmv_variant(A); double own = layout_own_bytes(A) + 16.0 * A->n + 12.0 * A->nnz_o;      // the layout's own compulsory bytes
     if (A->layout == KS_MAT_LAYOUT_SELL) own = csr_bytes;                                               // filed under the CSR stream's bytes (its padding is at most 12.5 %)
-    KsProfScope ps(ctx, KS_K_SPMV, csr_bytes, variant, own);
+    const bool gated = gate && gate->ctl;            // behind a forward final update: in the common case a launch that returns at once, filed with no bytes
+    KsProfScope ps(ctx, KS_K_SPMV, gated ? 0.0 : csr_bytes, variant, gated ? 0.0 : own);
     switch (A->layout) {
     case KS_MAT_LAYOUT_BINNED:
       hipLaunchKernelGGL(k_binned_gather, dim3((unsigned)A->bn_ns), dim3(1024), ks_binned_lds1(A->bn_cs, A->bn_wb), ctx->stream,
@@ -900,8 +907,9 @@ static int mult_assembled(ks_mat A, const double *x, double *y, const double *ro
       const LaunchGrid lg = dict_launch_grid(A, pairs ? 2 : 1);
       const size_t lds = pairs ? dict_pair_lds_bytes(A) : dict_pattern_lds_bytes(A);
 #define SPMV_PAIRS_NB(W, NBT) hipLaunchKernelGGL((k_spmv_dict<W, NBT>), dim3(lg.blocks), dim3(SPMV_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, \
-                                        A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, lg.remap, A->pr_args, A->pr_coef, A->pr_mask)
+                                        A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, lg.remap, A->pr_args, A->pr_coef, A->pr_mask, gated ? gate->ctl : nullptr, gated ? gate->epoch : 0u)
 #define SPMV_PAIRS(W) do { if (A->pr_args.nb <= 5) SPMV_PAIRS_NB(W, 5); else SPMV_PAIRS_NB(W, 9); } while (0)
+      if (gated && !pairs) KS_FAIL(KS_ERR_PLIB, "a gated product must take the pair form");
       if (pairs) { KS_DICT_W_SWITCH(A->dict_w, SPMV_PAIRS); break; }             // W is the real one: the last row of an odd n decodes its code word with it
 #define SPMV_DICT(W) hipLaunchKernelGGL((k_spmv_dict<W>), dim3(lg.blocks), dim3(SPMV_BLOCK), lds, ctx->stream, A->n, (const uint4 *)A->dc_codes, A->dc_rowpat, (const uint4 *)A->dc_pats, A->dict_npat, \
                                         A->dc_val, A->dict_nval, A->dc_off, A->dict_noff, x, y, lg.remap)
@@ -996,9 +1004,13 @@ static int mult_sharded_transpose(ks_mat At, const double *x, double *y)
   return mult_assembled(At, x, y, nullptr, t, overlap);
 }
 
-int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *rowscale)
+int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *rowscale, const KsFwdGate *gate)
 {
   if (rowscale && !ks_mat_can_rowscale(A)) KS_FAIL(KS_ERR_PLIB, "row scaling asked of a product that cannot fold it in");
+  if (gate && gate->ctl) {                           // only the forward form's own eligibility asks for a gate: an assembled one-rank dictionary matrix
+    if (A->shell_mult || A->sht || A->layout != KS_MAT_LAYOUT_DICT) KS_FAIL(KS_ERR_PLIB, "a gated product needs the dictionary layout");
+    return mult_assembled(A, x, y, nullptr, nullptr, false, gate);
+  }
   if (A->shell_mult) return A->shell_mult(A->shell_user, x, y);
   if (A->sht) return mult_sharded_transpose(A, x, y);
   return mult_assembled(A, x, y, rowscale, nullptr, false);

@@ -126,9 +126,11 @@ __device__ __forceinline__ void dot_tiles(const double *__restrict__ A, long lon
 template <int KT, int VEC>
 __global__ __launch_bounds__(SW_BLOCK) void k_dot_sweep(const double *__restrict__ A, long long lda, int n, int ncols,
                                                         const double *__restrict__ y, double *__restrict__ partials,
-                                                        const KsGsState *__restrict__ gate, int *__restrict__ pgrid, int rev, int plain)
+                                                        const KsGsState *__restrict__ gate, int *__restrict__ pgrid, int rev, int plain,
+                                                        const unsigned *fctl = nullptr, unsigned fepoch = 0)
 {
   if (gate && !gate->active) return;
+  if (fctl && fctl[KS_FWD_TAKEN] == fepoch && fctl[KS_FWD_ABORT] != fepoch) return;      // the forward final update in front of this launch left these dots (ks_gs.hip)
   if (pgrid && blockIdx.x == 0 && threadIdx.x == 0) *pgrid = gridDim.x;     // the partials' stride travels with them
   double acc[KT];
 #pragma unroll

@@ -23,7 +23,7 @@ int ks_occupancy(const void *kernel, int block_threads, size_t lds_bytes, int fa
 
 // ---- profiling ----------------------------------------------------------------------------------
 struct KsProfSlot { long long launches = 0; double ms = 0.0; double bytes = 0.0; double hbm = 0.0; };
-struct KsProfPending { hipEvent_t e0, e1; int kclass; int variant; double bytes; double hbm; int tag_col; int tag_slot; int tag_k; long long tag_n; bool done; };
+struct KsProfPending { hipEvent_t e0, e1; int kclass; int variant; double bytes; double hbm; int tag_col; int tag_slot; int tag_k; long long tag_n; bool done; double tag_extra = 0.0; };
 
 // Host mailbox of the ops->gramschmidt slot (one per context, pinned coherent host memory): the update kernel's bookkeeping writes the scalars
 // the slot returns here and stamps them with the call's sequence number; the host polls the stamp instead of waiting for the stream.
@@ -71,7 +71,7 @@ struct ks_ctx_s {
   hipStream_t halo_stream = nullptr; hipEvent_t ev_x = nullptr, ev_halo = nullptr;
   bool halo_overlap = true;
   // test hooks (ks_ctx_set_debug; each makes a test run the path the fast one replaces, or a multi-rank path on one rank)
-  struct { bool no_fused_gs = false, no_mfma = false, no_spmv_dot = false, force_multi = false, no_dict_patterns = false, no_restart_fusion = false, no_dict_pairs = false; unsigned oneshot_seq0 = 0; } dbg;
+  struct { bool no_fused_gs = false, no_mfma = false, no_spmv_dot = false, force_multi = false, no_dict_patterns = false, no_restart_fusion = false, no_dict_pairs = false, no_step_forward = false; unsigned oneshot_seq0 = 0; } dbg;
   long long nsync = 0;              // host synchronisations of the context's stream made by the library (ks_ctx_sync_count)
   int num_cu = 256;
   char arch[64] = {0};
@@ -123,7 +123,7 @@ struct KsProfScope {      // scopes may nest (an allreduce inside a bookkeeping 
   }
   ~KsProfScope() { if (on) ks_prof_end(ctx, index); }
   // tag the record of a speculative Gram-Schmidt slot so it can be re-filed once pass counts are known
-  void tag(int col, int slot, int k, long long n) { if (on && index < ctx->pending.size()) { auto &p = ctx->pending[index]; p.tag_col = col; p.tag_slot = slot; p.tag_k = k; p.tag_n = n; } }
+  void tag(int col, int slot, int k, long long n, double extra = 0.0) { if (on && index < ctx->pending.size()) { auto &p = ctx->pending[index]; p.tag_col = col; p.tag_slot = slot; p.tag_k = k; p.tag_n = n; p.tag_extra = extra; } }
 };
 struct KsStepRec;
 void ks_prof_resolve_gs(ks_ctx ctx, const KsStepRec *recs, int col0, int col1);   // re-file tagged records of columns [col0,col1]
@@ -389,6 +389,11 @@ struct KsGsState {
   long long passes_total;
 };
 struct KsStepRec { double nrm, onrm; int passes, lindep, expl, col; };
+// Forward form of the final update (ks_gs.hip): the device words of a BV's forward launches and the gate the ordinary product and
+// dot sweep behind such a launch carry. Words: [KS_FWD_TAKEN] epoch of the launch whose bookkeeping chose the forward A-phases, [KS_FWD_ABORT] epoch of
+// a launch in which a wait ran out of budget, then three running counts: launches that took the form, launches that gave up, fallback products that ran.
+enum { KS_FWD_TAKEN = 0, KS_FWD_ABORT = 1, KS_FWD_NTAKEN = 2, KS_FWD_NABORT = 3, KS_FWD_NFALLBACK = 4, KS_FWD_WORDS = 8 };
+struct KsFwdGate { unsigned *ctl = nullptr; unsigned epoch = 0; };      // ctl == nullptr: no gate. The gated launch does nothing iff ctl[TAKEN] == epoch && ctl[ABORT] != epoch
 
 struct ks_bv_s {
   ks_ctx ctx = nullptr;
@@ -432,6 +437,11 @@ struct ks_bv_s {
   // k = nc + col columns before it, in sweep direction `rev` (taken, and toggled, where the update would have been launched). Whoever touches
   // column data or Gram-Schmidt state next flushes it (ksb_flush); the restart (ksb_restart) applies it inside the restart product instead.
   struct { bool want = false, pending = false, one_pass = false; int col = 0, k = 0, rev = 0; long long flushes = 0, fused = 0; } defer;
+  // Forward form of the final update: per-tile flags (never reset: a launch's epoch is its flag value, epochs only grow and are never 0), the control
+  // words, the gate of the launches enqueued behind the newest forward launch (gate: what ksk_dot reads while enqueue_dots runs under it), the test
+  // hooks (ks_bv_step_forward_hooks) and the reason of the last refusal
+  struct { unsigned *flags = nullptr; size_t nflags = 0; unsigned *ctl = nullptr; unsigned epoch = 0; KsFwdGate next, gate; long long enqueued = 0;
+           int force = 0, force_grid = 0, abort_wg = -1, lag_odd = 0; long long budget = -1; const char *why = ""; } fwd;
 };
 
 constexpr size_t KS_PINNED_D2H_BYTES = 65536;
@@ -450,7 +460,7 @@ int ksk_multvec(ks_bv bv, const double *A, int lda, int ncols, double alpha, dou
 int ksk_scale(ks_ctx ctx, double *x, size_t n, double alpha);
 int ksk_copy(ks_ctx ctx, const double *src, double *dst, size_t n);
 
-int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *rowscale = nullptr);   // rowscale: y = rowscale .* (A x) where the layout can fold it into its last pass (else the caller scales)
+int ks_mat_mult_internal(ks_mat A, const double *x, double *y, const double *rowscale = nullptr, const KsFwdGate *gate = nullptr);   // rowscale: y = rowscale .* (A x) where the layout can fold it into its last pass (else the caller scales)
 bool ks_mat_can_rowscale(ks_mat A);
 int ks_mat_mult_multi_internal(ks_mat A, int ncols, const double *X, int ldx, double *Y, int ldy);   // Y(:,j) = A X(:,j), j < ncols (ks_spmm.hip)
 int ksb_matmult_block(ks_bv method_bv, ks_mat A, const double *X, int ldx, double *Y, int ldy, int ncols);   // BVMatMult's block product under method_bv's method
