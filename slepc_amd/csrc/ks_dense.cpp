@@ -461,37 +461,40 @@ int trtri_upper(int n, double *A, int ld)
   return 0;
 }
 
-int sym_eig(int n, double *A, int ld, double *w)
+// cyclic Jacobi rotations in the arithmetic T; the eigenvectors and eigenvalues are rounded to double at the end
+template <typename T> static int sym_eig_in(int n, double *A, int ld, double *w)
 {
   if (n <= 0) return 0;
-  std::vector<double> S_((size_t)n * n), V_((size_t)n * n);
-  double *S = S_.data(), *V = V_.data();
+  std::vector<T> S_((size_t)n * n), V_((size_t)n * n);
+  T *S = S_.data(), *V = V_.data();
   for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) { S[i + j * n] = (i >= j) ? AT(A, i, j) : AT(A, j, i); V[i + j * n] = (i == j) ? 1.0 : 0.0; }
   for (int sweep = 0; sweep < 60; sweep++) {
-    double off = 0.0, dg = 0.0;
+    T off = 0.0, dg = 0.0;
     for (int j = 0; j < n; j++) { dg += S[j + j * n] * S[j + j * n]; for (int i = j + 1; i < n; i++) off += S[i + j * n] * S[i + j * n]; }
-    if (off <= 1e-34 * dg || off == 0.0) break;
+    if (off <= T(1e-34) * dg || off == 0.0) break;
     for (int p = 0; p < n - 1; p++)
       for (int q = p + 1; q < n; q++) {
-        const double apq = S[p + q * n];
+        const T apq = S[p + q * n];
         if (apq == 0.0) continue;
-        const double app = S[p + p * n], aqq = S[q + q * n];
+        const T app = S[p + p * n], aqq = S[q + q * n];
         if (std::fabs(apq) < 1e-300) continue;
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double t = sgn(1.0, theta) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-        const double c = 1.0 / std::sqrt(t * t + 1.0), s2 = t * c;
-        for (int k = 0; k < n; k++) { const double skp = S[k + p * n], skq = S[k + q * n]; S[k + p * n] = c * skp - s2 * skq; S[k + q * n] = s2 * skp + c * skq; }
-        for (int k = 0; k < n; k++) { const double spk = S[p + k * n], sqk = S[q + k * n]; S[p + k * n] = c * spk - s2 * sqk; S[q + k * n] = s2 * spk + c * sqk; }
-        for (int k = 0; k < n; k++) { const double vkp = V[k + p * n], vkq = V[k + q * n]; V[k + p * n] = c * vkp - s2 * vkq; V[k + q * n] = s2 * vkp + c * vkq; }
+        const T theta = (aqq - app) / (T(2.0) * apq);
+        const T t = (theta >= 0.0 ? T(1.0) : T(-1.0)) / (std::fabs(theta) + std::sqrt(theta * theta + T(1.0)));
+        const T c = T(1.0) / std::sqrt(t * t + T(1.0)), s2 = t * c;
+        for (int k = 0; k < n; k++) { const T skp = S[k + p * n], skq = S[k + q * n]; S[k + p * n] = c * skp - s2 * skq; S[k + q * n] = s2 * skp + c * skq; }
+        for (int k = 0; k < n; k++) { const T spk = S[p + k * n], sqk = S[q + k * n]; S[p + k * n] = c * spk - s2 * sqk; S[q + k * n] = s2 * spk + c * sqk; }
+        for (int k = 0; k < n; k++) { const T vkp = V[k + p * n], vkq = V[k + q * n]; V[k + p * n] = c * vkp - s2 * vkq; V[k + q * n] = s2 * vkp + c * vkq; }
       }
   }
   std::vector<int> idx_(n);
   int *idx = idx_.data();
   for (int i = 0; i < n; i++) idx[i] = i;
   std::sort(idx, idx + n, [&](int a, int b) { return S[a + a * n] < S[b + b * n]; });
-  for (int j = 0; j < n; j++) { w[j] = S[idx[j] + idx[j] * n]; for (int i = 0; i < n; i++) AT(A, i, j) = V[i + idx[j] * n]; }
+  for (int j = 0; j < n; j++) { w[j] = (double)S[idx[j] + idx[j] * n]; for (int i = 0; i < n; i++) AT(A, i, j) = (double)V[i + idx[j] * n]; }
   return 0;
 }
+int sym_eig(int n, double *A, int ld, double *w) { return sym_eig_in<double>(n, A, ld, w); }
+int sym_eig_extended(int n, double *A, int ld, double *w) { return sym_eig_in<long double>(n, A, ld, w); }
 
 void qr_explicit(int M, int n, double *A, int ld, double *R, int ldr, double *Q, int ldq)
 {
@@ -646,6 +649,7 @@ int ksd_trevc_one(int n, const double *T, int ld, int k, double *xr, double *xi)
 int ksd_potrf_upper(int n, double *A, int ld) { return ksd::potrf_upper(n, A, ld); }
 int ksd_trtri_upper(int n, double *A, int ld) { return ksd::trtri_upper(n, A, ld); }
 int ksd_sym_eig(int n, double *A, int ld, double *w) { return ksd::sym_eig(n, A, ld, w); }
+int ksd_sym_eig_extended(int n, double *A, int ld, double *w) { return ksd::sym_eig_extended(n, A, ld, w); }
 void ksd_tsqr_combine(int n, double *R1, int ld1, double *R2, int ld2) { ksd::tsqr_combine(n, R1, ld1, R2, ld2); }
 void ksd_qr_explicit(int M, int n, double *A, int ld, double *R, int ldr, double *Q, int ldq) { ksd::qr_explicit(M, n, A, ld, R, ldr, Q, ldq); }
 int ksd_lu_solve_trans(int n, double *A, int ld, double *b) { return ksd::lu_solve_trans(n, A, ld, b); }

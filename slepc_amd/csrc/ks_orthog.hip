@@ -129,7 +129,7 @@ __global__ __launch_bounds__(TS_BLOCK) void k_tsqr_formq(double *__restrict__ V,
   }
 }
 
-// R factor (host, nc x nc upper triangular, ldr) of V(:, s:s+nc): per-block factors, combined in block order, then in
+// R factor (host, nc x nc upper triangular, ldr) of V(:, s:s+nc): per-block factors, combined pairwise in a fixed tree, then in
 // rank order across the communicator - deterministic and identical on every rank
 int tsqr_r(ks_bv V, int s, int nc, double *R, int ldr)
 {
@@ -152,7 +152,9 @@ int tsqr_r(ks_bv V, int s, int nc, double *R, int ldr)
   if (!rc && ks_sync(ctx) != hipSuccess) rc = KS_ERR_LIB;
   hipFree(dR);
   KS_CHECK(!rc, KS_ERR_LIB, "TSQR panel kernel failed");
-  for (long long b = 1; b < nb; b++) ksd::tsqr_combine(nc, h.data(), nc, h.data() + (size_t)b * nc * nc, nc);
+  // pairwise, in a fixed binary tree: a factor goes through log2(nb) combines (along a chain over up to 2 num_cu blocks the rounding errors add up)
+  for (long long stride = 1; stride < nb; stride *= 2)
+    for (long long b = 0; b + stride < nb; b += 2 * stride) ksd::tsqr_combine(nc, h.data() + (size_t)b * nc * nc, nc, h.data() + (size_t)(b + stride) * nc * nc, nc);
   if (ks_is_multi(ctx) && ctx->comm.size > 1) {
     std::vector<double> all((size_t)ctx->comm.size * nc * nc);
     KS_CALL(ks_comm_allgather_host(ctx, h.data(), (int)(sizeof(double) * nc * nc), all.data()));
@@ -161,6 +163,24 @@ int tsqr_r(ks_bv V, int s, int nc, double *R, int ldr)
   }
   for (int c = 0; c < nc; c++) for (int r = 0; r < nc; r++) R[(size_t)r + (size_t)c * ldr] = (r <= c) ? h[(size_t)r + (size_t)c * nc] : 0.0;
   return KS_SUCCESS;
+}
+
+// A = Q R of the stack of the ranks' triangular factors (M x nc, column-major, leading dimension M), Q explicit (M x nc, leading dimension M).
+// Rows of the stack that are exactly zero stay out of the factorisation and get zero rows of Q. A rank with fewer rows than columns, or with no
+// rows at all, has such rows in its factor from its own row count on, and k_tsqr_formq drops the rows of its block of Q that belong to them (the
+// panel has no row to take them). In the first rank's block a zero row is the pivot row of its column, and its row of Q, zero in exact arithmetic,
+// comes out as eps cond(A): dropped, it takes that much of Q's orthogonality with it. Without zero rows this is qr_explicit on the stack itself.
+void stack_qr(int M, int nc, std::vector<double> &stack, double *R, std::vector<double> &Q)
+{
+  std::vector<int> keep;
+  for (int i = 0; i < M; i++) { bool nz = false; for (int c = 0; c < nc && !nz; c++) nz = stack[(size_t)i + (size_t)c * M] != 0.0; if (nz) keep.push_back(i); }
+  if ((int)keep.size() == M) { ksd::qr_explicit(M, nc, stack.data(), M, R, nc, Q.data(), M); return; }
+  const int Mk = std::max<int>((int)keep.size(), nc);              // fewer than nc rows left: a rank-deficient panel, zero rows at the end
+  std::vector<double> A((size_t)Mk * nc, 0.0), Qk((size_t)Mk * nc);
+  for (int c = 0; c < nc; c++) for (size_t i = 0; i < keep.size(); i++) A[i + (size_t)c * Mk] = stack[(size_t)keep[i] + (size_t)c * M];
+  ksd::qr_explicit(Mk, nc, A.data(), Mk, R, nc, Qk.data(), Mk);
+  std::fill(Q.begin(), Q.end(), 0.0);
+  for (int c = 0; c < nc; c++) for (size_t i = 0; i < keep.size(); i++) Q[(size_t)keep[i] + (size_t)c * M] = Qk[i + (size_t)c * Mk];
 }
 
 // V(:, s:s+nc) = Q R with Q formed from the accumulated reflectors, in place; R (host, nc x nc, ldr) identical on every rank.
@@ -198,7 +218,7 @@ int tsqr_q(ks_bv V, int s, int nc, double *R, int ldr)
     int rc = ks_comm_allgather_host(ctx, Rs.data(), (int)(sizeof(double) * nc * nc), all.data());
     if (rc) return done(rc);
     for (int q = 0; q < size; q++) for (int c = 0; c < nc; c++) for (int r = 0; r < nc; r++) st2[(size_t)(q * nc + r) + (size_t)c * Mr] = all[(size_t)q * nc * nc + (size_t)c * nc + r];
-    ksd::qr_explicit(Mr, nc, st2.data(), Mr, R2.data(), nc, Q2.data(), Mr);
+    stack_qr(Mr, nc, st2, R2.data(), Q2);
     const double *Cr = Q2.data() + (size_t)ctx->comm.rank * nc;          // this rank's nc x nc block, leading dimension Mr
     for (long long b = 0; b < nb; b++)
       for (int c = 0; c < nc; c++) for (int r = 0; r < nc; r++) {
@@ -309,7 +329,7 @@ extern "C" int ks_bv_orthogonalize(ks_bv V, double *R, int ldr)       // BVOrtho
       std::vector<double> D(nact), eig(nact), U((size_t)nact * nact);
       for (int i = 0; i < nact; i++) D[i] = 1.0 / sqrt(R22[(size_t)i + (size_t)i * ldb]);
       for (int j = 0; j < nact; j++) for (int i = 0; i < nact; i++) U[(size_t)i + (size_t)j * nact] = R22[(size_t)i + (size_t)j * ldb] * D[i] * D[j];
-      const int info = ksd::sym_eig(nact, U.data(), nact, eig.data());
+      const int info = ksd::sym_eig_extended(nact, U.data(), nact, eig.data());       // R = inv(S) below takes U^-1 = U^T: U orthogonal to a few eps, not to n eps
       KS_CHECK(!info, KS_ERR_LIB, "Error in LAPACK subroutine syev: info=%d", info);
       for (int j = 0; j < nact; j++) for (int i = 0; i < nact; i++) {
         const double u = U[(size_t)i + (size_t)j * nact];

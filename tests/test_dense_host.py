@@ -28,6 +28,7 @@ def lib():
     lib.ksd_potrf_upper.argtypes = [C.c_int, P, C.c_int]
     lib.ksd_trtri_upper.argtypes = [C.c_int, P, C.c_int]
     lib.ksd_sym_eig.argtypes = [C.c_int, P, C.c_int, P]
+    lib.ksd_sym_eig_extended.argtypes = [C.c_int, P, C.c_int, P]
     lib.ksd_tsqr_combine.argtypes = [C.c_int, P, C.c_int, P, C.c_int]
     lib.ksd_tsqr_combine.restype = None
     lib.ksd_lu_solve_trans.argtypes = [C.c_int, P, C.c_int, P]
@@ -236,3 +237,35 @@ def test_explicit_householder_qr_of_the_tsqr_stack(lib, M, n):
         if np.linalg.matrix_rank(A0) == n:
             Rref = np.linalg.qr(A0, mode="r")
             assert np.abs(np.abs(R) - np.abs(Rref)).max() <= 1e3 * max(M, 8) * eps * np.abs(Rref).max()
+
+
+def _eig_extended(lib, A):
+    """(w, X, |X^T X - I|, |X diag(w) X^T - A|) of sym_eig_extended on the lower triangle of A."""
+    n = A.shape[0]
+    L = np.tril(A) + np.tril(A, -1).T
+    E = np.asfortranarray(A.copy()); w = np.zeros(n)
+    assert lib.ksd_sym_eig_extended(n, p(E), n, p(w)) == 0
+    return w, E, np.abs(E.T @ E - np.eye(n)).max(), np.abs((E * w) @ E.T - L).max()
+
+
+@pytest.mark.parametrize("n", [1, 2, 8, 12, 64, 100])
+def test_sym_eig_extended_is_accurate_to_a_few_eps(lib, n):
+    """The rotations of sym_eig in double leave X^T X = I and A = X diag(w) X^T to n eps (2e-14 at n = 64); carried out in long double and rounded
+    once they leave a few eps whatever n - what SVQB needs, which takes R = inv(S) from X^T - and however the eigenvalues cluster: a scaled Gram
+    matrix, an exactly multiple eigenvalue, distinct eigenvalues with gaps from 1e-14 to 1e-8 (the scaled Gram matrix of a nearly orthonormal
+    block), and an upper triangle that differs from the lower one in the last bits (only the lower one is read)."""
+    eps = np.finfo(float).eps
+    rng = np.random.default_rng(n)
+    X0 = rng.standard_normal((40 * n + 5, n))
+    G = X0.T @ X0
+    d = 1.0 / np.sqrt(np.diag(G))
+    Q = np.linalg.qr(rng.standard_normal((n, n)))[0]
+    cases = [G * d[:, None] * d[None, :], np.diag(np.repeat([1.0, 2.0], [n // 2, n - n // 2]))]
+    cases += [Q @ np.diag(1.0 + gap * np.arange(n)) @ Q.T for gap in (1e-14, 1e-13, 1e-12, 1e-11, 1e-10, 1e-8)]
+    cases += [np.eye(n) + pp * (X0[:n] + X0[:n].T) for pp in (1e-14, 1e-12, 1e-9)]
+    cases.append(cases[0] + np.triu(1e-13 * rng.standard_normal((n, n)), 1))
+    for A in cases:
+        w, E, orth, res = _eig_extended(lib, A)
+        assert np.all(np.diff(w) >= 0)
+        assert np.abs(w - np.linalg.eigvalsh(A, UPLO="L")).max() <= 16 * eps * np.sqrt(n) * abs(w).max()
+        assert orth <= 16 * eps * np.sqrt(n) and res <= 16 * eps * np.sqrt(n) * np.abs(A).max(), (orth, res)
