@@ -648,8 +648,25 @@ int ks_st_get_matmode(ks_st st, int *mode);
 /* KS_KSP_PREONLY is KSPPREONLY: the solve is ONE application of the preconditioner - no residual, no convergence test, no Krylov basis - which is
    exact with KS_PC_LU (the reference's default pair, -st_ksp_type preonly -st_pc_type lu) and allowed with every PC type, as in PETSc.
    ks_st_get_ksp_stats counts one solve and one iteration per application and leaves last_rnorm alone. */
-enum { KS_KSP_GMRES = 0, KS_KSP_BCGS = 1, KS_KSP_PREONLY = 2 };
-int ks_st_set_ksp_type(ks_st st, int type);                                /* KSPSetType on STGetKSP: GMRES (restarted, the shell mode's default), BiCGStab - both preconditioned on the left - or PREONLY */
+/* KS_KSP_CG is KSPCG (-st_ksp_type cg, ex11.c's second test) with the preconditioner on the left and PETSc's default norm for it, the preconditioned
+   residual: y = 0, r = b, z = M^-1 r, tol = max(rtol ||z||, 1e-50); per iteration gamma = (r,z), p = z + (gamma / gamma_old) p, w = P p,
+   delta = (p,w), alpha = gamma / delta, y += alpha p, r -= alpha w, z = M^-1 r, converged when ||z|| <= tol. For a symmetric positive definite P
+   and M: the symmetry is the caller's business, as in PETSc. One product and 12 vector passes per iteration, four work vectors. The KSP of the ST
+   is strict: KS_ERR_NOT_CONVERGED when (p,w) <= 0 ("indefinite matrix"), (r,z) < 0 ("indefinite preconditioner"), either is not finite ("not a
+   number") or max_it is reached ("reached %d iterations"). Every transformation with a solve, both matrix modes, every PC type, the transposed
+   side (ks_st_set_transpose_solves) and, with the PC types that have it, more than one rank. A Jacobi-Davidson solve whose ST has it set is
+   KS_ERR_SUP at set-up (its projected operator is not symmetric as applied). A zero right-hand side gives y = 0 and counts no iteration.
+   Its value is 4: the value 3 names no solver and stays KS_ERR_SUP, which is what callers of earlier versions got for it. */
+enum { KS_KSP_GMRES = 0, KS_KSP_BCGS = 1, KS_KSP_PREONLY = 2, KS_KSP_CG = 4 };
+int ks_st_set_ksp_type(ks_st st, int type);                                /* KSPSetType on STGetKSP: GMRES (restarted, the shell mode's default), BiCGStab, CG - all preconditioned on the left - or PREONLY; any other value: KS_ERR_SUP */
+/* KS_KSP_CG keeps its scalars on the device and switches itself off there once a solve has ended: the host enqueues c iterations, then reads the
+   solver's state once. c: 1..1024 (KS_ERR_ARG_OUTOFRANGE otherwise), default 8; c = 1 is the classic loop with one host test per iteration. The
+   iteration count, the solution and last_rnorm are the same bits for every c. */
+int ks_st_cg_set_check_interval(ks_st st, int c);
+int ks_st_cg_get_check_interval(ks_st st, int *c);
+/* Since the ST was created (any pointer may be NULL): launches of the solver's own kernels, host reads of the device state, and iterations that were
+   enqueued but switched themselves off on the device because the solve had already ended. */
+int ks_st_cg_get_stats(ks_st st, long long *sweeps, long long *host_waits, long long *gated_iterations);
 /* KSPGMRESSetCGSRefinementType on STGetKSP, with the BV constants: KS_BV_ORTHOG_REFINE_NEVER (PETSc's default for KSPGMRES: one pass of
    classical Gram-Schmidt, then the norm), _IFNEEDED (PETSc's test is the BV's, eta 0.7071) or _ALWAYS */
 int ks_st_set_gmres_cgs_refinement(ks_st st, int refine);
@@ -784,7 +801,7 @@ int ks_st_pc_multi_columns(ks_st st, int *columns);   /* instrumentation: column
 /* STApplyMat stsolve.c:62: Y(:,j) = Op X(:,j). KS_ST_PRECOND: ks_st_pc_apply_multi; the other transformations: ks_st_apply column by column. Same arguments. */
 int ks_st_apply_mat(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy);
 int ks_st_backtransform(ks_st st, int n, double *eigr, double *eigi);     /* STBackTransform stsolve.c:563 */
-int ks_st_get_ksp_stats(ks_st st, long long *solves, long long *iterations, double *last_rnorm);
+int ks_st_get_ksp_stats(ks_st st, long long *solves, long long *iterations, double *last_rnorm);   /* solves and iterations of every KSP type since the ST was created; last_rnorm: the preconditioned residual norm of the last solve */
 
 /* ---- profiling: HIP-event timing per kernel class, on the context's stream -------------------- */
 /* A class is one __global__ kernel template; `variant` is its compile-time column tile KT (0 when

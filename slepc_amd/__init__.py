@@ -814,7 +814,8 @@ class BV:
 
 
 class ST:
-    """Spectral transformation (STSHIFT / STSINVERT, shell matrix mode, GMRES + Jacobi inner solves)."""
+    """Spectral transformation (STSHIFT / STSINVERT / STCAYLEY / STPRECOND). Inner solves: GMRES + Jacobi by default; SetKSPType chooses BiCGStab,
+    PREONLY or, for a symmetric positive definite system, CG (CGSetCheckInterval, GetCGStats); SetPC the preconditioner."""
 
     def __init__(self, ctx, _handle=None):
         self.ctx = ctx
@@ -956,8 +957,24 @@ class ST:
         v = C.c_int(); _lib.check(self.ctx.L.ks_st_get_matmode(self.h, C.byref(v))); return {0: "copy", 2: "shell"}[v.value]
 
     def SetKSPType(self, t):
-        """KSPSetType on the ST's KSP: "gmres" (default), "bcgs", or "preonly" (one application of the preconditioner: exact with SetPC("lu"))."""
-        _lib.check(self.ctx.L.ks_st_set_ksp_type(self.h, {"gmres": 0, "bcgs": 1, "preonly": 2}.get(t, t)))
+        """KSPSetType on the ST's KSP: "gmres" (default), "bcgs", "preonly" (one application of the preconditioner: exact with SetPC("lu")), or "cg"
+        (conjugate gradients for a symmetric positive definite P and preconditioner; its scalars stay on the device, see CGSetCheckInterval)."""
+        _lib.check(self.ctx.L.ks_st_set_ksp_type(self.h, {"gmres": 0, "bcgs": 1, "preonly": 2, "cg": 4}.get(t, t)))
+
+    def CGSetCheckInterval(self, c):
+        """Iterations of "cg" enqueued before the host reads the solver's state (1..1024, default 8; 1: one host test per iteration). The count,
+        the solution and the residual norm do not depend on it."""
+        _lib.check(self.ctx.L.ks_st_cg_set_check_interval(self.h, int(c)))
+
+    def CGGetCheckInterval(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_st_cg_get_check_interval(self.h, C.byref(v))); return v.value
+
+    def GetCGStats(self):
+        """Since the ST was created: sweeps (launches of the CG kernels), host_waits (reads of the device state), gated_iterations (enqueued
+        iterations that found the solve already ended and did nothing)."""
+        a, b, c = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        _lib.check(self.ctx.L.ks_st_cg_get_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"sweeps": a.value, "host_waits": b.value, "gated_iterations": c.value}
 
     def SetUp(self):
         _lib.check(self.ctx.L.ks_st_setup(self.h))

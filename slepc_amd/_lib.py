@@ -241,6 +241,9 @@ _SIG = {
     "ks_st_set_matrices": [vp, vp, vp],
     "ks_st_set_ksp": [vp, C.c_double, C.c_int, C.c_int],
     "ks_st_set_ksp_type": [vp, C.c_int],
+    "ks_st_cg_set_check_interval": [vp, C.c_int],
+    "ks_st_cg_get_check_interval": [vp, ip],
+    "ks_st_cg_get_stats": [vp, llp, llp, llp],
     "ks_st_set_matmode": [vp, C.c_int],
     "ks_st_set_pc": [vp, C.c_int, C.c_int],
     "ks_st_set_gmres_cgs_refinement": [vp, C.c_int],

@@ -328,6 +328,21 @@ int ks_ksp_preonly(const KsKsp &k, KsKspOp &op, const double *rhs, double *y)
   return op.residual(rhs, nullptr, y);
 }
 
+// the product of a CG iteration: the calls of apply_P without the combining sweep of a P with two terms, which the (p,w) sweep does (ks_cg.hip)
+int ks_st_cg_product(ks_st st, bool tr, const double *p, double *w, const double **v, double *b)
+{
+  ks_mat Pm = tr ? st->PmatT : st->Pmat, A = tr ? st->At : st->A, B = tr ? st->Bt : st->B;
+  *v = nullptr; *b = 0.0;
+  if (Pm) return ks_mat_mult_internal(Pm, p, w);
+  if (st->type == KS_ST_SHIFT) return ks_mat_mult_internal(B, p, w);                // shift, nmat = 2: P = B
+  KS_CALL(ks_mat_mult_internal(A, p, w));
+  if (st->sigma == 0.0) return KS_SUCCESS;                                          // a zero shift leaves A alone, as in linop_apply
+  *b = -st->sigma; *v = p;
+  if (B) { double *tmp = ks_bv_col(st->W, 1); KS_CALL(ks_mat_mult_internal(B, p, tmp)); *v = tmp; }
+  return KS_SUCCESS;
+}
+int ks_st_blocks_apply(ks_st st, const double *in, double *out, bool tr) { return blocks_apply(st, in, out, tr); }
+
 namespace {
 int gmres_solve(ks_st st, const double *rhs, double *y, bool tr) { StKspOp op(st, tr); return ks_ksp_gmres(st_ksp(st), op, rhs, y); }
 int bcgs_solve(ks_st st, const double *rhs, double *y, bool tr) { StKspOp op(st, tr); return ks_ksp_bcgs(st_ksp(st), op, rhs, y); }
@@ -335,6 +350,7 @@ int preonly_solve(ks_st st, const double *rhs, double *y, bool tr) { StKspOp op(
 int inner_solve(ks_st st, const double *rhs, double *y, bool tr = false)
 {
   if (st->ksp_type == KS_KSP_PREONLY) return preonly_solve(st, rhs, y, tr);
+  if (st->ksp_type == KS_KSP_CG) return ks_ksp_cg(st_ksp(st), st, tr, rhs, y);
   return st->ksp_type == KS_KSP_BCGS ? bcgs_solve(st, rhs, y, tr) : gmres_solve(st, rhs, y, tr);
 }
 
@@ -495,10 +511,11 @@ int ks_st_setup_internal(ks_st st)
   if (need_solve || precond) {
     if (st->K && !need_solve) { ks_bv_destroy(st->K); st->K = nullptr; }
     if (st->K) { int km = 0; ks_bv_get_sizes(st->K, nullptr, nullptr, &km, nullptr); if (km != st->restart + 1) { ks_bv_destroy(st->K); st->K = nullptr; } }
-    if (st->K && st->ksp_type == KS_KSP_PREONLY) { ks_bv_destroy(st->K); st->K = nullptr; }      // KSPPREONLY keeps no basis
-    if (need_solve && !st->K && st->ksp_type != KS_KSP_PREONLY) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, st->restart + 1, 0, &st->K)); st->K->row_start = A->row_start; }
+    if (st->K && (st->ksp_type == KS_KSP_PREONLY || st->ksp_type == KS_KSP_CG)) { ks_bv_destroy(st->K); st->K = nullptr; }      // KSPPREONLY and KSPCG keep no basis
+    if (need_solve && !st->K && st->ksp_type != KS_KSP_PREONLY && st->ksp_type != KS_KSP_CG) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, st->restart + 1, 0, &st->K)); st->K->row_start = A->row_start; }
     if (need_solve && st->K) KS_CALL(ks_bv_set_orthogonalization(st->K, KS_BV_ORTHOG_CGS, st->gmres_refine, 0.7071));      // KSPGMRESClassicalGramSchmidtOrthogonalization + refinement type
-    if (need_solve && st->ksp_type == KS_KSP_BCGS && !st->Kb) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 7, 0, &st->Kb)); st->Kb->row_start = A->row_start; }
+    if (need_solve && st->ksp_type == KS_KSP_CG) KS_CALL(ks_st_cg_alloc(st));
+    if (need_solve && (st->ksp_type == KS_KSP_BCGS || st->ksp_type == KS_KSP_CG) && !st->Kb) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 7, 0, &st->Kb)); st->Kb->row_start = A->row_start; }
     if (!st->dinv) KS_HIP(hipMalloc(&st->dinv, sizeof(double) * std::max(A->n, 1)));
     // Jacobi: diag(P)
     double *da = ks_bv_col(st->W, 1), *db = ks_bv_col(st->W, 2);
@@ -572,6 +589,7 @@ extern "C" int ks_st_destroy(ks_st st)
   if (st->Pmat) ks_mat_destroy(st->Pmat);
   if (st->binv) hipFree(st->binv);
   if (st->pcwork) hipFree(st->pcwork);
+  ks_st_cg_free(st);
   ks_pc_ilu_free(st->ilu);
   ks_pc_lu_free(st->lu);
   ks_pc_amg_free(st->amg);
@@ -625,12 +643,26 @@ extern "C" int ks_st_set_ksp(ks_st st, double rtol, int max_it, int restart)   /
   if (restart > 0 && restart != st->restart) { st->restart = restart; st->ready = false; }   // a basis wider than 64 columns orthogonalises through the host-driven loop
   return KS_SUCCESS;
 }
-extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType on STGetKSP: KSPGMRES (default) or KSPBCGS
+extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType on STGetKSP: KSPGMRES (default), KSPBCGS, KSPPREONLY or KSPCG
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  KS_CHECK(type == KS_KSP_GMRES || type == KS_KSP_BCGS || type == KS_KSP_PREONLY, KS_ERR_SUP, "only KSPGMRES, KSPBCGS and KSPPREONLY are built");
+  KS_CHECK(type == KS_KSP_GMRES || type == KS_KSP_BCGS || type == KS_KSP_PREONLY || type == KS_KSP_CG, KS_ERR_SUP, "only KSPGMRES, KSPBCGS, KSPPREONLY and KSPCG are built");
   if (st->ksp_type != type) { st->ksp_type = type; st->ready = false; }
   st->ksp_type_set = true;
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_cg_set_check_interval(ks_st st, int c)
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  KS_CHECK(c >= 1 && c <= 1024, KS_ERR_ARG_OUTOFRANGE, "check interval %d (1..1024)", c);
+  st->cg_check = c;
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_cg_get_check_interval(ks_st st, int *c) { KS_CHECK(st && c, KS_ERR_ARG_NULL, "NULL argument"); *c = st->cg_check; return KS_SUCCESS; }
+extern "C" int ks_st_cg_get_stats(ks_st st, long long *sweeps, long long *host_waits, long long *gated_iterations)
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  if (sweeps) *sweeps = st->cg_sweeps; if (host_waits) *host_waits = st->cg_waits; if (gated_iterations) *gated_iterations = st->cg_gated;
   return KS_SUCCESS;
 }
 extern "C" int ks_st_set_pc(ks_st st, int type, int block_size)       // PCSetType (+ PCBJacobiSetLocalBlocks, -sub_pc_type lu | ilu) on the KSP's PC

@@ -318,10 +318,14 @@ struct ks_st_s {
   ks_mat bil = nullptr;                       // STCAYLEY: shell matrix A + nu B, the bilinear form of symmetric problems (cayley.c:70-77)
   ks_mat A = nullptr, B = nullptr;            // borrowed
   double rtol = 1e-8; int max_it = 10000, restart = 30;   // KSP: SLEPC_DEFAULT_TOL (stsles.c:407), PETSc defaults
-  int ksp_type = KS_KSP_GMRES;                // KSPGMRES (the default of the shell matrix mode), KSPBCGS or KSPPREONLY
+  int ksp_type = KS_KSP_GMRES;                // KSPGMRES (the default of the shell matrix mode), KSPBCGS, KSPPREONLY or KSPCG
   bool ksp_type_set = false, rtol_set = false, max_it_set = false;   // chosen by the caller (ks_st_set_ksp_type, ks_st_set_ksp): a solver with KSP defaults of its own (JD) keeps off those
   int gmres_refine = KS_BV_ORTHOG_REFINE_NEVER;   // KSPGMRESSetCGSRefinementType: PETSc's default is classical Gram-Schmidt without refinement
-  ks_bv Kb = nullptr;                         // BiCGStab work vectors (7 columns)
+  ks_bv Kb = nullptr;                         // BiCGStab work vectors (7 columns); CG's r, z, p, w are its first four
+  // KS_KSP_CG (ks_cg.hip): iterations enqueued per host read of the state; the device scratch (KsCgState, the ranks' sums, the sweeps' partials) and the
+  // pinned copy the host reads; launches of the solver's own kernels, host reads, iterations that found the solve ended (ks_st_cg_get_stats)
+  int cg_check = 8; char *cg_dev = nullptr; struct KsCgState *cg_host = nullptr;
+  long long cg_sweeps = 0, cg_waits = 0, cg_gated = 0;
   ks_bv K = nullptr, W = nullptr;             // GMRES basis (restart+1 columns), work vectors (3 columns)
   double *dinv = nullptr;                     // Jacobi: 1/diag(P)
   int pc_type = KS_PC_JACOBI, pc_bs = 0;      // PCSetType on the KSP's PC: point Jacobi, or block Jacobi (dense inverses or ILU(0) factors) with blocks of pc_bs consecutive local rows
@@ -361,6 +365,17 @@ struct KsKsp { ks_ctx ctx; long long n; ks_bv K, Kb; double rtol; int max_it, re
 int ks_ksp_gmres(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);
 int ks_ksp_bcgs(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);
 int ks_ksp_preonly(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);     // KSPPREONLY: y = M^-1 rhs, one application, no residual, no test; K and Kb are not used
+// CG (ks_cg.hip) takes P and M^-1 apart, which KsKspOp does not offer: its own entry on the ST, tr: the transposed side. Its state block on the device:
+// written by thread 0 of workgroup 0 of the direction and update sweeps, read by every workgroup of the sweeps behind them and, once per batch, by the host
+enum { KS_CG_CONVERGED = 1, KS_CG_ITS = 2, KS_CG_INDEFINITE_MAT = 3, KS_CG_INDEFINITE_PC = 4, KS_CG_NAN = 5 };
+struct KsCgState { double gamma, gamma_old, delta, dp, tol; int its, done, reason; long long gated; };
+constexpr size_t KS_CG_STATE_BYTES = 256;    // the state and the four sums of the ranks; the partials follow
+int ks_ksp_cg(const KsKsp &k, ks_st st, bool tr, const double *rhs, double *y);
+int ks_st_cg_alloc(ks_st st);
+void ks_st_cg_free(ks_st st);
+// w = P p but for one term: *v non-NULL on return means w += (*b) (*v) is still to be done (P applied term by term; the (p,w) sweep adds it). tmp: W(:,1)
+int ks_st_cg_product(ks_st st, bool tr, const double *p, double *w, const double **v, double *b);
+int ks_st_blocks_apply(ks_st st, const double *in, double *out, bool tr);      // out = M^-1 in for the preconditioners with kernels of their own
 bool ks_st_pc_pointwise(ks_st st, const double **dinv);   // set-up done. true: no preconditioner (*dinv NULL) or point Jacobi (*dinv its diagonal); false: blocks (ks_st_pc_apply_multi_internal)
 int ksk_lincomb(ks_ctx ctx, long long n, const double *s, double a, const double *u, double b, const double *v, double *out);   // out = s.*(a*u + b*v)   // diagonal of the local diagonal block (MatGetDiagonal)
 
