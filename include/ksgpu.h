@@ -657,8 +657,32 @@ int ks_st_get_matmode(ks_st st, int *mode);
    side (ks_st_set_transpose_solves) and, with the PC types that have it, more than one rank. A Jacobi-Davidson solve whose ST has it set is
    KS_ERR_SUP at set-up (its projected operator is not symmetric as applied). A zero right-hand side gives y = 0 and counts no iteration.
    Its value is 4: the value 3 names no solver and stays KS_ERR_SUP, which is what callers of earlier versions got for it. */
-enum { KS_KSP_GMRES = 0, KS_KSP_BCGS = 1, KS_KSP_PREONLY = 2, KS_KSP_CG = 4 };
-int ks_st_set_ksp_type(ks_st st, int type);                                /* KSPSetType on STGetKSP: GMRES (restarted, the shell mode's default), BiCGStab, CG - all preconditioned on the left - or PREONLY; any other value: KS_ERR_SUP */
+/* KS_KSP_MINRES is KSPMINRES (-st_ksp_type minres) after Paige and Saunders, for a symmetric P that may be indefinite - shift-and-invert at a target
+   inside the spectrum - with a symmetric positive definite preconditioner M applied symmetrically. The norm it minimises, tests and reports as
+   last_rnorm is phibar = ||b - P y|| in the M^-1 inner product:
+     y = 0; r1 = r2 = b; z = M^-1 b; beta1 = sqrt((b,z)); tol = max(rtol beta1, 1e-50); beta = beta1; phibar = beta1; cs = -1; sn = dbar = epsln = 0
+     iteration i:  v = z / beta;  u = P v;  if i > 0: u -= (beta / oldb) r1;  alfa = (v,u);  u -= (alfa / beta) r2;  r1 = r2; r2 = u;  z = M^-1 r2
+                   oldb = beta;  beta = sqrt((r2,z));  oldeps = epsln;  delta = cs dbar + sn alfa;  gbar = sn dbar - cs alfa;  epsln = sn beta
+                   dbar = -cs beta;  gamma = max(hypot(gbar, beta), DBL_EPSILON);  cs = gbar / gamma;  sn = beta / gamma;  phi = cs phibar
+                   phibar = sn phibar;  w1 = w2; w2 = w;  w = (v - oldeps w1 - delta w2) / gamma;  y += phi w;  converged when phibar <= tol
+   One product and 16 vector passes per iteration, seven work vectors, no restart. The KSP of the ST is strict: KS_ERR_NOT_CONVERGED when (b,z) or
+   (r2,z) < 0 ("indefinite preconditioner": point Jacobi of an indefinite P has negative entries, see ks_st_pc_jacobi_set_use_abs), alfa or either
+   inner product is not finite ("not a number") or max_it is reached ("reached %d iterations"). beta = 0 after an iteration is the lucky breakdown:
+   phibar = 0, converged. Supported where KS_KSP_CG is: every transformation with a solve, both matrix modes, every PC type, the transposed side
+   and, with the PC types that have it, more than one rank; a Jacobi-Davidson solve whose ST has it set is KS_ERR_SUP at set-up. A zero right-hand
+   side gives y = 0 and counts no iteration. The symmetry of P and M is the caller's business.
+   Its value is 6: the values 3 and 5 name no solver and stay KS_ERR_SUP, which is what callers of earlier versions got for them. */
+enum { KS_KSP_GMRES = 0, KS_KSP_BCGS = 1, KS_KSP_PREONLY = 2, KS_KSP_CG = 4, KS_KSP_MINRES = 6 };
+int ks_st_set_ksp_type(ks_st st, int type);                                /* KSPSetType on STGetKSP: GMRES (restarted, the shell mode's default), BiCGStab, CG - all preconditioned on the left -, MINRES or PREONLY; any other value: KS_ERR_SUP */
+/* KS_KSP_MINRES has the device-resident form of KS_KSP_CG (below) with a check interval and counters of its own: setting one solver's leaves the other's alone. */
+int ks_st_minres_set_check_interval(ks_st st, int c);                      /* 1..1024 (KS_ERR_ARG_OUTOFRANGE otherwise), default 8; count, solution and last_rnorm are the same bits for every c */
+int ks_st_minres_get_check_interval(ks_st st, int *c);
+int ks_st_minres_get_stats(ks_st st, long long *sweeps, long long *host_waits, long long *gated_iterations);
+/* PCJacobiSetUseAbs (-pc_jacobi_abs): with flag != 0 KS_PC_JACOBI scales by 1 / |diag(P)|, a positive definite M whatever the signs of the diagonal -
+   what MINRES needs on an indefinite P. A zero entry still leaves its row unscaled. Default off, and off gives the diagonal of earlier versions bit
+   for bit. The setter clears the set-up. No effect on the other PC types. */
+int ks_st_pc_jacobi_set_use_abs(ks_st st, int flag);
+int ks_st_pc_jacobi_get_use_abs(ks_st st, int *flag);
 /* KS_KSP_CG keeps its scalars on the device and switches itself off there once a solve has ended: the host enqueues c iterations, then reads the
    solver's state once. c: 1..1024 (KS_ERR_ARG_OUTOFRANGE otherwise), default 8; c = 1 is the classic loop with one host test per iteration. The
    iteration count, the solution and last_rnorm are the same bits for every c. */
@@ -801,7 +825,7 @@ int ks_st_pc_multi_columns(ks_st st, int *columns);   /* instrumentation: column
 /* STApplyMat stsolve.c:62: Y(:,j) = Op X(:,j). KS_ST_PRECOND: ks_st_pc_apply_multi; the other transformations: ks_st_apply column by column. Same arguments. */
 int ks_st_apply_mat(ks_st st, int ncols, const double *X_dev, int ldx, double *Y_dev, int ldy);
 int ks_st_backtransform(ks_st st, int n, double *eigr, double *eigi);     /* STBackTransform stsolve.c:563 */
-int ks_st_get_ksp_stats(ks_st st, long long *solves, long long *iterations, double *last_rnorm);   /* solves and iterations of every KSP type since the ST was created; last_rnorm: the preconditioned residual norm of the last solve */
+int ks_st_get_ksp_stats(ks_st st, long long *solves, long long *iterations, double *last_rnorm);   /* solves and iterations of every KSP type since the ST was created; last_rnorm: the preconditioned residual norm of the last solve (KS_KSP_MINRES: its phibar) */
 
 /* ---- profiling: HIP-event timing per kernel class, on the context's stream -------------------- */
 /* A class is one __global__ kernel template; `variant` is its compile-time column tile KT (0 when

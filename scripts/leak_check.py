@@ -39,6 +39,11 @@ def cycle(i):
     samg = ks.ST(ctx); samg.SetType("sinvert"); samg.SetShift(-0.3); samg.SetMatrices(Lk, Bk); samg.SetPC("amg"); samg.PCAMGSetCoarse(8, 10)
     samg.Apply(np.ones(Lo.n)); samg.SetShift(-0.2 - 0.01 * i); samg.PCApplyMulti(np.ones((Lo.n, 9))); samg.PCAMGSetSmoother(3); samg.PCAMGSetProlongatorSmoothing(False); samg.PCApply(np.ones(Lo.n))
     del samg
+    # MINRES on the same indefinite P with Jacobi-abs: state, pinned copy and work vectors set up, a solve, set up again by a new shift
+    smr = ks.ST(ctx); smr.SetType("sinvert"); smr.SetShift(1.3); smr.SetMatrices(Lk, Bk); smr.SetKSPType("minres"); smr.SetPC("jacobi"); smr.PCJacobiSetUseAbs(True)
+    smr.Apply(np.ones(Lo.n)); smr.SetShift(2.1 + 0.01 * i); smr.Apply(np.ones(Lo.n))
+    assert smr.GetMINRESStats()["sweeps"] > 0
+    del smr
     del slu, Lk, Bk
     V = ks.BV(ctx, 3000, 90); V.set_dense(np.random.default_rng(i).standard_normal((3000, 90)))
     V.SetOrthogBlock(["chol", "svqb", "gs", "tsqr"][i % 4])

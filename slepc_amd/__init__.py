@@ -815,7 +815,8 @@ class BV:
 
 class ST:
     """Spectral transformation (STSHIFT / STSINVERT / STCAYLEY / STPRECOND). Inner solves: GMRES + Jacobi by default; SetKSPType chooses BiCGStab,
-    PREONLY or, for a symmetric positive definite system, CG (CGSetCheckInterval, GetCGStats); SetPC the preconditioner."""
+    PREONLY or, for a symmetric positive definite system, CG (CGSetCheckInterval, GetCGStats), for a symmetric indefinite one MINRES
+    (MINRESSetCheckInterval, GetMINRESStats, PCJacobiSetUseAbs); SetPC the preconditioner."""
 
     def __init__(self, ctx, _handle=None):
         self.ctx = ctx
@@ -958,8 +959,31 @@ class ST:
 
     def SetKSPType(self, t):
         """KSPSetType on the ST's KSP: "gmres" (default), "bcgs", "preonly" (one application of the preconditioner: exact with SetPC("lu")), or "cg"
-        (conjugate gradients for a symmetric positive definite P and preconditioner; its scalars stay on the device, see CGSetCheckInterval)."""
-        _lib.check(self.ctx.L.ks_st_set_ksp_type(self.h, {"gmres": 0, "bcgs": 1, "preonly": 2, "cg": 4}.get(t, t)))
+        (conjugate gradients for a symmetric positive definite P and preconditioner; its scalars stay on the device, see CGSetCheckInterval), or
+        "minres" (symmetric P that may be indefinite, positive definite preconditioner - PCJacobiSetUseAbs -; device-resident like "cg")."""
+        _lib.check(self.ctx.L.ks_st_set_ksp_type(self.h, {"gmres": 0, "bcgs": 1, "preonly": 2, "cg": 4, "minres": 6}.get(t, t)))
+
+    def MINRESSetCheckInterval(self, c):
+        """Iterations of "minres" enqueued before the host reads the solver's state (1..1024, default 8). The count, the solution and the residual
+        norm do not depend on it. CG's interval is a setting of its own."""
+        _lib.check(self.ctx.L.ks_st_minres_set_check_interval(self.h, int(c)))
+
+    def MINRESGetCheckInterval(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_st_minres_get_check_interval(self.h, C.byref(v))); return v.value
+
+    def GetMINRESStats(self):
+        """Since the ST was created: sweeps (launches of the MINRES kernels), host_waits, gated_iterations, as GetCGStats."""
+        a, b, c = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        _lib.check(self.ctx.L.ks_st_minres_get_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"sweeps": a.value, "host_waits": b.value, "gated_iterations": c.value}
+
+    def PCJacobiSetUseAbs(self, flag=True):
+        """PCJacobiSetUseAbs: point Jacobi with 1 / |diag(P)|, positive definite whatever the signs of the diagonal (what "minres" needs on an
+        indefinite P). Default off."""
+        _lib.check(self.ctx.L.ks_st_pc_jacobi_set_use_abs(self.h, 1 if flag else 0))
+
+    def PCJacobiGetUseAbs(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_st_pc_jacobi_get_use_abs(self.h, C.byref(v))); return bool(v.value)
 
     def CGSetCheckInterval(self, c):
         """Iterations of "cg" enqueued before the host reads the solver's state (1..1024, default 8; 1: one host test per iteration). The count,

@@ -244,6 +244,11 @@ _SIG = {
     "ks_st_cg_set_check_interval": [vp, C.c_int],
     "ks_st_cg_get_check_interval": [vp, ip],
     "ks_st_cg_get_stats": [vp, llp, llp, llp],
+    "ks_st_minres_set_check_interval": [vp, C.c_int],
+    "ks_st_minres_get_check_interval": [vp, ip],
+    "ks_st_minres_get_stats": [vp, llp, llp, llp],
+    "ks_st_pc_jacobi_set_use_abs": [vp, C.c_int],
+    "ks_st_pc_jacobi_get_use_abs": [vp, ip],
     "ks_st_set_matmode": [vp, C.c_int],
     "ks_st_set_pc": [vp, C.c_int, C.c_int],
     "ks_st_set_gmres_cgs_refinement": [vp, C.c_int],

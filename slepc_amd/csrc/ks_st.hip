@@ -33,11 +33,12 @@ __global__ void k_lincomb(long long n, const double *__restrict__ s, double a, c
     out[i] = s ? s[i] * t : t;
   }
 }
-// d = 1 / (a*da + b*db), db NULL = identity; a zero diagonal entry leaves the row unscaled (PCJacobi does the same)
-__global__ void k_jacobi_setup(long long n, double a, const double *__restrict__ da, double b, const double *__restrict__ db, double *__restrict__ d)
+// d = 1 / (a*da + b*db), db NULL = identity; a zero diagonal entry leaves the row unscaled (PCJacobi does the same); use_abs: 1 / |a*da + b*db| (PCJacobiSetUseAbs)
+__global__ void k_jacobi_setup(long long n, double a, const double *__restrict__ da, double b, const double *__restrict__ db, double *__restrict__ d, int use_abs)
 {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const double t = (da ? a * da[i] : 0.0) + b * (db ? db[i] : 1.0);
+    double t = (da ? a * da[i] : 0.0) + b * (db ? db[i] : 1.0);
+    if (use_abs) t = fabs(t);
     d[i] = (t != 0.0) ? 1.0 / t : 1.0;
   }
 }
@@ -351,6 +352,7 @@ int inner_solve(ks_st st, const double *rhs, double *y, bool tr = false)
 {
   if (st->ksp_type == KS_KSP_PREONLY) return preonly_solve(st, rhs, y, tr);
   if (st->ksp_type == KS_KSP_CG) return ks_ksp_cg(st_ksp(st), st, tr, rhs, y);
+  if (st->ksp_type == KS_KSP_MINRES) return ks_ksp_minres(st_ksp(st), st, tr, rhs, y);
   return st->ksp_type == KS_KSP_BCGS ? bcgs_solve(st, rhs, y, tr) : gmres_solve(st, rhs, y, tr);
 }
 
@@ -511,29 +513,32 @@ int ks_st_setup_internal(ks_st st)
   if (need_solve || precond) {
     if (st->K && !need_solve) { ks_bv_destroy(st->K); st->K = nullptr; }
     if (st->K) { int km = 0; ks_bv_get_sizes(st->K, nullptr, nullptr, &km, nullptr); if (km != st->restart + 1) { ks_bv_destroy(st->K); st->K = nullptr; } }
-    if (st->K && (st->ksp_type == KS_KSP_PREONLY || st->ksp_type == KS_KSP_CG)) { ks_bv_destroy(st->K); st->K = nullptr; }      // KSPPREONLY and KSPCG keep no basis
-    if (need_solve && !st->K && st->ksp_type != KS_KSP_PREONLY && st->ksp_type != KS_KSP_CG) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, st->restart + 1, 0, &st->K)); st->K->row_start = A->row_start; }
+    const bool short_rec = st->ksp_type == KS_KSP_CG || st->ksp_type == KS_KSP_MINRES;
+    if (st->K && (st->ksp_type == KS_KSP_PREONLY || short_rec)) { ks_bv_destroy(st->K); st->K = nullptr; }      // KSPPREONLY, KSPCG and KSPMINRES keep no basis
+    if (need_solve && !st->K && st->ksp_type != KS_KSP_PREONLY && !short_rec) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, st->restart + 1, 0, &st->K)); st->K->row_start = A->row_start; }
     if (need_solve && st->K) KS_CALL(ks_bv_set_orthogonalization(st->K, KS_BV_ORTHOG_CGS, st->gmres_refine, 0.7071));      // KSPGMRESClassicalGramSchmidtOrthogonalization + refinement type
     if (need_solve && st->ksp_type == KS_KSP_CG) KS_CALL(ks_st_cg_alloc(st));
-    if (need_solve && (st->ksp_type == KS_KSP_BCGS || st->ksp_type == KS_KSP_CG) && !st->Kb) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 7, 0, &st->Kb)); st->Kb->row_start = A->row_start; }
+    if (need_solve && st->ksp_type == KS_KSP_MINRES) KS_CALL(ks_st_minres_alloc(st));
+    if (need_solve && (st->ksp_type == KS_KSP_BCGS || short_rec) && !st->Kb) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 7, 0, &st->Kb)); st->Kb->row_start = A->row_start; }
     if (!st->dinv) KS_HIP(hipMalloc(&st->dinv, sizeof(double) * std::max(A->n, 1)));
     // Jacobi: diag(P)
     double *da = ks_bv_col(st->W, 1), *db = ks_bv_col(st->W, 2);
     const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>(((long long)A->n + 255) / 256, (long long)ctx->num_cu * 16));
+    const int use_abs = st->jacobi_abs ? 1 : 0;
     if (st->matmode == KS_ST_MATMODE_COPY && (st->type == KS_ST_SINVERT || st->type == KS_ST_CAYLEY)) {
       // STMatMAXPY_Private, ST_MATMODE_COPY (stsolve.c:603-631): P = A - sigma B assembled (nmat = 1: MatShift); a zero shift takes A itself
       // there (:611-614) - here a copy of it, so that the ST owns what it destroys
       KS_CALL(ks_mat_create_axpy(A, -st->sigma, B, st->tsolves ? (unsigned)KS_MAT_KEEP_CSR : 0u, &st->Pmat));     // its transposed view needs its arrays
       if (st->tsolves) KS_CALL(ks_mat_create_transpose(st->Pmat, &st->PmatT));
       KS_CALL(ks_mat_get_diagonal_internal(st->Pmat, da));
-      hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 1.0, da, 0.0, (const double *)nullptr, st->dinv);
+      hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 1.0, da, 0.0, (const double *)nullptr, st->dinv, use_abs);
     } else if (st->type != KS_ST_SHIFT && !inf) {
       KS_CALL(ks_mat_get_diagonal_internal(A, da));
       if (B) KS_CALL(ks_mat_get_diagonal_internal(B, db));
-      hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 1.0, da, -st->sigma, B ? db : nullptr, st->dinv);
+      hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 1.0, da, -st->sigma, B ? db : nullptr, st->dinv, use_abs);
     } else if (B) {                                                    // shift with two matrices, or the infinite default shift: diag(B); one matrix there: nothing to build
       KS_CALL(ks_mat_get_diagonal_internal(B, db));
-      hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 0.0, (const double *)nullptr, 1.0, db, st->dinv);
+      hipLaunchKernelGGL(k_jacobi_setup, dim3(nb), dim3(256), 0, ctx->stream, (long long)A->n, 0.0, (const double *)nullptr, 1.0, db, st->dinv, use_abs);
     }
     KS_HIP(hipGetLastError());
     if (st->pc_type == KS_PC_BJACOBI && !st->pc_identity) KS_CALL(bjacobi_setup(st));
@@ -590,6 +595,7 @@ extern "C" int ks_st_destroy(ks_st st)
   if (st->binv) hipFree(st->binv);
   if (st->pcwork) hipFree(st->pcwork);
   ks_st_cg_free(st);
+  ks_st_minres_free(st);
   ks_pc_ilu_free(st->ilu);
   ks_pc_lu_free(st->lu);
   ks_pc_amg_free(st->amg);
@@ -643,10 +649,10 @@ extern "C" int ks_st_set_ksp(ks_st st, double rtol, int max_it, int restart)   /
   if (restart > 0 && restart != st->restart) { st->restart = restart; st->ready = false; }   // a basis wider than 64 columns orthogonalises through the host-driven loop
   return KS_SUCCESS;
 }
-extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType on STGetKSP: KSPGMRES (default), KSPBCGS, KSPPREONLY or KSPCG
+extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType on STGetKSP: KSPGMRES (default), KSPBCGS, KSPPREONLY, KSPCG or KSPMINRES
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  KS_CHECK(type == KS_KSP_GMRES || type == KS_KSP_BCGS || type == KS_KSP_PREONLY || type == KS_KSP_CG, KS_ERR_SUP, "only KSPGMRES, KSPBCGS, KSPPREONLY and KSPCG are built");
+  KS_CHECK(type == KS_KSP_GMRES || type == KS_KSP_BCGS || type == KS_KSP_PREONLY || type == KS_KSP_CG || type == KS_KSP_MINRES, KS_ERR_SUP, "only KSPGMRES, KSPBCGS, KSPPREONLY, KSPCG and KSPMINRES are built");
   if (st->ksp_type != type) { st->ksp_type = type; st->ready = false; }
   st->ksp_type_set = true;
   return KS_SUCCESS;
@@ -665,7 +671,28 @@ extern "C" int ks_st_cg_get_stats(ks_st st, long long *sweeps, long long *host_w
   if (sweeps) *sweeps = st->cg_sweeps; if (host_waits) *host_waits = st->cg_waits; if (gated_iterations) *gated_iterations = st->cg_gated;
   return KS_SUCCESS;
 }
-extern "C" int ks_st_set_pc(ks_st st, int type, int block_size)       // PCSetType (+ PCBJacobiSetLocalBlocks, -sub_pc_type lu | ilu) on the KSP's PC
+extern "C" int ks_st_minres_set_check_interval(ks_st st, int c)
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  KS_CHECK(c >= 1 && c <= 1024, KS_ERR_ARG_OUTOFRANGE, "check interval %d (1..1024)", c);
+  st->mr_check = c;
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_minres_get_check_interval(ks_st st, int *c) { KS_CHECK(st && c, KS_ERR_ARG_NULL, "NULL argument"); *c = st->mr_check; return KS_SUCCESS; }
+extern "C" int ks_st_minres_get_stats(ks_st st, long long *sweeps, long long *host_waits, long long *gated_iterations)
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  if (sweeps) *sweeps = st->mr_sweeps; if (host_waits) *host_waits = st->mr_waits; if (gated_iterations) *gated_iterations = st->mr_gated;
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_jacobi_set_use_abs(ks_st st, int flag)        // PCJacobiSetUseAbs on the KSP's PC; the diagonal is rebuilt at the next set-up
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  st->jacobi_abs = flag != 0; st->ready = false;
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_pc_jacobi_get_use_abs(ks_st st, int *flag) { KS_CHECK(st && flag, KS_ERR_ARG_NULL, "NULL argument"); *flag = st->jacobi_abs ? 1 : 0; return KS_SUCCESS; }
+extern "C" int ks_st_set_pc(ks_st st, int type, int block_size)      // PCSetType (+ PCBJacobiSetLocalBlocks, -sub_pc_type lu | ilu) on the KSP's PC
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
   KS_CHECK(type == KS_PC_JACOBI || type == KS_PC_BJACOBI || type == KS_PC_BJACOBI_ILU || type == KS_PC_NONE || type == KS_PC_LU || type == KS_PC_AMG, KS_ERR_SUP, "only PCNONE, PCJACOBI, PCBJACOBI (sub-solves: LU on dense blocks, or ILU(0)), PCLU and PCGAMG are built");

@@ -318,14 +318,18 @@ struct ks_st_s {
   ks_mat bil = nullptr;                       // STCAYLEY: shell matrix A + nu B, the bilinear form of symmetric problems (cayley.c:70-77)
   ks_mat A = nullptr, B = nullptr;            // borrowed
   double rtol = 1e-8; int max_it = 10000, restart = 30;   // KSP: SLEPC_DEFAULT_TOL (stsles.c:407), PETSc defaults
-  int ksp_type = KS_KSP_GMRES;                // KSPGMRES (the default of the shell matrix mode), KSPBCGS, KSPPREONLY or KSPCG
+  int ksp_type = KS_KSP_GMRES;                // KSPGMRES (the default of the shell matrix mode), KSPBCGS, KSPPREONLY, KSPCG or KSPMINRES
   bool ksp_type_set = false, rtol_set = false, max_it_set = false;   // chosen by the caller (ks_st_set_ksp_type, ks_st_set_ksp): a solver with KSP defaults of its own (JD) keeps off those
   int gmres_refine = KS_BV_ORTHOG_REFINE_NEVER;   // KSPGMRESSetCGSRefinementType: PETSc's default is classical Gram-Schmidt without refinement
-  ks_bv Kb = nullptr;                         // BiCGStab work vectors (7 columns); CG's r, z, p, w are its first four
+  ks_bv Kb = nullptr;                         // BiCGStab work vectors (7 columns); CG's r, z, p, w are its first four, MINRES takes all seven
   // KS_KSP_CG (ks_cg.hip): iterations enqueued per host read of the state; the device scratch (KsCgState, the ranks' sums, the sweeps' partials) and the
   // pinned copy the host reads; launches of the solver's own kernels, host reads, iterations that found the solve ended (ks_st_cg_get_stats)
   int cg_check = 8; char *cg_dev = nullptr; struct KsCgState *cg_host = nullptr;
   long long cg_sweeps = 0, cg_waits = 0, cg_gated = 0;
+  // KS_KSP_MINRES (ks_minres.hip): the same five of its own (ks_st_minres_set_check_interval, ks_st_minres_get_stats); its seven work vectors are Kb's columns
+  int mr_check = 8; char *mr_dev = nullptr; struct KsMinresState *mr_host = nullptr;
+  long long mr_sweeps = 0, mr_waits = 0, mr_gated = 0;
+  bool jacobi_abs = false;                    // PCJacobiSetUseAbs: KS_PC_JACOBI scales by 1 / |diag(P)| (a positive definite M for MINRES on an indefinite P)
   ks_bv K = nullptr, W = nullptr;             // GMRES basis (restart+1 columns), work vectors (3 columns)
   double *dinv = nullptr;                     // Jacobi: 1/diag(P)
   int pc_type = KS_PC_JACOBI, pc_bs = 0;      // PCSetType on the KSP's PC: point Jacobi, or block Jacobi (dense inverses or ILU(0) factors) with blocks of pc_bs consecutive local rows
@@ -375,6 +379,15 @@ int ks_st_cg_alloc(ks_st st);
 void ks_st_cg_free(ks_st st);
 // w = P p but for one term: *v non-NULL on return means w += (*b) (*v) is still to be done (P applied term by term; the (p,w) sweep adds it). tmp: W(:,1)
 int ks_st_cg_product(ks_st st, bool tr, const double *p, double *w, const double **v, double *b);
+// MINRES (ks_minres.hip), the second tenant of that design. Its state block: rot[] is double-buffered by the parity of the iteration (iteration i reads
+// rot[i & 1], its update sweep writes rot[(i + 1) & 1]); done: ended without vector work, conv: ended after the update's vector work (see the file's head)
+enum { KS_MINRES_CONVERGED = 1, KS_MINRES_ITS = 2, KS_MINRES_INDEFINITE_PC = 3, KS_MINRES_NAN = 4 };
+struct KsMinresRot { double cs, sn, dbar, epsln, phibar, beta; };
+struct KsMinresState { KsMinresRot rot[2]; double alfa, bz, beta1, tol; int its, done, conv, reason; long long gated; };
+constexpr size_t KS_MINRES_STATE_BYTES = 256;    // the state and the two sums of the ranks; the partials follow
+int ks_ksp_minres(const KsKsp &k, ks_st st, bool tr, const double *rhs, double *y);
+int ks_st_minres_alloc(ks_st st);
+void ks_st_minres_free(ks_st st);
 int ks_st_blocks_apply(ks_st st, const double *in, double *out, bool tr);      // out = M^-1 in for the preconditioners with kernels of their own
 bool ks_st_pc_pointwise(ks_st st, const double **dinv);   // set-up done. true: no preconditioner (*dinv NULL) or point Jacobi (*dinv its diagonal); false: blocks (ks_st_pc_apply_multi_internal)
 int ksk_lincomb(ks_ctx ctx, long long n, const double *s, double a, const double *u, double b, const double *v, double *out);   // out = s.*(a*u + b*v)   // diagonal of the local diagonal block (MatGetDiagonal)
