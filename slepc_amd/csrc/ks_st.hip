@@ -329,8 +329,8 @@ int ks_ksp_preonly(const KsKsp &k, KsKspOp &op, const double *rhs, double *y)
   return op.residual(rhs, nullptr, y);
 }
 
-// the product of a CG iteration: the calls of apply_P without the combining sweep of a P with two terms, which the (p,w) sweep does (ks_cg.hip)
-int ks_st_cg_product(ks_st st, bool tr, const double *p, double *w, const double **v, double *b)
+// the product of a CG or MINRES iteration: the calls of apply_P without the combining sweep of a P with two terms, which the solver's next sweep does
+int ks_st_product_one_term_left(ks_st st, bool tr, const double *p, double *w, const double **v, double *b)
 {
   ks_mat Pm = tr ? st->PmatT : st->Pmat, A = tr ? st->At : st->A, B = tr ? st->Bt : st->B;
   *v = nullptr; *b = 0.0;
@@ -343,6 +343,20 @@ int ks_st_cg_product(ks_st st, bool tr, const double *p, double *w, const double
   return KS_SUCCESS;
 }
 int ks_st_blocks_apply(ks_st st, const double *in, double *out, bool tr) { return blocks_apply(st, in, out, tr); }
+int ks_resident_alloc(KsResident *r)
+{
+  if (r->dev && r->host) return KS_SUCCESS;
+  ks_resident_free(r);                                                              // an earlier call that got only the device half: begin again
+  KS_HIP(hipMalloc(&r->dev, KS_RESIDENT_HEAD_BYTES + sizeof(double) * 3 * (size_t)KS_MAX_BLOCKS));
+  KS_HIP(hipHostMalloc(&r->host, KS_RESIDENT_HEAD_BYTES, hipHostMallocDefault));
+  return KS_SUCCESS;
+}
+void ks_resident_free(KsResident *r)
+{
+  if (r->dev) hipFree(r->dev);
+  if (r->host) hipHostFree(r->host);
+  r->dev = nullptr; r->host = nullptr;
+}
 
 namespace {
 int gmres_solve(ks_st st, const double *rhs, double *y, bool tr) { StKspOp op(st, tr); return ks_ksp_gmres(st_ksp(st), op, rhs, y); }
@@ -517,8 +531,8 @@ int ks_st_setup_internal(ks_st st)
     if (st->K && (st->ksp_type == KS_KSP_PREONLY || short_rec)) { ks_bv_destroy(st->K); st->K = nullptr; }      // KSPPREONLY, KSPCG and KSPMINRES keep no basis
     if (need_solve && !st->K && st->ksp_type != KS_KSP_PREONLY && !short_rec) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, st->restart + 1, 0, &st->K)); st->K->row_start = A->row_start; }
     if (need_solve && st->K) KS_CALL(ks_bv_set_orthogonalization(st->K, KS_BV_ORTHOG_CGS, st->gmres_refine, 0.7071));      // KSPGMRESClassicalGramSchmidtOrthogonalization + refinement type
-    if (need_solve && st->ksp_type == KS_KSP_CG) KS_CALL(ks_st_cg_alloc(st));
-    if (need_solve && st->ksp_type == KS_KSP_MINRES) KS_CALL(ks_st_minres_alloc(st));
+    if (need_solve && st->ksp_type == KS_KSP_CG) KS_CALL(ks_resident_alloc(&st->cg));
+    if (need_solve && st->ksp_type == KS_KSP_MINRES) KS_CALL(ks_resident_alloc(&st->mr));
     if (need_solve && (st->ksp_type == KS_KSP_BCGS || short_rec) && !st->Kb) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 7, 0, &st->Kb)); st->Kb->row_start = A->row_start; }
     if (!st->dinv) KS_HIP(hipMalloc(&st->dinv, sizeof(double) * std::max(A->n, 1)));
     // Jacobi: diag(P)
@@ -594,8 +608,8 @@ extern "C" int ks_st_destroy(ks_st st)
   if (st->Pmat) ks_mat_destroy(st->Pmat);
   if (st->binv) hipFree(st->binv);
   if (st->pcwork) hipFree(st->pcwork);
-  ks_st_cg_free(st);
-  ks_st_minres_free(st);
+  ks_resident_free(&st->cg);
+  ks_resident_free(&st->mr);
   ks_pc_ilu_free(st->ilu);
   ks_pc_lu_free(st->lu);
   ks_pc_amg_free(st->amg);
@@ -657,34 +671,28 @@ extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType
   st->ksp_type_set = true;
   return KS_SUCCESS;
 }
-extern "C" int ks_st_cg_set_check_interval(ks_st st, int c)
+// the check interval and the statistics of the two device-resident solvers: which: the ST's cg or mr
+static int resident_set_check(ks_st st, KsResident ks_st_s::*which, int c)
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
   KS_CHECK(c >= 1 && c <= 1024, KS_ERR_ARG_OUTOFRANGE, "check interval %d (1..1024)", c);
-  st->cg_check = c;
+  (st->*which).check = c;
   return KS_SUCCESS;
 }
-extern "C" int ks_st_cg_get_check_interval(ks_st st, int *c) { KS_CHECK(st && c, KS_ERR_ARG_NULL, "NULL argument"); *c = st->cg_check; return KS_SUCCESS; }
-extern "C" int ks_st_cg_get_stats(ks_st st, long long *sweeps, long long *host_waits, long long *gated_iterations)
+static int resident_get_check(ks_st st, KsResident ks_st_s::*which, int *c) { KS_CHECK(st && c, KS_ERR_ARG_NULL, "NULL argument"); *c = (st->*which).check; return KS_SUCCESS; }
+static int resident_get_stats(ks_st st, KsResident ks_st_s::*which, long long *sweeps, long long *host_waits, long long *gated_iterations)
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  if (sweeps) *sweeps = st->cg_sweeps; if (host_waits) *host_waits = st->cg_waits; if (gated_iterations) *gated_iterations = st->cg_gated;
+  const KsResident &r = st->*which;
+  if (sweeps) *sweeps = r.sweeps; if (host_waits) *host_waits = r.waits; if (gated_iterations) *gated_iterations = r.gated;
   return KS_SUCCESS;
 }
-extern "C" int ks_st_minres_set_check_interval(ks_st st, int c)
-{
-  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  KS_CHECK(c >= 1 && c <= 1024, KS_ERR_ARG_OUTOFRANGE, "check interval %d (1..1024)", c);
-  st->mr_check = c;
-  return KS_SUCCESS;
-}
-extern "C" int ks_st_minres_get_check_interval(ks_st st, int *c) { KS_CHECK(st && c, KS_ERR_ARG_NULL, "NULL argument"); *c = st->mr_check; return KS_SUCCESS; }
-extern "C" int ks_st_minres_get_stats(ks_st st, long long *sweeps, long long *host_waits, long long *gated_iterations)
-{
-  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  if (sweeps) *sweeps = st->mr_sweeps; if (host_waits) *host_waits = st->mr_waits; if (gated_iterations) *gated_iterations = st->mr_gated;
-  return KS_SUCCESS;
-}
+extern "C" int ks_st_cg_set_check_interval(ks_st st, int c) { return resident_set_check(st, &ks_st_s::cg, c); }
+extern "C" int ks_st_cg_get_check_interval(ks_st st, int *c) { return resident_get_check(st, &ks_st_s::cg, c); }
+extern "C" int ks_st_cg_get_stats(ks_st st, long long *sweeps, long long *waits, long long *gated) { return resident_get_stats(st, &ks_st_s::cg, sweeps, waits, gated); }
+extern "C" int ks_st_minres_set_check_interval(ks_st st, int c) { return resident_set_check(st, &ks_st_s::mr, c); }
+extern "C" int ks_st_minres_get_check_interval(ks_st st, int *c) { return resident_get_check(st, &ks_st_s::mr, c); }
+extern "C" int ks_st_minres_get_stats(ks_st st, long long *sweeps, long long *waits, long long *gated) { return resident_get_stats(st, &ks_st_s::mr, sweeps, waits, gated); }
 extern "C" int ks_st_pc_jacobi_set_use_abs(ks_st st, int flag)        // PCJacobiSetUseAbs on the KSP's PC; the diagonal is rebuilt at the next set-up
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");

@@ -306,6 +306,13 @@ void ks_pc_amg_info(const KsAmg *p, KsAmgInfo *out);
 int ks_pc_amg_level(const KsAmg *p, int level, int *n, int *nagg, const int **arp, const int **acol, const double **aval, const int **prp, const int **pcol, const double **pval, const int **agg);
 void ks_pc_amg_free(KsAmg *p);
 
+// A solver of the ST whose scalars stay on the device (ks_ksp_resident.cuh). Its state block begins with this head: iterations done, the two flags of
+// the end of the solve (done: ended without vector work, conv: ended after a sweep's vector work), why it ended, iterations that found it ended
+struct KsKspHead { int its, done, conv, reason; long long gated; };
+// What the ST keeps of such a solver: iterations enqueued per host read of the state; the device scratch and the pinned copy the host reads; launches of
+// the solver's own kernels, host reads, iterations that found the solve ended (the get_stats triple)
+struct KsResident { int check = 8; char *dev = nullptr; void *host = nullptr; long long sweeps = 0, waits = 0, gated = 0; };
+constexpr size_t KS_RESIDENT_HEAD_BYTES = 256;   // the state and up to four sums of the ranks; three partials arrays follow
 // ---- ST: spectral transformation (ks_st.hip) ----------------------------------------------------
 struct ks_st_s {
   ks_ctx ctx = nullptr;
@@ -322,13 +329,8 @@ struct ks_st_s {
   bool ksp_type_set = false, rtol_set = false, max_it_set = false;   // chosen by the caller (ks_st_set_ksp_type, ks_st_set_ksp): a solver with KSP defaults of its own (JD) keeps off those
   int gmres_refine = KS_BV_ORTHOG_REFINE_NEVER;   // KSPGMRESSetCGSRefinementType: PETSc's default is classical Gram-Schmidt without refinement
   ks_bv Kb = nullptr;                         // BiCGStab work vectors (7 columns); CG's r, z, p, w are its first four, MINRES takes all seven
-  // KS_KSP_CG (ks_cg.hip): iterations enqueued per host read of the state; the device scratch (KsCgState, the ranks' sums, the sweeps' partials) and the
-  // pinned copy the host reads; launches of the solver's own kernels, host reads, iterations that found the solve ended (ks_st_cg_get_stats)
-  int cg_check = 8; char *cg_dev = nullptr; struct KsCgState *cg_host = nullptr;
-  long long cg_sweeps = 0, cg_waits = 0, cg_gated = 0;
-  // KS_KSP_MINRES (ks_minres.hip): the same five of its own (ks_st_minres_set_check_interval, ks_st_minres_get_stats); its seven work vectors are Kb's columns
-  int mr_check = 8; char *mr_dev = nullptr; struct KsMinresState *mr_host = nullptr;
-  long long mr_sweeps = 0, mr_waits = 0, mr_gated = 0;
+  // KS_KSP_CG and KS_KSP_MINRES, each with a check interval and statistics of its own (ks_st_cg_*, ks_st_minres_*); their work vectors are Kb's columns
+  KsResident cg, mr;
   bool jacobi_abs = false;                    // PCJacobiSetUseAbs: KS_PC_JACOBI scales by 1 / |diag(P)| (a positive definite M for MINRES on an indefinite P)
   ks_bv K = nullptr, W = nullptr;             // GMRES basis (restart+1 columns), work vectors (3 columns)
   double *dinv = nullptr;                     // Jacobi: 1/diag(P)
@@ -369,25 +371,15 @@ struct KsKsp { ks_ctx ctx; long long n; ks_bv K, Kb; double rtol; int max_it, re
 int ks_ksp_gmres(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);
 int ks_ksp_bcgs(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);
 int ks_ksp_preonly(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);     // KSPPREONLY: y = M^-1 rhs, one application, no residual, no test; K and Kb are not used
-// CG (ks_cg.hip) takes P and M^-1 apart, which KsKspOp does not offer: its own entry on the ST, tr: the transposed side. Its state block on the device:
-// written by thread 0 of workgroup 0 of the direction and update sweeps, read by every workgroup of the sweeps behind them and, once per batch, by the host
-enum { KS_CG_CONVERGED = 1, KS_CG_ITS = 2, KS_CG_INDEFINITE_MAT = 3, KS_CG_INDEFINITE_PC = 4, KS_CG_NAN = 5 };
-struct KsCgState { double gamma, gamma_old, delta, dp, tol; int its, done, reason; long long gated; };
-constexpr size_t KS_CG_STATE_BYTES = 256;    // the state and the four sums of the ranks; the partials follow
+// CG (ks_cg.hip) and MINRES (ks_minres.hip) take P and M^-1 apart, which KsKspOp does not offer: their own entries on the ST, tr: the transposed side.
+// Both keep their scalars on the device (ks_ksp_resident.cuh); the reasons a solve ends with are the solver's own, 1 being converged
 int ks_ksp_cg(const KsKsp &k, ks_st st, bool tr, const double *rhs, double *y);
-int ks_st_cg_alloc(ks_st st);
-void ks_st_cg_free(ks_st st);
-// w = P p but for one term: *v non-NULL on return means w += (*b) (*v) is still to be done (P applied term by term; the (p,w) sweep adds it). tmp: W(:,1)
-int ks_st_cg_product(ks_st st, bool tr, const double *p, double *w, const double **v, double *b);
-// MINRES (ks_minres.hip), the second tenant of that design. Its state block: rot[] is double-buffered by the parity of the iteration (iteration i reads
-// rot[i & 1], its update sweep writes rot[(i + 1) & 1]); done: ended without vector work, conv: ended after the update's vector work (see the file's head)
-enum { KS_MINRES_CONVERGED = 1, KS_MINRES_ITS = 2, KS_MINRES_INDEFINITE_PC = 3, KS_MINRES_NAN = 4 };
-struct KsMinresRot { double cs, sn, dbar, epsln, phibar, beta; };
-struct KsMinresState { KsMinresRot rot[2]; double alfa, bz, beta1, tol; int its, done, conv, reason; long long gated; };
-constexpr size_t KS_MINRES_STATE_BYTES = 256;    // the state and the two sums of the ranks; the partials follow
 int ks_ksp_minres(const KsKsp &k, ks_st st, bool tr, const double *rhs, double *y);
-int ks_st_minres_alloc(ks_st st);
-void ks_st_minres_free(ks_st st);
+// the device scratch of such a solver (its state, the ranks' sums, the sweeps' partials) and the pinned copy of the state the host reads
+int ks_resident_alloc(KsResident *r);
+void ks_resident_free(KsResident *r);
+// w = P p but for one term: *v non-NULL on return means w += (*b) (*v) is still to be done (P applied term by term; the sweep behind the product adds it: k_cg_pw, k_minres_alfa). tmp: W(:,1)
+int ks_st_product_one_term_left(ks_st st, bool tr, const double *p, double *w, const double **v, double *b);
 int ks_st_blocks_apply(ks_st st, const double *in, double *out, bool tr);      // out = M^-1 in for the preconditioners with kernels of their own
 bool ks_st_pc_pointwise(ks_st st, const double **dinv);   // set-up done. true: no preconditioner (*dinv NULL) or point Jacobi (*dinv its diagonal); false: blocks (ks_st_pc_apply_multi_internal)
 int ksk_lincomb(ks_ctx ctx, long long n, const double *s, double a, const double *u, double b, const double *v, double *out);   // out = s.*(a*u + b*v)   // diagonal of the local diagonal block (MatGetDiagonal)

@@ -27,6 +27,8 @@ LAP = [(0, 1.5), (1, 1.1), (0, 0.9)]
 # (index into LAP, pc) whose count is exact (tests/test_minres_cases_host.py): all but LAP[1] without a preconditioner, which fails the rule there
 LAP_COUNTS = [(0, "none"), (0, "jacobi-abs"), (1, "jacobi-abs"), (2, "none"), (2, "jacobi-abs")]
 LAP_ALL = LAP_COUNTS + [(1, "none")]
+# LAP[0] under block Jacobi with dense blocks of 8 rows: the count is exact at the widest step above this floor (tests/test_minres_cases_host.py)
+BJACOBI_BLOCK, BJACOBI_FLOOR = 8, 1e-7
 
 
 def minres_reference(P, b, minv=None, rtol=1e-8, max_it=10000, perm=None):
@@ -105,6 +107,13 @@ def jacobi_abs(P):
     return lambda r: d * r
 
 
+def block_jacobi(P, bs):
+    """Block Jacobi with dense blocks (KS_PC_BJACOBI): the exact inverses of the diagonal blocks of bs consecutive rows."""
+    D = P.toarray()
+    inv = [np.linalg.inv(D[i:i + bs, i:i + bs]) for i in range(0, D.shape[0], bs)]
+    return lambda r: np.concatenate([m @ r[j * bs:j * bs + len(m)] for j, m in enumerate(inv)])
+
+
 def minv_of(P, pc):
     return jacobi_abs(P) if pc == "jacobi-abs" else None
 
@@ -129,16 +138,16 @@ def kron_reference(m, blocks, pc):
     return case, minres_reference(case.P, case.b, minv_of(case.P, pc), rtol=1e-8)
 
 
-def pick_k(hist):
-    """The step k with the largest ratio h[k-1] / h[k] among those with 1e-10 < h[k] < 1e-5; the tolerance is the geometric mean of the two.
+def pick_k(hist, lo=1e-10):
+    """The step k with the largest ratio h[k-1] / h[k] among those with lo < h[k] < 1e-5; the tolerance is the geometric mean of the two.
     Returns (k, rtol, ratio)."""
     best = None
     for k in range(1, len(hist)):
-        if 1e-10 < hist[k] < 1e-5:
+        if lo < hist[k] < 1e-5:
             ratio = hist[k - 1] / hist[k]
             if best is None or ratio > best[2]:
                 best = (k, float(np.sqrt(hist[k - 1] * hist[k])), float(ratio))
-    assert best is not None, "the history does not pass through (1e-10, 1e-5)"
+    assert best is not None, "the history does not pass through (%g, 1e-5)" % lo
     return best
 
 

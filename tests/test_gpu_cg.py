@@ -131,6 +131,56 @@ def test_block_preconditioners(ctx, pc, block):
         assert stats["iterations"] <= cc.cg_reference(case.P, case.b, cc.jacobi(case.P), rtol=1e-8).its
 
 
+# ---- 3b: a misaligned solution vector ---------------------------------------------------------------------------------------------------------------
+def _apply_unaligned(ctx, st, b):
+    """st.Apply(b) with y eight bytes past a 16-byte boundary, in a BV of n + 1 rows; the row in front of y is checked untouched"""
+    import ctypes as C
+    import slepc_amd as ks
+    n = len(b)
+    W = ks.BV(ctx, n + 1, 2)
+    W.set_column(0, np.concatenate([b, [0.0]])); W.set_column(1, np.full(n + 1, 7.0))
+    assert W.column_ptr(1) % 16 == 0
+    ks._lib.check(ctx.L.ks_st_apply(st.h, C.c_void_p(W.column_ptr(0)), C.c_void_p(W.column_ptr(1) + 8)))
+    full = W.column(1)
+    assert full[0] == 7.0
+    return full[1:]
+
+
+UNALIGNED = [("kron", pc, mode) for pc in ("jacobi", "none") for mode in ("shell", "copy")] + [("lap", "jacobi", "shell"), ("lap", "bjacobi", "shell")]
+
+
+@pytest.mark.parametrize("which,pc,mode", UNALIGNED)
+def test_unaligned_solution_vector_takes_the_one_row_sweeps(ctx, which, pc, mode):
+    """y eight bytes past a 16-byte boundary: every sweep runs its one-row-per-lane form. Counts and bounds of the aligned tests. kron: n = 513, two
+    tiles of the one-row form and a row; lap with Jacobi at sigma = -0.5 in shell mode: the combining (p,w) sweep; lap with blocks of 8: the update
+    that ends after r and the dot sweep. M^-1 of that restatement and of the residual is ST.PCApply, as in test_block_preconditioners; its count of
+    17 is exact too: the history passes 1e-8 between 2.89e-8 and 9.59e-9, 4 % below the tolerance, where the pair form and the one-row form of the
+    device differ in the thirteenth digit."""
+    if pc == "bjacobi":
+        case = cc.lap(*cc.LAP[0]); P = case.P
+        st = _sinvert(ctx, case, 0.0, pc, block=8)
+        st.SetUp()
+        minv = st.PCApply
+        ref = cc.cg_reference(P, case.b, minv, rtol=1e-8)
+        assert ref.reason == "converged" and ref.its == 17 and ref.hist[16] > 2e-8 and ref.hist[17] < 0.97e-8
+    elif which == "lap":
+        case, P, rtol, ref, _ = cc.lap_reference(0, pc, -0.5, 1e-8)
+        st = _sinvert(ctx, case, -0.5, pc, mode, rtol=rtol)
+        minv = cc.jacobi(P)
+    else:
+        case, ref = cc.kron_reference(3, pc); P = case.P
+        assert case.n == 513
+        st = _sinvert(ctx, case, 0.0, pc, mode)
+        minv = cc.jacobi(P) if pc == "jacobi" else (lambda r: r)
+    y = _apply_unaligned(ctx, st, case.b)
+    stats = st.GetKSPStats()
+    res = float(np.linalg.norm(minv(case.b - P @ y)))
+    print("its %d (reference %d), last_rnorm %.3e, tol %.3e, true residual %.3e, gap %.2e" % (stats["iterations"], ref.its, stats["last_rnorm"], ref.tol, res, ref.gap))
+    assert stats["solves"] == 1 and stats["iterations"] == ref.its
+    assert stats["last_rnorm"] <= ref.tol
+    assert res <= ref.tol + 8 * ref.gap
+
+
 # ---- 4: the other transformations -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind,sigma", [("shift", 0.3), ("cayley", -0.7)])
 @pytest.mark.parametrize("mode", ["shell", "copy"])

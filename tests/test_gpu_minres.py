@@ -128,25 +128,59 @@ def test_interval_defaults_and_range_checks(ctx):
     assert st.PCJacobiGetUseAbs() is True
 
 
-def test_unaligned_solution_vector_takes_the_one_row_sweeps(ctx):
-    """y eight bytes past a 16-byte boundary: every sweep runs its one-row-per-lane form. Count and bounds of the aligned run."""
+def _apply_unaligned(ctx, st, b):
+    """st.Apply(b) with y eight bytes past a 16-byte boundary, in a BV of n + 1 rows; the row in front of y is checked untouched"""
     import ctypes as C
     import slepc_amd as ks
+    n = len(b)
+    W = ks.BV(ctx, n + 1, 2)
+    W.set_column(0, np.concatenate([b, [0.0]])); W.set_column(1, np.full(n + 1, 7.0))
+    assert W.column_ptr(1) % 16 == 0
+    ks._lib.check(ctx.L.ks_st_apply(st.h, C.c_void_p(W.column_ptr(0)), C.c_void_p(W.column_ptr(1) + 8)))
+    full = W.column(1)
+    assert full[0] == 7.0
+    return full[1:]
+
+
+def test_unaligned_solution_vector_takes_the_one_row_sweeps(ctx):
+    """y eight bytes past a 16-byte boundary: every sweep runs its one-row-per-lane form. Counts and bounds of the aligned runs. Jacobi-abs: lanczos with
+    the diagonal; none (n = 513: two tiles of the one-row form and a row): lanczos on the residual itself; LAP[0] at its shift in shell mode: the
+    combining alfa sweep; blocks of 8: lanczos ends after the residual, the dot sweep follows. M^-1 of that restatement is ST.PCApply, as in the
+    aligned test; at its rtol of 1e-8 rounding moves the count (101 to 106 with permuted dots), so the tolerance sits in the widest step of the history above 1e-7,
+    k = 87, which tests/test_minres_cases_host.py pins."""
     case, ref = mc.kron_reference(7, 151, "jacobi-abs")
     for mode in ("shell", "copy"):
         st = _sinvert(ctx, case.P, 0.0, "jacobi-abs", mode)
-        W = ks.BV(ctx, case.n + 1, 2)
-        W.set_column(0, np.concatenate([case.b, [0.0]])); W.set_column(1, np.full(case.n + 1, 7.0))
-        assert W.column_ptr(1) % 16 == 0
-        ks._lib.check(ctx.L.ks_st_apply(st.h, C.c_void_p(W.column_ptr(0)), C.c_void_p(W.column_ptr(1) + 8)))
-        full = W.column(1)
-        y = full[1:]
-        assert full[0] == 7.0                                                        # the row in front of y is not touched
+        y = _apply_unaligned(ctx, st, case.b)
         stats = st.GetKSPStats()
         minv = mc.minv_of(case.P, "jacobi-abs")
         assert stats["iterations"] == ref.its and stats["last_rnorm"] <= ref.tol
         assert mc.mnorm(minv, case.b - case.P @ y) <= ref.tol + 8 * ref.gap
         assert mc.mnorm(minv, case.P @ (y - ref.y)) <= ref.tol + 8 * ref.gap
+    case, ref = mc.kron_reference(9, 57, "none")
+    lcase, lP, lrtol, lref, _, _ = mc.lap_reference(0, "jacobi-abs")
+    for A, sigma, P, b, pc, rtol, r in [(case.P, 0.0, case.P, case.b, "none", 1e-8, ref), (lcase.P, mc.LAP[0][1], lP, lcase.b, "jacobi-abs", lrtol, lref)]:
+        st = _sinvert(ctx, A, sigma, pc, "shell", rtol=rtol)
+        y = _apply_unaligned(ctx, st, b)
+        stats = st.GetKSPStats()
+        minv = mc.minv_of(P, pc)
+        print("%s n %d: its %d (restatement %d), last_rnorm %.3e, tol %.3e" % (pc, len(b), stats["iterations"], r.its, stats["last_rnorm"], r.tol))
+        assert stats["iterations"] == r.its and stats["last_rnorm"] <= r.tol
+        assert mc.mnorm(minv, b - P @ y) <= r.tol + 8 * r.gap
+        assert mc.mnorm(minv, P @ (y - r.y)) <= r.tol + 8 * r.gap
+    st = _sinvert(ctx, lcase.P, mc.LAP[0][1], "bjacobi", block=mc.BJACOBI_BLOCK)
+    st.SetUp()
+    k, brtol, ratio = mc.pick_k(mc.minres_reference(lP, lcase.b, st.PCApply, rtol=1e-12).hist, mc.BJACOBI_FLOOR)
+    bref = mc.minres_reference(lP, lcase.b, st.PCApply, rtol=brtol)
+    assert bref.reason == "converged" and bref.its == k == 87 and ratio >= 1.4
+    st.SetKSP(rtol=brtol)
+    y = _apply_unaligned(ctx, st, lcase.b)
+    stats = st.GetKSPStats()
+    res, diff = mc.mnorm(st.PCApply, lcase.b - lP @ y), mc.mnorm(st.PCApply, lP @ (y - bref.y))
+    print("bjacobi: its %d (restatement %d), last_rnorm %.3e, tol %.3e, true residual %.3e, P (y - y_ref) %.3e, gap %.2e" % (stats["iterations"], bref.its, stats["last_rnorm"], bref.tol, res, diff, bref.gap))
+    assert stats["solves"] == 1 and stats["iterations"] == bref.its and stats["last_rnorm"] <= bref.tol
+    assert res <= bref.tol + 8 * bref.gap
+    assert diff <= bref.tol + 8 * bref.gap
 
 
 # ---- 3: endings -----------------------------------------------------------------------------------------------------------------------------------

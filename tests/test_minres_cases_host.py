@@ -74,6 +74,28 @@ def test_lap_1_without_preconditioner_fails_the_rule():
     assert counts == [k] * 6 and dev < margin
 
 
+def test_block_jacobi_count_is_exact_above_the_floor():
+    """LAP[0] at sigma 1.5 with dense blocks of 8 rows. At rtol 1e-8 the history is flat (h[104] = 1.25e-8, h[105] = 9.4e-9) and the six permuted
+    runs count 101 to 106: no exact count there. Over all of (1e-10, 1e-5) the widest step is k = 116, ratio 1.70, margin 0.303, but the permuted
+    runs deviate by up to 6.0e-2 at it, above a tenth of the margin. Above the floor of 1e-7 the widest step is k = 87, ratio 1.56, margin 0.250,
+    deviation 2.1e-5: the rule of this file holds, and the GPU test of the one-row sweeps takes its tolerance there."""
+    case = cc.lap(*cc.LAP[mc.LAP[0][0]])
+    P = cc.shifted(case, mc.LAP[0][1])
+    minv = mc.block_jacobi(P, mc.BJACOBI_BLOCK)
+    long = mc.minres_reference(P, case.b, minv, rtol=1e-12)
+    k, rtol, ratio = mc.pick_k(long.hist, mc.BJACOBI_FLOOR)
+    ref = mc.minres_reference(P, case.b, minv, rtol=rtol)
+    assert ref.reason == "converged" and ref.its == k == 87 and ratio >= 1.4
+    dev, counts = 0.0, []
+    for seed in range(6):
+        run = mc.minres_reference(P, case.b, minv, rtol=rtol, perm=np.random.default_rng(1000 + seed).permutation(case.n))
+        counts.append(run.its)
+        dev = max(dev, abs(run.hist[k - 1] / ref.hist[k - 1] - 1.0), abs(run.hist[k] / ref.hist[k] - 1.0))
+    margin = np.sqrt(ratio) - 1.0
+    print("k %d, rtol %.3e, ratio %.3f, margin %.3f, deviation %.2e" % (k, rtol, ratio, margin, dev))
+    assert counts == [k] * 6 and dev < 0.1 * margin
+
+
 def test_sizes_cover_the_tail_and_the_tile():
     assert [mc.kron(*c).n for c in mc.KRON_NONE] == [1057, 512, 513, 1027]
     assert [cc.lap(*cc.LAP[i]).n for i, _ in mc.LAP] == [1023, 1073, 1023]
