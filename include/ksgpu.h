@@ -672,8 +672,36 @@ int ks_st_get_matmode(ks_st st, int *mode);
    and, with the PC types that have it, more than one rank; a Jacobi-Davidson solve whose ST has it set is KS_ERR_SUP at set-up. A zero right-hand
    side gives y = 0 and counts no iteration. The symmetry of P and M is the caller's business.
    Its value is 6: the values 3 and 5 name no solver and stay KS_ERR_SUP, which is what callers of earlier versions got for them. */
-enum { KS_KSP_GMRES = 0, KS_KSP_BCGS = 1, KS_KSP_PREONLY = 2, KS_KSP_CG = 4, KS_KSP_MINRES = 6 };
-int ks_st_set_ksp_type(ks_st st, int type);                                /* KSPSetType on STGetKSP: GMRES (restarted, the shell mode's default), BiCGStab, CG - all preconditioned on the left -, MINRES or PREONLY; any other value: KS_ERR_SUP */
+/* KS_KSP_BCGSL is KSPBCGSL (-st_ksp_type bcgsl), the BiCGStab(l) of Sleijpen and Fokkema, for a P that need not be symmetric: l BiCG steps, then one
+   minimum-residual polynomial of degree l, whose roots may be complex pairs - where BiCGStab's one-step polynomial with its real root stagnates or
+   breaks down (convection-dominated operators, A - sigma I with the target inside a non-symmetric spectrum). 2 l + 4 work vectors, no restart. The
+   preconditioner is on the left, A^ = M^-1 P, and the norm that is tested and reported as last_rnorm is the preconditioned residual, as for KS_KSP_BCGS:
+     y = 0; r_0 = M^-1 b; rt = r_0; u_0 = 0; rho0 = 1; alpha = 0; omega = 1; dp0 = ||r_0||; tol = max(rtol dp0, 1e-50)
+     cycle:  converged when ||r_0|| <= tol; its >= max_it: "reached %d iterations"                 (both tested at the start of a cycle only)
+             rho0 = -omega rho0
+             for j = 0 .. l-1:  rho1 = (r_j, rt); beta = alpha (rho1 / rho0); rho0 = rho1;  u_i = r_i - beta u_i (i <= j);  u_{j+1} = A^ u_j
+                                sigma = (u_{j+1}, rt); alpha = rho1 / sigma;  y += alpha u_0;  r_i -= alpha u_{i+1} (i <= j);  r_{j+1} = A^ r_j
+             G = [r_0 .. r_l]^T [r_0 .. r_l];  gamma = argmin ||r_0 - sum_j gamma_j r_j||  (Cholesky of G(1:l,1:l), right-hand side G(1:l,0))
+             y += sum gamma_j r_{j-1};  r_0 -= sum gamma_j r_j;  u_0 -= sum gamma_j u_j;  omega = gamma_l
+   ks_st_get_ksp_stats counts BiCG steps as iterations, l per cycle (two products each); last_rnorm is ||M^-1 (b - P y)|| as the recurrence has it after
+   the last minimum-residual step. The KSP of the ST is strict: KS_ERR_NOT_CONVERGED when rho0 or sigma is zero ("breakdown"), a Cholesky pivot is
+   <= 0 ("singular minimum-residual step"), a value is not finite ("not a number") or max_it is reached ("reached %d iterations"). Not built:
+   PETSc's convex polynomial (KSPBCGSLSetPol), its residual replacement (KSPBCGSLSetXRes) and the pseudo-inverse (KSPBCGSLSetUsePseudoinverse).
+   Supported where KS_KSP_CG is: every transformation with a solve, both matrix modes, every PC type, the transposed side and, with the PC types
+   that have it, more than one rank; a Jacobi-Davidson solve whose ST has it set is KS_ERR_SUP at set-up (the device-resident solvers run on the
+   ST's own operator, not on the projected one). A zero right-hand side gives y = 0 and counts no iteration.
+   Its value is 8: the values 3, 5 and 7 name no solver and stay KS_ERR_SUP. */
+enum { KS_KSP_GMRES = 0, KS_KSP_BCGS = 1, KS_KSP_PREONLY = 2, KS_KSP_CG = 4, KS_KSP_MINRES = 6, KS_KSP_BCGSL = 8 };
+int ks_st_set_ksp_type(ks_st st, int type);                                /* KSPSetType on STGetKSP: GMRES (restarted, the shell mode's default), BiCGStab, BiCGStab(l), CG - all preconditioned on the left -, MINRES or PREONLY; any other value: KS_ERR_SUP */
+/* KS_KSP_BCGSL: l of BiCGStab(l) (KSPBCGSLSetEll), 1..4 (KS_ERR_ARG_OUTOFRANGE otherwise), default 2; l = 1 is a device-resident BiCGStab. The setter
+   clears the set-up: the work vectors depend on l. */
+int ks_st_bcgsl_set_ell(ks_st st, int ell);
+int ks_st_bcgsl_get_ell(ks_st st, int *ell);
+/* KS_KSP_BCGSL has the device-resident form of KS_KSP_CG (below) with a check interval and counters of its own. The interval counts CYCLES of l steps:
+   1..1024 (KS_ERR_ARG_OUTOFRANGE otherwise), default 4; count, solution and last_rnorm are the same bits for every c. gated_iterations counts cycles. */
+int ks_st_bcgsl_set_check_interval(ks_st st, int c);
+int ks_st_bcgsl_get_check_interval(ks_st st, int *c);
+int ks_st_bcgsl_get_stats(ks_st st, long long *sweeps, long long *host_waits, long long *gated_cycles);
 /* KS_KSP_MINRES has the device-resident form of KS_KSP_CG (below) with a check interval and counters of its own: setting one solver's leaves the other's alone. */
 int ks_st_minres_set_check_interval(ks_st st, int c);                      /* 1..1024 (KS_ERR_ARG_OUTOFRANGE otherwise), default 8; count, solution and last_rnorm are the same bits for every c */
 int ks_st_minres_get_check_interval(ks_st st, int *c);

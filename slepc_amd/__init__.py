@@ -816,7 +816,7 @@ class BV:
 class ST:
     """Spectral transformation (STSHIFT / STSINVERT / STCAYLEY / STPRECOND). Inner solves: GMRES + Jacobi by default; SetKSPType chooses BiCGStab,
     PREONLY or, for a symmetric positive definite system, CG (CGSetCheckInterval, GetCGStats), for a symmetric indefinite one MINRES
-    (MINRESSetCheckInterval, GetMINRESStats, PCJacobiSetUseAbs); SetPC the preconditioner."""
+    (MINRESSetCheckInterval, GetMINRESStats, PCJacobiSetUseAbs), for a non-symmetric one BiCGStab(l) (BCGSLSetEll); SetPC the preconditioner."""
 
     def __init__(self, ctx, _handle=None):
         self.ctx = ctx
@@ -960,8 +960,30 @@ class ST:
     def SetKSPType(self, t):
         """KSPSetType on the ST's KSP: "gmres" (default), "bcgs", "preonly" (one application of the preconditioner: exact with SetPC("lu")), or "cg"
         (conjugate gradients for a symmetric positive definite P and preconditioner; its scalars stay on the device, see CGSetCheckInterval), or
-        "minres" (symmetric P that may be indefinite, positive definite preconditioner - PCJacobiSetUseAbs -; device-resident like "cg")."""
-        _lib.check(self.ctx.L.ks_st_set_ksp_type(self.h, {"gmres": 0, "bcgs": 1, "preonly": 2, "cg": 4, "minres": 6}.get(t, t)))
+        "minres" (symmetric P that may be indefinite, positive definite preconditioner - PCJacobiSetUseAbs -; device-resident like "cg"), or
+        "bcgsl" (BiCGStab(l) for any P, device-resident too: BCGSLSetEll, BCGSLSetCheckInterval, GetBCGSLStats)."""
+        _lib.check(self.ctx.L.ks_st_set_ksp_type(self.h, {"gmres": 0, "bcgs": 1, "preonly": 2, "cg": 4, "minres": 6, "bcgsl": 8}.get(t, t)))
+
+    def BCGSLSetEll(self, ell):
+        """KSPBCGSLSetEll: the l of "bcgsl", 1..4, default 2 (1: a device-resident BiCGStab). Clears the set-up."""
+        _lib.check(self.ctx.L.ks_st_bcgsl_set_ell(self.h, int(ell)))
+
+    def BCGSLGetEll(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_st_bcgsl_get_ell(self.h, C.byref(v))); return v.value
+
+    def BCGSLSetCheckInterval(self, c):
+        """Cycles (l steps each) of "bcgsl" enqueued before the host reads the solver's state (1..1024, default 4). The count, the solution and
+        the residual norm do not depend on it. A setting apart from CG's and MINRES's."""
+        _lib.check(self.ctx.L.ks_st_bcgsl_set_check_interval(self.h, int(c)))
+
+    def BCGSLGetCheckInterval(self):
+        v = C.c_int(); _lib.check(self.ctx.L.ks_st_bcgsl_get_check_interval(self.h, C.byref(v))); return v.value
+
+    def GetBCGSLStats(self):
+        """Since the ST was created: sweeps (launches of the BiCGStab(l) kernels), host_waits, gated_iterations (counted in cycles), as GetCGStats."""
+        a, b, c = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        _lib.check(self.ctx.L.ks_st_bcgsl_get_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"sweeps": a.value, "host_waits": b.value, "gated_iterations": c.value}
 
     def MINRESSetCheckInterval(self, c):
         """Iterations of "minres" enqueued before the host reads the solver's state (1..1024, default 8). The count, the solution and the residual

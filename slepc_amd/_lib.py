@@ -247,6 +247,11 @@ _SIG = {
     "ks_st_minres_set_check_interval": [vp, C.c_int],
     "ks_st_minres_get_check_interval": [vp, ip],
     "ks_st_minres_get_stats": [vp, llp, llp, llp],
+    "ks_st_bcgsl_set_ell": [vp, C.c_int],
+    "ks_st_bcgsl_get_ell": [vp, ip],
+    "ks_st_bcgsl_set_check_interval": [vp, C.c_int],
+    "ks_st_bcgsl_get_check_interval": [vp, ip],
+    "ks_st_bcgsl_get_stats": [vp, llp, llp, llp],
     "ks_st_pc_jacobi_set_use_abs": [vp, C.c_int],
     "ks_st_pc_jacobi_get_use_abs": [vp, ip],
     "ks_st_set_matmode": [vp, C.c_int],

@@ -298,6 +298,7 @@ struct Jd : Gd {
     rtol = st->rtol_set ? st->rtol : 1e-4; max_it = st->max_it_set ? st->max_it : 90; restart = st->restart;
     KS_CHECK(ksp_type != KS_KSP_CG, KS_ERR_SUP, "Jacobi-Davidson cannot solve its correction equation with KSPCG: the projected operator is not symmetric in the form it is applied here (use BiCGStab or GMRES)");
     KS_CHECK(ksp_type != KS_KSP_MINRES, KS_ERR_SUP, "Jacobi-Davidson cannot solve its correction equation with KSPMINRES: the projected operator is not symmetric in the form it is applied here (use BiCGStab or GMRES)");
+    KS_CHECK(ksp_type != KS_KSP_BCGSL, KS_ERR_SUP, "Jacobi-Davidson cannot solve its correction equation with KSPBCGSL: the device-resident solvers run on the ST's own operator, not on the projected one (use BiCGStab or GMRES)");
     if (ksp_type == KS_KSP_BCGS) KS_CALL(make(7, &Kb));
     else if (ksp_type == KS_KSP_PREONLY) {}      // the preconditioned, projected right-hand side is the correction: no vectors
     else { KS_CALL(make(restart + 1, &Kg)); KS_CALL(ks_bv_set_orthogonalization(Kg, KS_BV_ORTHOG_CGS, st->gmres_refine, 0.7071)); }

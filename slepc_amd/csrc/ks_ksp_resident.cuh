@@ -48,7 +48,15 @@ __device__ __forceinline__ void ksp_sums(const double *__restrict__ red, const d
   if (red) { if ((int)threadIdx.x < ncols) c_lds[threadIdx.x] = red[threadIdx.x]; __syncthreads(); }
   else reduce_partials_to_lds(part, nblocks, ncols, c_lds);
 }
-// more than one rank: red[i] = this rank's sum of column i < NCOLS <= 2 of the partials, for the allreduce behind it. Not gated: its inputs are left
+// the same for a solver with more sums per sweep (BiCGStab(l): the 15 of a Gram matrix): their number is a template argument, and the sweeps of CG and
+// MINRES keep the form above and the instructions they had
+template <int NCOLS>
+__device__ __forceinline__ void ksp_sums(const double *__restrict__ red, const double *__restrict__ part, int nblocks, double *c_lds)
+{
+  if (red) { if ((int)threadIdx.x < NCOLS) c_lds[threadIdx.x] = red[threadIdx.x]; __syncthreads(); }
+  else reduce_partials_to_lds(part, nblocks, NCOLS, c_lds);
+}
+// more than one rank: red[i] = this rank's sum of column i < NCOLS of the partials, for the allreduce behind it. Not gated: its inputs are left
 // alone once the solve has ended, and every rank keeps issuing the same collectives. NCOLS is a template argument for the sake of the sweeps beside it:
 // with a run-time count here the compiler stops specialising reduce_partials_to_lds in a file whose every other caller sums one column (MINRES: 56
 // VGPRs and some 90 instructions more in each of start, lanczos and update: scripts/isa_diff.py)
@@ -123,8 +131,9 @@ template <typename F> int ksp_flag(bool b, F f) { return b ? f(std::true_type())
 inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 
 // One solve: the launch shape, the scratch carved behind its head (the state, then the ranks' sums; the partials arrays follow the head, KS_MAX_BLOCKS
-// doubles per column) and what every resident solver does with them. State begins with a KsKspHead `h`
-template <typename State>
+// doubles per column) and what every resident solver does with them. State begins with a KsKspHead `h`. The scratch has a size per solver: HEAD bytes
+// for the state and NRED sums of the ranks, then COLS partials columns (CG and MINRES: 256 bytes, 4 sums, 3 columns)
+template <typename State, size_t HEAD = KS_RESIDENT_HEAD_BYTES, int COLS = KS_RESIDENT_PART_COLS, int NRED = 4>
 struct KspResident {
   ks_st st; ks_ctx ctx; KsResident *res; int n, grid; bool multi, v2, tr;
   State *state; double *red, *part;
@@ -132,13 +141,13 @@ struct KspResident {
 
   int init(const KsKsp &k, ks_st st_, KsResident *res_, bool tr_)
   {
-    static_assert(sizeof(State) + 4 * sizeof(double) <= KS_RESIDENT_HEAD_BYTES, "state and the ranks' sums share the head of the scratch");
+    static_assert(sizeof(State) + NRED * sizeof(double) <= HEAD, "state and the ranks' sums share the head of the scratch");
     st = st_; ctx = k.ctx; res = res_; n = (int)k.n; tr = tr_; multi = ks_is_multi(ctx);
-    KS_CALL(ks_resident_alloc(res));
+    KS_CALL(ks_resident_alloc(res, HEAD, COLS));
     // one grid for every sweep, so that the partials line up: at most 4 workgroups per CU, KS_MAX_BLOCKS at the most (what a partials array holds); the
     // one-row-per-lane forms of a misaligned vector keep it and walk twice the tiles per workgroup
     grid = ks_sweep_grid(ctx, n, 2);
-    state = (State *)res->dev; red = (double *)(res->dev + sizeof(State)); part = (double *)(res->dev + KS_RESIDENT_HEAD_BYTES);
+    state = (State *)res->dev; red = (double *)(res->dev + sizeof(State)); part = (double *)(res->dev + HEAD);
     dinv = nullptr;
     const bool pointwise = ks_st_pc_pointwise(st, &dinv);
     pc = !pointwise ? 2 : (dinv ? 1 : 0);
@@ -148,7 +157,7 @@ struct KspResident {
   // state = 0, y = 0
   int zero(double *y)
   {
-    KS_HIP(hipMemsetAsync(state, 0, KS_RESIDENT_HEAD_BYTES, ctx->stream));
+    KS_HIP(hipMemsetAsync(state, 0, HEAD, ctx->stream));
     KS_HIP(hipMemsetAsync(y, 0, sizeof(double) * std::max<long long>(n, 1), ctx->stream));
     return KS_SUCCESS;
   }

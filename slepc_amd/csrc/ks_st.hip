@@ -343,12 +343,12 @@ int ks_st_product_one_term_left(ks_st st, bool tr, const double *p, double *w, c
   return KS_SUCCESS;
 }
 int ks_st_blocks_apply(ks_st st, const double *in, double *out, bool tr) { return blocks_apply(st, in, out, tr); }
-int ks_resident_alloc(KsResident *r)
+int ks_resident_alloc(KsResident *r, size_t head_bytes, int part_cols)               // a KsResident belongs to one solver: the same sizes at every call
 {
   if (r->dev && r->host) return KS_SUCCESS;
   ks_resident_free(r);                                                              // an earlier call that got only the device half: begin again
-  KS_HIP(hipMalloc(&r->dev, KS_RESIDENT_HEAD_BYTES + sizeof(double) * 3 * (size_t)KS_MAX_BLOCKS));
-  KS_HIP(hipHostMalloc(&r->host, KS_RESIDENT_HEAD_BYTES, hipHostMallocDefault));
+  KS_HIP(hipMalloc(&r->dev, head_bytes + sizeof(double) * part_cols * (size_t)KS_MAX_BLOCKS));
+  KS_HIP(hipHostMalloc(&r->host, head_bytes, hipHostMallocDefault));
   return KS_SUCCESS;
 }
 void ks_resident_free(KsResident *r)
@@ -367,6 +367,7 @@ int inner_solve(ks_st st, const double *rhs, double *y, bool tr = false)
   if (st->ksp_type == KS_KSP_PREONLY) return preonly_solve(st, rhs, y, tr);
   if (st->ksp_type == KS_KSP_CG) return ks_ksp_cg(st_ksp(st), st, tr, rhs, y);
   if (st->ksp_type == KS_KSP_MINRES) return ks_ksp_minres(st_ksp(st), st, tr, rhs, y);
+  if (st->ksp_type == KS_KSP_BCGSL) return ks_ksp_bcgsl(st_ksp(st), st, tr, rhs, y);
   return st->ksp_type == KS_KSP_BCGS ? bcgs_solve(st, rhs, y, tr) : gmres_solve(st, rhs, y, tr);
 }
 
@@ -522,18 +523,25 @@ int ks_st_setup_internal(ks_st st)
     KS_CALL(ks_mat_create_transpose(A, &st->At));
     if (B) KS_CALL(ks_mat_create_transpose(B, &st->Bt));
   }
-  if (st->W) { int wn = 0; ks_bv_get_sizes(st->W, &wn, nullptr, nullptr, nullptr); if (wn != A->n) { ks_bv_destroy(st->W); ks_bv_destroy(st->K); ks_bv_destroy(st->Kb); st->W = st->K = st->Kb = nullptr; if (st->dinv) hipFree(st->dinv); st->dinv = nullptr; } }
+  if (st->W) { int wn = 0; ks_bv_get_sizes(st->W, &wn, nullptr, nullptr, nullptr); if (wn != A->n) { ks_bv_destroy(st->W); ks_bv_destroy(st->K); ks_bv_destroy(st->Kb); ks_bv_destroy(st->Kl); st->W = st->K = st->Kb = st->Kl = nullptr; if (st->dinv) hipFree(st->dinv); st->dinv = nullptr; } }
   if (!st->W) KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 3, 0, &st->W));
   if (need_solve || precond) {
     if (st->K && !need_solve) { ks_bv_destroy(st->K); st->K = nullptr; }
     if (st->K) { int km = 0; ks_bv_get_sizes(st->K, nullptr, nullptr, &km, nullptr); if (km != st->restart + 1) { ks_bv_destroy(st->K); st->K = nullptr; } }
-    const bool short_rec = st->ksp_type == KS_KSP_CG || st->ksp_type == KS_KSP_MINRES;
-    if (st->K && (st->ksp_type == KS_KSP_PREONLY || short_rec)) { ks_bv_destroy(st->K); st->K = nullptr; }      // KSPPREONLY, KSPCG and KSPMINRES keep no basis
+    const bool resident_sym = st->ksp_type == KS_KSP_CG || st->ksp_type == KS_KSP_MINRES;
+    const bool short_rec = resident_sym || st->ksp_type == KS_KSP_BCGSL;
+    if (st->K && (st->ksp_type == KS_KSP_PREONLY || short_rec)) { ks_bv_destroy(st->K); st->K = nullptr; }      // KSPPREONLY, KSPCG, KSPMINRES and KSPBCGSL keep no basis
     if (need_solve && !st->K && st->ksp_type != KS_KSP_PREONLY && !short_rec) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, st->restart + 1, 0, &st->K)); st->K->row_start = A->row_start; }
     if (need_solve && st->K) KS_CALL(ks_bv_set_orthogonalization(st->K, KS_BV_ORTHOG_CGS, st->gmres_refine, 0.7071));      // KSPGMRESClassicalGramSchmidtOrthogonalization + refinement type
     if (need_solve && st->ksp_type == KS_KSP_CG) KS_CALL(ks_resident_alloc(&st->cg));
     if (need_solve && st->ksp_type == KS_KSP_MINRES) KS_CALL(ks_resident_alloc(&st->mr));
-    if (need_solve && (st->ksp_type == KS_KSP_BCGS || short_rec) && !st->Kb) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 7, 0, &st->Kb)); st->Kb->row_start = A->row_start; }
+    if (need_solve && st->ksp_type == KS_KSP_BCGSL) {                      // r_0..r_l, u_0..u_l, rt, one scratch column: 2 l + 4 columns, made anew when l changed
+      KS_CALL(ks_resident_alloc(&st->bl, KS_BCGSL_HEAD_BYTES, KS_BCGSL_PART_COLS));
+      const int cols = 2 * st->bcgsl_ell + 4;
+      if (st->Kl) { int km = 0; ks_bv_get_sizes(st->Kl, nullptr, nullptr, &km, nullptr); if (km != cols) { ks_bv_destroy(st->Kl); st->Kl = nullptr; } }
+      if (!st->Kl) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, cols, 0, &st->Kl)); st->Kl->row_start = A->row_start; }
+    }
+    if (need_solve && (st->ksp_type == KS_KSP_BCGS || resident_sym) && !st->Kb) { KS_CALL(ks_bv_create(ctx, A->n, A->n_global, 7, 0, &st->Kb)); st->Kb->row_start = A->row_start; }
     if (!st->dinv) KS_HIP(hipMalloc(&st->dinv, sizeof(double) * std::max(A->n, 1)));
     // Jacobi: diag(P)
     double *da = ks_bv_col(st->W, 1), *db = ks_bv_col(st->W, 2);
@@ -601,7 +609,7 @@ extern "C" int ks_st_create(ks_ctx ctx, ks_st *out)
 extern "C" int ks_st_destroy(ks_st st)
 {
   if (!st) return KS_SUCCESS;
-  ks_bv_destroy(st->K); ks_bv_destroy(st->W); ks_bv_destroy(st->Kb);
+  ks_bv_destroy(st->K); ks_bv_destroy(st->W); ks_bv_destroy(st->Kb); ks_bv_destroy(st->Kl);
   if (st->dinv) hipFree(st->dinv);
   if (st->op) ks_mat_destroy(st->op);
   if (st->bil) ks_mat_destroy(st->bil);
@@ -610,6 +618,7 @@ extern "C" int ks_st_destroy(ks_st st)
   if (st->pcwork) hipFree(st->pcwork);
   ks_resident_free(&st->cg);
   ks_resident_free(&st->mr);
+  ks_resident_free(&st->bl);
   ks_pc_ilu_free(st->ilu);
   ks_pc_lu_free(st->lu);
   ks_pc_amg_free(st->amg);
@@ -663,15 +672,16 @@ extern "C" int ks_st_set_ksp(ks_st st, double rtol, int max_it, int restart)   /
   if (restart > 0 && restart != st->restart) { st->restart = restart; st->ready = false; }   // a basis wider than 64 columns orthogonalises through the host-driven loop
   return KS_SUCCESS;
 }
-extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType on STGetKSP: KSPGMRES (default), KSPBCGS, KSPPREONLY, KSPCG or KSPMINRES
+extern "C" int ks_st_set_ksp_type(ks_st st, int type)              // KSPSetType on STGetKSP: KSPGMRES (default), KSPBCGS, KSPPREONLY, KSPCG, KSPMINRES or KSPBCGSL
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
-  KS_CHECK(type == KS_KSP_GMRES || type == KS_KSP_BCGS || type == KS_KSP_PREONLY || type == KS_KSP_CG || type == KS_KSP_MINRES, KS_ERR_SUP, "only KSPGMRES, KSPBCGS, KSPPREONLY, KSPCG and KSPMINRES are built");
+  KS_CHECK(type == KS_KSP_GMRES || type == KS_KSP_BCGS || type == KS_KSP_PREONLY || type == KS_KSP_CG || type == KS_KSP_MINRES || type == KS_KSP_BCGSL, KS_ERR_SUP,
+           "only KSPGMRES, KSPBCGS, KSPPREONLY, KSPCG, KSPMINRES and KSPBCGSL are built");
   if (st->ksp_type != type) { st->ksp_type = type; st->ready = false; }
   st->ksp_type_set = true;
   return KS_SUCCESS;
 }
-// the check interval and the statistics of the two device-resident solvers: which: the ST's cg or mr
+// the check interval and the statistics of the device-resident solvers: which: the ST's cg, mr or bl
 static int resident_set_check(ks_st st, KsResident ks_st_s::*which, int c)
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
@@ -693,6 +703,17 @@ extern "C" int ks_st_cg_get_stats(ks_st st, long long *sweeps, long long *waits,
 extern "C" int ks_st_minres_set_check_interval(ks_st st, int c) { return resident_set_check(st, &ks_st_s::mr, c); }
 extern "C" int ks_st_minres_get_check_interval(ks_st st, int *c) { return resident_get_check(st, &ks_st_s::mr, c); }
 extern "C" int ks_st_minres_get_stats(ks_st st, long long *sweeps, long long *waits, long long *gated) { return resident_get_stats(st, &ks_st_s::mr, sweeps, waits, gated); }
+extern "C" int ks_st_bcgsl_set_check_interval(ks_st st, int c) { return resident_set_check(st, &ks_st_s::bl, c); }
+extern "C" int ks_st_bcgsl_get_check_interval(ks_st st, int *c) { return resident_get_check(st, &ks_st_s::bl, c); }
+extern "C" int ks_st_bcgsl_get_stats(ks_st st, long long *sweeps, long long *waits, long long *gated) { return resident_get_stats(st, &ks_st_s::bl, sweeps, waits, gated); }
+extern "C" int ks_st_bcgsl_set_ell(ks_st st, int ell)                 // KSPBCGSLSetEll on STGetKSP; the work vectors depend on it: the set-up is cleared
+{
+  KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");
+  KS_CHECK(ell >= 1 && ell <= KS_BCGSL_MAX_ELL, KS_ERR_ARG_OUTOFRANGE, "BiCGStab(l): l = %d (1..%d)", ell, KS_BCGSL_MAX_ELL);
+  st->bcgsl_ell = ell; st->ready = false;
+  return KS_SUCCESS;
+}
+extern "C" int ks_st_bcgsl_get_ell(ks_st st, int *ell) { KS_CHECK(st && ell, KS_ERR_ARG_NULL, "NULL argument"); *ell = st->bcgsl_ell; return KS_SUCCESS; }
 extern "C" int ks_st_pc_jacobi_set_use_abs(ks_st st, int flag)        // PCJacobiSetUseAbs on the KSP's PC; the diagonal is rebuilt at the next set-up
 {
   KS_CHECK(st, KS_ERR_ARG_NULL, "ST is NULL");

@@ -313,6 +313,11 @@ struct KsKspHead { int its, done, conv, reason; long long gated; };
 // the solver's own kernels, host reads, iterations that found the solve ended (the get_stats triple)
 struct KsResident { int check = 8; char *dev = nullptr; void *host = nullptr; long long sweeps = 0, waits = 0, gated = 0; };
 constexpr size_t KS_RESIDENT_HEAD_BYTES = 256;   // the state and up to four sums of the ranks; three partials arrays follow
+constexpr int KS_RESIDENT_PART_COLS = 3;
+// BiCGStab(l) (ks_bcgsl.hip) sums a Gram matrix of up to 15 entries: a head of 512 bytes (its state and 18 sums of the ranks) and 18 partials columns
+constexpr size_t KS_BCGSL_HEAD_BYTES = 512;
+constexpr int KS_BCGSL_PART_COLS = 18;
+constexpr int KS_BCGSL_MAX_ELL = 4;
 // ---- ST: spectral transformation (ks_st.hip) ----------------------------------------------------
 struct ks_st_s {
   ks_ctx ctx = nullptr;
@@ -325,12 +330,17 @@ struct ks_st_s {
   ks_mat bil = nullptr;                       // STCAYLEY: shell matrix A + nu B, the bilinear form of symmetric problems (cayley.c:70-77)
   ks_mat A = nullptr, B = nullptr;            // borrowed
   double rtol = 1e-8; int max_it = 10000, restart = 30;   // KSP: SLEPC_DEFAULT_TOL (stsles.c:407), PETSc defaults
-  int ksp_type = KS_KSP_GMRES;                // KSPGMRES (the default of the shell matrix mode), KSPBCGS, KSPPREONLY, KSPCG or KSPMINRES
+  int ksp_type = KS_KSP_GMRES;                // KSPGMRES (the default of the shell matrix mode), KSPBCGS, KSPPREONLY, KSPCG, KSPMINRES or KSPBCGSL
   bool ksp_type_set = false, rtol_set = false, max_it_set = false;   // chosen by the caller (ks_st_set_ksp_type, ks_st_set_ksp): a solver with KSP defaults of its own (JD) keeps off those
   int gmres_refine = KS_BV_ORTHOG_REFINE_NEVER;   // KSPGMRESSetCGSRefinementType: PETSc's default is classical Gram-Schmidt without refinement
   ks_bv Kb = nullptr;                         // BiCGStab work vectors (7 columns); CG's r, z, p, w are its first four, MINRES takes all seven
   // KS_KSP_CG and KS_KSP_MINRES, each with a check interval and statistics of its own (ks_st_cg_*, ks_st_minres_*); their work vectors are Kb's columns
   KsResident cg, mr;
+  // KS_KSP_BCGSL: the same for BiCGStab(l), its check interval counted in cycles of l steps; its 2 l + 4 work vectors are a BV of its own
+  // (r_0..r_l, u_0..u_l, rt and a scratch column for P x ahead of a block preconditioner), made at set-up when the type is set
+  KsResident bl = KsResident{4};
+  int bcgsl_ell = 2;
+  ks_bv Kl = nullptr;
   bool jacobi_abs = false;                    // PCJacobiSetUseAbs: KS_PC_JACOBI scales by 1 / |diag(P)| (a positive definite M for MINRES on an indefinite P)
   ks_bv K = nullptr, W = nullptr;             // GMRES basis (restart+1 columns), work vectors (3 columns)
   double *dinv = nullptr;                     // Jacobi: 1/diag(P)
@@ -375,10 +385,11 @@ int ks_ksp_preonly(const KsKsp &k, KsKspOp &op, const double *rhs, double *y);  
 // Both keep their scalars on the device (ks_ksp_resident.cuh); the reasons a solve ends with are the solver's own, 1 being converged
 int ks_ksp_cg(const KsKsp &k, ks_st st, bool tr, const double *rhs, double *y);
 int ks_ksp_minres(const KsKsp &k, ks_st st, bool tr, const double *rhs, double *y);
+int ks_ksp_bcgsl(const KsKsp &k, ks_st st, bool tr, const double *rhs, double *y);   // BiCGStab(l) (ks_bcgsl.hip), any P: st->bl, st->Kl, st->bcgsl_ell
 // the device scratch of such a solver (its state, the ranks' sums, the sweeps' partials) and the pinned copy of the state the host reads
-int ks_resident_alloc(KsResident *r);
+int ks_resident_alloc(KsResident *r, size_t head_bytes = KS_RESIDENT_HEAD_BYTES, int part_cols = KS_RESIDENT_PART_COLS);
 void ks_resident_free(KsResident *r);
-// w = P p but for one term: *v non-NULL on return means w += (*b) (*v) is still to be done (P applied term by term; the sweep behind the product adds it: k_cg_pw, k_minres_alfa). tmp: W(:,1)
+// w = P p but for one term: *v non-NULL on return means w += (*b) (*v) is still to be done (P applied term by term; the sweep behind the product adds it: k_cg_pw, k_minres_alfa, k_bcgsl_apply). tmp: W(:,1)
 int ks_st_product_one_term_left(ks_st st, bool tr, const double *p, double *w, const double **v, double *b);
 int ks_st_blocks_apply(ks_st st, const double *in, double *out, bool tr);      // out = M^-1 in for the preconditioners with kernels of their own
 bool ks_st_pc_pointwise(ks_st st, const double **dinv);   // set-up done. true: no preconditioner (*dinv NULL) or point Jacobi (*dinv its diagonal); false: blocks (ks_st_pc_apply_multi_internal)
