@@ -10,6 +10,8 @@
 // Waits are bounded by wall time (s_memrealtime, 100 MHz): a wave whose budget runs out sets the abort word, every workgroup that sees it skips its
 // remaining A-phases and still completes every C-phase; the host then runs the ordinary product and dot sweep. Wait graph: a C-phase never waits, the
 // A-phase of round i - 1 waits for C-phases of rounds <= i only, and every workgroup runs C(i) before A(i - 1): the graph descends in the round index.
+// k_forward_pipe: four variants of the forward launch with the next tile's panel loads in flight through the hand-off and one panel parked in LDS (which
+// panel; polls in front of the loads or behind), each compared with k_forward bit for bit - v, y and the dots - and timed alternating with it.
 // build: hipcc -O3 --offload-arch=gfx950 -I../../slepc_amd/csrc step_forward.hip -o step_forward        run: ./step_forward [side = 216]
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -54,6 +56,7 @@ __device__ __forceinline__ void fill_tables(const ksp::PairArgs &pa, const doubl
   for (int i = threadIdx.x; i < npat * 3 * pa.nb; i += BLOCK) sc[i] = pcoef[i];
   for (int i = threadIdx.x; i < npat; i += BLOCK) sm[i] = pmask[i];
 }
+__host__ __device__ inline size_t park_offset(int npat, int nb) { return ((size_t)npat * (3 * nb * sizeof(double) + sizeof(unsigned)) + 15) & ~(size_t)15; }      // the parked panel of the pipelined form, behind the tables
 template <int NACC>
 __device__ __forceinline__ void put_partials(const double (&acc)[NACC], int ncols, double *__restrict__ partials)
 {
@@ -244,6 +247,168 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   put_partials<KT + 2>(acc, KT + 2, partials);
 }
 
+// ---- the pipelined forward launch -------------------------------------------------------------------------------------------------------------
+// Same tiles, same hand-off, same sums; the panel loads of tile i + 1 are issued behind publish(i), in front of the A-phase of tile i - 1, so that they are in
+// flight through the poll, the barrier, the neighbour loads, the walk and the dots. Three panels are live then and the register file holds two: one is
+// parked in LDS (KT columns x 256 lanes x 16 B behind the dictionary tables; lane l writes and reads column i at park[i * BLOCK + l], so the panel itself
+// needs no barrier).
+//   PARK 0: the panel just computed (tile i) is parked, the loads of tile i + 1 land in its registers, and it comes back to registers behind A(i - 1);
+//   PARK 1: the waiting panel (tile i - 1) is parked, the loads land in ITS registers, and the dots of A(i - 1) read it from LDS.
+//   POLL_FIRST: wave 0 issues its first flag and abort polls in front of the panel loads (they return first: vector loads return in order), else behind them.
+// Progress as k_forward: C(i) waits for nothing but its own loads of V(:,0:k) and of its own rows of v, publish(i) stands in front of A(i - 1), a re-poll
+// queues behind panel loads, which wait for nothing.
+// The panel loads stand under NO branch: the compiler's wait for wave 0's first polls counts the loads issued behind them (s_waitcnt vmcnt(KT + 1)), and
+// where a path around the loads joins, it has to take that path's count, 0 - the whole panel. A lane without a row pair (past n, or no tile left) reads
+// rows 0 and 1 of every column instead, one line per column, and nobody uses what it gets.
+template <int KT>
+__device__ __forceinline__ void load_panel(const double *V, long long ld, int n, const double *v, long long t, bool has, d2 (&xv)[KT], d2 &s)
+{
+  const long long r = t * TILE + 2LL * threadIdx.x;
+  const bool ok = has && r + 1 < n;
+  const long long rr = ok ? r : 0;
+  s = *reinterpret_cast<const d2 *>(ok ? v + r : V);    // the tile's own rows of v: written by the launch before this one, stored in this launch by this lane only
+#pragma unroll
+  for (int i = 0; i < KT; i++) xv[i] = __builtin_nontemporal_load(reinterpret_cast<const d2 *>(V + (long long)i * ld + rr));
+}
+// The barrier between wave 0's matched poll and the other waves' loads of v. __syncthreads() puts s_waitcnt vmcnt(0) behind s_barrier (its workgroup-scope
+// acquire), which would hold every wave until its panel loads of the next tile are in: order LDS only (go_sh), and keep the compiler from moving a load over it.
+__device__ __forceinline__ void barrier_lds_only()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+  asm volatile("" ::: "memory");
+}
+template <int KT, int PARK, bool POLL_FIRST>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_forward_pipe(const double *V, long long ld, int n, double *v, double *__restrict__ y, const double *__restrict__ cg, double alpha,
+                                                   const unsigned char *__restrict__ rowpat, int npat, ksp::PairArgs pa, const double *__restrict__ pcoef, const unsigned *__restrict__ pmask,
+                                                   unsigned *flags, unsigned epoch, unsigned *ctl, double *__restrict__ partials, unsigned long long budget, int hooks)
+{
+  __shared__ double cc[2][KT];
+  __shared__ int go_sh;
+  double *sc; unsigned *sm;
+  fill_tables(pa, pcoef, pmask, npat, sc, sm);
+  d2 *park = reinterpret_cast<d2 *>(reinterpret_cast<char *>(dyn_lds) + park_offset(npat, pa.nb)) + threadIdx.x;
+  for (int i = threadIdx.x; i < 2 * KT; i += BLOCK) cc[i / KT][i % KT] = -cg[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long ntiles = ((long long)n + TILE - 1) / TILE;
+  double acc[KT + 2];
+#pragma unroll
+  for (int i = 0; i < KT + 2; i++) acc[i] = 0.0;
+  d2 pv[KT]; d2 ps = {0.0, 0.0};                      // the panel (PARK 0) and the new rows of the tile whose A-phase is still to come
+#pragma unroll
+  for (int i = 0; i < KT; i++) pv[i] = d2{0.0, 0.0};
+  long long pt = -1;
+  bool dead = false;
+  d2 nv[KT]; d2 ns;                                    // the panel and the rows of v of the tile of the next round, in flight
+  load_panel<KT>(V, ld, n, v, blockIdx.x, (long long)blockIdx.x < ntiles, nv, ns);
+  for (long long t = blockIdx.x;; t += gridDim.x) {
+    const bool has = t < ntiles;
+    d2 cv[KT]; d2 cs = ns;
+#pragma unroll
+    for (int i = 0; i < KT; i++) cv[i] = nv[i];
+    // ---- C-phase: the final update of tile t, as k_final; its loads went out a round ago ----
+    if (has) {
+      const long long r = t * TILE + 2LL * threadIdx.x;
+      if (r + 1 < n) {
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+          for (int i = 0; i < KT; i++) { const double c = cc[p][i]; cs.x = fma(c, cv[i].x, cs.x); cs.y = fma(c, cv[i].y, cs.y); }
+        cs.x *= alpha; cs.y *= alpha;
+        asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(reinterpret_cast<d2 *>(v + r)), "v"(cs) : "memory");
+      }
+      if ((hooks & 1) && (blockIdx.x & 1)) for (int q = 0; q < 40; q++) __builtin_amdgcn_s_sleep(127);
+    }
+    // ---- publish ----
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave
+    __syncthreads();
+    if (has && threadIdx.x == 0) __hip_atomic_store(flags + t, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool arun = pt >= 0 && !dead;
+    // ---- park ----
+    if (PARK == 0) {
+#pragma unroll
+      for (int i = 0; i < KT; i++) park[i * BLOCK] = cv[i];
+    } else if (arun) {
+#pragma unroll
+      for (int i = 0; i < KT; i++) park[i * BLOCK] = pv[i];
+    }
+    // ---- wave 0's first polls of A(t - gridDim.x), then every wave's loads of the next round's tile ----
+    long long tl = -1;
+    unsigned f0 = epoch, ab0 = 0;
+    if (arun && w == 0) {
+      const int kb = lane / 3, wh = lane % 3;
+      int b = 0; bool isb = false;
+#pragma unroll
+      for (int k = 0; k < NBT; k++) if (k == kb && k < pa.nb) { b = pa.base[k]; isb = true; }
+      if (isb) {
+        const int d = (int)(pa.dmask >> kb & 1u);
+        long long lo = pt * TILE + b - d, hi = pt * TILE + (TILE - 1) + b + d;
+        if (lo < 0) lo = 0;
+        if (hi > n - 1) hi = n - 1;
+        if (lo <= hi && (lo >> 9) + wh <= (hi >> 9)) tl = (lo >> 9) + wh;
+      }
+      if (tl == pt) tl = -1;
+      if (POLL_FIRST) {
+        if (tl >= 0) f0 = __hip_atomic_load(flags + tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 63) ab0 = __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_panel<KT>(V, ld, n, v, t + gridDim.x, has && t + gridDim.x < ntiles, nv, ns);
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- A-phase of the tile of the round before ----
+    if (arun) {
+      if (w == 0) {
+        int res;
+        bool first = true, fresh = POLL_FIRST;
+        const long long tstart = wall_clock64();
+        for (;;) {
+          unsigned f = f0, ab = ab0;
+          if (!fresh) {
+            f = epoch; ab = 0;
+            if (tl >= 0) f = __hip_atomic_load(flags + tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 63) ab = __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+          fresh = false;
+          if (__any(lane == 63 && ab == epoch)) { res = 0; break; }
+          if (__all(f == epoch)) { res = 1; break; }
+          if (first && lane == 0) atomicAdd(ctl + 2, 1u);
+          first = false;
+          if ((unsigned long long)(wall_clock64() - tstart) >= budget) {
+            if (lane == 0) { __hip_atomic_exchange(ctl, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); atomicAdd(ctl + 1, 1u); }
+            res = 0; break;
+          }
+          __builtin_amdgcn_s_sleep(8);
+        }
+        if (lane == 0) go_sh = res;
+      }
+      barrier_lds_only();                               // the other waves load v only behind this barrier
+      if (go_sh) {
+        const long long r = pt * TILE + 2LL * threadIdx.x;
+        const Lane<true, true> ln(v, n, r, ksp::D2{ps.x, ps.y});
+        const unsigned pp = *reinterpret_cast<const unsigned short *>(rowpat + (r < n ? r : 0));
+        double y0, y1;
+        ksp::dict_pair_walk<NBT>(pa, sc, sm, (int)(pp & 255u), (int)(pp >> 8), r, ln, y0, y1);
+        if (r + 1 < n) {
+          __builtin_nontemporal_store(d2{y0, y1}, reinterpret_cast<d2 *>(y + r));
+#pragma unroll
+          for (int i = 0; i < KT; i++) { const d2 x = PARK == 1 ? park[i * BLOCK] : pv[i]; acc[i] = fma(x.x, y0, acc[i]); acc[i] = fma(x.y, y1, acc[i]); }
+          acc[KT] = fma(ps.x, y0, acc[KT]); acc[KT] = fma(ps.y, y1, acc[KT]);
+          acc[KT + 1] = fma(y0, y0, acc[KT + 1]); acc[KT + 1] = fma(y1, y1, acc[KT + 1]);
+        }
+      } else dead = true;
+    }
+    if (!has) break;
+#pragma unroll
+    for (int i = 0; i < KT; i++) pv[i] = PARK == 0 ? park[i * BLOCK] : cv[i];
+    ps = cs; pt = t;
+  }
+  if (dead) return;
+  put_partials<KT + 2>(acc, KT + 2, partials);
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------------------------------
 struct Problem { int nx, n, npat; ksp::PairArgs pa; std::vector<double> coef; std::vector<unsigned> mask; std::vector<unsigned char> rowpat; };
 static Problem laplacian(int nx)
@@ -271,6 +436,7 @@ static Problem laplacian(int nx)
   return P;
 }
 
+using Kern = void (*)(const double *, long long, int, double *, double *, const double *, double, const unsigned char *, int, ksp::PairArgs, const double *, const unsigned *, unsigned *, unsigned, unsigned *, double *, unsigned long long, int);
 struct Dev { double *B; const unsigned char *rowpat; const double *coef; const unsigned *mask; double *cg, *p3, *p1; unsigned *flags, *ctl; long long ld; int ncu; size_t lds; };
 static unsigned g_epoch = 0;
 
@@ -288,43 +454,58 @@ static void run_k(const Problem &P, const Dev &D, const std::vector<double> &h0,
     hipLaunchKernelGGL(k_final<KT>, dim3(g_upd), dim3(BLOCK), 0, 0, D.B, ld, n, v, D.cg, alpha);
     hipLaunchKernelGGL(k_spmv, dim3(g_spmv), dim3(BLOCK), D.lds, 0, n, D.rowpat, P.npat, v, y, P.pa, D.coef, D.mask);
     hipLaunchKernelGGL((k_dots<KT + 1>), dim3(g_dot), dim3(BLOCK), 0, 0, D.B, ld, n, y, D.p3); };
-  auto fwd = [&](int hooks, unsigned long long bud) {
-    hipLaunchKernelGGL(k_forward<KT>, dim3(g_upd), dim3(BLOCK), D.lds, 0, D.B, ld, n, v, y, D.cg, alpha, D.rowpat, P.npat, P.pa, D.coef, D.mask, D.flags, ++g_epoch, D.ctl, D.p1, bud, hooks); };
+  // the forward launch and the variants of its pipelined form: same arguments, the parked panel behind the tables in dynamic LDS
+  struct Var { const char *name; Kern kern; size_t lds; };
+  const size_t lds_pipe = park_offset(P.npat, P.pa.nb) + (size_t)KT * BLOCK * sizeof(d2);
+  const Var vars[5] = {{"k_forward                         ", k_forward<KT>, D.lds},
+                       {"pipe: computed parked, polls first", k_forward_pipe<KT, 0, true>, lds_pipe}, {"pipe: computed parked, polls last ", k_forward_pipe<KT, 0, false>, lds_pipe},
+                       {"pipe: waiting parked, polls first ", k_forward_pipe<KT, 1, true>, lds_pipe}, {"pipe: waiting parked, polls last  ", k_forward_pipe<KT, 1, false>, lds_pipe}};
+  for (const Var &q : vars) CK(hipFuncSetAttribute((const void *)q.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds));
+  auto fwd = [&](const Var &q, int hooks, unsigned long long bud) {
+    hipLaunchKernelGGL(q.kern, dim3(g_upd), dim3(BLOCK), q.lds, 0, D.B, ld, n, v, y, D.cg, alpha, D.rowpat, P.npat, P.pa, D.coef, D.mask, D.flags, ++g_epoch, D.ctl, D.p1, bud, hooks); };
   auto reset = [&] { CK(hipMemcpy(v, h0.data(), sizeof(double) * n, hipMemcpyHostToDevice)); CK(hipMemcpy(y, hy0.data(), sizeof(double) * n, hipMemcpyHostToDevice)); };
   auto sums = [&](const double *p, int grid, int ncols) { std::vector<double> h((size_t)ncols * grid), s(ncols, 0.0); CK(hipMemcpy(h.data(), p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
     for (int c = 0; c < ncols; c++) for (int b = 0; b < grid; b++) s[c] += h[(size_t)c * grid + b]; return s; };
-  // ---- results: same bits of v and y, dots to rounding ----
+  // ---- results: same bits of v and y, dots to rounding (the pipelined forms add the same products in k_forward's order: their dots equal its dots) ----
   std::vector<double> va(n), ya(n), vb(n), yb(n);
   reset(); three(); CK(hipDeviceSynchronize());
   CK(hipMemcpy(va.data(), v, sizeof(double) * n, hipMemcpyDeviceToHost)); CK(hipMemcpy(ya.data(), y, sizeof(double) * n, hipMemcpyDeviceToHost));
   const std::vector<double> sa = sums(D.p3, g_dot, KT + 2);
-  for (int hooks : {0, 1}) {
-    unsigned ctl0[4]; CK(hipMemcpy(ctl0, D.ctl, sizeof(ctl0), hipMemcpyDeviceToHost));
-    reset(); fwd(hooks, hooks ? 100 * budget : budget); CK(hipDeviceSynchronize());
-    CK(hipMemcpy(vb.data(), v, sizeof(double) * n, hipMemcpyDeviceToHost)); CK(hipMemcpy(yb.data(), y, sizeof(double) * n, hipMemcpyDeviceToHost));
-    unsigned ctl1[4]; CK(hipMemcpy(ctl1, D.ctl, sizeof(ctl1), hipMemcpyDeviceToHost));
-    const std::vector<double> sb = sums(D.p1, g_upd, KT + 2);
-    double worst = 0.0;
-    for (int c = 0; c < KT + 2; c++) { const double d = fabs(sa[c] - sb[c]) / (fabs(sa[KT + 1]) + 1e-300); if (!(d <= worst)) worst = d; }      // a NaN shows
-    printf("k %2d %s: v %s, y %s, y.y = %.6e, largest dot difference %.2e of y.y, waits out of budget %u, aborted %s, polls that had to wait %u of %lld\n", KT, hooks ? "odd workgroups lag" : "even load       ",
-           memcmp(va.data(), vb.data(), sizeof(double) * n) ? "DIFFERS" : "same bits", memcmp(ya.data(), yb.data(), sizeof(double) * n) ? "DIFFERS" : "same bits", sa[KT + 1], worst,
-           ctl1[1] - ctl0[1], ctl1[0] == g_epoch ? "YES" : "no", ctl1[2] - ctl0[2], ntiles);
+  std::vector<double> s_fwd;
+  for (const Var &q : vars) {
+    hipFuncAttributes fa; CK(hipFuncGetAttributes(&fa, (const void *)q.kern));
+    printf("k %2d %s: %d registers, %zu B scratch, %zu B static + %zu B dynamic LDS\n", KT, q.name, fa.numRegs, (size_t)fa.localSizeBytes, (size_t)fa.sharedSizeBytes, q.lds);
+    for (int hooks : {0, 1}) {
+      unsigned ctl0[4]; CK(hipMemcpy(ctl0, D.ctl, sizeof(ctl0), hipMemcpyDeviceToHost));
+      reset(); fwd(q, hooks, hooks ? 100 * budget : budget); CK(hipDeviceSynchronize());
+      CK(hipMemcpy(vb.data(), v, sizeof(double) * n, hipMemcpyDeviceToHost)); CK(hipMemcpy(yb.data(), y, sizeof(double) * n, hipMemcpyDeviceToHost));
+      unsigned ctl1[4]; CK(hipMemcpy(ctl1, D.ctl, sizeof(ctl1), hipMemcpyDeviceToHost));
+      const std::vector<double> sb = sums(D.p1, g_upd, KT + 2);
+      if (&q == &vars[0] && !hooks) s_fwd = sb;
+      double worst = 0.0;
+      for (int c = 0; c < KT + 2; c++) { const double d = fabs(sa[c] - sb[c]) / (fabs(sa[KT + 1]) + 1e-300); if (!(d <= worst)) worst = d; }      // a NaN shows
+      printf("k %2d %s %s: v %s, y %s, dots %s k_forward's, largest dot difference %.2e of y.y, waits out of budget %u, aborted %s, polls that had to wait %u of %lld\n", KT, q.name, hooks ? "odd workgroups lag" : "even load       ",
+             memcmp(va.data(), vb.data(), sizeof(double) * n) ? "DIFFERS" : "same bits", memcmp(ya.data(), yb.data(), sizeof(double) * n) ? "DIFFERS" : "same bits",
+             memcmp(s_fwd.data(), sb.data(), sizeof(double) * sb.size()) ? "DIFFER from" : "equal", worst, ctl1[1] - ctl0[1], ctl1[0] == g_epoch ? "YES" : "no", ctl1[2] - ctl0[2], ntiles);
+    }
   }
-  // ---- times ----
+  // ---- times: the forms alternating, three rounds; then with odd workgroups lagging (one round) ----
   auto time = [&](auto fn, int reps) { for (int r = 0; r < 3; r++) fn(); CK(hipEventRecord(e0)); for (int r = 0; r < reps; r++) fn(); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms, e0, e1)); return 1e3 * ms / reps; };
   const int reps = 30;
   unsigned ctl0[4]; CK(hipMemcpy(ctl0, D.ctl, sizeof(ctl0), hipMemcpyDeviceToHost));
-  double t3[3], t1[3];
-  for (int rep = 0; rep < 3; rep++) { reset(); t3[rep] = time(three, reps); reset(); t1[rep] = time([&] { fwd(0, budget); }, reps); }      // alternating
+  double t3[3], t1[5][3], tl[5];
+  for (int rep = 0; rep < 3; rep++) { reset(); t3[rep] = time(three, reps); for (int q = 0; q < 5; q++) { reset(); t1[q][rep] = time([&] { fwd(vars[q], 0, budget); }, reps); } }
+  for (int q = 0; q < 5; q++) { reset(); tl[q] = time([&] { fwd(vars[q], 1, 100 * budget); }, 5); }
   unsigned ctl1[4]; CK(hipMemcpy(ctl1, D.ctl, sizeof(ctl1), hipMemcpyDeviceToHost));
   reset();
   const double ta = time([&] { hipLaunchKernelGGL(k_final<KT>, dim3(g_upd), dim3(BLOCK), 0, 0, D.B, ld, n, v, D.cg, alpha); }, reps);
   const double tb = time([&] { hipLaunchKernelGGL(k_spmv, dim3(g_spmv), dim3(BLOCK), D.lds, 0, n, D.rowpat, P.npat, v, y, P.pa, D.coef, D.mask); }, reps);
   const double tc = time([&] { hipLaunchKernelGGL((k_dots<KT + 1>), dim3(g_dot), dim3(BLOCK), 0, 0, D.B, ld, n, y, D.p3); }, reps);
   const double mb3 = 8e-6 * n * ((KT + 2) + 2.2 + (KT + 2)), mb1 = 8e-6 * n * ((KT + 2) + 1.2);
-  printf("k %2d: three launches %7.1f %7.1f %7.1f us (final update %6.1f, product %5.1f, dot sweep %6.1f alone; %.0f MB: %.2f TB/s) | forward launch %7.1f %7.1f %7.1f us (%.0f MB: %.2f TB/s), "
-         "aborted launches %s, polls that had to wait %.1f per launch of %lld\n", KT, t3[0], t3[1], t3[2], ta, tb, tc, mb3, mb3 / std::min({t3[0], t3[1], t3[2]}),
-         t1[0], t1[1], t1[2], mb1, mb1 / std::min({t1[0], t1[1], t1[2]}), ctl1[1] != ctl0[1] ? "SOME" : "none", (double)(ctl1[2] - ctl0[2]) / (3.0 * (reps + 3)), ntiles);
+  printf("k %2d: three launches %7.1f %7.1f %7.1f us (final update %6.1f, product %5.1f, dot sweep %6.1f alone; %.0f MB: %.2f TB/s), waits out of budget in the timed launches: %s\n",
+         KT, t3[0], t3[1], t3[2], ta, tb, tc, mb3, mb3 / std::min({t3[0], t3[1], t3[2]}), ctl1[1] != ctl0[1] ? "SOME" : "none");
+  for (int q = 0; q < 5; q++)
+    printf("k %2d %s: %7.1f %7.1f %7.1f us (%.0f MB: %.2f TB/s), odd workgroups lagging %7.1f us\n", KT, vars[q].name, t1[q][0], t1[q][1], t1[q][2], mb1, mb1 / std::min({t1[q][0], t1[q][1], t1[q][2]}), tl[q]);
   fflush(stdout);
 }
 

@@ -128,11 +128,13 @@ KS_PAIR_HD double pair_step(double acc, double a, double x, unsigned mask, int b
 // coef, mask: the plan's tables (the kernels keep them in LDS). NBT: compiled number of bases, >= pa.nb. Lane: how this lane reaches x and its neighbours -
 // lane(), pair(i) and one(i, want) under the rule above, up(v, i): the value v of the lane below (i: the index this lane loaded v from, for the host
 // emulation, which has no wave), down(v, i): of the lane above. Every lane of the wave must call this together.
+// The walk in its two halves, for a caller that asks for the loads in another way (the pipelined forward update, ks_gs.hip): dict_pair_loads fills v[k] = x[r + b_k],
+// x[r + b_k + 1] and, for a wide base, edge[k] = x[r + b_k - 1] in the wave's first lane, x[r + b_k + 2] in its last (set and read only under the same uniform
+// conditions); dict_pair_sums is every row's chain over them. dict_pair_walk is the one after the other.
 template <int NBT, class Lane>
-KS_PAIR_HD void dict_pair_walk(const PairArgs &pa, const double *coef, const unsigned *mask, int p0, int p1, long long r, const Lane &ln, double &y0, double &y1)
+KS_PAIR_HD void dict_pair_loads(const PairArgs &pa, long long r, const Lane &ln, D2 (&v)[NBT], double (&edge)[NBT])
 {
   static_assert(NBT >= 1 && NBT <= PAIR_MAX_BASES, "compiled bases");
-  D2 v[NBT]; double edge[NBT];                                        // x[r + b], x[r + b + 1]; edge: x[r + b - 1] in the wave's first lane, x[r + b + 2] in its last (set and read only under the same uniform conditions)
   const int lane = ln.lane();
 KS_PAIR_UNROLL
   for (int k = 0; k < NBT; k++) {                                     // every load first: nothing below waits for one base before the next is asked for
@@ -142,6 +144,11 @@ KS_PAIR_UNROLL
       if (pa.dmask >> k & 1u) edge[k] = ln.one(lane == 0 ? i - 1 : i + 2, lane == 0 || lane == 63);      // the wave's first and last lane have no neighbour to take these from: one load serves both
     }
   }
+}
+template <int NBT, class Lane>
+KS_PAIR_HD void dict_pair_sums(const PairArgs &pa, const double *coef, const unsigned *mask, int p0, int p1, long long r, const Lane &ln, const D2 (&v)[NBT], const double (&edge)[NBT], double &y0, double &y1)
+{
+  const int lane = ln.lane();
   const int stride = 3 * pa.nb;
   const double *c0 = coef + p0 * stride, *c1 = coef + p1 * stride;
   const unsigned m0 = mask[p0], m1 = mask[p1];
@@ -169,6 +176,13 @@ KS_PAIR_UNROLL
   a0 = pair_step(a0, 0.0, 0.0, m0, 31);                               // the padding slots of the one-row walk
   a1 = pair_step(a1, 0.0, 0.0, m1, 31);
   y0 = a0; y1 = a1;
+}
+template <int NBT, class Lane>
+KS_PAIR_HD void dict_pair_walk(const PairArgs &pa, const double *coef, const unsigned *mask, int p0, int p1, long long r, const Lane &ln, double &y0, double &y1)
+{
+  D2 v[NBT]; double edge[NBT];
+  dict_pair_loads<NBT>(pa, r, ln, v, edge);
+  dict_pair_sums<NBT>(pa, coef, mask, p0, p1, r, ln, v, edge, y0, y1);
 }
 
 } // namespace ksp

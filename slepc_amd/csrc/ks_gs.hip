@@ -532,6 +532,29 @@ struct FwdLane {
   __device__ __forceinline__ double up(double v, long long) const { return __shfl_up(v, 1); }
   __device__ __forceinline__ double down(double v, long long) const { return __shfl_down(v, 1); }
 };
+// The loads of the walk for the pipelined form, under no branch: a base the matrix does not have, an edge a base does not need and the lane's own pair ask with
+// the out-of-range offset (0 comes back, nothing is read), so the ten loads stand in one block behind each other and the only wait is the one in front of the
+// sums. With ksp::dict_pair_loads' uniform branches the compiler copied an edge value where two paths join and waited there, after the first base's loads:
+// behind the panel loads of the next tile that is a second pass through the queue. The own pair is put in from the registers afterwards (a select on a
+// uniform condition, behind every load). Same values as dict_pair_loads leaves in every element the sums read.
+template <int NBT>
+__device__ __forceinline__ void fwd_pair_loads(const ksp::PairArgs &pa, long long r, const FwdLane &ln, ksp::D2 (&v)[NBT], double (&edge)[NBT])
+{
+  const int lane = ln.lane();
+#pragma unroll
+  for (int q = 0; q < NBT; q++) {
+    const bool on = q < pa.nb;
+    const long long i = r + pa.base[q];
+    const auto t = __builtin_amdgcn_raw_buffer_load_b128(ln.rs, ln.off(i, on && i != ln.own), 0, 16); __builtin_memcpy(&v[q], &t, 16);
+    edge[q] = ln.one(lane == 0 ? i - 1 : i + 2, on && (pa.dmask >> q & 1u) && (lane == 0 || lane == 63));
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int q = 0; q < NBT; q++) {
+    const bool own = q < pa.nb && pa.base[q] == 0;
+    v[q].x = own ? ln.c.x : v[q].x; v[q].y = own ? ln.c.y : v[q].y;
+  }
+}
 // the last row of an odd n (ksp::dict_row_from_tables with x read by agent-scope loads: same entries, same chain)
 __device__ __forceinline__ double fwd_last_row(const FwdArgs &f, long long r, const double *x)
 {
@@ -546,12 +569,47 @@ __device__ __forceinline__ double fwd_last_row(const FwdArgs &f, long long r, co
   return acc;
 }
 
+// PIPE, the pipelined form: the panel loads of the tile of round i + 1 (and the tile's own rows of v) go out behind publish(i), in front of the A-phase of the
+// tile of round i - 1, and stay in flight through the poll, the barrier, the neighbour loads, the walk and the dots. Three panels are live then and the
+// registers hold two, so the panel just computed is parked in LDS (KT columns x 256 lanes x 16 B behind the pair tables; lane l writes and reads column i at
+// park[i * SW_BLOCK + l] and nobody else touches it: no barrier for the panel) and comes back to registers behind the A-phase. A round is
+//   C(i) from the registers the loads of the round before filled -> sc1 store, every wave's s_waitcnt vmcnt(0), barrier, flag (all as above; nothing else is
+//   in flight at that wait) -> park -> wave 0's first polls of A(i - 1) -> every wave's panel loads of round i + 1 -> A(i - 1) as above -> panel back.
+// Progress: C(i) waits for its own loads of V(:,0:k) and of its own rows of v only, which nobody stores in this launch before this lane does; publish(i)
+// still stands in front of A(i - 1), so the induction above holds word for word: A(i - 1) waits for C-phases of rounds <= i, every workgroup has run those
+// before it can wait, and the wait graph descends in the round index. The early loads read columns 0..k-1 and the tile's own rows of column c, never a row
+// another workgroup hands off. A re-poll queues behind the panel loads (vector loads return in order), and those wait for nothing.
+// What the form stands on, besides the branch-free loads of the walk (fwd_pair_loads above); all three were found in the assembly (profiles/r16_step_forward_pipeline.txt):
+//  - the panel loads stand under NO branch. The wait for wave 0's first polls counts the loads issued behind them (s_waitcnt vmcnt(KT + 2)); where a path
+//    around the loads joins, the compiler takes that path's count, 0, and wave 0 waits for the whole panel. A lane without a row pair (rows past n, no tile
+//    left, the last row of an odd n) reads rows 0 and 1 of columns 0..k-1 instead, one line per column, and nobody uses what it gets;
+//  - the barrier behind the matched poll orders LDS only. __syncthreads() puts s_waitcnt vmcnt(0) behind s_barrier (its workgroup-scope acquire), which
+//    holds every wave until its panel is in. The waves still load v only behind the s_barrier that wave 0 joins after its matched poll.
+template <int KT>
+__device__ __forceinline__ void fwd_load_panel(const double *V, long long ld, int n, int k, const double *v, long long t, bool has, ks_d2v (&xv)[KT], ks_d2v &s)
+{
+  const long long r = t * (2LL * SW_BLOCK) + 2LL * threadIdx.x;
+  const bool ok = has && r + 1 < n;
+  const long long rr = ok ? r : 0;
+  s = *reinterpret_cast<const ks_d2v *>(ok ? v + r : V);
+#pragma unroll
+  for (int i = 0; i < KT; i++) { const int ii = i < k ? i : k - 1; xv[i] = __builtin_nontemporal_load(reinterpret_cast<const ks_d2v *>(V + (long long)ii * ld + rr)); }
+}
+__device__ __forceinline__ void fwd_barrier_lds()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+  asm volatile("" ::: "memory");                           // no load of v moves over the barrier at compile time either
+}
+__host__ __device__ inline size_t fwd_park_offset(int npat, int nb) { return ((size_t)npat * (3 * nb * sizeof(double) + sizeof(unsigned)) + 15) & ~(size_t)15; }
+
 // amdgpu_waves_per_eu(1, 1): one workgroup of four waves per CU also where a narrow panel would leave registers for two (the hand-off's measured form)
 // S: the dots leave the launch as the partials of a dot sweep of S x gridDim.x workgroups in the same direction would - tile t0 of that sweep belongs to its
 // workgroup t0 mod (S gridDim.x), which is this launch's workgroup blockIdx.x in a round of parity (t0 / gridDim.x) mod S: S sets of accumulators, the
 // same products added in the same order, the same wave and block combine, so the next step starts from the bits the three launches leave.
 // rev: direction of the forward sweep (the replaced dot sweep's); rev_upd: the replaced update's, for a column that takes the generic form.
-template <int KT, int S>
+template <int KT, int S, bool PIPE = false>
 __global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_gs_update_fwd(const double *V, long long ld, int n, int k, double *v, double *__restrict__ partials, int rev, int rev_upd, FoldArgs fa, FwdArgs f)
 {
   __shared__ double c_lds[KS_MAX_COLS + 8];
@@ -635,19 +693,26 @@ __global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))
   for (int i = 0; i < KT; i++) pv[i] = ks_d2v{0.0, 0.0};
   long long pt = -1;
   bool dead = false;                                       // uniform: this workgroup has seen the abort word
+  ks_d2v *const park = reinterpret_cast<ks_d2v *>(reinterpret_cast<char *>(ksr::dict_pat_lds) + fwd_park_offset(f.npat, f.pa.nb)) + threadIdx.x;      // PIPE
+  ks_d2v nv[KT]; ks_d2v ns = {0.0, 0.0};                 // PIPE: panel and own rows of v of the next round's tile, in flight
+#pragma unroll
+  for (int i = 0; i < KT; i++) nv[i] = ks_d2v{0.0, 0.0};
+  if (PIPE) fwd_load_panel<KT>(V, ld, n, k, v, rev ? ntiles - 1 - (long long)blockIdx.x : (long long)blockIdx.x, (long long)blockIdx.x < ntiles, nv, ns);
   for (long long t0 = blockIdx.x;; t0 += gridDim.x) {
     const bool has = t0 < ntiles;
     const long long t = rev ? ntiles - 1 - t0 : t0;
-    ks_d2v cv[KT]; ks_d2v cs = {0.0, 0.0};
+    ks_d2v cv[KT]; ks_d2v cs = ns;
 #pragma unroll
-    for (int i = 0; i < KT; i++) cv[i] = ks_d2v{0.0, 0.0};
+    for (int i = 0; i < KT; i++) cv[i] = nv[i];
     if (has) {
       // ---- C-phase: upd_tiles<KT, 2, 2, 0, false>'s tile, the coefficients read from LDS as they are used ----
       const long long r = t * tile + 2LL * threadIdx.x;
       if (r + 1 < n) {
-        cs = *reinterpret_cast<const ks_d2v *>(v + r);
+        if (!PIPE) {
+          cs = *reinterpret_cast<const ks_d2v *>(v + r);
 #pragma unroll
-        for (int i = 0; i < KT; i++) { const int ii = i < k ? i : k - 1; cv[i] = __builtin_nontemporal_load(reinterpret_cast<const ks_d2v *>(V + (long long)ii * ld + r)); }
+          for (int i = 0; i < KT; i++) { const int ii = i < k ? i : k - 1; cv[i] = __builtin_nontemporal_load(reinterpret_cast<const ks_d2v *>(V + (long long)ii * ld + r)); }
+        }
 #pragma unroll
         for (int p = 0; p < 2; p++)
 #pragma unroll
@@ -657,13 +722,13 @@ __global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))
       } else if (r < n) {                                  // odd n: the last row on its own, stored by an 8-byte agent-scope (sc1) store
         double s1 = v[r];
 #pragma unroll
-        for (int i = 0; i < KT; i++) { const int ii = i < k ? i : k - 1; cv[i].x = V[(long long)ii * ld + r]; }
+        for (int i = 0; i < KT; i++) { const int ii = i < k ? i : k - 1; cv[i] = ks_d2v{V[(long long)ii * ld + r], 0.0}; }
 #pragma unroll
         for (int p = 0; p < 2; p++)
 #pragma unroll
           for (int i = 0; i < KT; i++) s1 = fma((i < k) ? -spend[p * KS_PSTRIDE + i] : 0.0, cv[i].x, s1);
         if (scal) s1 *= alpha;
-        cs.x = s1;
+        cs = ks_d2v{s1, 0.0};
         __hip_atomic_store(v + r, s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       if (f.lag_odd && (blockIdx.x & 1)) for (int q = 0; q < 8; q++) __builtin_amdgcn_s_sleep(127);
@@ -672,30 +737,55 @@ __global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave
     __syncthreads();
     if (has && threadIdx.x == 0) __hip_atomic_store(f.flags + t, f.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // ---- A-phase of the tile of the round before ----
-    if (pt >= 0 && !dead) {
-      if (w == 0) {
-        // lane 3 kb + wh polls the wh-th tile that holds rows of base kb's window [r0 + b - d, r0 + 511 + b + d] (d = 1 for a base with neighbours);
-        // lane 63 reads the abort word
-        const int kb = lane / 3, wh = lane % 3;
-        long long tl = -1;
-        int b = 0; bool isb = false;
+    // ---- wave 0: which flags the A-phase of the tile of the round before polls ----
+    const bool arun = pt >= 0 && !dead;
+    long long tl = -1;
+    if (arun && w == 0) {
+      // lane 3 kb + wh polls the wh-th tile that holds rows of base kb's window [r0 + b - d, r0 + 511 + b + d] (d = 1 for a base with neighbours);
+      // lane 63 reads the abort word
+      const int kb = lane / 3, wh = lane % 3;
+      int b = 0; bool isb = false;
 #pragma unroll
-        for (int q = 0; q < 5; q++) if (q == kb && q < f.pa.nb) { b = f.pa.base[q]; isb = true; }
-        if (isb) {
-          const int d = (int)(f.pa.dmask >> kb & 1u);
-          long long lo = pt * tile + b - d, hi = pt * tile + (tile - 1) + b + d;
-          if (lo < 0) lo = 0;
-          if (hi > (long long)n - 1) hi = (long long)n - 1;
-          if (lo <= hi && (lo >> 9) + wh <= (hi >> 9)) tl = (lo >> 9) + wh;
-        }
-        if (tl == pt) tl = -1;                             // the workgroup's own tile: stored, drained and behind the barrier above
+      for (int q = 0; q < 5; q++) if (q == kb && q < f.pa.nb) { b = f.pa.base[q]; isb = true; }
+      if (isb) {
+        const int d = (int)(f.pa.dmask >> kb & 1u);
+        long long lo = pt * tile + b - d, hi = pt * tile + (tile - 1) + b + d;
+        if (lo < 0) lo = 0;
+        if (hi > (long long)n - 1) hi = (long long)n - 1;
+        if (lo <= hi && (lo >> 9) + wh <= (hi >> 9)) tl = (lo >> 9) + wh;
+      }
+      if (tl == pt) tl = -1;                               // the workgroup's own tile: stored, drained and behind the barrier above
+    }
+    unsigned fl0 = f.epoch, ab0 = 0;
+    int pp0 = 0, pp1 = 0;                                  // PIPE: the row patterns of the A-phase's tile, asked for in front of the panel loads as well
+    if (PIPE) {
+      // ---- park the tile's panel, wave 0's first polls, every wave's loads of the next round's tile ----
+#pragma unroll
+      for (int i = 0; i < KT; i++) park[i * SW_BLOCK] = cv[i];
+      if (arun && w == 0) {
+        if (tl >= 0) fl0 = __hip_atomic_load(f.flags + tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 63) ab0 = __hip_atomic_load(f.ctl + KS_FWD_ABORT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      ksr::pair_patterns(f.rowpat, arun ? pt * tile + 2LL * threadIdx.x : 0, n, pp0, pp1);
+      __builtin_amdgcn_sched_barrier(0);
+      const long long tn0 = t0 + gridDim.x;
+      fwd_load_panel<KT>(V, ld, n, k, v, rev ? ntiles - 1 - tn0 : tn0, has && tn0 < ntiles, nv, ns);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // ---- A-phase of the tile of the round before ----
+    if (arun) {
+      if (w == 0) {
         int res;
+        bool polled = PIPE;                                // the first polls are on their way already
         const long long tstart = wall_clock64();
         for (;;) {
-          unsigned fl = f.epoch, ab = 0;
-          if (tl >= 0) fl = __hip_atomic_load(f.flags + tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (lane == 63) ab = __hip_atomic_load(f.ctl + KS_FWD_ABORT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          unsigned fl = fl0, ab = ab0;
+          if (!polled) {
+            fl = f.epoch; ab = 0;
+            if (tl >= 0) fl = __hip_atomic_load(f.flags + tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 63) ab = __hip_atomic_load(f.ctl + KS_FWD_ABORT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+          polled = false;
           if (__any(lane == 63 && ab == f.epoch)) { res = 0; break; }
           if (__all(fl == f.epoch) && (int)blockIdx.x != f.abort_wg && f.budget != 0) { res = 1; break; }      // (a budget of 0, a test hook: every wait gives up)
           if ((int)blockIdx.x == f.abort_wg || (unsigned long long)(wall_clock64() - tstart) >= f.budget) {
@@ -706,14 +796,18 @@ __global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
         if (lane == 0) poll_sh = res;
       }
-      __syncthreads();                                     // the other waves load v only behind this barrier
+      if (PIPE) fwd_barrier_lds(); else __syncthreads();   // the other waves load v only behind this barrier
       if (poll_sh) {
         const long long r = pt * tile + 2LL * threadIdx.x;
         const FwdLane ln(v, n, r, ksp::D2{ps.x, ps.y});
-        int p0, p1;
-        ksr::pair_patterns(f.rowpat, r, n, p0, p1);
+        int p0 = pp0, p1 = pp1;
+        if (!PIPE) ksr::pair_patterns(f.rowpat, r, n, p0, p1);
         double y0, y1;
-        ksp::dict_pair_walk<5>(f.pa, sc, sm, p0, p1, r, ln, y0, y1);
+        if (PIPE) {
+          ksp::D2 xv[5]; double edge[5];
+          fwd_pair_loads<5>(f.pa, r, ln, xv, edge);
+          ksp::dict_pair_sums<5>(f.pa, sc, sm, p0, p1, r, ln, xv, edge, y0, y1);
+        } else ksp::dict_pair_walk<5>(f.pa, sc, sm, p0, p1, r, ln, y0, y1);
         if (r + 1 < n) {
           __builtin_nontemporal_store(ks_d2v{y0, y1}, reinterpret_cast<ks_d2v *>(f.y + r));
 #pragma unroll
@@ -740,7 +834,7 @@ __global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))
     }
     if (!has) break;
 #pragma unroll
-    for (int i = 0; i < KT; i++) pv[i] = cv[i];
+    for (int i = 0; i < KT; i++) pv[i] = PIPE ? park[i * SW_BLOCK] : cv[i];
     ps = cs; pt = t; pset = rset; rset = rset + 1 == S ? 0 : rset + 1;
   }
   if (dead) return;                                        // the dot sweep behind this launch rewrites every partial
@@ -894,6 +988,32 @@ bool fwd_eligible(ks_bv bv, ks_mat A, int col, int *grid)
 // most one round (a few us) behind its consumer; 1 ms of wall time is some 180 such hops and twice the whole launch. Ticks of wall_clock64 (10 ns).
 constexpr long long FWD_BUDGET_TICKS = 100000;
 
+// The pipelined form (k_gs_update_fwd<KT, S, true>) from this column count on: below it a round's streaming is short and the parked panel costs what the early
+// loads gain (profiles/r16_step_forward_pipeline.txt). Its dynamic LDS is the pair tables plus KT x 4 KiB of parked panel; a matrix whose tables leave no
+// room for that beside the kernel's static LDS takes the form without the park.
+#ifndef KS_FWD_PIPE_MIN_K
+#define KS_FWD_PIPE_MIN_K 13
+#endif
+constexpr int FWD_PIPE_MIN_K = KS_FWD_PIPE_MIN_K;
+constexpr size_t FWD_LDS_CU = 160 * 1024;
+template <int KT, int S>
+static int fwd_pipe_prepare(ks_ctx ctx, size_t lds, bool *fits)
+{
+  static thread_local std::vector<std::pair<int, size_t>> seen;      // device -> static LDS of this symbol, its dynamic limit raised
+  const void *fn = (const void *)k_gs_update_fwd<KT, S, true>;
+  size_t stat = 0; bool have = false;
+  for (const auto &e : seen) if (e.first == ctx->device) { stat = e.second; have = true; }
+  if (!have) {
+    hipFuncAttributes at; KS_HIP(hipFuncGetAttributes(&at, fn));
+    stat = at.sharedSizeBytes;
+    KS_CHECK(stat < FWD_LDS_CU, KS_ERR_PLIB, "forward update: %zu bytes of static LDS", stat);
+    KS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FWD_LDS_CU - stat)));
+    seen.emplace_back(ctx->device, stat);
+  }
+  *fits = stat + lds <= FWD_LDS_CU;
+  return KS_SUCCESS;
+}
+
 int launch_update_fwd(ks_bv bv, ks_mat A, int col, double *v, const GsArgs &a, int grid)
 {
   ks_ctx ctx = bv->ctx;
@@ -943,7 +1063,11 @@ int launch_update_fwd(ks_bv bv, ks_mat A, int col, double *v, const GsArgs &a, i
   bv->last_grid = sets * grid;
   const size_t lds = ksr::dict_pair_lds_bytes(A);
 #define LAUNCH_FWD_S(KT, S) hipLaunchKernelGGL((k_gs_update_fwd<KT, S>), dim3(grid), dim3(SW_BLOCK), lds, ctx->stream, V, (long long)bv->ld, bv->n, k, v, bv->partials_alt, rev, rev_upd, fa, f)
-#define LAUNCH_FWD(KT) do { constexpr int SK = KT + 2 <= 9 ? 4 : (KT + 2 <= 14 ? 3 : (KT + 2 <= 29 ? 2 : 1)); if (sets == SK) LAUNCH_FWD_S(KT, SK); else LAUNCH_FWD_S(KT, 1); } while (0)
+#define LAUNCH_FWD_P(KT, S) do { bool pipe = false; const size_t lds_pipe = fwd_park_offset(f.npat, f.pa.nb) + (size_t)KT * SW_BLOCK * sizeof(ks_d2v);                                   \
+    if constexpr (KT >= FWD_PIPE_MIN_K) { const int rc = fwd_pipe_prepare<KT, S>(ctx, lds_pipe, &pipe); if (rc) return rc;                                                               \
+      if (pipe) hipLaunchKernelGGL((k_gs_update_fwd<KT, S, true>), dim3(grid), dim3(SW_BLOCK), lds_pipe, ctx->stream, V, (long long)bv->ld, bv->n, k, v, bv->partials_alt, rev, rev_upd, fa, f); } \
+    if (!pipe) LAUNCH_FWD_S(KT, S); } while (0)
+#define LAUNCH_FWD(KT) do { constexpr int SK = KT + 2 <= 9 ? 4 : (KT + 2 <= 14 ? 3 : (KT + 2 <= 29 ? 2 : 1)); if (sets == SK) LAUNCH_FWD_P(KT, SK); else LAUNCH_FWD_P(KT, 1); } while (0)
   switch (k) {
     KS_KT_CASE(1, LAUNCH_FWD) KS_KT_CASE(2, LAUNCH_FWD) KS_KT_CASE(3, LAUNCH_FWD) KS_KT_CASE(4, LAUNCH_FWD) KS_KT_CASE(5, LAUNCH_FWD) KS_KT_CASE(6, LAUNCH_FWD) KS_KT_CASE(7, LAUNCH_FWD) KS_KT_CASE(8, LAUNCH_FWD)
     KS_KT_CASE(9, LAUNCH_FWD) KS_KT_CASE(10, LAUNCH_FWD) KS_KT_CASE(11, LAUNCH_FWD) KS_KT_CASE(12, LAUNCH_FWD) KS_KT_CASE(13, LAUNCH_FWD) KS_KT_CASE(14, LAUNCH_FWD) KS_KT_CASE(15, LAUNCH_FWD) KS_KT_CASE(16, LAUNCH_FWD)
@@ -952,6 +1076,7 @@ int launch_update_fwd(ks_bv bv, ks_mat A, int col, double *v, const GsArgs &a, i
     default: KS_FAIL(KS_ERR_PLIB, "forward update with %d columns", k);
   }
 #undef LAUNCH_FWD
+#undef LAUNCH_FWD_P
 #undef LAUNCH_FWD_S
   KS_HIP(hipGetLastError());
   std::swap(bv->gs, bv->gs_alt); std::swap(bv->partials, bv->partials_alt);
