@@ -109,6 +109,12 @@ enum { KS_DEBUG_NO_FUSED_GS = 0, KS_DEBUG_NO_MFMA = 1, KS_DEBUG_NO_SPMV_DOT = 2,
        KS_DEBUG_NO_DICT_PAIRS = 8 /* read at launch: the dictionary product one row per lane also where the matrix has the pair form */,
        KS_DEBUG_NO_STEP_FORWARD = 9 /* read at enqueue: the final update of a Krylov step, the next product and the next dot sweep as the launches of their own */ };
 int ks_ctx_set_debug(ks_ctx ctx, int key, long long value);
+/* Test hook (KSD_TEST_HOOKS): how often the library decided, on this context since the last reset, that a basis is resident in the Infinity Cache
+ * (plain loads) and how often that it streams (nontemporal loads). Every evaluation of that rule counts: one per launch in the dot sweep, the
+ * Gram-Schmidt update, the fused restart, the Ritz residual, the block residual and the oblique projection, and one where the forward update asks
+ * whether it applies (no launch of its own; not reached when an earlier condition already rules it out). A test reads the counts around a call instead
+ * of restating the size rule. plain, streaming: either may be NULL; reset != 0 clears both after reading. */
+int ks_ctx_basis_load_counts(ks_ctx ctx, long long *plain, long long *streaming, int reset);
 int ks_ctx_sync_count(ks_ctx ctx, long long *count);   /* instrumentation: host waits on the context's stream made by the library so far */
 int ks_ctx_device_info(ks_ctx ctx, char *arch, int arch_len, int *num_cu, size_t *mem_total);
 /* Which HIP runtime the library's calls are bound to. A process can map TWO copies of libamdhip64 (PyTorch wheels bundle one under the file name

@@ -4,6 +4,7 @@
   kernel_inventory.py --compiled                 instantiations of each family, from `nm -C slepc_amd/libksgpu.so`
   kernel_inventory.py --launched TRACE.csv ...   per family: compiled / launched / never launched, from rocprofv3 --kernel-trace
                                                  CSV files (*_kernel_trace.csv; a directory is searched for them)
+  --family NAME ...                              report these families only (a trace of part of the suite)
 
 Host tool, no GPU needed. Instantiations no input can reach are listed in UNREACHABLE with the reason and reported apart."""
 import argparse
@@ -16,7 +17,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "slepc_amd", "libksgpu.so")
-FAMILIES = ["k_gs_update", "k_dot_sweep", "k_dot_spmv_dict", "k_panel_mult", "k_panel_dot_direct", "k_panel_mult_direct", "k_multvec"]
+FAMILIES = ["k_gs_update", "k_dot_sweep", "k_dot_spmv_dict", "k_panel_mult", "k_panel_dot_direct", "k_panel_mult_direct", "k_multvec",
+            "k_ritz_residual", "k_block_residual", "k_oblique_dot", "k_oblique_update", "k_restart_fused"]
 _PAT = re.compile(r"\b(%s)<([^<>()]*)>\(" % "|".join(FAMILIES))
 
 # instantiations no input reaches (the dispatch compiles them, nothing selects them)
@@ -69,12 +71,14 @@ def main(argv=None):
     ap.add_argument("--compiled", action="store_true", help="list the compiled instantiations")
     ap.add_argument("--launched", nargs="+", metavar="TRACE_CSV", help="rocprofv3 kernel-trace CSV files or directories")
     ap.add_argument("--lib", default=LIB)
+    ap.add_argument("--family", nargs="+", choices=FAMILIES, metavar="NAME", help="report these families only")
     ap.add_argument("--verbose", action="store_true", help="with --launched: name every never-launched instantiation")
     a = ap.parse_args(argv)
     comp = compiled(a.lib)
-    total = sum(len(v) for v in comp.values())
+    families = a.family or FAMILIES
+    total = sum(len(comp[f]) for f in families)
     if a.compiled or not a.launched:
-        for f in FAMILIES:
+        for f in families:
             print("%-22s %4d" % (f, len(comp[f])))
             for k in sorted(comp[f], key=_sort_key):
                 print("    " + k)
@@ -84,7 +88,7 @@ def main(argv=None):
         print("trace files: %d" % len(files))
         print("%-22s %8s %8s %13s %11s" % ("family", "compiled", "launched", "never-launch", "unreachable"))
         never_all = []
-        for f in FAMILIES:
+        for f in families:
             c = comp[f]
             hit = {k for k in c if k in seen}
             unr = {k for k in c - hit if k in UNREACHABLE}

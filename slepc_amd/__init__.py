@@ -124,6 +124,12 @@ class Context:
         """Test hooks (ks_ctx_set_debug): run the path a fast one replaces, or the multi-rank path on one rank."""
         _lib.check(self.L.ks_ctx_set_debug(self.h, self.DEBUG_KEYS[key], int(value)))
 
+    def basis_load_counts(self, reset=False):
+        """Test hook (ks_ctx_basis_load_counts): (plain, streaming) - how often the library chose each load form for a basis since the last reset."""
+        p = C.c_longlong(); s = C.c_longlong()
+        _lib.check(self.L.ks_ctx_basis_load_counts(self.h, C.byref(p), C.byref(s), int(bool(reset))))
+        return p.value, s.value
+
     def sync_count(self):
         v = C.c_longlong(); _lib.check(self.L.ks_ctx_sync_count(self.h, C.byref(v))); return v.value
 

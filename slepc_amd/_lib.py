@@ -35,6 +35,7 @@ _SIG = {
     "ks_ctx_synchronize": [vp],
     "ks_ctx_sync_count": [vp, llp],
     "ks_ctx_set_debug": [vp, C.c_int, C.c_longlong],
+    "ks_ctx_basis_load_counts": [vp, llp, llp, C.c_int],
     "ks_ctx_device_info": [vp, C.c_char_p, C.c_int, ip, C.POINTER(C.c_size_t)],
     "ks_runtime_info": [C.c_char_p, C.c_int],
     "ks_runtime_allow_multiple": [C.c_int],

@@ -151,7 +151,7 @@ int ksk_dot(ks_bv bv, const double *A, int lda, int ncols, const double *y, bool
   const int dot_per_cu = std::max(1, std::min(4, (30 + ncols - 1) / ncols));
   const KsGsState *g = gate ? bv->gs : nullptr;
   bv->spec.valid = false;                                       // the partials a chained Gram-Schmidt pass would have read are rewritten
-  const int plain = ks_basis_is_cache_resident((size_t)(bv->nc + bv->m), (size_t)bv->ld);
+  const int plain = ks_basis_loads_plain(bv->ctx, (size_t)(bv->nc + bv->m), (size_t)bv->ld);
   // behind a forward final update (bv->fwd.gate, set by the enqueue around this call) the sweep is the fallback: in the common case it returns at once. It
   // takes and toggles the direction like any sweep: the forward launch ran in this direction and left the sums this sweep would leave
   unsigned *const fctl = bv->fwd.gate.ctl; const unsigned fepoch = bv->fwd.gate.epoch;

@@ -210,6 +210,16 @@ extern "C" int ks_ctx_set_debug(ks_ctx ctx, int key, long long value)
   }
   return KS_SUCCESS;
 }
+
+// the verdicts of ks_basis_loads_plain (ks_sweeps.cuh) on this context since the last reset: evaluations of the rule that said plain loads, and streaming ones
+extern "C" int ks_ctx_basis_load_counts(ks_ctx ctx, long long *plain, long long *streaming, int reset)
+{
+  KS_CHECK(ctx, KS_ERR_ARG_NULL, "ctx is NULL");
+  if (plain) *plain = ctx->basis_loads[0];
+  if (streaming) *streaming = ctx->basis_loads[1];
+  if (reset) ctx->basis_loads[0] = ctx->basis_loads[1] = 0;
+  return KS_SUCCESS;
+}
 #endif
 
 extern "C" int ks_ctx_sync_count(ks_ctx ctx, long long *count)

@@ -191,7 +191,7 @@ int ks_ritz_residual(ks_bv R, double *Rd, ks_bv Vs, const double *Vd, long long 
     const bool out = Xd || BXd;
     const bool v2 = ldv % 2 == 0 && ldav % 2 == 0 && (!gen || ldbv % 2 == 0) && ldr % 2 == 0 && aligned16(Vd) && aligned16(AVd) && (!gen || aligned16(BVd)) && aligned16(Rd)
                     && (!Xd || (ldx % 2 == 0 && aligned16(Xd))) && (!BXd || (ldbx % 2 == 0 && aligned16(BXd)));
-    const bool plain = ks_basis_is_cache_resident((size_t)(gen ? 3 : 2) * m + ncols, (size_t)R->ld);
+    const bool plain = ks_basis_loads_plain(ctx, (size_t)(gen ? 3 : 2) * m + ncols, (size_t)R->ld);
     const int grid = ks_sweep_grid_for(ctx, n, v2 ? 2 : 1, nullptr, 2);      // two workgroups per CU: what the registers of the widest form leave room for; the same grid for every pass
     R->last_grid = grid;
     const int jt = gen ? GD_JT_GEN : GD_JT_STD;

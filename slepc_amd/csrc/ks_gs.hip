@@ -922,7 +922,7 @@ int launch_update(ks_bv bv, int col, double *v, int slot, const GsArgs *fold = n
   const long long ntl = ((long long)bv->n + 511) / 512;
   const int upd_per_cu = ntl >= 16LL * ctx->num_cu ? 1 : (ntl >= 4LL * ctx->num_cu ? 2 : 0);
   (void)slot;
-  const int plain = ks_basis_is_cache_resident((size_t)(bv->nc + bv->m), (size_t)bv->ld);
+  const int plain = ks_basis_loads_plain(ctx, (size_t)(bv->nc + bv->m), (size_t)bv->ld);
   const int rev = rev_saved >= 0 ? rev_saved : bv->sweep_dir;
   if (rev_saved < 0) bv->sweep_dir ^= 1;               // every sweep over the basis runs opposite to the one before it (dot sweeps included): it starts on
                                                        // the tail the previous one left in the 256 MB Infinity Cache (about a tenth of a 2.4 GB basis)
@@ -976,7 +976,7 @@ bool fwd_eligible(ks_bv bv, ks_mat A, int col, int *grid)
   if ((far + 511) / 512 + 2 > g) return no("the far neighbours are more than one round away");
   if (!bv->fwd.force) {
     if (ntiles < 16LL * ctx->num_cu) return no("fewer than 16 tiles per CU");
-    if (ks_basis_is_cache_resident((size_t)(bv->nc + bv->m), (size_t)bv->ld)) return no("the basis is resident in the Infinity Cache");
+    if (ks_basis_loads_plain(ctx, (size_t)(bv->nc + bv->m), (size_t)bv->ld)) return no("the basis is resident in the Infinity Cache");
   }
   if (g > KS_MAX_BLOCKS) return no("grid");
   bv->fwd.why = "";

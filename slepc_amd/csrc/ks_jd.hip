@@ -177,7 +177,7 @@ int launch_oblique_dot(ks_bv Z, const double *Zd, int k, double a, const double 
   ks_ctx ctx = Z->ctx;
   const int n = Z->n;
   const int per_cu = std::max(1, std::min(4, (30 + k - 1) / k));                 // ksk_dot's rule: about 120 KiB of loads in flight per CU
-  const int plain = ks_basis_is_cache_resident((size_t)(2 * (Z->nc + Z->m)), (size_t)Z->ld);
+  const int plain = ks_basis_loads_plain(ctx, (size_t)(2 * (Z->nc + Z->m)), (size_t)Z->ld);
   const long long ldz = Z->ld;
   Z->spec.valid = false;
   int grid = 1;

@@ -82,7 +82,7 @@ int ksl_block_residual(ks_bv R, int ncols, const double *AX, long long ldax, con
   R->spec.valid = false;                                        // the partials of this BV are rewritten
   if (n > 0) {
     const bool v2 = ldax % 2 == 0 && ldbx % 2 == 0 && ldr % 2 == 0 && aligned16(AX) && aligned16(BX) && aligned16(Rd);
-    const bool plain = ks_basis_is_cache_resident((size_t)3 * ncols, (size_t)R->ld);
+    const bool plain = ks_basis_loads_plain(ctx, (size_t)3 * ncols, (size_t)R->ld);
     KsProfScope ps(ctx, KS_K_OTHER, 24.0 * n * ncols);
 #define KSL_LAUNCH(KT, VEC, PL) do { const int grid = ks_sweep_grid_for(ctx, n, VEC, (const void *)k_block_residual<KT, VEC, PL>, 0); R->last_grid = grid;            \
       hipLaunchKernelGGL((k_block_residual<KT, VEC, PL>), dim3(grid), dim3(SW_BLOCK), 0, ctx->stream, AX, ldax, BX, ldbx, Rd, ldr, n, th, R->partials); } while (0)

@@ -385,7 +385,7 @@ int ksp_restart_fused(ks_bv bv, const double *V0, int k, double *vsrc, double *v
   const int n = bv->n, a0 = (int)((A - V0) / bv->ld);
   KS_CHECK(k >= 1 && k <= RF_KMAX && nout >= 1 && nout <= 16 && kin >= 1 && a0 >= 0 && a0 + kin <= k, KS_ERR_PLIB, "fused restart %d columns, %d active from %d, %d out", k, kin, a0, nout);
   KS_CHECK(bv->ld % 2 == 0 && (((uintptr_t)V0 | (uintptr_t)vsrc | (uintptr_t)vdst | (uintptr_t)C) & 15) == 0, KS_ERR_PLIB, "fused restart needs 16-byte aligned columns");
-  const int plain = ksk::ks_basis_is_cache_resident((size_t)(bv->nc + bv->m), (size_t)bv->ld);
+  const int plain = ksk::ks_basis_loads_plain(ctx, (size_t)(bv->nc + bv->m), (size_t)bv->ld);
   static thread_local std::vector<int> prepared[2];               // devices on which this symbol may already have 128 KB of dynamic LDS
   if (std::find(prepared[plain].begin(), prepared[plain].end(), ctx->device) == prepared[plain].end()) {
     KS_HIP(hipFuncSetAttribute(plain ? (const void *)k_restart_fused<true> : (const void *)k_restart_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RF_LDS));

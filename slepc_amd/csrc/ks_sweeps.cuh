@@ -33,6 +33,14 @@ __device__ __forceinline__ uint4 ldstream4(const uint4 *p) { const ks_u4v t = __
 __device__ __forceinline__ double2 ldplain2(const double *p) { return *reinterpret_cast<const double2 *>(p); }
 template <bool PLAIN> __device__ __forceinline__ double2 ldbasis2(const double *p) { return PLAIN ? ldplain2(p) : ldcol2(p); }
 static inline int ks_basis_is_cache_resident(size_t columns, size_t ld) { return columns * ld * sizeof(double) <= (size_t)200 * 1000 * 1000; }
+// The launchers' form of that choice: the verdict, counted on the context (ks_ctx_basis_load_counts: a test reads which form of a sweep it ran
+// instead of restating the size rule). Host side only; nothing a kernel sees changes.
+static inline int ks_basis_loads_plain(ks_ctx ctx, size_t columns, size_t ld)
+{
+  const int plain = ks_basis_is_cache_resident(columns, ld);
+  ctx->basis_loads[plain ? 0 : 1]++;
+  return plain;
+}
 
 constexpr int SW_BLOCK = 256;
 constexpr int SW_WAVES = SW_BLOCK / 64;

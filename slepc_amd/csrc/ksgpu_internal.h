@@ -73,6 +73,7 @@ struct ks_ctx_s {
   // test hooks (ks_ctx_set_debug; each makes a test run the path the fast one replaces, or a multi-rank path on one rank)
   struct { bool no_fused_gs = false, no_mfma = false, no_spmv_dot = false, force_multi = false, no_dict_patterns = false, no_restart_fusion = false, no_dict_pairs = false, no_step_forward = false; unsigned oneshot_seq0 = 0; } dbg;
   long long nsync = 0;              // host synchronisations of the context's stream made by the library (ks_ctx_sync_count)
+  long long basis_loads[2] = {0, 0};   // verdicts of ks_basis_loads_plain (ks_sweeps.cuh): plain loads [0], streaming loads [1]
   int num_cu = 256;
   char arch[64] = {0};
   size_t mem_total = 0;

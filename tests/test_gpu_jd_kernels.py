@@ -7,6 +7,9 @@ Exact test. Integer-valued data: |u|, |v| <= 2, |a|, |b| <= 2, |s| <= 2, so |w0|
 included, stays below 2^53 and is exact in double; the test also checks that on the data itself with sums of absolute values. w must equal numpy's bit
 for bit and dot exactly.
 
+The same exact test with nontemporal loads of Z (a few rows, the large leading dimension of tests/stream_cases.py) and with a second tile per workgroup
+(n above 2^17: the bounds for those rows are in that test's docstring); every exact call asserts the load form the library reports.
+
 Random doubles, against numpy.longdouble. With w0abs = |s| (|a u| + |b v|), Habs = |Z|^T w0abs, Cabs = |Minv| Habs: forming w0 is three roundings
 (a u, the fma with b v, the scaling): 3 eps w0abs; h is a sum of n products in some order: (n + 1) eps Habs plus |Z|^T of the error of w0, together
 (n + 4) eps Habs; c is a k-term fma chain on it: (n + k + 5) eps Cabs; w is a k-term fma chain from w0: (k + 1) eps (w0abs + |Y| Cabs) plus the errors
@@ -21,6 +24,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import stream_cases as sc
 from thread_comm import ThreadComm, run_ranks
 
 pytestmark = pytest.mark.gpu
@@ -28,6 +32,10 @@ pytestmark = pytest.mark.gpu
 EPS = np.finfo(float).eps
 ARG_SIZ, ARG_WRONG, ARG_OUTOFRANGE, ARG_INCOMP, ARG_NULL = 60, 62, 63, 75, 85
 KS = [0, 1, 2, 7, 8, 9, 33, 64, 65]
+# oblique_kt_for compiles the column tiles 1..8, 10, 12, 16, 20, 24, 32, 40, 48, 56, 64: the ones KS does not reach, filled exactly, and one column past
+# a tile (the next tile with its last columns clamped)
+KS_TILES_EXACT = [3, 4, 5, 6, 12, 16, 20, 24, 32, 48, 56]
+KS_TILES_PAST = [11, 13, 17, 21, 25, 41, 49, 57]
 WCOLS = 68                           # columns of Y and Z: l <= 2, k <= 65
 LIMIT = 2.0 ** 53
 
@@ -95,21 +103,23 @@ def _reference(Zk, Yk, Minv, a, u, b, v, s, e_is_w, e):
     return w, dot, big
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 4099])
-@pytest.mark.parametrize("odd_ld", [True, False])
-def test_oblique_project_exact(ctx, n, odd_ld):
-    """Every k of KS with every combination of s, v and e present or absent (8 per k), u == w on every other call, e == w on every other call that has an
-    e, the active ranges of Y and Z starting at 0 or 2 independently, ldm > k on every third call. Odd ld: the scalar path; the default ld: the 16-byte
-    path. Y, Z and the inputs keep their bits."""
-    rng = np.random.default_rng(9000 * n + odd_ld)
-    H = _Harness(ctx, n, ld=_odd_ld(n) if odd_ld else 0)
-    assert (H.Y.ld % 2 == 1) == odd_ld
+def _exact_plan(every_tile):
+    """(k, combinations of s, v and e) of an exact run: KS with all eight; every_tile: also the other tiles of oblique_kt_for, filled exactly with all
+    eight and one column past with two (everything present, nothing present)"""
+    plan = [(k, range(8)) for k in KS]
+    if every_tile:
+        plan += [(k, range(8)) for k in KS_TILES_EXACT] + [(k, (7, 0)) for k in KS_TILES_PAST]
+    return plan
+
+
+def _oblique_exact(ctx, H, n, rng, plan, form, idx):
+    """The calls of `plan` on the harness H against numpy on integer data, bit for bit. `form`: the load form the library must report for the dot
+    sweep of every call, "plain" or "streaming" (one verdict per chunk of 64 columns; none at k = 0, which has no sweep over Z)."""
     Zm = _ints(rng, (n, WCOLS), 1)
     Ym = _sparse_rows(rng, n, WCOLS, 2)
     H.Z.set_dense(Zm); H.Y.set_dense(Ym)
-    idx = int(odd_ld)
-    for k in KS:
-        for combo in range(8):
+    for k, combos in plan:
+        for combo in combos:
             has_s, has_v, has_e = bool(combo & 1), bool(combo & 2), bool(combo & 4)
             lz = (0, 2)[idx % 2]; ly = (0, 2)[(idx // 2) % 2]; ldm = max(k, 1) + (3 if idx % 3 == 0 else 0)
             u_is_w = idx % 2 == 1; e_is_w = has_e and (idx // 2) % 2 == 1
@@ -128,8 +138,10 @@ def test_oblique_project_exact(ctx, n, odd_ld):
             H.Z.SetActiveColumns(lz, lz + k); H.Y.SetActiveColumns(ly, ly + k)
             iw = 0 if u_is_w else 3
             ie = (iw if e_is_w else 4) if has_e else None
-            rc, dot = H.call(ldm, a, 0, b, 1 if has_v else None, 2 if has_s else None, iw, ie, want_dot=has_e)
+            (rc, dot), counts = sc.counted(ctx, lambda: H.call(ldm, a, 0, b, 1 if has_v else None, 2 if has_s else None, iw, ie, want_dot=has_e))
             assert rc == 0, (k, combo, rc)
+            sweeps = (k + 63) // 64
+            assert counts == ((sweeps, 0) if form == "plain" else (0, sweeps)), (k, combo, form, counts)
             w, dref, big = _reference(Zk, Yk, Minv, a, vecs[:, 0], b, vecs[:, 1] if has_v else None, vecs[:, 2] if has_s else None, e_is_w, vecs[:, 4] if has_e else None)
             assert big < LIMIT, (k, combo, big)
             got = H.vec.dense()
@@ -142,6 +154,93 @@ def test_oblique_project_exact(ctx, n, odd_ld):
             assert np.array_equal(got[:, keep], vecs[:, keep])
     H.Z.SetActiveColumns(0, WCOLS); H.Y.SetActiveColumns(0, WCOLS)
     assert np.array_equal(H.Z.dense(), Zm) and np.array_equal(H.Y.dense(), Ym)
+    H.destroy()
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 4099])
+@pytest.mark.parametrize("odd_ld", [True, False])
+def test_oblique_project_exact(ctx, n, odd_ld):
+    """Every k of KS with every combination of s, v and e present or absent (8 per k), u == w on every other call, e == w on every other call that has an
+    e, the active ranges of Y and Z starting at 0 or 2 independently, ldm > k on every third call. Odd ld: the scalar path; the default ld: the 16-byte
+    path. Y, Z and the inputs keep their bits. At n = 65 and n = 4099 also the column tiles of oblique_kt_for that KS leaves out (_exact_plan). Y and Z
+    of a few thousand rows: every dot sweep reports plain loads."""
+    rng = np.random.default_rng(9000 * n + odd_ld)
+    H = _Harness(ctx, n, ld=_odd_ld(n) if odd_ld else 0)
+    assert (H.Y.ld % 2 == 1) == odd_ld
+    _oblique_exact(ctx, H, n, rng, _exact_plan(n in (65, 4099)), "plain", int(odd_ld))
+
+
+@pytest.mark.parametrize("n", [1, 511, 513, 4099])
+def test_oblique_project_streaming_loads_exact(ctx, n):
+    """The plain == 0 branch of k_oblique_dot<KT, 2> for every KT: the data and the bounds of test_oblique_project_exact on a few rows of Y and Z (68
+    columns each) whose leading dimension puts their storage above the size at which the library streams the basis (stream_cases.streaming_ld asks
+    the library). Every column tile filled exactly and one column past it, two combinations of s, v and e each and all eight at k = 7 and k = 33; k = 65
+    is left out (its second chunk is a dot sweep of Z alone, which is resident). The rows n .. ld - 1 hold NaN bytes."""
+    rng = np.random.default_rng(9500 * n)
+    H = _Harness(ctx, n, ld=sc.streaming_ld(ctx, n, 2 * WCOLS))
+    sc.fill_nan(ctx, H.Y, H.Z, H.vec)
+    ks_ = sorted(set(KS[1:-1] + KS_TILES_EXACT + KS_TILES_PAST))
+    assert max(ks_) == 64
+    _oblique_exact(ctx, H, n, rng, [(k, (7, 0)) for k in ks_] + [(7, range(8)), (33, range(8))], "streaming", 0)
+
+
+@pytest.mark.parametrize("k", [2, 8, 33])
+@pytest.mark.parametrize("form", ["plain", "streaming"])
+def test_oblique_project_second_tile_of_a_workgroup(ctx, k, form):
+    """More tiles than workgroups: n = per_cu num_cu 512 + 513 rows with per_cu the factor of the dot sweep (4 at k = 2 and k = 8, 1 at k = 33), so every
+    workgroup of k_oblique_dot walks its first tile, some a second one, and the last tile is a single row; at k = 2 and k = 8 the update sweep
+    (4 workgroups per CU, eight columns in flight and the columns left over) walks the same way, at k = 33 it has one tile per workgroup.
+
+    Exactness at these n. Z and Y are dense (entries -1, 0, 1) and u, v and e are zero outside at most 4096 rows, some in every tile. Then
+    |w0| <= 2^4 on those rows and 0 elsewhere, and zeros add exactly nothing: |h| <= 4096 2^4 = 2^16, |c| <= 4 2^16 = 2^18 (four entries per row of
+    Minv), |w| <= 2^4 + 33 2^18 < 2^24 in every row, and e^T w with |e| <= 2 on 4096 rows stays below 2^37: exact, and checked on the data itself
+    (big < 2^53). The one quantity that cannot stay exact is the dot with e == w: w^2 < 2^48 summed over n > 2^17 rows passes 2^53. It is held to
+    the bound of the random-doubles test, (n + 1) eps |w|^T |w| against the longdouble sum over the device's own w.
+
+    Y and Z of k + 3 columns are resident (plain loads); of 24 columns (k = 2, 8) or 68 (k = 33) with the leading dimension of
+    stream_cases.streaming_ld they stream. Two calls per case: s, v and a separate e; and none of them with u == w and e == w."""
+    num_cu = ctx.device_info()["num_cu"]
+    n = sc.two_round_n(sc.dot_per_cu(k), num_cu)
+    ntiles, grid = sc.walk(n, sc.dot_per_cu(k), num_cu)
+    assert ntiles > grid and ntiles < 2 * grid and n % sc.TILE == 1, (n, ntiles, grid)
+    if k <= 8:
+        assert ntiles > sc.walk(n, sc.SWEEP_PER_CU, num_cu)[1]                      # the update sweep too
+    wcols = k + 3 if form == "plain" else (24 if k <= 8 else WCOLS)
+    ld = sc.even_ld(n) if form == "plain" else sc.streaming_ld(ctx, n, 2 * wcols)
+    rng = np.random.default_rng(4400 + 10 * k + (form == "plain"))
+    H = _Harness(ctx, n, ld=ld, wcols=wcols, kmax=k)
+    sc.fill_nan(ctx, H.Y, H.Z, H.vec)                                                  # the columns outside the active ranges and the rows past n: NaN bytes
+    lz, ly = 2, 1
+    Zk, Yk, Minv = _ints(rng, (n, k), 1), _ints(rng, (n, k), 1), _sparse_rows(rng, k, k, 4)
+    for j in range(k):
+        H.Z.set_column(lz + j, Zk[:, j]); H.Y.set_column(ly + j, Yk[:, j])
+    H.Z.SetActiveColumns(lz, lz + k); H.Y.SetActiveColumns(ly, ly + k)
+    H.set_minv(Minv, k + 3)
+    rows = sc.spread_rows(n)
+    for e_is_w in (False, True):
+        vecs = np.zeros((n, 6))
+        vecs[rows] = _ints(rng, (len(rows), 6), 2)
+        vecs[:, 2] = _ints(rng, n, 2)                                                  # s is dense: it scales zeros
+        H.vec.set_dense(vecs)
+        a, b = float(rng.choice([-2, -1, 1, 2])), float(rng.choice([-2, -1, 1, 2]))
+        if e_is_w:
+            (rc, dot), counts = sc.counted(ctx, lambda: H.call(k + 3, a, 0, b, None, None, 0, 0))
+            w, dref, big = _reference(Zk, Yk, Minv, a, vecs[:, 0], b, None, None, False, None)
+        else:
+            (rc, dot), counts = sc.counted(ctx, lambda: H.call(k + 3, a, 0, b, 1, 2, 3, 4))
+            w, dref, big = _reference(Zk, Yk, Minv, a, vecs[:, 0], b, vecs[:, 1], vecs[:, 2], False, vecs[:, 4])
+        assert rc == 0
+        assert counts == ((1, 0) if form == "plain" else (0, 1)), (form, counts)
+        assert big < LIMIT, big
+        got = H.vec.column(0 if e_is_w else 3)
+        assert np.array_equal(got, w), (k, form, e_is_w, np.argwhere(got != w)[:4])
+        if e_is_w:
+            wl = got.astype(np.longdouble)
+            assert abs(dot - float(wl @ wl)) <= (n + 1) * EPS * float(np.abs(got) @ np.abs(got)), (dot, float(wl @ wl))
+        else:
+            assert dot == dref, (dot, dref)
+    for j in range(k):
+        assert np.array_equal(H.Z.column(lz + j), Zk[:, j]) and np.array_equal(H.Y.column(ly + j), Yk[:, j]), j
     H.destroy()
 
 
@@ -340,9 +439,13 @@ def test_ritz_residual_vectors_exact(ctx, n, generalized, odd_ld):
     Vb.set_dense(V); AVb.set_dense(AV)
     if generalized:
         BVb.set_dense(BV)
+    # beyond one row: every pass width the dispatch compiles (1, 2, 4, 8 and, without B, 16) and, with B, second passes of 1, 2, 4 and 8 columns
+    widths = (1, 3, 8, 9, 16) if n == 1 else (1, 2, 3, 4, 5, 8, 9, 10, 12, 16)
     idx = 0
     for m in (1, 7, 9, 40):
-        for ncols in (1, 3, 8, 9, 16):
+        idx += (len(widths) + 1) % 2 if m != 1 else 0        # an odd stride from one m to the next (5 or 11): over the four m every width meets all four
+                                                             # choices of outputs and both l
+        for ncols in widths:
             l = (0, 2)[idx % 2]; lX = (0, 3)[(idx // 2) % 2]; lBX = (3, 0)[(idx // 4) % 2]; outs = idx % 4            # 0: both, 1: X, 2: BX, 3: none
             idx += 1
             S = np.asfortranarray(_ints(rng, (m, ncols), 8)); theta = _ints(rng, ncols, 8)
@@ -352,8 +455,9 @@ def test_ritz_residual_vectors_exact(ctx, n, generalized, odd_ld):
                 bvv.SetActiveColumns(l, l + m)
             Xb.SetActiveColumns(lX, WR); BXb.SetActiveColumns(lBX, WR)
             Xa = Xb if outs in (0, 1) else None; BXa = BXb if outs in (0, 2) else None
-            rn, xn = Rb.RitzResidualVectors(Vb, AVb, BVb, S, theta, X=Xa, BX=BXa)
-            rn2, xn2 = R2.RitzResidual(Vb, AVb, BVb, S, theta)
+            (rn, xn), counts = sc.counted(ctx, lambda: Rb.RitzResidualVectors(Vb, AVb, BVb, S, theta, X=Xa, BX=BXa))
+            (rn2, xn2), counts2 = sc.counted(ctx, lambda: R2.RitzResidual(Vb, AVb, BVb, S, theta))
+            assert counts == (1, 0) and counts2 == (1, 0), (m, ncols, counts, counts2)          # panels of a few thousand rows: plain loads
             assert np.array_equal(Rb.dense(), R2.dense()) and np.array_equal(rn, rn2) and np.array_equal(xn, xn2)
             x = V[:, l:l + m] @ S; bx = BV[:, l:l + m] @ S if generalized else x
             if Xa is not None:

@@ -2,6 +2,8 @@
 
 k_block_residual (ks_bv_block_residual): integer-valued data small enough that every product and every sum is exact in double, so R must equal
 numpy's bit for bit whatever the order of operations, and the squared norms are exact integers: the norm is within 2 ulp of their square root.
+Every active width 1..16 in the three compiled forms - one row per lane, 16-byte plain loads, 16-byte nontemporal loads (a few rows with the large leading
+dimension of tests/stream_cases.py) - and a second tile per workgroup; each call asserts the load form the library reports (Context.basis_load_counts).
 
 ks_st_pc_apply_multi: every column against ks_st_pc_apply of that column, bit for bit, for every PC type; the ILU(0) blocks on the matrices of
 tests/ilu_cases.py at the sizes where the passes of k_bjacobi_ilu_apply_multi change (ncols against the columns of a pass, the LDS budget at
@@ -12,6 +14,7 @@ import numpy as np
 import pytest
 
 import ilu_cases as ic
+import stream_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -23,36 +26,92 @@ def _ints(rng, shape, lo, hi):
     return rng.integers(lo, hi + 1, size=shape).astype(np.float64)
 
 
+def _block_residual_case(ctx, n, bs, l, generalized, ld, form, nan=False):
+    """One call on integer data (the bounds of test_block_residual_exact) against numpy, bit for bit; `form`: the load form the library must report
+    for it, "plain" or "streaming". nan: the storage beyond row n holds NaN bytes."""
+    import slepc_amd as ks
+    rng = np.random.default_rng(1000 * (n % 100003) + 10 * bs + l)
+    Rb, AXb, Xb = (ks.BV(ctx, n, bs, ld=ld) for _ in range(3))
+    BXb = ks.BV(ctx, n, bs, ld=ld) if generalized else Xb
+    assert Rb.ld > n
+    if nan:
+        sc.fill_nan(ctx, Rb, AXb, Xb, BXb)
+    theta = _ints(rng, bs - l, -32, 32); theta[0] = 0.0
+    if bs - l > 1:
+        theta[1] = -3.0
+    # one column at a time on the host: a panel of 16 columns and a million rows is 134 MB
+    cols = []
+    for j in range(bs):
+        ax = _ints(rng, n, -1024, 1024); x = _ints(rng, n, -64, 64); bx = _ints(rng, n, -64, 64) if generalized else x
+        r0 = _ints(rng, n, -7, 7)
+        Rb.set_column(j, r0); AXb.set_column(j, ax); Xb.set_column(j, x)
+        if generalized:
+            BXb.set_column(j, bx)
+        cols.append((ax, x, bx, r0))
+    Rb.SetActiveColumns(l, bs)
+    nrm, counts = sc.counted(ctx, lambda: Rb.BlockResidual(AXb, BXb, theta))
+    assert counts == ((1, 0) if form == "plain" else (0, 1)), (form, counts)
+    for j, (ax, x, bx, r0) in enumerate(cols):
+        got = Rb.column(j)
+        assert np.array_equal(Xb.column(j), x) and np.array_equal(AXb.column(j), ax)
+        if generalized:
+            assert np.array_equal(BXb.column(j), bx)
+        if j < l:
+            assert np.array_equal(got, r0), j
+            continue
+        ref = ax - bx * theta[j - l]
+        assert np.abs(ref).max() < 2.0 ** 12
+        assert np.array_equal(got, ref), (j, np.argwhere(got != ref)[:4])
+        exact = np.sqrt((ref * ref).sum())
+        assert abs(nrm[j - l] - exact) <= 2 * np.spacing(exact), (j, nrm[j - l], exact)
+    for b in {Rb, AXb, Xb, BXb}:
+        b.destroy()
+
+
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 4099])
 @pytest.mark.parametrize("bs,l", [(1, 0), (3, 0), (16, 0), (16, 2), (5, 2)])
 @pytest.mark.parametrize("generalized", [True, False])
 def test_block_residual_exact(ctx, n, bs, l, generalized):
     """|ax| <= 2^10, |bx| <= 2^6, |theta| <= 2^5: |r| < 2^12, the sum of n <= 4099 squares < 2^37 - all exact. ld > n (odd for the small sizes: the
     scalar path; the default even ld: the 16-byte path). Active range from column l: the columns before it keep their bits. theta holds 0 and a
-    negative value. generalized = False: BX is the BV of X itself."""
-    import slepc_amd as ks
-    rng = np.random.default_rng(1000 * n + 10 * bs + l)
-    ld = n + 3 if n < 257 else 0
-    Rb, AXb, Xb = (ks.BV(ctx, n, bs, ld=ld) for _ in range(3))
-    BXb = ks.BV(ctx, n, bs, ld=ld) if generalized else Xb
-    assert Rb.ld > n
-    AX = _ints(rng, (n, bs), -1024, 1024); X = _ints(rng, (n, bs), -64, 64); BX = _ints(rng, (n, bs), -64, 64) if generalized else X
-    R0 = _ints(rng, (n, bs), -7, 7)
-    theta = _ints(rng, bs - l, -32, 32); theta[0] = 0.0
-    if bs - l > 1:
-        theta[1] = -3.0
-    Rb.set_dense(R0); AXb.set_dense(AX); Xb.set_dense(X)
-    if generalized:
-        BXb.set_dense(BX)
-    Rb.SetActiveColumns(l, bs)
-    nrm = Rb.BlockResidual(AXb, BXb, theta)
-    R = Rb.dense()
-    ref = AX[:, l:] - BX[:, l:] * theta
-    assert np.array_equal(R[:, l:], ref)
-    assert np.array_equal(R[:, :l], R0[:, :l])
-    assert np.array_equal(Xb.dense(), X) and np.array_equal(AXb.dense(), AX)
-    exact = np.sqrt((ref * ref).sum(axis=0))
-    assert np.all(np.abs(nrm - exact) <= 2 * np.spacing(exact)), (nrm, exact)
+    negative value. generalized = False: BX is the BV of X itself. Three blocks of a few thousand rows: the library reports plain loads."""
+    _block_residual_case(ctx, n, bs, l, generalized, n + 3 if n < 257 else 0, "plain")
+
+
+# the active widths test_block_residual_exact leaves out (it reaches 1, 3, 14 and 16): with them every k_block_residual<KT, VEC, true> is launched
+@pytest.mark.parametrize("n", [65, 4099])
+@pytest.mark.parametrize("width", [2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15])
+@pytest.mark.parametrize("generalized", [True, False])
+def test_block_residual_exact_every_other_width(ctx, n, width, generalized):
+    """n = 65 with ld = 67: the scalar path; n = 4099 with the default ld: the 16-byte path. Odd widths start at column 2 of a wider BV."""
+    l = 2 if width % 2 else 0
+    _block_residual_case(ctx, n, width + l, l, generalized, n + 2 if n == 65 else 0, "plain")
+
+
+@pytest.mark.parametrize("n", [1, 511, 513, 4099])
+@pytest.mark.parametrize("generalized", [True, False])
+def test_block_residual_streaming_loads_exact(ctx, n, generalized):
+    """k_block_residual<KT, 2, false> for every width: the same data and bounds on a few rows of BVs whose leading dimension puts three blocks of
+    the active width above the size at which the library streams the basis (asked from the library: stream_cases.streaming_ld). The rows
+    n .. ld - 1 hold NaN bytes. The odd widths from 3 start at column 1 of the BV (an even ld keeps the columns 16-byte aligned)."""
+    for width in range(1, 17):
+        l = 1 if width % 2 and width > 1 else 0
+        _block_residual_case(ctx, n, width + l, l, generalized, sc.streaming_ld(ctx, n, 3 * width), "streaming", nan=True)
+
+
+@pytest.mark.parametrize("width,form", [(1, "plain"), (2, "plain"), (16, "streaming")])
+@pytest.mark.parametrize("generalized", [True, False])
+def test_block_residual_second_tile_of_a_workgroup(ctx, width, form, generalized):
+    """n = 8 num_cu 512 + 513 rows: more tiles than the largest grid ksl_block_residual can choose (the occupancy result, at most 8 workgroups per
+    CU), so every workgroup walks its first tile, some a second one, and the last tile is a single row; with 8 per CU the partial sums of more than
+    512 workgroups go through the general form of reduce_partials_to_lds. |r| < 2^12: the sum of n < 2^21 squares stays below 2^45, exact as
+    before. Three blocks of 1 and 2 columns stay resident (plain loads), of 16 columns they stream."""
+    num_cu = ctx.device_info()["num_cu"]
+    n = sc.two_round_n(sc.BLOCK_RESIDUAL_PER_CU, num_cu)
+    ntiles, grid = sc.walk(n, sc.BLOCK_RESIDUAL_PER_CU, num_cu)
+    assert ntiles > grid and ntiles < 2 * grid and n % sc.TILE == 1 and n < 2 ** 21, (n, ntiles, grid)
+    ld = sc.streaming_ld(ctx, n, 3 * width) if form == "streaming" else sc.even_ld(n)
+    _block_residual_case(ctx, n, width, 0, generalized, ld, form)
 
 
 def test_block_residual_arguments(ctx):

@@ -1,12 +1,15 @@
 """The end of a restart cycle in one launch: the deferred final Gram-Schmidt update of a Krylov run's last column, the restart product
 and the copy of the residual column (k_restart_fused, BV.SetDeferFinal / BV.Restart) against the three launches they replace
 (KS_DEBUG_NO_RESTART_FUSION). The update is a per-row fma chain and the product a per-row MFMA sequence, neither has a sum across rows:
-every comparison here is bit for bit - basis storage, coefficient buffer, projected matrix, pass counts, eigenvalues, error estimates."""
+every comparison here is bit for bit - basis storage, coefficient buffer, projected matrix, pass counts, eigenvalues, error estimates.
+Both load forms of the kernel (k_restart_fused<true> on a resident basis, <false> on one whose leading dimension makes it stream) and a second and
+third tile per wave (restart_cases.TWO_ROUNDS); which form ran is read from the library's counters (Context.basis_load_counts)."""
 import numpy as np
 import pytest
 
 import nhep_cases as nc_
 import restart_cases as rc
+import stream_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -19,8 +22,18 @@ def _matrix(ctx, kind, n):
 
 
 def _collect(bv, extra):
-    out = {"V": np.stack([bv.column(j) for j in range(-bv.nc, bv.m)], axis=1), "buffer": bv.buffer(), "passes": bv.gs_passes()}
-    out.update(extra)
+    out = dict(extra)
+    out.update({"V": np.stack([bv.column(j) for j in range(-bv.nc, bv.m)], axis=1), "buffer": bv.buffer(), "passes": bv.gs_passes()})
+    return out
+
+
+def _raw_columns(ctx, base, ld, n, count):
+    """The first `count` columns of a BV's storage read straight from the device (BV.column would apply a pending update first)."""
+    out = np.empty((n, count))
+    col = np.empty(n)
+    for j in range(count):
+        ctx.memcpy_d2h(col, base + 8 * j * ld)
+        out[:, j] = col
     return out
 
 
@@ -37,11 +50,14 @@ def _run(ctx, debug, fused, A, n, k, *, window=None, nc=0, ld=0, arnoldi=False, 
     if refine is not None:
         bv.SetOrthogonalization(ks.CGS, refine, 0.7071)
     bv.set_column(0, rc.start_vector(n) if v0 is None else v0)
+    base = bv.column_ptr(-nc)                          # (taken before the run: asking for a column later would apply the pending update)
     bv.SetDeferFinal(True)
     s, e = window if window else (0, min(k, 15))
     T = np.zeros((m, m), order="F") if arnoldi else np.zeros((m, 3), order="F")
     res = bv.MatArnoldi(A, T, 0, k) if arnoldi else bv.MatLanczos(A, T, 0, k)
     st0 = bv.restart_stats()
+    # what the run left before the action: the constraints and the columns before the last one (the last one still waits for its update when deferred)
+    Vpre = _raw_columns(ctx, base, bv.ld, n, nc + k)
     bv.SetActiveColumns(s, k)
     Q = rc.restart_q(m, s, k)
     ret = None
@@ -66,37 +82,76 @@ def _run(ctx, debug, fused, A, n, k, *, window=None, nc=0, ld=0, arnoldi=False, 
     else:
         raise AssertionError(action)
     st1 = bv.restart_stats()
-    out = _collect(bv, {"T": T, "res": (res[0], res[2]), "beta": np.array([res[1]])})
+    out = _collect(bv, {"Vpre": Vpre, "T": T, "res": (res[0], res[2]), "beta": np.array([res[1]])})
     if ret is not None:
         out["ret"] = np.asarray(ret, dtype=np.float64)
+    out["stages"] = rc.restart_stages(Vpre, out["V"], Q, nc, s, e, k) if action == "restart" and not res[2] else ()
+    bv.destroy()
     return out, st0, st1
 
 
 def _both(ctx, debug, *args, **kw):
+    """The deferred run and the run under no_restart_fusion. The first entry that differs names the stage: Vpre, T, res, beta are the Krylov run's
+    (before the restart), V, buffer, passes what the restart left."""
     a, sa0, sa1 = _run(ctx, debug, True, *args, **kw)
     b, sb0, sb1 = _run(ctx, debug, False, *args, **kw)
     assert not sb0["pending"] and sb1["fused"] == 0 and sb1["flushes"] == 0, (sb0, sb1)        # the hook keeps today's launches
     _both.last = a                                   # (what the deferred run left, for a test that looks at more than the difference)
-    return rc.first_difference(a, b), sa0, sa1
+    # each run against its own state before the restart: a failure names the run and the stage, whatever the other run did
+    assert a["stages"] == () and b["stages"] == (), ("fused", a["stages"], "unfused", b["stages"])
+    diff = rc.first_difference(a, b)
+    _both.detail = rc.describe_difference(a, b) if diff is not None else None       # (for the message of a failure)
+    return diff, sa0, sa1
 
 
 # ---- kernel level ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["laplacian", "csr"])
 @pytest.mark.parametrize("n", rc.SIZES)
 def test_restart_row_counts(ctx, debug, kind, n):
-    """Every row count: one row group, partial last 32-row group, partial last 128-row tile, several workgroups; short and full-width bases."""
+    """Every row count: one row group, partial last 32-row group, partial last 128-row tile, several workgroups, a second and a third tile per wave;
+    short and full-width bases. A basis of these sizes is resident: every launch that chooses a load form reports plain loads."""
     import slepc_amd as ks
+    num_cu = ctx.device_info()["num_cu"]
+    two_rounds = n == rc.TWO_ROUNDS
+    n = rc.rows(n, num_cu)
+    if two_rounds:
+        tiles = -(-n // sc.RESTART_TILE); waves = sc.RESTART_WAVES * min(-(-tiles // sc.RESTART_WAVES), num_cu)
+        assert tiles > 2 * waves and n % 32 == 2, (n, tiles, waves)
+    ctx.basis_load_counts(reset=True)
     A = _matrix(ctx, kind, n)
     for k in (1, 5, 30):
         if k >= n:
             continue
         for refine in (ks.REFINE_IFNEEDED, ks.REFINE_ALWAYS):
             diff, st0, st1 = _both(ctx, debug, A, n, k, window=(0, max(1, min(k - 1, 15))), refine=refine)
-            assert diff is None, (kind, n, k, refine, diff)
+            assert diff is None, (kind, n, k, refine, diff, _both.detail)
             if n >= 510 and refine == ks.REFINE_ALWAYS:
                 assert st0["pending"], (kind, n, k, st0)      # two passes by policy: the update of the last column waits
             if st0["pending"]:
                 assert (st1["fused"], st1["flushes"]) == ((1, 0) if k > 1 else (0, 1)), (kind, n, k, refine, st1)
+    plain, streaming = ctx.basis_load_counts(reset=True)
+    assert plain > 0 and streaming == 0, (plain, streaming)
+
+
+@pytest.mark.parametrize("n", [514, 4098, rc.TWO_ROUNDS])
+def test_restart_streaming_loads(ctx, debug, n):
+    """k_restart_fused<false>: the same runs on a basis whose leading dimension puts its storage above the size at which the library streams it
+    (stream_cases.streaming_ld asks the library; the rows n .. ld - 1 are never touched). The reference is the three launches under
+    no_restart_fusion as before - streaming forms of k_gs_update and the panel product, which tests/test_gpu_sweep_variants.py holds to numpy.
+    No launch of either run may report plain loads, and the deferred run must have taken the one-launch form."""
+    import slepc_amd as ks
+    num_cu = ctx.device_info()["num_cu"]
+    kind = "laplacian" if n == rc.TWO_ROUNDS else "csr"
+    n = rc.rows(n, num_cu)
+    A = _matrix(ctx, kind, n)
+    for k, nc in ((5, 0), (30, 0), (16, 1)):
+        ld = sc.streaming_ld(ctx, n, nc + k + 1)
+        ctx.basis_load_counts(reset=True)
+        diff, st0, st1 = _both(ctx, debug, A, n, k, window=(0, max(1, min(k - 1, 15))), nc=nc, ld=ld, refine=ks.REFINE_ALWAYS)
+        plain, streaming = ctx.basis_load_counts(reset=True)
+        assert diff is None, (n, k, nc, diff, _both.detail)
+        assert st0["pending"] and (st1["fused"], st1["flushes"]) == (1, 0), (n, k, nc, st0, st1)
+        assert streaming > 0 and plain == 0, (n, k, nc, plain, streaming)
 
 
 @pytest.mark.parametrize("k", rc.LAST_COLUMNS)

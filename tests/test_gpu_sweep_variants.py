@@ -13,6 +13,8 @@ import math
 import numpy as np
 import pytest
 
+import stream_cases as sc
+
 pytestmark = pytest.mark.gpu
 
 ETA = 0.7071
@@ -66,10 +68,10 @@ def ints(rng, shape, lo=-4, hi=4):
 class Store:
     """A BV whose whole storage is NaN bytes before the columns the case needs are written."""
 
-    def __init__(self, ctx, n, m, odd=False, nc_cols=None):
+    def __init__(self, ctx, n, m, odd=False, nc_cols=None, ld=None):
         import slepc_amd as ks
         self.ctx = ctx
-        self.V = ks.BV(ctx, n, m, ld=ld_for(n, odd))
+        self.V = ks.BV(ctx, n, m, ld=ld_for(n, odd) if ld is None else ld)
         if nc_cols is not None:
             assert self.V.InsertConstraints(nc_cols) == nc_cols.shape[1]
         self.nc = self.V.nc
@@ -120,6 +122,26 @@ def test_dot_sweep_every_tile(ctx, odd):
         S.V.SetActiveColumns(0, nc)
         out, prof = profiled(ctx, lambda: S.V.DotVec(S.V.column_ptr(nc)))
         assert np.array_equal(out, A.T @ y), (nc, n, odd)
+        assert launched(prof, "bv_dot_sweep", kt_for(nc)) >= 1, (nc, prof.keys())
+        S.V.destroy()
+
+
+@pytest.mark.parametrize("n", [1, 511, 513, 4099])
+def test_dot_sweep_streaming_loads_every_tile(ctx, n):
+    """The plain == 0 branch of k_dot_sweep<KT, 2> for every KT: a few rows of a basis whose leading dimension puts its storage above the size at
+    which the library streams it (stream_cases.streaming_ld asks the library, and the call must report one streaming verdict and no plain one)."""
+    rng = np.random.default_rng(13 + n)
+    for nc in KTS:
+        S = Store(ctx, n, nc + 1, ld=sc.streaming_ld(ctx, n, nc + 1))
+        A = ints(rng, (n, nc)); y = ints(rng, n)
+        for j in range(nc):
+            S.put(j, A[:, j])
+        S.put(nc, y)
+        assert_exact((A, y, n))
+        S.V.SetActiveColumns(0, nc)
+        (out, prof), counts = sc.counted(ctx, lambda: profiled(ctx, lambda: S.V.DotVec(S.V.column_ptr(nc))))
+        assert counts == (0, 1), (nc, n, counts)
+        assert np.array_equal(out, A.T @ y), (nc, n)
         assert launched(prof, "bv_dot_sweep", kt_for(nc)) >= 1, (nc, prof.keys())
         S.V.destroy()
 
