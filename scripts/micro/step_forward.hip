@@ -12,6 +12,8 @@
 // A-phase of round i - 1 waits for C-phases of rounds <= i only, and every workgroup runs C(i) before A(i - 1): the graph descends in the round index.
 // k_forward_pipe: four variants of the forward launch with the next tile's panel loads in flight through the hand-off and one panel parked in LDS (which
 // panel; polls in front of the loads or behind), each compared with k_forward bit for bit - v, y and the dots - and timed alternating with it.
+// k_forward_round: the kept pipelined variant with its round reordered - the tile's dots a round later in the shadow of the store drain, the park in front
+// of the drain or behind the flag, a part of the next panel issued behind the neighbour loads - compared and timed the same way.
 // build: hipcc -O3 --offload-arch=gfx950 -I../../slepc_amd/csrc step_forward.hip -o step_forward        run: ./step_forward [side = 216]
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -19,6 +21,7 @@
 #include <cstring>
 #include <cmath>
 #include <vector>
+#include <array>
 #include <algorithm>
 #include "ks_dict_pairs.h"
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
@@ -409,6 +412,198 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   put_partials<KT + 2>(acc, KT + 2, partials);
 }
 
+// ---- the round reordered ------------------------------------------------------------------------------------------------------------------------
+// k_forward_pipe<KT, 0, true> with the work that needs no vector memory moved into the shadow of the store drain, and the neighbour loads moved into the
+// panel stream. The hand-off is untouched: sc1 store, every wave's s_waitcnt vmcnt(0), barrier, one lane's flag, wave 0's sc1 polls, the barrier it joins,
+// every load of the column an sc1 load. The A-phase is split into A1 (poll, barrier, neighbour loads, walk, y store) and D (the dots of that tile):
+//   DEFER:      A1(i - 1) runs in round i and keeps y0, y1; D(i - 1) runs in round i + 1 between the sc1 store of C(i + 1) and the wave's wait for it, from
+//               the panel that stayed in pv; behind it, still in front of the wait, panel i comes back from LDS into pv. The last tile's D runs behind the
+//               loop. Each lane's sums receive their tiles in the same order as before: same bits.
+//   EARLY_PARK: the panel just computed goes to LDS in front of the wait as well (behind the un-park: a lane reads and then writes its own 16 bytes of a
+//               column, in program order) instead of behind the flag.
+//   LATE:       the last LATE columns of the next tile's panel are issued behind the ten neighbour loads instead of in front of the poll wait, so the walk
+//               waits for KT - LATE columns and the walk, the y store and the next C arithmetic run with loads in flight.
+// The neighbour loads and the late columns stand under NO branch (a phi of a loaded value is a copy, and a copy is a wait): in a round without a matched
+// poll the neighbour loads ask with the out-of-range offset, which reads nothing, so no load of the column is issued in front of the barrier behind the
+// matched poll. The row patterns of A1's tile are asked for in front of the panel, as the library kernel does.
+// Between a wave's sc1 store and its s_waitcnt vmcnt(0) stand fmas, ds_read and ds_write only.
+template <int KT, int LO, int HI>
+__device__ __forceinline__ void load_cols(const double *V, long long ld, int n, long long t, bool has, d2 (&xv)[KT])
+{
+  const long long r = t * TILE + 2LL * threadIdx.x;
+  const long long rr = has && r + 1 < n ? r : 0;
+#pragma unroll
+  for (int i = LO; i < HI; i++) xv[i] = __builtin_nontemporal_load(reinterpret_cast<const d2 *>(V + (long long)i * ld + rr));
+}
+template <int KT>
+__device__ __forceinline__ void tile_dots(const d2 (&xv)[KT], d2 s, double y0, double y1, double (&acc)[KT + 2])
+{
+#pragma unroll
+  for (int i = 0; i < KT; i++) { acc[i] = fma(xv[i].x, y0, acc[i]); acc[i] = fma(xv[i].y, y1, acc[i]); }
+  acc[KT] = fma(s.x, y0, acc[KT]); acc[KT] = fma(s.y, y1, acc[KT]);
+  acc[KT + 1] = fma(y0, y0, acc[KT + 1]); acc[KT + 1] = fma(y1, y1, acc[KT + 1]);
+}
+template <int KT, bool DEFER, bool EARLY_PARK, int LATE>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_forward_round(const double *V, long long ld, int n, double *v, double *__restrict__ y, const double *__restrict__ cg, double alpha,
+                                                    const unsigned char *__restrict__ rowpat, int npat, ksp::PairArgs pa, const double *__restrict__ pcoef, const unsigned *__restrict__ pmask,
+                                                    unsigned *flags, unsigned epoch, unsigned *ctl, double *__restrict__ partials, unsigned long long budget, int hooks)
+{
+  static_assert(LATE >= 0 && LATE < KT, "columns issued behind the neighbour loads");
+  __shared__ double cc[2][KT];
+  __shared__ int go_sh;
+  double *sc; unsigned *sm;
+  fill_tables(pa, pcoef, pmask, npat, sc, sm);
+  d2 *park = reinterpret_cast<d2 *>(reinterpret_cast<char *>(dyn_lds) + park_offset(npat, pa.nb)) + threadIdx.x;
+  for (int i = threadIdx.x; i < 2 * KT; i += BLOCK) cc[i / KT][i % KT] = -cg[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long ntiles = ((long long)n + TILE - 1) / TILE;
+  double acc[KT + 2];
+#pragma unroll
+  for (int i = 0; i < KT + 2; i++) acc[i] = 0.0;
+  d2 pv[KT]; d2 ps = {0.0, 0.0};                      // the panel and the new rows of the tile whose A1 is still to come (DEFER: the panel is one tile behind)
+#pragma unroll
+  for (int i = 0; i < KT; i++) pv[i] = d2{0.0, 0.0};
+  long long pt = -1;
+  d2 ds = {0.0, 0.0}; double dy0 = 0.0, dy1 = 0.0;     // DEFER: new rows and y of the tile whose dots are still to come; its panel is pv
+  long long dt = -1;
+  bool dead = false;
+  d2 nv[KT]; d2 ns;
+  load_panel<KT>(V, ld, n, v, blockIdx.x, (long long)blockIdx.x < ntiles, nv, ns);
+  for (long long t = blockIdx.x;; t += gridDim.x) {
+    const bool has = t < ntiles;
+    d2 cv[KT]; d2 cs = ns;
+#pragma unroll
+    for (int i = 0; i < KT; i++) cv[i] = nv[i];
+    // ---- C-phase: the arithmetic under NO branch (a lane without rows, or a round without a tile, computes on rows 0, 1 and stores nothing): on a path
+    // around it the panel loads would still be pending at the park behind the join, the compiler would count them there, and since the sc1 store counts
+    // in vmcnt too the last ds_write of the park would wait for the store they are meant to shadow ----
+#pragma unroll
+    for (int p = 0; p < 2; p++)
+#pragma unroll
+      for (int i = 0; i < KT; i++) { const double c = cc[p][i]; cs.x = fma(c, cv[i].x, cs.x); cs.y = fma(c, cv[i].y, cs.y); }
+    cs.x *= alpha; cs.y *= alpha;
+    if (has) {
+      const long long r = t * TILE + 2LL * threadIdx.x;
+      if (r + 1 < n) asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(reinterpret_cast<d2 *>(v + r)), "v"(cs) : "memory");
+      if ((hooks & 1) && (blockIdx.x & 1)) for (int q = 0; q < 40; q++) __builtin_amdgcn_s_sleep(127);
+    }
+    // ---- in the shadow of the drain: D of the tile two rounds back, its successor's panel back from LDS, this round's panel to LDS ----
+    __builtin_amdgcn_sched_barrier(0);
+    if (DEFER) {
+      if (dt >= 0 && !dead && dt * TILE + 2LL * threadIdx.x + 1 < n) tile_dots<KT>(pv, ds, dy0, dy1, acc);
+#pragma unroll
+      for (int i = 0; i < KT; i++) pv[i] = park[i * BLOCK];      // (the first round reads what nobody wrote and nobody uses)
+    }
+    if (EARLY_PARK) {
+#pragma unroll
+      for (int i = 0; i < KT; i++) park[i * BLOCK] = cv[i];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- publish ----
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave
+    __syncthreads();
+    if (has && threadIdx.x == 0) __hip_atomic_store(flags + t, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool arun = pt >= 0 && !dead;
+    if (!EARLY_PARK) {
+#pragma unroll
+      for (int i = 0; i < KT; i++) park[i * BLOCK] = cv[i];
+    }
+    // ---- wave 0's first polls of A1(t - gridDim.x), the row patterns, then every wave's first KT - LATE columns of the next round's tile ----
+    long long tl = -1;
+    unsigned f0 = epoch, ab0 = 0;
+    if (arun && w == 0) {
+      const int kb = lane / 3, wh = lane % 3;
+      int b = 0; bool isb = false;
+#pragma unroll
+      for (int k = 0; k < NBT; k++) if (k == kb && k < pa.nb) { b = pa.base[k]; isb = true; }
+      if (isb) {
+        const int d = (int)(pa.dmask >> kb & 1u);
+        long long lo = pt * TILE + b - d, hi = pt * TILE + (TILE - 1) + b + d;
+        if (lo < 0) lo = 0;
+        if (hi > n - 1) hi = n - 1;
+        if (lo <= hi && (lo >> 9) + wh <= (hi >> 9)) tl = (lo >> 9) + wh;
+      }
+      if (tl == pt) tl = -1;
+      if (tl >= 0) f0 = __hip_atomic_load(flags + tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (lane == 63) ab0 = __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const long long r = (arun ? pt : 0) * TILE + 2LL * threadIdx.x;
+    const unsigned pp = *reinterpret_cast<const unsigned short *>(rowpat + (r < n ? r : 0));
+    __builtin_amdgcn_sched_barrier(0);
+    {
+      const long long tn = t + gridDim.x, rn = tn * TILE + 2LL * threadIdx.x;
+      const bool hn = has && tn < ntiles;
+      ns = *reinterpret_cast<const d2 *>(hn && rn + 1 < n ? v + rn : V);
+      load_cols<KT, 0, KT - LATE>(V, ld, n, tn, hn, nv);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- A1 of the tile of the round before ----
+    bool go = false;
+    if (arun) {
+      if (w == 0) {
+        int res;
+        bool first = true, fresh = true;
+        const long long tstart = wall_clock64();
+        for (;;) {
+          unsigned f = f0, ab = ab0;
+          if (!fresh) {
+            f = epoch; ab = 0;
+            if (tl >= 0) f = __hip_atomic_load(flags + tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 63) ab = __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+          fresh = false;
+          if (__any(lane == 63 && ab == epoch)) { res = 0; break; }
+          if (__all(f == epoch)) { res = 1; break; }
+          if (first && lane == 0) atomicAdd(ctl + 2, 1u);
+          first = false;
+          if ((unsigned long long)(wall_clock64() - tstart) >= budget) {
+            if (lane == 0) { __hip_atomic_exchange(ctl, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); atomicAdd(ctl + 1, 1u); }
+            res = 0; break;
+          }
+          __builtin_amdgcn_s_sleep(8);
+        }
+        if (lane == 0) go_sh = res;
+      }
+      barrier_lds_only();                               // the other waves load v only behind this barrier
+      go = go_sh != 0;
+      if (!go) dead = true;
+    }
+    // the ten neighbour loads (sc1; out of range, reading nothing, unless the poll matched), then the rest of the panel: one block, no branch
+    const Lane<true, true> ln(v, n, r, ksp::D2{ps.x, ps.y});
+    ksp::D2 xv[NBT]; double edge[NBT];
+#pragma unroll
+    for (int q = 0; q < NBT; q++) {
+      const bool on = go && q < pa.nb;
+      const long long i = r + pa.base[q];
+      const auto tq = __builtin_amdgcn_raw_buffer_load_b128(ln.rs, ln.off(i, on && i != r), 0, 16); __builtin_memcpy(&xv[q], &tq, 16);
+      edge[q] = ln.one(lane == 0 ? i - 1 : i + 2, on && (pa.dmask >> q & 1u) && (lane == 0 || lane == 63));
+    }
+    if (LATE) { const long long tn = t + gridDim.x; load_cols<KT, KT - LATE, KT>(V, ld, n, tn, has && tn < ntiles, nv); }
+    __builtin_amdgcn_sched_barrier(0);
+    double y0 = 0.0, y1 = 0.0;
+    if (go) {
+#pragma unroll
+      for (int q = 0; q < NBT; q++) { const bool own = q < pa.nb && pa.base[q] == 0; xv[q].x = own ? ps.x : xv[q].x; xv[q].y = own ? ps.y : xv[q].y; }
+      ksp::dict_pair_sums<NBT>(pa, sc, sm, (int)(pp & 255u), (int)(pp >> 8), r, ln, xv, edge, y0, y1);
+      if (r + 1 < n) {
+        __builtin_nontemporal_store(d2{y0, y1}, reinterpret_cast<d2 *>(y + r));
+        if (!DEFER) tile_dots<KT>(pv, ps, y0, y1, acc);
+      }
+    }
+    if (DEFER) { ds = ps; dy0 = y0; dy1 = y1; dt = go ? pt : -1; }
+    if (!has) break;
+    if (!DEFER) {
+#pragma unroll
+      for (int i = 0; i < KT; i++) pv[i] = park[i * BLOCK];
+    }
+    ps = cs; pt = t;
+  }
+  if (dead) return;
+  if (DEFER && dt >= 0 && dt * TILE + 2LL * threadIdx.x + 1 < n) tile_dots<KT>(pv, ds, dy0, dy1, acc);      // the last tile's dots; its panel came back in the last round
+  put_partials<KT + 2>(acc, KT + 2, partials);
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------------------------------
 struct Problem { int nx, n, npat; ksp::PairArgs pa; std::vector<double> coef; std::vector<unsigned> mask; std::vector<unsigned char> rowpat; };
 static Problem laplacian(int nx)
@@ -457,9 +652,19 @@ static void run_k(const Problem &P, const Dev &D, const std::vector<double> &h0,
   // the forward launch and the variants of its pipelined form: same arguments, the parked panel behind the tables in dynamic LDS
   struct Var { const char *name; Kern kern; size_t lds; };
   const size_t lds_pipe = park_offset(P.npat, P.pa.nb) + (size_t)KT * BLOCK * sizeof(d2);
-  const Var vars[5] = {{"k_forward                         ", k_forward<KT>, D.lds},
+  constexpr int H = KT / 2, Q = KT / 4;                 // columns behind the neighbour loads: a half, a quarter, three quarters
+  const std::vector<Var> vars = {{"k_forward                         ", k_forward<KT>, D.lds},
                        {"pipe: computed parked, polls first", k_forward_pipe<KT, 0, true>, lds_pipe}, {"pipe: computed parked, polls last ", k_forward_pipe<KT, 0, false>, lds_pipe},
-                       {"pipe: waiting parked, polls first ", k_forward_pipe<KT, 1, true>, lds_pipe}, {"pipe: waiting parked, polls last  ", k_forward_pipe<KT, 1, false>, lds_pipe}};
+                       {"pipe: waiting parked, polls first ", k_forward_pipe<KT, 1, true>, lds_pipe}, {"pipe: waiting parked, polls last  ", k_forward_pipe<KT, 1, false>, lds_pipe},
+                       {"round: as pipe, loads branch-free ", k_forward_round<KT, false, false, 0>, lds_pipe}, {"round: (c) park before the wait   ", k_forward_round<KT, false, true, 0>, lds_pipe},
+                       {"round: (a) dots deferred, park aft", k_forward_round<KT, true, false, 0>, lds_pipe}, {"round: (a)+(c)                    ", k_forward_round<KT, true, true, 0>, lds_pipe},
+                       {"round: (b) half the panel late    ", k_forward_round<KT, false, false, H>, lds_pipe}, {"round: (a)+(c)+(b) a quarter late  ", k_forward_round<KT, true, true, Q>, lds_pipe},
+                       {"round: (a)+(c)+(b) half late      ", k_forward_round<KT, true, true, H>, lds_pipe}, {"round: (a)+(c)+(b) 3 quarters late ", k_forward_round<KT, true, true, KT - Q>, lds_pipe},
+                       {"round: (b) a quarter late         ", k_forward_round<KT, false, false, Q>, lds_pipe}, {"round: (b) 3 quarters late        ", k_forward_round<KT, false, false, KT - Q>, lds_pipe},
+                       {"round: (b) all but one late       ", k_forward_round<KT, false, false, KT - 1>, lds_pipe},
+                       {"round: (a)+(b) a quarter late     ", k_forward_round<KT, true, false, Q>, lds_pipe}, {"round: (a)+(b) half late          ", k_forward_round<KT, true, false, H>, lds_pipe},
+                       {"round: (a)+(b) 3 quarters late    ", k_forward_round<KT, true, false, KT - Q>, lds_pipe}, {"round: (a)+(b) all but one late    ", k_forward_round<KT, true, false, KT - 1>, lds_pipe}};
+  const int NV = (int)vars.size();
   for (const Var &q : vars) CK(hipFuncSetAttribute((const void *)q.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds));
   auto fwd = [&](const Var &q, int hooks, unsigned long long bud) {
     hipLaunchKernelGGL(q.kern, dim3(g_upd), dim3(BLOCK), q.lds, 0, D.B, ld, n, v, y, D.cg, alpha, D.rowpat, P.npat, P.pa, D.coef, D.mask, D.flags, ++g_epoch, D.ctl, D.p1, bud, hooks); };
@@ -493,9 +698,9 @@ static void run_k(const Problem &P, const Dev &D, const std::vector<double> &h0,
   auto time = [&](auto fn, int reps) { for (int r = 0; r < 3; r++) fn(); CK(hipEventRecord(e0)); for (int r = 0; r < reps; r++) fn(); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms, e0, e1)); return 1e3 * ms / reps; };
   const int reps = 30;
   unsigned ctl0[4]; CK(hipMemcpy(ctl0, D.ctl, sizeof(ctl0), hipMemcpyDeviceToHost));
-  double t3[3], t1[5][3], tl[5];
-  for (int rep = 0; rep < 3; rep++) { reset(); t3[rep] = time(three, reps); for (int q = 0; q < 5; q++) { reset(); t1[q][rep] = time([&] { fwd(vars[q], 0, budget); }, reps); } }
-  for (int q = 0; q < 5; q++) { reset(); tl[q] = time([&] { fwd(vars[q], 1, 100 * budget); }, 5); }
+  double t3[3]; std::vector<std::array<double, 3>> t1(NV); std::vector<double> tl(NV);
+  for (int rep = 0; rep < 3; rep++) { reset(); t3[rep] = time(three, reps); for (int q = 0; q < NV; q++) { reset(); t1[q][rep] = time([&] { fwd(vars[q], 0, budget); }, reps); } }
+  for (int q = 0; q < NV; q++) { reset(); tl[q] = time([&] { fwd(vars[q], 1, 100 * budget); }, 5); }
   unsigned ctl1[4]; CK(hipMemcpy(ctl1, D.ctl, sizeof(ctl1), hipMemcpyDeviceToHost));
   reset();
   const double ta = time([&] { hipLaunchKernelGGL(k_final<KT>, dim3(g_upd), dim3(BLOCK), 0, 0, D.B, ld, n, v, D.cg, alpha); }, reps);
@@ -504,7 +709,7 @@ static void run_k(const Problem &P, const Dev &D, const std::vector<double> &h0,
   const double mb3 = 8e-6 * n * ((KT + 2) + 2.2 + (KT + 2)), mb1 = 8e-6 * n * ((KT + 2) + 1.2);
   printf("k %2d: three launches %7.1f %7.1f %7.1f us (final update %6.1f, product %5.1f, dot sweep %6.1f alone; %.0f MB: %.2f TB/s), waits out of budget in the timed launches: %s\n",
          KT, t3[0], t3[1], t3[2], ta, tb, tc, mb3, mb3 / std::min({t3[0], t3[1], t3[2]}), ctl1[1] != ctl0[1] ? "SOME" : "none");
-  for (int q = 0; q < 5; q++)
+  for (int q = 0; q < NV; q++)
     printf("k %2d %s: %7.1f %7.1f %7.1f us (%.0f MB: %.2f TB/s), odd workgroups lagging %7.1f us\n", KT, vars[q].name, t1[q][0], t1[q][1], t1[q][2], mb1, mb1 / std::min({t1[q][0], t1[q][1], t1[q][2]}), tl[q]);
   fflush(stdout);
 }

@@ -532,23 +532,26 @@ struct FwdLane {
   __device__ __forceinline__ double up(double v, long long) const { return __shfl_up(v, 1); }
   __device__ __forceinline__ double down(double v, long long) const { return __shfl_down(v, 1); }
 };
-// The loads of the walk for the pipelined form, under no branch: a base the matrix does not have, an edge a base does not need and the lane's own pair ask with
-// the out-of-range offset (0 comes back, nothing is read), so the ten loads stand in one block behind each other and the only wait is the one in front of the
-// sums. With ksp::dict_pair_loads' uniform branches the compiler copied an edge value where two paths join and waited there, after the first base's loads:
-// behind the panel loads of the next tile that is a second pass through the queue. The own pair is put in from the registers afterwards (a select on a
+// The loads of the walk for the pipelined form, under no branch: a base the matrix does not have, an edge a base does not need, the lane's own pair and every
+// load of a round whose poll did not match (go false) ask with the out-of-range offset (0 comes back, nothing is read), so the ten loads stand in one block
+// behind each other and the only wait is the one in front of the sums. With ksp::dict_pair_loads' uniform branches the compiler copied an edge value where two paths join and waited there, after the first base's loads:
+// behind the panel loads of the next tile that is a second pass through the queue. The own pair is put in from the registers afterwards (fwd_pair_own: a select on a
 // uniform condition, behind every load). Same values as dict_pair_loads leaves in every element the sums read.
 template <int NBT>
-__device__ __forceinline__ void fwd_pair_loads(const ksp::PairArgs &pa, long long r, const FwdLane &ln, ksp::D2 (&v)[NBT], double (&edge)[NBT])
+__device__ __forceinline__ void fwd_pair_loads(const ksp::PairArgs &pa, long long r, const FwdLane &ln, bool go, ksp::D2 (&v)[NBT], double (&edge)[NBT])
 {
   const int lane = ln.lane();
 #pragma unroll
   for (int q = 0; q < NBT; q++) {
-    const bool on = q < pa.nb;
+    const bool on = go && q < pa.nb;
     const long long i = r + pa.base[q];
     const auto t = __builtin_amdgcn_raw_buffer_load_b128(ln.rs, ln.off(i, on && i != ln.own), 0, 16); __builtin_memcpy(&v[q], &t, 16);
     edge[q] = ln.one(lane == 0 ? i - 1 : i + 2, on && (pa.dmask >> q & 1u) && (lane == 0 || lane == 63));
   }
-  __builtin_amdgcn_sched_barrier(0);
+}
+template <int NBT>
+__device__ __forceinline__ void fwd_pair_own(const ksp::PairArgs &pa, const FwdLane &ln, ksp::D2 (&v)[NBT])
+{
 #pragma unroll
   for (int q = 0; q < NBT; q++) {
     const bool own = q < pa.nb && pa.base[q] == 0;
@@ -569,32 +572,77 @@ __device__ __forceinline__ double fwd_last_row(const FwdArgs &f, long long r, co
   return acc;
 }
 
-// PIPE, the pipelined form: the panel loads of the tile of round i + 1 (and the tile's own rows of v) go out behind publish(i), in front of the A-phase of the
-// tile of round i - 1, and stay in flight through the poll, the barrier, the neighbour loads, the walk and the dots. Three panels are live then and the
-// registers hold two, so the panel just computed is parked in LDS (KT columns x 256 lanes x 16 B behind the pair tables; lane l writes and reads column i at
-// park[i * SW_BLOCK + l] and nobody else touches it: no barrier for the panel) and comes back to registers behind the A-phase. A round is
-//   C(i) from the registers the loads of the round before filled -> sc1 store, every wave's s_waitcnt vmcnt(0), barrier, flag (all as above; nothing else is
-//   in flight at that wait) -> park -> wave 0's first polls of A(i - 1) -> every wave's panel loads of round i + 1 -> A(i - 1) as above -> panel back.
+// PIPE, the pipelined form: the panel loads of the tile of round i + 1 (and the tile's own rows of v) go out behind publish(i), around the A-phase of the
+// tile of round i - 1, and stay in flight through the poll, the barrier, the neighbour loads and the walk. Three panels are live then and the registers
+// hold two, so the panel just computed is parked in LDS (KT columns x 256 lanes x 16 B behind the pair tables; lane l writes and reads column i at
+// park[i * SW_BLOCK + l] and nobody else touches it: no barrier for the panel). The A-phase is split into A1 (poll, barrier, neighbour loads, walk, y
+// store) and D (the tile's dots, fmas only); D runs a round later, in the shadow of the next store drain. A round is
+//   C(i) from the registers the loads of the round before filled -> sc1 store -> D(i - 2) from pv, then panel i - 1 back from LDS into pv (fmas and
+//   ds_read only: no vector-memory instruction between a wave's store and its wait) -> every wave's s_waitcnt vmcnt(0), barrier, flag (all as above) ->
+//   park panel i -> wave 0's first polls of A1(i - 1), every wave's row patterns -> the tile's own rows and the first KT - LATE columns of round i + 1 ->
+//   wave 0's poll wait, barrier -> the ten neighbour loads -> the last LATE columns of round i + 1 -> walk, y store (y0, y1 stay in registers for D).
+// The last tile's D runs behind the loop. Every accumulator set still receives its tiles in ascending round order: the sums keep their bits. A workgroup
+// that has gone dead skips D and returns without partials as before.
+// The neighbour loads stand in the middle of the panel stream, so the walk waits for KT - LATE columns instead of KT (vector loads return in order), and
+// the walk, the y store and the next C arithmetic - which consumes the columns in ascending order, as they land - run with loads in flight.
 // Progress: C(i) waits for its own loads of V(:,0:k) and of its own rows of v only, which nobody stores in this launch before this lane does; publish(i)
-// still stands in front of A(i - 1), so the induction above holds word for word: A(i - 1) waits for C-phases of rounds <= i, every workgroup has run those
-// before it can wait, and the wait graph descends in the round index. The early loads read columns 0..k-1 and the tile's own rows of column c, never a row
-// another workgroup hands off. A re-poll queues behind the panel loads (vector loads return in order), and those wait for nothing.
-// What the form stands on, besides the branch-free loads of the walk (fwd_pair_loads above); all three were found in the assembly (profiles/r16_step_forward_pipeline.txt):
-//  - the panel loads stand under NO branch. The wait for wave 0's first polls counts the loads issued behind them (s_waitcnt vmcnt(KT + 2)); where a path
-//    around the loads joins, the compiler takes that path's count, 0, and wave 0 waits for the whole panel. A lane without a row pair (rows past n, no tile
-//    left, the last row of an odd n) reads rows 0 and 1 of columns 0..k-1 instead, one line per column, and nobody uses what it gets;
+// still stands in front of A1(i - 1), so the induction above holds word for word: A1(i - 1) waits for C-phases of rounds <= i, every workgroup has run
+// those before it can wait, and the wait graph descends in the round index. The early and the late loads read columns 0..k-1 and the tile's own rows of
+// column c, never a row another workgroup hands off: they wait for nothing. D touches no memory. A re-poll queues behind the early panel loads.
+// What the form stands on; all of it was found in the assembly (profiles/r16_step_forward_pipeline.txt, profiles/r17_step_forward_round.txt):
+//  - the panel loads stand under NO branch. The wait for wave 0's first polls counts the loads issued behind them (s_waitcnt vmcnt(KT - LATE + 2)); where
+//    a path around the loads joins, the compiler takes that path's count, 0, and wave 0 waits for the whole panel. A lane without a row pair (rows past n,
+//    no tile left, the last row of an odd n) reads rows 0 and 1 of columns 0..k-1 instead, one line per column, and nobody uses what it gets;
+//  - the neighbour loads and the late columns stand under no branch either, in one block: in a round whose poll did not match (the first round, a dead
+//    workgroup) the neighbour loads ask with the out-of-range offset and read nothing, so no load of the column is ever issued in front of the barrier
+//    behind the matched poll. Late columns issued on both sides of a branch would meet in a copy, and a copy of a loaded value is a wait;
+//  - the C arithmetic stands under no branch (such a lane computes on rows 0, 1 and stores nothing). On a path around it the panel loads are still pending
+//    where the park reads cv, the compiler counts them there, and as stores count in vmcnt too, wave 0 sat out its flag store in front of its first polls;
 //  - the barrier behind the matched poll orders LDS only. __syncthreads() puts s_waitcnt vmcnt(0) behind s_barrier (its workgroup-scope acquire), which
 //    holds every wave until its panel is in. The waves still load v only behind the s_barrier that wave 0 joins after its matched poll.
-template <int KT>
+// Not kept (measured slower in the probe at every width): the park in front of the wait as well.
+template <int KT, int LO, int HI>
+__device__ __forceinline__ void fwd_load_cols(const double *V, long long ld, int n, int k, long long t, bool has, ks_d2v (&xv)[KT])
+{
+  const long long r = t * (2LL * SW_BLOCK) + 2LL * threadIdx.x;
+  const long long rr = has && r + 1 < n ? r : 0;
+#pragma unroll
+  for (int i = LO; i < HI; i++) { const int ii = i < k ? i : k - 1; xv[i] = __builtin_nontemporal_load(reinterpret_cast<const ks_d2v *>(V + (long long)ii * ld + rr)); }
+}
+// the tile's own rows of v and the panel's columns [0, HI)
+template <int KT, int HI>
 __device__ __forceinline__ void fwd_load_panel(const double *V, long long ld, int n, int k, const double *v, long long t, bool has, ks_d2v (&xv)[KT], ks_d2v &s)
 {
   const long long r = t * (2LL * SW_BLOCK) + 2LL * threadIdx.x;
-  const bool ok = has && r + 1 < n;
-  const long long rr = ok ? r : 0;
-  s = *reinterpret_cast<const ks_d2v *>(ok ? v + r : V);
-#pragma unroll
-  for (int i = 0; i < KT; i++) { const int ii = i < k ? i : k - 1; xv[i] = __builtin_nontemporal_load(reinterpret_cast<const ks_d2v *>(V + (long long)ii * ld + rr)); }
+  s = *reinterpret_cast<const ks_d2v *>(has && r + 1 < n ? v + r : V);
+  fwd_load_cols<KT, 0, HI>(V, ld, n, k, t, has, xv);
 }
+// The dots of one tile from its panel, its new rows and its rows of y into accumulator set `set`; a lane with the odd last row has its y in y0.
+template <int KT, int S>
+__device__ __forceinline__ void fwd_tile_dots(const ks_d2v (&xv)[KT], ks_d2v s, double y0, double y1, long long r, int n, int set, double (&acc)[S][KT + 2])
+{
+  if (r + 1 < n) {
+#pragma unroll
+    for (int q = 0; q < S; q++)
+      if (q == set) {
+#pragma unroll
+        for (int i = 0; i < KT; i++) { acc[q][i] = fma(xv[i].x, y0, acc[q][i]); acc[q][i] = fma(xv[i].y, y1, acc[q][i]); }
+        acc[q][KT] = fma(s.x, y0, acc[q][KT]); acc[q][KT] = fma(s.y, y1, acc[q][KT]);
+        acc[q][KT + 1] = fma(y0, y0, acc[q][KT + 1]); acc[q][KT + 1] = fma(y1, y1, acc[q][KT + 1]);
+      }
+  } else if (r < n) {
+#pragma unroll
+    for (int q = 0; q < S; q++)
+      if (q == set) {
+#pragma unroll
+        for (int i = 0; i < KT; i++) acc[q][i] = fma(xv[i].x, y0, acc[q][i]);
+        acc[q][KT] = fma(s.x, y0, acc[q][KT]);
+        acc[q][KT + 1] = fma(y0, y0, acc[q][KT + 1]);
+      }
+  }
+}
+// columns of the next tile's panel issued behind the neighbour loads: half (a quarter, three quarters and all but one measured slower, profiles/r17_step_forward_round.txt)
+constexpr int fwd_late_cols(int kt) { return kt / 2; }
 __device__ __forceinline__ void fwd_barrier_lds()
 {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
@@ -697,27 +745,40 @@ __global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))
   ks_d2v nv[KT]; ks_d2v ns = {0.0, 0.0};                 // PIPE: panel and own rows of v of the next round's tile, in flight
 #pragma unroll
   for (int i = 0; i < KT; i++) nv[i] = ks_d2v{0.0, 0.0};
-  if (PIPE) fwd_load_panel<KT>(V, ld, n, k, v, rev ? ntiles - 1 - (long long)blockIdx.x : (long long)blockIdx.x, (long long)blockIdx.x < ntiles, nv, ns);
+  ks_d2v ds = {0.0, 0.0}; double dy0 = 0.0, dy1 = 0.0;  // PIPE: new rows and rows of y of the tile whose dots are still to come (its panel is pv), its tile and set
+  long long dt = -1; int dset = 0;
+  constexpr int LATE = PIPE ? fwd_late_cols(KT) : 0;       // PIPE: columns of the next tile's panel that are issued behind the neighbour loads
+  if (PIPE) fwd_load_panel<KT, KT>(V, ld, n, k, v, rev ? ntiles - 1 - (long long)blockIdx.x : (long long)blockIdx.x, (long long)blockIdx.x < ntiles, nv, ns);
   for (long long t0 = blockIdx.x;; t0 += gridDim.x) {
     const bool has = t0 < ntiles;
     const long long t = rev ? ntiles - 1 - t0 : t0;
     ks_d2v cv[KT]; ks_d2v cs = ns;
 #pragma unroll
     for (int i = 0; i < KT; i++) cv[i] = nv[i];
+    // ---- C-phase: upd_tiles<KT, 2, 2, 0, false>'s tile, the coefficients read from LDS as they are used ----
+    if (PIPE) {
+      // the arithmetic under NO branch (a lane without a row pair, a round without a tile: rows 0 and 1, nothing stored): on a path around it the panel
+      // loads are still pending where the park reads cv, the compiler counts them there, and wave 0 sits out its flag store in front of its first polls
+#pragma unroll
+      for (int p = 0; p < 2; p++)
+#pragma unroll
+        for (int i = 0; i < KT; i++) { const double c = (i < k) ? -spend[p * KS_PSTRIDE + i] : 0.0; cs.x = fma(c, cv[i].x, cs.x); cs.y = fma(c, cv[i].y, cs.y); }
+      if (scal) { cs.x *= alpha; cs.y *= alpha; }
+      asm volatile("" ::: "memory");                       // the odd last row below reads its coefficients again: 2 KT values kept live for it cost up to 60 registers
+    }
     if (has) {
-      // ---- C-phase: upd_tiles<KT, 2, 2, 0, false>'s tile, the coefficients read from LDS as they are used ----
       const long long r = t * tile + 2LL * threadIdx.x;
       if (r + 1 < n) {
         if (!PIPE) {
           cs = *reinterpret_cast<const ks_d2v *>(v + r);
 #pragma unroll
           for (int i = 0; i < KT; i++) { const int ii = i < k ? i : k - 1; cv[i] = __builtin_nontemporal_load(reinterpret_cast<const ks_d2v *>(V + (long long)ii * ld + r)); }
+#pragma unroll
+          for (int p = 0; p < 2; p++)
+#pragma unroll
+            for (int i = 0; i < KT; i++) { const double c = (i < k) ? -spend[p * KS_PSTRIDE + i] : 0.0; cs.x = fma(c, cv[i].x, cs.x); cs.y = fma(c, cv[i].y, cs.y); }
+          if (scal) { cs.x *= alpha; cs.y *= alpha; }
         }
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-          for (int i = 0; i < KT; i++) { const double c = (i < k) ? -spend[p * KS_PSTRIDE + i] : 0.0; cs.x = fma(c, cv[i].x, cs.x); cs.y = fma(c, cv[i].y, cs.y); }
-        if (scal) { cs.x *= alpha; cs.y *= alpha; }
         asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(reinterpret_cast<ks_d2v *>(v + r)), "v"(cs) : "memory");
       } else if (r < n) {                                  // odd n: the last row on its own, stored by an 8-byte agent-scope (sc1) store
         double s1 = v[r];
@@ -732,6 +793,15 @@ __global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))
         __hip_atomic_store(v + r, s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       if (f.lag_odd && (blockIdx.x & 1)) for (int q = 0; q < 8; q++) __builtin_amdgcn_s_sleep(127);
+    }
+    if (PIPE) {
+      // ---- in the shadow of the drain, fmas and ds_read only: D of the tile two rounds back, then its successor's panel back from LDS (the first round
+      // reads what nobody wrote and nobody uses) ----
+      __builtin_amdgcn_sched_barrier(0);
+      if (dt >= 0 && !dead) fwd_tile_dots<KT, S>(pv, ds, dy0, dy1, dt * tile + 2LL * threadIdx.x, n, dset, acc);
+#pragma unroll
+      for (int i = 0; i < KT; i++) pv[i] = park[i * SW_BLOCK];
+      __builtin_amdgcn_sched_barrier(0);
     }
     // ---- publish ----
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave
@@ -758,8 +828,10 @@ __global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))
     }
     unsigned fl0 = f.epoch, ab0 = 0;
     int pp0 = 0, pp1 = 0;                                  // PIPE: the row patterns of the A-phase's tile, asked for in front of the panel loads as well
+    const long long tn0 = t0 + gridDim.x, tn = rev ? ntiles - 1 - tn0 : tn0;      // PIPE: the next round's tile
+    const bool hn = has && tn0 < ntiles;
     if (PIPE) {
-      // ---- park the tile's panel, wave 0's first polls, every wave's loads of the next round's tile ----
+      // ---- park the tile's panel; wave 0's first polls, the row patterns, every wave's first KT - LATE columns of the next round's tile ----
 #pragma unroll
       for (int i = 0; i < KT; i++) park[i * SW_BLOCK] = cv[i];
       if (arun && w == 0) {
@@ -768,11 +840,11 @@ __global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))
       }
       ksr::pair_patterns(f.rowpat, arun ? pt * tile + 2LL * threadIdx.x : 0, n, pp0, pp1);
       __builtin_amdgcn_sched_barrier(0);
-      const long long tn0 = t0 + gridDim.x;
-      fwd_load_panel<KT>(V, ld, n, k, v, rev ? ntiles - 1 - tn0 : tn0, has && tn0 < ntiles, nv, ns);
+      fwd_load_panel<KT, KT - LATE>(V, ld, n, k, v, tn, hn, nv, ns);
       __builtin_amdgcn_sched_barrier(0);
     }
-    // ---- A-phase of the tile of the round before ----
+    // ---- A-phase of the tile of the round before: wave 0's wait, the barrier, then A1 (neighbour loads, walk, y) and the dots ----
+    bool go = false;                                       // uniform: the poll matched
     if (arun) {
       if (w == 0) {
         int res;
@@ -797,47 +869,65 @@ __global__ __launch_bounds__(SW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))
         if (lane == 0) poll_sh = res;
       }
       if (PIPE) fwd_barrier_lds(); else __syncthreads();   // the other waves load v only behind this barrier
-      if (poll_sh) {
-        const long long r = pt * tile + 2LL * threadIdx.x;
-        const FwdLane ln(v, n, r, ksp::D2{ps.x, ps.y});
-        int p0 = pp0, p1 = pp1;
-        if (!PIPE) ksr::pair_patterns(f.rowpat, r, n, p0, p1);
-        double y0, y1;
-        if (PIPE) {
-          ksp::D2 xv[5]; double edge[5];
-          fwd_pair_loads<5>(f.pa, r, ln, xv, edge);
-          ksp::dict_pair_sums<5>(f.pa, sc, sm, p0, p1, r, ln, xv, edge, y0, y1);
-        } else ksp::dict_pair_walk<5>(f.pa, sc, sm, p0, p1, r, ln, y0, y1);
-        if (r + 1 < n) {
-          __builtin_nontemporal_store(ks_d2v{y0, y1}, reinterpret_cast<ks_d2v *>(f.y + r));
+      go = poll_sh != 0;
+      if (!go) dead = true;
+    }
+    if (PIPE) {
+      // the ten neighbour loads, sc1 (asking out of range, which reads nothing, unless the poll matched: no load of the column in front of the barrier
+      // above), then the rest of the next tile's panel: one block under no branch
+      const long long r = (arun ? pt : 0) * tile + 2LL * threadIdx.x;
+      const FwdLane ln(v, n, r, ksp::D2{ps.x, ps.y});
+      ksp::D2 xv[5]; double edge[5];
+      fwd_pair_loads<5>(f.pa, r, ln, go, xv, edge);
+      fwd_load_cols<KT, KT - LATE, KT>(V, ld, n, k, tn, hn, nv);
+      __builtin_amdgcn_sched_barrier(0);
+      double y0 = 0.0, y1 = 0.0;
+      if (go) {
+        fwd_pair_own<5>(f.pa, ln, xv);
+        ksp::dict_pair_sums<5>(f.pa, sc, sm, pp0, pp1, r, ln, xv, edge, y0, y1);
+        if (r + 1 < n) __builtin_nontemporal_store(ks_d2v{y0, y1}, reinterpret_cast<ks_d2v *>(f.y + r));
+        else if (r < n) { y0 = fwd_last_row(f, r, v); __builtin_nontemporal_store(y0, f.y + r); }
+      }
+      ds = ps; dy0 = y0; dy1 = y1; dt = go ? pt : -1; dset = pset;      // D of this tile: in the next round's shadow, or behind the loop
+    } else if (go) {
+      const long long r = pt * tile + 2LL * threadIdx.x;
+      const FwdLane ln(v, n, r, ksp::D2{ps.x, ps.y});
+      int p0, p1;
+      ksr::pair_patterns(f.rowpat, r, n, p0, p1);
+      double y0, y1;
+      ksp::dict_pair_walk<5>(f.pa, sc, sm, p0, p1, r, ln, y0, y1);
+      if (r + 1 < n) {
+        __builtin_nontemporal_store(ks_d2v{y0, y1}, reinterpret_cast<ks_d2v *>(f.y + r));
 #pragma unroll
-          for (int q = 0; q < S; q++)
-            if (q == pset) {
+        for (int q = 0; q < S; q++)
+          if (q == pset) {
 #pragma unroll
-              for (int i = 0; i < KT; i++) { acc[q][i] = fma(pv[i].x, y0, acc[q][i]); acc[q][i] = fma(pv[i].y, y1, acc[q][i]); }
-              acc[q][KT] = fma(ps.x, y0, acc[q][KT]); acc[q][KT] = fma(ps.y, y1, acc[q][KT]);
-              acc[q][KT + 1] = fma(y0, y0, acc[q][KT + 1]); acc[q][KT + 1] = fma(y1, y1, acc[q][KT + 1]);
-            }
-        } else if (r < n) {
-          const double yl = fwd_last_row(f, r, v);
-          __builtin_nontemporal_store(yl, f.y + r);
+            for (int i = 0; i < KT; i++) { acc[q][i] = fma(pv[i].x, y0, acc[q][i]); acc[q][i] = fma(pv[i].y, y1, acc[q][i]); }
+            acc[q][KT] = fma(ps.x, y0, acc[q][KT]); acc[q][KT] = fma(ps.y, y1, acc[q][KT]);
+            acc[q][KT + 1] = fma(y0, y0, acc[q][KT + 1]); acc[q][KT + 1] = fma(y1, y1, acc[q][KT + 1]);
+          }
+      } else if (r < n) {
+        const double yl = fwd_last_row(f, r, v);
+        __builtin_nontemporal_store(yl, f.y + r);
 #pragma unroll
-          for (int q = 0; q < S; q++)
-            if (q == pset) {
+        for (int q = 0; q < S; q++)
+          if (q == pset) {
 #pragma unroll
-              for (int i = 0; i < KT; i++) acc[q][i] = fma(pv[i].x, yl, acc[q][i]);
-              acc[q][KT] = fma(ps.x, yl, acc[q][KT]);
-              acc[q][KT + 1] = fma(yl, yl, acc[q][KT + 1]);
-            }
-        }
-      } else dead = true;
+            for (int i = 0; i < KT; i++) acc[q][i] = fma(pv[i].x, yl, acc[q][i]);
+            acc[q][KT] = fma(ps.x, yl, acc[q][KT]);
+            acc[q][KT + 1] = fma(yl, yl, acc[q][KT + 1]);
+          }
+      }
     }
     if (!has) break;
+    if (!PIPE) {
 #pragma unroll
-    for (int i = 0; i < KT; i++) pv[i] = PIPE ? park[i * SW_BLOCK] : cv[i];
+      for (int i = 0; i < KT; i++) pv[i] = cv[i];
+    }
     ps = cs; pt = t; pset = rset; rset = rset + 1 == S ? 0 : rset + 1;
   }
   if (dead) return;                                        // the dot sweep behind this launch rewrites every partial
+  if (PIPE && dt >= 0) fwd_tile_dots<KT, S>(pv, ds, dy0, dy1, dt * tile + 2LL * threadIdx.x, n, dset, acc);      // the last tile's dots; its panel came back in the last round
   // block combine, set by set, as block_write_partials does it for the sweep's workgroup blockIdx.x + q gridDim.x: partial index i < k <- acc[i] (y against
   // column i), k <- acc[KT] (against the new column), k + 1 <- acc[KT + 1] (the self dot)
   __shared__ double red2[SW_WAVES][KT + 2];
