@@ -227,13 +227,33 @@ int ks_mat_get_sizes(ks_mat A, int *n_local, int *n_global, long long *nnz_local
    gathers from memory. Values, row pointers, entry order and the bits of y are those of CSR. Built only when asked for: KSGPU_SPMV=window
    builds it for any matrix with rows and entries; no automatic rule picks it yet. */
 enum { KS_MAT_LAYOUT_CSR = 0, KS_MAT_LAYOUT_SELL = 1, KS_MAT_LAYOUT_SLICED = 2, KS_MAT_LAYOUT_SHELL = 3, KS_MAT_LAYOUT_DICT = 4, KS_MAT_LAYOUT_ODICT = 5, KS_MAT_LAYOUT_BINNED = 6,
-       KS_MAT_LAYOUT_WINDOW = 7 };
+       KS_MAT_LAYOUT_WINDOW = 7, KS_MAT_LAYOUT_BSR = 8 };
 int ks_mat_get_layout(ks_mat A, int *layout);
 /* The windowed CSR layout (KS_MAT_LAYOUT_WINDOW). *block_rows (rows of a block) and *max_segments (segments of x a window holds) are the library's two
    constants and are returned for any matrix. For a matrix in this layout: *blocks, *direct_blocks (blocks that reference more segments than a window
    holds), *window_entries (entries of the other blocks) and *index_bytes, the column information a product reads: 2 bytes per window entry, 4 per
    direct entry, 4 per listed segment. Any other layout: these four 0. */
 int ks_mat_get_window_info(ks_mat A, int *block_rows, int *max_segments, long long *blocks, long long *direct_blocks, long long *window_entries, long long *index_bytes);
+/* MatCreateSeqBAIJWithArrays / MatCreateMPIBAIJWithArrays: a matrix of dense bs x bs blocks. browptr[n_local / bs + 1], bcol[nnzb] (GLOBAL block
+   columns; inside a block row in any order, repeats allowed), bval[nnzb bs bs] with block k column-major at bval + k bs bs, as in PETSc's
+   Mat_SeqBAIJ::a. The matrix is, in every respect but the device layout of its diagonal block, ks_mat_create_csr_flags of its EXPANSION: scalar row
+   bs I + i holds, for each block k of block row I in stored order and then c = 0 .. bs - 1, the entry (bs bcol[k] + c, blk_k(i, c)); explicit zeros
+   inside blocks are entries. flags as there (KS_MAT_KEEP_CSR keeps the expanded arrays, so ks_mat_create_axpy, both transposes and every PC
+   set-up work unchanged); ks_mat_get_diagonal, ks_mat_norm_inf and ks_mat_get_sizes answer for the expansion.
+   Device layout: 2 <= bs <= 8 and KSGPU_SPMV unset: KS_MAT_LAYOUT_BSR - the values at 8 bytes per stored scalar, one int per block, one int per
+   block row, no per-entry index: 8 + 4 / bs^2 bytes per scalar against the CSR stream's 12, and one gather of bs contiguous doubles of x per block.
+   y = A x and every column of ks_mat_mult_multi are bit for bit what the CSR kernels give on the expansion. bs == 1 or bs > 8: the expansion goes
+   through the ordinary chooser; KSGPU_SPMV=<name> forces that layout on the expansion. Matrices from the other creation calls never get this layout,
+   nor do ks_mat_create_axpy results and transposes of such a matrix. More than one rank: n_local, row_start and n_global are multiples of bs.
+   Errors: bs < 1: KS_ERR_ARG_OUTOFRANGE; a size that is not a multiple of bs: KS_ERR_ARG_SIZ (before any collective); browptr[I + 1] < browptr[I]:
+   KS_ERR_ARG_WRONG, and a block column outside [0, n_global / bs): KS_ERR_ARG_OUTOFRANGE, both naming the block row (all row pointers are checked
+   before the first block column); more than 2^31 - 1 stored scalars: KS_ERR_ARG_OUTOFRANGE; a failed allocation: KS_ERR_MEM, nothing left half-built. */
+int ks_mat_create_bsr(ks_ctx ctx, int bs, int n_local, int row_start, int n_global, const int *browptr, const int *bcol, const double *bval,
+                      unsigned flags, ks_mat *A);
+/* The block CSR layout (KS_MAT_LAYOUT_BSR): *bs, the library's two constants for that bs - *group_block_rows, the block rows a workgroup takes per
+   step, and *chunk_entries, the stored scalars one staging step of a wave brings in - *block_rows and *blocks of the local diagonal block, and
+   *index_bytes = 4 blocks + 4 (block_rows + 1), all the index information a product reads. Any other layout: all outputs 0. */
+int ks_mat_get_bsr_info(ks_mat A, int *bs, int *group_block_rows, int *chunk_entries, long long *block_rows, long long *blocks, long long *index_bytes);
 /* The dictionary layout (KS_MAT_LAYOUT_DICT) stores a row as W 2-byte codes (W = 8, 16 or 32 entry slots). When the matrix has at most 256 distinct
    rows of codes it keeps one byte per row instead, the index of the row's code word in a table of *npatterns words (the row-pattern form), and frees the
    codes. *patterns = 1 in that form, 0 otherwise; *npatterns = 0 and *index_bytes = 2 W n with the codes, n (plus padding to 256 rows) with the

@@ -256,6 +256,26 @@ class Mat:
         _lib.check(ctx.L.ks_mat_create_csr_flags(ctx.h, n, row_start, n_global, _pi(rowptr), _pi(col), _p(val), (1 if keep_csr else 0) | (2 if sharded_transpose else 0), C.byref(h)))
         return cls(ctx, h)
 
+    @classmethod
+    def from_bsr(cls, ctx, browptr, bcol, blocks, row_start=0, n_global=None, keep_csr=False, sharded_transpose=False):
+        """MatCreateSeqBAIJWithArrays / MatCreateMPIBAIJWithArrays (ks_mat_create_bsr): browptr (block rows + 1), bcol (GLOBAL block columns) and
+        blocks[k, i, c], entry (i, c) of block k; the block size is blocks.shape[1]. row_start and n_global are scalar rows, multiples of it.
+        The matrix is from_csr of the expansion (scalar row bs I + i: the blocks of block row I in stored order, c ascending) except for its device
+        layout: "bsr" for block sizes 2 to 8 unless KSGPU_SPMV forces another."""
+        browptr = np.ascontiguousarray(browptr, dtype=np.int32)
+        bcol = np.ascontiguousarray(bcol, dtype=np.int32)
+        blocks = np.asarray(blocks, dtype=np.float64)
+        if blocks.ndim != 3 or blocks.shape[1] != blocks.shape[2]:
+            raise ValueError("blocks must have shape (nnzb, bs, bs)")
+        bs = blocks.shape[1]
+        bval = np.ascontiguousarray(blocks.transpose(0, 2, 1)).reshape(-1)       # column-major blocks, as Mat_SeqBAIJ::a
+        n = (len(browptr) - 1) * bs
+        if n_global is None:
+            n_global = n
+        h = C.c_void_p()
+        _lib.check(ctx.L.ks_mat_create_bsr(ctx.h, bs, n, row_start, n_global, _pi(browptr), _pi(bcol), _p(bval), (1 if keep_csr else 0) | (2 if sharded_transpose else 0), C.byref(h)))
+        return cls(ctx, h)
+
     def axpy_new(self, alpha, B=None, keep_csr=False):
         """MatDuplicate(self) + MatAXPY(P, alpha, B, DIFFERENT_NONZERO_PATTERN); B None: MatShift(P, alpha). P has a transposed product across
         ranks (and keeps its arrays) when every operand was created with sharded_transpose (ks_mat_create_axpy)."""
@@ -344,7 +364,15 @@ class Mat:
 
     def layout(self):
         v = C.c_int(); _lib.check(self.ctx.L.ks_mat_get_layout(self.h, C.byref(v)))
-        return ["csr", "sell", "sliced", "shell", "dict", "odict", "binned", "window"][v.value]
+        return ["csr", "sell", "sliced", "shell", "dict", "odict", "binned", "window", "bsr"][v.value]
+
+    def bsr_info(self):
+        """The block CSR layout (ks_mat_get_bsr_info): block size, the two constants of the product for it, the counts and the index bytes; all 0
+        unless layout() is "bsr"."""
+        bs, g, ch = C.c_int(), C.c_int(), C.c_int()
+        nb, b, ib = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        _lib.check(self.ctx.L.ks_mat_get_bsr_info(self.h, C.byref(bs), C.byref(g), C.byref(ch), C.byref(nb), C.byref(b), C.byref(ib)))
+        return {"bs": bs.value, "group_block_rows": g.value, "chunk_entries": ch.value, "block_rows": nb.value, "blocks": b.value, "index_bytes": ib.value}
 
     def window_info(self):
         """The windowed CSR layout (ks_mat_get_window_info): the two constants for any matrix, the counts 0 unless layout() is "window"."""
@@ -414,7 +442,11 @@ class Mat:
         return YB.dense()
 
     def spmv_bytes(self):
-        """Algorithmic bytes of one MatMult: 12*nnz + 4*(n+1) + 16*n."""
+        """Algorithmic bytes of one MatMult: 12*nnz + 4*(n+1) + 16*n. A block CSR matrix (one rank): the bytes of its own stream,
+        8*bs^2*nnzb + 4*nnzb + 4*(nb+1), and the same 16*n."""
+        if self.layout() == "bsr":
+            i = self.bsr_info()
+            return 8.0 * i["bs"] ** 2 * i["blocks"] + 4.0 * i["blocks"] + 4.0 * (i["block_rows"] + 1) + 16.0 * self.n
         return 12.0 * self.nnz + 4.0 * (self.n + 1) + 16.0 * self.n
 
 

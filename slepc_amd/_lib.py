@@ -68,6 +68,8 @@ _SIG = {
     "ks_mat_get_dict_info": [vp, ip, ip, ip, llp],
     "ks_mat_get_dict_pairs_info": [vp, ip, ip, llp, llp],
     "ks_mat_get_window_info": [vp, ip, ip, llp, llp, llp, llp],
+    "ks_mat_create_bsr": [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, dp, C.c_uint, C.POINTER(vp)],
+    "ks_mat_get_bsr_info": [vp, ip, ip, ip, llp, llp, llp],
     "ks_mat_load_petsc_binary": [vp, C.c_char_p, C.POINTER(vp)],
     "ks_mat_create_shell": [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(vp)],
     "ks_mat_shell_set_enqueue_only": [vp, C.c_int],

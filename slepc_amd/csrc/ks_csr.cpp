@@ -895,6 +895,75 @@ void amg_plan(int n, const int *rp, const int *col, const double *val, const Amg
     Lc.n = nagg; Lc.rp.swap(Ac.rp); Lc.col.swap(Ac.col); Lc.val.swap(Ac.val);
   }
 }
+
+// ---- block CSR (BAIJ) input -------------------------------------------------------------------------------------------------------------------------
+void bsr_expand(int bs, int nb, int nb_global, const int *browptr, const int *bcol, const double *bval, BsrExpansion &out)
+{
+  out = BsrExpansion();
+  for (int I = 0; I < nb; I++) if (browptr[I + 1] < browptr[I]) { out.status = BSR_ROWPTR; out.bad_row = I; return; }
+  const long long nnzb = browptr[nb], b2 = (long long)bs * bs;
+  if (nnzb * b2 > 2147483647LL) { out.status = BSR_TOO_LARGE; return; }
+  for (int I = 0; I < nb; I++)
+    for (int k = browptr[I]; k < browptr[I + 1]; k++)
+      if (bcol[k] < 0 || bcol[k] >= nb_global) { out.status = BSR_COLUMN; out.bad_row = I; out.bad_col = bcol[k]; return; }
+  out.rp.assign((size_t)nb * bs + 1, 0); out.col.resize((size_t)(nnzb * b2)); out.val.resize((size_t)(nnzb * b2));
+  for (int I = 0; I < nb; I++) {
+    const int k0 = browptr[I], len = browptr[I + 1] - k0;
+    for (int i = 0; i < bs; i++) {
+      size_t e = (size_t)k0 * b2 + (size_t)i * len * bs;             // the rows of a block row have the same length
+      out.rp[(size_t)I * bs + i] = (int)e;
+      for (int k = k0; k < k0 + len; k++)
+        for (int c = 0; c < bs; c++, e++) { out.col[e] = bs * bcol[k] + c; out.val[e] = bval[(size_t)k * b2 + (size_t)c * bs + i]; }
+    }
+  }
+  out.rp[(size_t)nb * bs] = (int)(nnzb * b2);
+}
+void bsr_diag(int bs, int nb, int bstart, const int *browptr, const int *bcol, const double *bval, BsrBlocks &out)
+{
+  out = BsrBlocks();
+  const size_t b2 = (size_t)bs * bs;
+  out.browptr.assign((size_t)nb + 1, 0);
+  for (int I = 0; I < nb; I++) {
+    for (int k = browptr[I]; k < browptr[I + 1]; k++)
+      if (bcol[k] >= bstart && bcol[k] < bstart + nb) { out.bcol.push_back(bcol[k] - bstart); out.bval.insert(out.bval.end(), bval + (size_t)k * b2, bval + (size_t)(k + 1) * b2); }
+    out.browptr[(size_t)I + 1] = (int)out.bcol.size();
+  }
+}
+void bsr_plan(int bs, int nb, const int *browptr, const int *bcol, const double *bval, int group_rows, int chunk_blocks, int pad, BsrPlan &out)
+{
+  out = BsrPlan();
+  const long long nnzb = browptr[nb]; const size_t b2 = (size_t)bs * bs;
+  out.bs = bs; out.nb = nb; out.group_rows = group_rows; out.chunk_blocks = chunk_blocks; out.blocks = nnzb;
+  out.groups = ((long long)nb + group_rows - 1) / group_rows;
+  out.browptr.assign(browptr, browptr + nb + 1);
+  out.bcol.assign((size_t)nnzb + pad, 0); std::copy(bcol, bcol + nnzb, out.bcol.begin());
+  out.val.assign((size_t)nnzb * b2 + pad, 0.0);
+  for (long long k = 0; k < nnzb; k++)
+    for (int i = 0; i < bs; i++)
+      for (int c = 0; c < bs; c++) out.val[(size_t)k * b2 + (size_t)i * bs + c] = bval[(size_t)k * b2 + (size_t)c * bs + i];
+  out.gptr.resize((size_t)out.groups + 1);
+  for (long long g = 0; g <= out.groups; g++) out.gptr[(size_t)g] = browptr[std::min<long long>(g * group_rows, nb)];
+}
+void bsr_apply_host(const BsrPlan &p, const double *x, double *y)
+{
+  const int bs = p.bs, wr = p.group_rows / 4; const size_t b2 = (size_t)bs * bs;
+  for (long long g = 0; g < p.groups; g++)
+    for (int w = 0; w < 4; w++) {
+      const long long I0 = g * p.group_rows + (long long)w * wr, I1 = std::min<long long>(I0 + wr, p.nb);
+      if (I0 >= p.nb) continue;
+      std::vector<double> acc((size_t)(I1 - I0) * bs, 0.0);
+      const int B0 = p.browptr[(size_t)I0], B1 = p.browptr[(size_t)I1];
+      for (int b0 = B0; b0 < B1; b0 += p.chunk_blocks)                       // a chunk: every lane sums its row's part of it
+        for (long long I = I0; I < I1; I++)
+          for (int i = 0; i < bs; i++) {
+            double &a = acc[(size_t)(I - I0) * bs + i];
+            const int lo = std::max(p.browptr[(size_t)I], b0), hi = std::min(p.browptr[(size_t)I + 1], b0 + p.chunk_blocks);
+            for (int k = lo; k < hi; k++)
+              for (int c = 0; c < bs; c++) a = std::fma(p.val[(size_t)k * b2 + (size_t)i * bs + c], x[(size_t)bs * p.bcol[(size_t)k] + c], a);
+          }
+      for (long long I = I0; I < I1; I++) for (int i = 0; i < bs; i++) y[(size_t)I * bs + i] = acc[(size_t)(I - I0) * bs + i];
+    }
+}
 } // namespace ksc
 
 #ifdef KSD_TEST_HOOKS
@@ -1022,6 +1091,28 @@ long long ksc_window_plan(int n, const int *rp, const int *col, int block_rows, 
   totals[0] = p.blocks; totals[1] = p.direct_blocks; totals[2] = p.window_entries; totals[3] = p.direct_entries; totals[4] = p.total_segments;
   totals[5] = (long long)p.dcol.size() - 8;
   return p.total_segments;
+}
+// test hook: the CSR expansion of block CSR arrays. info: status, bad block row, bad block column, entries. rp (nb bs + 1), col, val (browptr[nb] bs bs
+// each) may be NULL (a first call for the status alone). Returns the status.
+int ksc_bsr_expand(int bs, int nb, int nb_global, const int *browptr, const int *bcol, const double *bval, int *rp, int *col, double *val, long long *info)
+{
+  ksc::BsrExpansion e;
+  ksc::bsr_expand(bs, nb, nb_global, browptr, bcol, bval, e);
+  info[0] = e.status; info[1] = e.bad_row; info[2] = e.bad_col; info[3] = (long long)e.col.size();
+  if (e.status) return e.status;
+  if (rp) { std::copy(e.rp.begin(), e.rp.end(), rp); std::copy(e.col.begin(), e.col.end(), col); std::copy(e.val.begin(), e.val.end(), val); }
+  return 0;
+}
+// test hook: the diagonal block of a rank's block CSR arrays, its device image and the host walk of that. info: blocks of the diagonal block, groups.
+// val (room for browptr[nb] bs bs) receives the row-major image without its padding, x / y (may be NULL): nb bs each.
+void ksc_bsr_plan(int bs, int nb, int bstart, const int *browptr, const int *bcol, const double *bval, int group_rows, int chunk_blocks, double *val, const double *x, double *y, long long *info)
+{
+  ksc::BsrBlocks d; ksc::BsrPlan p;
+  ksc::bsr_diag(bs, nb, bstart, browptr, bcol, bval, d);
+  ksc::bsr_plan(bs, nb, d.browptr.data(), d.bcol.data(), d.bval.data(), group_rows, chunk_blocks, 8, p);
+  info[0] = p.blocks; info[1] = p.groups;
+  if (val) std::copy(p.val.begin(), p.val.end() - 8, val);
+  if (x && y) ksc::bsr_apply_host(p, x, y);
 }
 // test hook: ILU(0) of the diagonal blocks (block size bs) and the solve the kernel runs, on the host. frp (n + 1), fcol, fval (cap entries, may be
 // NULL): the factors on the blocks' sorted patterns, block-local columns. in / out (may be NULL): out = (LU)^-1 in through the level layout.

@@ -111,6 +111,31 @@ struct WindowPlan {
 // pad: what the code and column arrays are longer than their last entry (CW_PAD)
 void csr_window_plan(int n, const int *rp, const int *col, int block_rows, int max_segments, int pad, WindowPlan &out);
 
+// Block CSR (BAIJ) input, ks_mat_create_bsr. A rank's nb block rows of bs x bs blocks: browptr (nb + 1), bcol (GLOBAL block columns, any order, repeats
+// allowed), bval (block k column-major at bval + k bs bs, as PETSc's Mat_SeqBAIJ::a).
+//   bsr_expand  the CSR arrays that define the matrix: scalar row bs I + i holds, for each block k of block row I in stored order and then c = 0 .. bs - 1,
+//               the entry (bs bcol[k] + c, blk_k(i, c)); explicit zeros inside blocks are entries. Checked first, in this order: every row pointer
+//               (BSR_ROWPTR: browptr[bad_row + 1] < browptr[bad_row]), the size (BSR_TOO_LARGE: more than 2^31 - 1 stored scalars; nothing of bcol has
+//               been read by then), every block column in block row order (BSR_COLUMN: bad_col of block row bad_row is outside [0, nb_global)). On a
+//               status nothing is filled.
+constexpr int BSR_ROWPTR = 1, BSR_COLUMN = 2, BSR_TOO_LARGE = 3;
+struct BsrExpansion { int status = 0, bad_row = -1, bad_col = 0; std::vector<int> rp, col; std::vector<double> val; };
+void bsr_expand(int bs, int nb, int nb_global, const int *browptr, const int *bcol, const double *bval, BsrExpansion &out);
+//   bsr_diag    the blocks of the rank's own block columns [bstart, bstart + nb), with local block columns and in stored order: the diagonal block of
+//               the expansion's split (csr_split_block), block by block.
+//   bsr_plan    the device image of those (KS_MAT_LAYOUT_BSR; the kernels that walk it: k_spmv_bsr, k_spmm_bsr). val holds every block ROW-major - the lane
+//               of scalar row i reads blk(i, 0 .. bs - 1) as one contiguous run - block after block in stored order, and is `pad` scalars longer than
+//               its last block, as bcol is `pad` blocks longer (the CW_PAD rule: what a chunk load may read past the end; zeros). A workgroup takes
+//               group_rows consecutive block rows per step, wave w of it wave_rows = group_rows / 4 of them; gptr (groups + 1) are the groups' bounds
+//               in the block stream, gptr[g] = browptr[min(g group_rows, nb)].
+struct BsrBlocks { std::vector<int> browptr, bcol; std::vector<double> bval; };       // bval as given: column-major blocks
+void bsr_diag(int bs, int nb, int bstart, const int *browptr, const int *bcol, const double *bval, BsrBlocks &out);
+struct BsrPlan { int bs = 0, nb = 0, group_rows = 0, chunk_blocks = 0; long long blocks = 0, groups = 0; std::vector<int> browptr, bcol, gptr; std::vector<double> val; };
+void bsr_plan(int bs, int nb, const int *browptr, const int *bcol, const double *bval, int group_rows, int chunk_blocks, int pad, BsrPlan &out);
+// the kernel's walk on the host: group by group, wave by wave, the wave's run of blocks in chunks of chunk_blocks; inside a chunk scalar row i of a block
+// row runs acc = fma(blk(i, c), x[bs bcol + c], acc) over its blocks of the chunk in stored order, c ascending - from 0.0: the entry order of the expansion
+void bsr_apply_host(const BsrPlan &p, const double *x, double *y);
+
 // ILU(0) of the diagonal blocks of a CSR row block, laid out for k_bjacobi_ilu_apply (ks_pc.hip): PCBJACOBI with -sub_pc_type ilu at zero fill
 // (PETSc's MatILUFactorSymbolic/Numeric on each block, natural ordering). Block b is local rows b*bs .. min(n, (b+1)*bs) - 1 and the columns
 // row_start + the same range; everything else in those rows (other blocks, ghost columns) is dropped. A block's rows are sorted by column and

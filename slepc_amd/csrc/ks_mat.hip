@@ -689,6 +689,27 @@ int choose_layout(ks_mat A)
   return build_sell(A, want == SELL);
 }
 
+// The block CSR layout of a matrix that came as block CSR (ks_mat_create_bsr): the rank's own block columns of the arrays it was given, planned on
+// the host (ks_csr.cpp) and uploaded; the CSR arrays of the diagonal block, which the assembly has on the device by now, give the diagonal and the
+// norm and are released. A failed allocation is KS_ERR_MEM (the caller destroys the matrix).
+struct BsrInput { int bs; const int *browptr, *bcol; const double *bval; };
+int build_bsr(ks_mat A, const BsrInput &in)
+{
+  const int bs = in.bs, nb = A->n / bs;
+  try {
+    ksc::BsrBlocks d; ksc::BsrPlan p;
+    ksc::bsr_diag(bs, nb, A->row_start / bs, in.browptr, in.bcol, in.bval, d);
+    ksc::bsr_plan(bs, nb, d.browptr.data(), d.bcol.data(), d.bval.data(), bsr_group_rows(bs), bsr_chunk_blocks(bs), CW_PAD, p);
+    KS_CHECK(p.blocks * bs * bs == A->nnz_d, KS_ERR_PLIB, "block CSR: %lld blocks of %d x %d against %lld entries of the diagonal block", p.blocks, bs, bs, A->nnz_d);
+    const bool ok = upload(&A->bsr_rowptr, p.browptr) == hipSuccess && upload(&A->bsr_col, p.bcol) == hipSuccess && upload(&A->bsr_val, p.val) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); KS_FAIL(KS_ERR_MEM, "block CSR: no device memory for %lld blocks of %d x %d", p.blocks, bs, bs); }
+    if (A->n > 0) KS_CALL(release_csr(A));
+    A->bsr_bs = bs; A->bsr_nb = nb; A->bsr_blocks = p.blocks;
+    A->layout = KS_MAT_LAYOUT_BSR;
+  } catch (const std::exception &e) { KS_FAIL(KS_ERR_MEM, "block CSR plan on the host: %s", e.what()); }
+  return KS_SUCCESS;
+}
+
 } // namespace
 
 extern "C" int ks_mat_create_csr(ks_ctx ctx, int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val, ks_mat *out)
@@ -698,7 +719,8 @@ extern "C" int ks_mat_create_csr(ks_ctx ctx, int n_local, int row_start, int n_g
 
 // the one assembly path. local_only: the block is assembled as a matrix of its own whatever the communicator - no halo plan, so no collective
 // (every column must then be the rank's own): the transposed diagonal block of a row-sharded matrix
-static int mat_assemble(ks_ctx ctx, int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val, unsigned flags, bool local_only, ks_mat *out)
+// bsr: the block CSR arrays the CSR arrays are the expansion of (ks_mat_create_bsr) - the diagonal block then gets the block CSR layout, not the chooser's
+static int mat_assemble(ks_ctx ctx, int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val, unsigned flags, bool local_only, ks_mat *out, const BsrInput *bsr = nullptr)
 {
   KS_CHECK(ctx && out, KS_ERR_ARG_NULL, "ctx/out is NULL");
   KS_CHECK((flags & ~(KS_MAT_KEEP_CSR | KS_MAT_SHARDED_TRANSPOSE)) == 0, KS_ERR_ARG_OUTOFRANGE, "unknown matrix creation flags 0x%x", flags);
@@ -731,7 +753,7 @@ static int mat_assemble(ks_ctx ctx, int n_local, int row_start, int n_global, co
     try { A->h_ghosts = garray; } catch (const std::exception &e) { ks_set_error("KS_MAT_SHARDED_TRANSPOSE: %s", e.what()); rc = KS_ERR_MEM; }
   }
   if (!rc) rc = compact_offdiag_rows(A);
-  if (!rc) rc = choose_layout(A);
+  if (!rc) rc = bsr ? build_bsr(A, *bsr) : choose_layout(A);
   if (rc) { ks_mat_destroy(A); return rc; }
   if (flags & KS_MAT_KEEP_CSR) {
     try { A->k_rowptr.assign(rowptr, rowptr + n_local + 1); A->k_col.assign(col, col + nnz); A->k_val.assign(val, val + nnz); }
@@ -748,6 +770,37 @@ extern "C" int ks_mat_create_csr_flags(ks_ctx ctx, int n_local, int row_start, i
 int ks_mat_assemble_local(ks_ctx ctx, int n_local, int row_start, int n_global, const int *rowptr, const int *col, const double *val, ks_mat *out)
 {
   return mat_assemble(ctx, n_local, row_start, n_global, rowptr, col, val, 0u, true, out);
+}
+// MatCreateSeqBAIJWithArrays / MatCreateMPIBAIJWithArrays: the matrix IS ks_mat_create_csr_flags of the expansion (ksc::bsr_expand), apart from the device
+// layout of its diagonal block: block CSR for 2 <= bs <= 8 unless KSGPU_SPMV forces one of the chooser's on the expansion
+extern "C" int ks_mat_create_bsr(ks_ctx ctx, int bs, int n_local, int row_start, int n_global, const int *browptr, const int *bcol, const double *bval, unsigned flags, ks_mat *out)
+{
+  KS_CHECK(ctx && out, KS_ERR_ARG_NULL, "ctx/out is NULL");
+  KS_CHECK(bs >= 1, KS_ERR_ARG_OUTOFRANGE, "block size %d must be at least 1", bs);
+  KS_CHECK(n_local >= 0 && row_start >= 0 && n_global >= 0 && n_local % bs == 0 && row_start % bs == 0 && n_global % bs == 0, KS_ERR_ARG_SIZ,
+           "local rows %d, first row %d and global size %d must be multiples of the block size %d", n_local, row_start, n_global, bs);
+  KS_CHECK(row_start + (long long)n_local <= n_global, KS_ERR_ARG_OUTOFRANGE, "bad row range [%d,%lld) of %d", row_start, row_start + (long long)n_local, n_global);
+  const int nb = n_local / bs;
+  KS_CHECK(browptr && (browptr[nb] == 0 || (bcol && bval)), KS_ERR_ARG_NULL, "block CSR arrays are NULL");
+  KS_CHECK(browptr[0] == 0, KS_ERR_ARG_WRONG, "rowptr[0] must be 0");
+  ksc::BsrExpansion e;
+  try { ksc::bsr_expand(bs, nb, n_global / bs, browptr, bcol, bval, e); }
+  catch (const std::exception &x) { KS_FAIL(KS_ERR_MEM, "expansion of the block CSR arrays: %s", x.what()); }
+  KS_CHECK(e.status != ksc::BSR_ROWPTR, KS_ERR_ARG_WRONG, "rowptr not monotone at block row %d", e.bad_row);
+  KS_CHECK(e.status != ksc::BSR_TOO_LARGE, KS_ERR_ARG_OUTOFRANGE, "%d blocks of %d x %d exceed 32-bit PetscInt indices", browptr[nb], bs, bs);
+  KS_CHECK(e.status != ksc::BSR_COLUMN, KS_ERR_ARG_OUTOFRANGE, "block column %d out of range at block row %d", e.bad_col, e.bad_row);
+  const BsrInput in = {bs, browptr, bcol, bval};
+  const bool blocked = bs >= BSR_BS_MIN && bs <= BSR_BS_MAX && !getenv("KSGPU_SPMV");
+  return mat_assemble(ctx, n_local, row_start, n_global, e.rp.data(), e.col.data(), e.val.data(), flags, false, out, blocked ? &in : nullptr);
+}
+extern "C" int ks_mat_get_bsr_info(ks_mat A, int *bs, int *group_block_rows, int *chunk_entries, long long *block_rows, long long *blocks, long long *index_bytes)
+{
+  KS_CHECK(A && bs && group_block_rows && chunk_entries && block_rows && blocks && index_bytes, KS_ERR_ARG_NULL, "NULL argument");
+  *bs = *group_block_rows = *chunk_entries = 0; *block_rows = *blocks = *index_bytes = 0;
+  if (A->shell_mult || A->layout != KS_MAT_LAYOUT_BSR) return KS_SUCCESS;
+  *bs = A->bsr_bs; *group_block_rows = bsr_group_rows(A->bsr_bs); *chunk_entries = bsr_chunk_blocks(A->bsr_bs) * A->bsr_bs * A->bsr_bs;
+  *block_rows = A->bsr_nb; *blocks = A->bsr_blocks; *index_bytes = 4 * A->bsr_blocks + 4 * ((long long)A->bsr_nb + 1);
+  return KS_SUCCESS;
 }
 bool ks_mat_has_transpose_across_ranks(ks_mat A)
 {
@@ -861,6 +914,7 @@ extern "C" int ks_mat_destroy(ks_mat A)
   hipFree(A->sl_rowptr); hipFree(A->sl_col); hipFree(A->sl_val); hipFree(A->sl_base); hipFree(A->ypart); hipFree(A->diag_cache); hipFree(A->mm_xi);
   hipFree(A->bn_col16); hipFree(A->bn_row16); hipFree(A->bn_val); hipFree(A->bn_g); hipFree(A->bn_off1); hipFree(A->bn_off2t); hipFree(A->bn_wseg); hipFree(A->bn_sbase); hipFree(A->bn_off2); hipFree(A->bn_log2);
   hipFree(A->wn_codes); hipFree(A->wn_dcol); hipFree(A->wn_segptr); hipFree(A->wn_seg); hipFree(A->wn_dbase);
+  hipFree(A->bsr_rowptr); hipFree(A->bsr_col); hipFree(A->bsr_val);
   delete A;
   return KS_SUCCESS;
 }

@@ -194,6 +194,138 @@ __device__ __forceinline__ void pair_patterns(const unsigned char *__restrict__ 
   const unsigned pp = *reinterpret_cast<const unsigned short *>(rowpat + (r < n ? r : 0));
   p0 = (int)(pp & 255u); p1 = (int)(pp >> 8);
 }
+// ---- block CSR (KS_MAT_LAYOUT_BSR): the wave's block rows, its one contiguous run of blocks, and the walk both products share -------------------------
+// wave_groups_xcd for groups that are not 256 rows: NG groups, with xcd_remap each XCD one contiguous eighth of them
+__device__ __forceinline__ WaveGroups group_range_xcd(int NG, int xcd_remap)
+{
+  if (xcd_remap) {
+    const int xcd = blockIdx.x & 7, li = blockIdx.x >> 3, lc = gridDim.x >> 3;
+    return {(int)((long long)NG * xcd / 8) + li, (int)((long long)NG * (xcd + 1) / 8), lc};
+  }
+  return {(int)blockIdx.x, NG, (int)gridDim.x};
+}
+// wave w of group g owns 64 / BS block rows: lane = scalar row (lanes past 64 / BS * BS idle). p0, p1: the lane's block row in the block stream;
+// B0, B1: the wave's run of blocks (uniform)
+struct BsrRows { int p0, p1, B0, B1; long long r; bool has; };
+template <int BS>
+__device__ __forceinline__ BsrRows bsr_rows(int nb, const int *__restrict__ brp, int g, int w, int lane)
+{
+  constexpr int R = bsr_wave_rows(BS);
+  BsrRows q; q.p0 = q.p1 = q.B0 = q.B1 = 0; q.r = 0; q.has = false;
+  const long long I0 = (long long)g * (4 * R) + (long long)w * R;
+  if (I0 >= nb) return q;
+  const long long I = I0 + lane / BS;
+  q.has = lane < R * BS && I < nb;
+  q.r = I * BS + lane % BS;
+  if (q.has) { ks_i2v pp; __builtin_memcpy(&pp, brp + I, sizeof(pp)); q.p0 = pp.x; q.p1 = pp.y; }
+  q.B0 = brp[I0]; q.B1 = brp[I0 + R < nb ? I0 + R : nb];
+  return q;
+}
+// a chunk of NBK blocks from block b0 in registers: the values as STEPS 16-byte nontemporal loads per lane from the even scalar at or below the chunk's
+// first (lane l of step u: scalars 128 u + 2 l, + 1; may take one scalar past the run: CW_PAD), and the block column of each (block, c) item the lane
+// gathers x for (item t = 64 u + l: block t / BS, column t % BS; the BS lanes of a block read one address), -1 where there is none
+template <int BS, int NBK> struct BsrRegs {
+  static constexpr int STEPS = (NBK * BS * BS + (BS & 1) + 127) / 128, U = (NBK * BS + 63) / 64;
+  ksk::ks_d2v a[STEPS]; int c[U];
+};
+template <int BS, int NBK>
+__device__ __forceinline__ void bsr_load(BsrRegs<BS, NBK> &r, const int *__restrict__ bcol, const double *__restrict__ val, int b0, int B1, int lane)
+{
+  const int e0 = (b0 * BS * BS) & ~1, E1 = B1 * BS * BS;
+#pragma unroll
+  for (int u = 0; u < BsrRegs<BS, NBK>::STEPS; u++) {
+    const int e = e0 + 128 * u + 2 * lane;
+    r.a[u] = e < E1 ? __builtin_nontemporal_load(reinterpret_cast<const ksk::ks_d2v *>(val + e)) : ksk::ks_d2v{0.0, 0.0};
+  }
+#pragma unroll
+  for (int u = 0; u < BsrRegs<BS, NBK>::U; u++) {
+    const int t = 64 * u + lane, j = t / BS;
+    r.c[u] = (t < NBK * BS && b0 + j < B1) ? bcol[b0 + j] : -1;
+  }
+}
+// The walk (k_spmv_bsr: KB = 1; k_spmm_bsr: KB = 4 or 8 accumulators per lane, kb <= KB columns live). k_spmv_csr_wave's software pipeline with blocks
+// in place of entries: the chunk in `cur` is parked in the wave's own LDS - values as they came, x gathered once per (block, c) and column of the pass,
+// KB values side by side - the NEXT chunk's loads (of the same block rows, or the first chunk of the wave's next block rows) are issued, then lane =
+// scalar row i runs acc = fma(blk(i, c), x, acc) over its block row's blocks of the chunk, c ascending: the expansion's entry order, from 0.0. LDS
+// operations of one wave execute in order: no workgroup barrier anywhere. sa: 128 STEPS doubles, sx: NBK BS KB doubles, both the wave's own.
+template <int BS, int KB, int NBK>
+__device__ __forceinline__ void bsr_walk(double *sa, double *sx, int nb, const int *__restrict__ brp, const int *__restrict__ bcol, const double *__restrict__ val,
+                                         const double *__restrict__ X, long long ldx, double *__restrict__ Y, long long ldy, int kb, int xcd_remap)
+{
+  typedef BsrRegs<BS, NBK> Regs;
+  constexpr int B2 = BS * BS, GR = bsr_group_rows(BS);
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const WaveGroups wg = group_range_xcd((nb + GR - 1) / GR, xcd_remap);
+  int g = wg.g;
+  const int gend = wg.gend, gstep = wg.gstep;
+  if (g >= gend) return;
+  BsrRows cu = bsr_rows<BS>(nb, brp, g, w, lane);
+  BsrRows nx = g + gstep < gend ? bsr_rows<BS>(nb, brp, g + gstep, w, lane) : BsrRows{0, 0, 0, 0, 0, false};
+  Regs cur, nxt;
+  int b0 = cu.B0;
+  if (b0 < cu.B1) bsr_load<BS, NBK>(cur, bcol, val, b0, cu.B1, lane);
+  bool nxt_loaded = false;                                 // the first chunk of group nx is already in `nxt`
+  const int i = lane % BS;
+  double acc[KB];
+#pragma unroll
+  for (int k = 0; k < KB; k++) acc[k] = 0.0;
+  for (;;) {
+    if (b0 < cu.B1) {
+#pragma unroll
+      for (int u = 0; u < Regs::STEPS; u++) *reinterpret_cast<ksk::ks_d2v *>(sa + 128 * u + 2 * lane) = cur.a[u];
+      double xg[Regs::U][KB];
+#pragma unroll
+      for (int u = 0; u < Regs::U; u++) {
+        const long long xi = (long long)cur.c[u] * BS + (64 * u + lane) % BS;
+#pragma unroll
+        for (int k = 0; k < KB; k++) xg[u][k] = (cur.c[u] >= 0 && k < kb) ? X[k * ldx + xi] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < Regs::U; u++) {
+        const int t = 64 * u + lane;
+        if (t < NBK * BS) {
+#pragma unroll
+          for (int k = 0; k < KB; k++) sx[t * KB + k] = xg[u][k];
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const int bn = b0 + NBK;
+      if (bn < cu.B1) bsr_load<BS, NBK>(nxt, bcol, val, bn, cu.B1, lane);
+      else if (nx.B0 < nx.B1) { bsr_load<BS, NBK>(nxt, bcol, val, nx.B0, nx.B1, lane); nxt_loaded = true; }
+      const int lo = max(cu.p0, b0), hi = min(cu.p1, bn);
+      const double *av = sa + ((b0 * B2) & 1) + i * BS;
+      for (int p = lo; p < hi; p++) {
+        const double *ap = av + (p - b0) * B2, *xp = sx + (p - b0) * BS * KB;
+#pragma unroll
+        for (int c = 0; c < BS; c++) {
+          const double a = ap[c];
+#pragma unroll
+          for (int k = 0; k < KB; k++) acc[k] = fma(a, xp[c * KB + k], acc[k]);
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      if (bn < cu.B1) { cur = nxt; b0 = bn; continue; }
+    }
+    // this wave's block rows are complete
+    if (cu.has) {
+#pragma unroll
+      for (int k = 0; k < KB; k++) if (k < kb) __builtin_nontemporal_store(acc[k], Y + k * ldy + cu.r);
+    }
+#pragma unroll
+    for (int k = 0; k < KB; k++) acc[k] = 0.0;
+    g += gstep;
+    if (g >= gend) break;
+    cu = nx;
+    nx = g + gstep < gend ? bsr_rows<BS>(nb, brp, g + gstep, w, lane) : BsrRows{0, 0, 0, 0, 0, false};
+    b0 = cu.B0;
+    if (nxt_loaded) cur = nxt;
+    else if (b0 < cu.B1) bsr_load<BS, NBK>(cur, bcol, val, b0, cu.B1, lane);
+    nxt_loaded = false;
+  }
+}
+#define KS_BSR_SWITCH(bs, F) \
+  switch (bs) { case 2: F(2); break; case 3: F(3); break; case 4: F(4); break; case 5: F(5); break; case 6: F(6); break; case 7: F(7); break; default: F(8); break; }
+
 // ---- host side: the grid of each walk, the LDS of the pattern table, the bytes a layout must move ----------------------------------------------------
 struct LaunchGrid { unsigned blocks; int remap; };
 static inline LaunchGrid dict_launch_grid(ks_mat A, int rows_per_lane = 1)   // dictionary forms: up to 64 workgroups per CU (the pair form, rows_per_lane = 2: groups of 512 rows)
@@ -227,6 +359,14 @@ static inline LaunchGrid window_launch_grid(ks_mat A)              // windowed C
   const int remap = nb >= 64 ? 1 : 0;
   return {(unsigned)(remap ? (nb + 7) / 8 * 8 : nb), remap};
 }
+static inline LaunchGrid bsr_launch_grid(ks_mat A, int per_cu)      // block CSR: per_cu workgroups of four waves per CU, a group of bsr_group_rows block rows per step; a multiple of 8 as for the CSR row blocks
+{
+  const int gr = bsr_group_rows(A->bsr_bs);
+  long long nb = std::min<long long>(((long long)A->bsr_nb + gr - 1) / gr, (long long)A->ctx->num_cu * per_cu);
+  const int remap = nb >= 64 ? 1 : 0;
+  if (remap) nb = (nb / 8) * 8;
+  return {(unsigned)nb, remap};
+}
 static inline size_t dict_pair_lds_bytes(ks_mat A) { return (size_t)A->dict_npat * (3 * A->pr_args.nb * sizeof(double) + sizeof(unsigned)); }   // the pair form's tables instead
 static inline bool pair_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 static inline bool pair_fits32(long long n) { return n * 8 <= (long long)PAIR_OOB_OFFSET; }        // the descriptor's 32-bit size, and PAIR_OOB_OFFSET stays outside it
@@ -241,7 +381,8 @@ static inline double layout_own_bytes(ks_mat A)
   case KS_MAT_LAYOUT_SELL: return 12.0 * A->s_entries + 4.0 * A->n;
   case KS_MAT_LAYOUT_WINDOW:                                                                   // values + codes or columns, row pointers, every window filled once, the segment lists and the two per-block tables
     return 10.0 * A->wn_entries + 12.0 * A->wn_direct_entries + 4.0 * (A->n + 1) + 512.0 * A->wn_segments + 4.0 * A->wn_segments + 8.0 * A->wn_blocks;
-  default: return 12.0 * A->nnz_d + 4.0 * (A->n + 1);                                        // the CSR stream
+  case KS_MAT_LAYOUT_BSR: return (8.0 * A->bsr_bs * A->bsr_bs + 4.0) * A->bsr_blocks + 4.0 * (A->bsr_nb + 1);      // values, one column per block, one pointer per block row
+  default: return 12.0 * A->nnz_d + 4.0 * (A->n + 1);                                       // the CSR stream
   }
 }
 #define KS_DICT_W_SWITCH(w, F) do { if ((w) == 8) { F(8); } else if ((w) == 32) { F(32); } else { F(16); } } while (0)

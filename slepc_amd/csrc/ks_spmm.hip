@@ -207,6 +207,22 @@ __global__ __launch_bounds__(256, 4) void k_spmm_csr(int n, const int *__restric
   }
 }
 
+// ---- block CSR (k_spmv_bsr's storage and walk, bsr_walk in ks_rows.cuh): KB chains per lane, the x of a (block, c) item gathered for every column of
+// the pass and parked side by side, so a row lane reads one value and KB consecutive x per fma set. Chunks of half the single-vector kernel's blocks: with
+// 8 columns the parked x of a full chunk would be up to 10.5 KB per wave next to 4 KB of values (58 KB per workgroup: two per CU); halved, a workgroup
+// holds at most 29 KB and the 94 registers of the widest form decide: five waves per SIMD. KB = 8 - registers and LDS allow it - or 4 for passes of up
+// to four columns (half the parked x, 62-80 registers); the columns past kb are neither gathered nor stored.
+template <int BS, int KB>
+__global__ __launch_bounds__(256, 3) void k_spmm_bsr(int nb, const int *__restrict__ brp, const int *__restrict__ bcol, const double *__restrict__ val,
+                                                     const double *__restrict__ X, long long ldx, double *__restrict__ Y, long long ldy, int kb, int xcd_remap)
+{
+  constexpr int NBK = bsr_chunk_blocks(BS) / 2;
+  __shared__ __attribute__((aligned(16))) double sa_all[4][128 * BsrRegs<BS, NBK>::STEPS];
+  __shared__ __attribute__((aligned(16))) double sx_all[4][NBK * BS * KB];
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  bsr_walk<BS, KB, NBK>(sa_all[w], sx_all[w], nb, brp, bcol, val, X, ldx, Y, ldy, kb, xcd_remap);
+}
+
 // X(:, 0:KB) column-major -> Xi (n x KB, row-major): thread = row; the loads of a column and the stores of a row block are contiguous
 template <int KB>
 __global__ __launch_bounds__(256) void k_spmm_pack(int n, const double *__restrict__ X, long long ldx, double *__restrict__ Xi)
@@ -251,6 +267,7 @@ int spmm_pass(ks_mat A, int kb, const double *X, long long ldx, double *Y, long 
   case KS_MAT_LAYOUT_DICT: variant = KS_SPMM_DICT; break;
   case KS_MAT_LAYOUT_ODICT: variant = KS_SPMM_ODICT; break;
   case KS_MAT_LAYOUT_SELL: variant = KS_SPMM_SELL; break;
+  case KS_MAT_LAYOUT_BSR: variant = KS_SPMM_BSR; break;
   }
   KsProfScope ps(ctx, KS_K_SPMV, alg, variant, layout_own_bytes(A) + (il ? 2.0 : 1.0) * xy);      // interleaved: the pack reads the pass's columns and writes them once more
   switch (A->layout) {
@@ -272,6 +289,15 @@ int spmm_pass(ks_mat A, int kb, const double *X, long long ldx, double *Y, long 
 #define MM_SELL(KB) hipLaunchKernelGGL((k_spmm_sell<KB>), dim3(lg.blocks), dim3(MM_BLOCK), 0, ctx->stream, A->n, A->nslices, A->s_ptr, A->s_len, A->s_col, A->s_val, X, ldx, Y, ldy, lg.remap)
     MM_KB_SWITCH(kb, MM_SELL);
 #undef MM_SELL
+    break;
+  }
+  case KS_MAT_LAYOUT_BSR: {
+    const LaunchGrid lg = bsr_launch_grid(A, 3);
+    if (lg.blocks == 0) break;
+#define MM_BSR(BS) do { if (kb <= 4) hipLaunchKernelGGL((k_spmm_bsr<BS, 4>), dim3(lg.blocks), dim3(256), 0, ctx->stream, A->bsr_nb, A->bsr_rowptr, A->bsr_col, A->bsr_val, X, ldx, Y, ldy, kb, lg.remap); \
+                        else hipLaunchKernelGGL((k_spmm_bsr<BS, 8>), dim3(lg.blocks), dim3(256), 0, ctx->stream, A->bsr_nb, A->bsr_rowptr, A->bsr_col, A->bsr_val, X, ldx, Y, ldy, kb, lg.remap); } while (0)
+    KS_BSR_SWITCH(A->bsr_bs, MM_BSR);
+#undef MM_BSR
     break;
   }
   default: {                                                                      // CSR row blocks (n >= 2048, not the CSR-vector form)
@@ -306,6 +332,7 @@ int ks_mat_mult_multi_internal(ks_mat A, int ncols, const double *X, int ldx, do
   bool loop = ncols == 1 || A->shell_mult || halo || A->n_orows > 0 || A->sht;      // sht: the transposed view of a row-sharded matrix, a reverse exchange per column
   switch (A->layout) {
   case KS_MAT_LAYOUT_DICT: case KS_MAT_LAYOUT_ODICT: case KS_MAT_LAYOUT_SELL: break;
+  case KS_MAT_LAYOUT_BSR: if (A->n < 2048) loop = true; break;                                           // small block matrices: the vector form (k_spmv_bsr_vec), as for CSR below
   case KS_MAT_LAYOUT_CSR: if (A->n < 2048 || A->csr_form == ks_mat_s::CSR_VEC) loop = true; break;      // the CSR-vector kernel: its sums are not in entry order
   case KS_MAT_LAYOUT_WINDOW: loop = true; break;                                                          // no block kernel: spmm_pass's default is the CSR block kernel, which would read the released d_col
   default: loop = true; break;                                                                            // BINNED, SLICED

@@ -359,6 +359,49 @@ __global__ __launch_bounds__(WIN_ROWS, 2) void k_spmv_window(int n, const int *_
 #define KS_WIN_STEPS 4      // chunks of 256 entries: 49.6 KB of LDS per workgroup, three workgroups per CU (8: 66.5 KB, two)
 #endif
 
+// ---- block CSR (KS_MAT_LAYOUT_BSR; the plan: ks_csr.h, the walk: bsr_walk, ks_rows.cuh) ----------------------------------------------------------------
+// A matrix of dense BS x BS node blocks, one 4-byte column per block: 8 + 4 / BS^2 bytes per stored scalar against the CSR stream's 12, and one gather
+// of BS contiguous doubles of x per block where the CSR kernels gather 8 bytes per scalar. The entry side of k_spmv_csr_wave, block by block: a wave
+// owns the 64 / BS block rows of at most 64 scalar rows, whose blocks are one contiguous run; it streams that run in chunks of bsr_chunk_blocks(BS)
+// whole blocks - at most 512 scalars, four 16-byte nontemporal loads per lane, never a lane-per-row load of the value stream (one 128-byte line per
+// block row) - and parks values and x in its own 6 KB of LDS. y is bit for bit the CSR kernels' y on the expansion.
+template <int BS>
+__global__ __launch_bounds__(256, 4) void k_spmv_bsr(int nb, const int *__restrict__ brp, const int *__restrict__ bcol, const double *__restrict__ val,
+                                                     const double *__restrict__ x, double *__restrict__ y, int xcd_remap)
+{
+  constexpr int NB = bsr_chunk_blocks(BS);
+  __shared__ __attribute__((aligned(16))) double sa_all[4][128 * BsrRegs<BS, NB>::STEPS];
+  __shared__ double sx_all[4][NB * BS];
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  bsr_walk<BS, 1, NB>(sa_all[w], sx_all[w], nb, brp, bcol, val, x, 0, y, 0, 1, xcd_remap);
+}
+// The same storage for the small matrices (fewer than 2048 local rows), which the CSR layout gives to the CSR-vector kernel k_spmv_csr: 64 rows per wave
+// leave most of the machine idle there. G lanes share a scalar row exactly as there - lane g takes entries g, g + G, ... of the row's expansion by fma
+// from 0.0, then the butterfly of group_reduce - so y is bit for bit k_spmv_csr<G>'s on the expansion (G = lanes_per_row, picked from the expansion at
+// assembly): a block matrix has the bits of its CSR expansion at every size. Entry p of scalar row bs I + i is (block p / bs of block row I, column
+// p % bs). The block size is a runtime argument: nothing here is tuned per size.
+template <int G>
+__global__ __launch_bounds__(SPMV_BLOCK) void k_spmv_bsr_vec(int n, int bs, const int *__restrict__ brp, const int *__restrict__ bcol, const double *__restrict__ val,
+                                                             const double *__restrict__ x, double *__restrict__ y)
+{
+  constexpr int GPW = 64 / G;
+  const int lane = threadIdx.x & 63, gi = lane / G, lane_g = lane % G;
+  const long long wave = ((long long)blockIdx.x * SPMV_BLOCK + threadIdx.x) >> 6, nwaves = ((long long)gridDim.x * SPMV_BLOCK) >> 6;
+  for (long long wb = wave * GPW; wb < n; wb += nwaves * GPW) {
+    const long long r = wb + gi;
+    double acc = 0.0;
+    if (r < n) {
+      const int I = (int)(r / bs), i = (int)(r - (long long)I * bs), k0 = brp[I], len = (brp[I + 1] - k0) * bs;
+      for (int p = lane_g; p < len; p += G) {
+        const int k = p / bs, c = p - k * bs;
+        acc = fma(val[((long long)(k0 + k) * bs + i) * bs + c], x[(long long)bcol[k0 + k] * bs + c], acc);
+      }
+    }
+    const double t = group_reduce<G>(acc);
+    if (lane_g == 0 && r < n) __builtin_nontemporal_store(t, y + r);
+  }
+}
+
 // ---- sliced ELL (SELL-64) ---------------------------------------------------------------------------
 // lane <-> row: every val/col load of a wavefront is one contiguous run, the x gather of a
 // stencil matrix is contiguous too (consecutive rows -> consecutive columns), y is stored 512 B per wave,
@@ -848,6 +891,7 @@ static int spmv_variant(ks_mat A)
   case KS_MAT_LAYOUT_ODICT: return KS_SPMV_ODICT;
   case KS_MAT_LAYOUT_SELL: return KS_SPMV_SELL;
   case KS_MAT_LAYOUT_WINDOW: return KS_SPMV_WINDOW;
+  case KS_MAT_LAYOUT_BSR: return KS_SPMV_BSR;
   }
   return KS_SPMV_CSR;
 }
@@ -930,6 +974,22 @@ static int mult_assembled(ks_mat A, const double *x, double *y, const double *ro
       const LaunchGrid lg = window_launch_grid(A);
       hipLaunchKernelGGL((k_spmv_window<KS_WIN_STEPS>), dim3(lg.blocks), dim3(WIN_ROWS), 0, ctx->stream, A->n, A->d_rowptr, A->wn_codes, A->wn_dcol, A->d_val,
                          A->wn_segptr, A->wn_seg, A->wn_dbase, x, y, lg.remap);
+      break;
+    }
+    case KS_MAT_LAYOUT_BSR: {
+      const LaunchGrid lg = bsr_launch_grid(A, 4);
+      if (lg.blocks == 0) break;                 // a rank without rows
+      if (A->n < 2048) {                         // small matrices: the CSR-vector walk on the blocks, as the CSR layout does below
+        const int gpw = 64 / A->lanes_per_row;
+        const unsigned nbv = (unsigned)std::max<long long>(1, std::min<long long>(((long long)A->n + 4 * gpw - 1) / (4 * gpw), (long long)ctx->num_cu * 32));
+#define SPMV_BSR_VEC(G) hipLaunchKernelGGL((k_spmv_bsr_vec<G>), dim3(nbv), dim3(SPMV_BLOCK), 0, ctx->stream, A->n, A->bsr_bs, A->bsr_rowptr, A->bsr_col, A->bsr_val, x, y)
+        switch (A->lanes_per_row) { case 2: SPMV_BSR_VEC(2); break; case 4: SPMV_BSR_VEC(4); break; case 8: SPMV_BSR_VEC(8); break; case 16: SPMV_BSR_VEC(16); break; case 32: SPMV_BSR_VEC(32); break; default: SPMV_BSR_VEC(64); break; }
+#undef SPMV_BSR_VEC
+        break;
+      }
+#define SPMV_BSR(BS) hipLaunchKernelGGL((k_spmv_bsr<BS>), dim3(lg.blocks), dim3(256), 0, ctx->stream, A->bsr_nb, A->bsr_rowptr, A->bsr_col, A->bsr_val, x, y, lg.remap)
+      KS_BSR_SWITCH(A->bsr_bs, SPMV_BSR);
+#undef SPMV_BSR
       break;
     }
     default:                                   // CSR

@@ -215,6 +215,12 @@ struct ks_mat_s {
   int *wn_dcol = nullptr;                     // [direct entries + gaps + CW_PAD]
   int *wn_segptr = nullptr, *wn_seg = nullptr, *wn_dbase = nullptr;      // [blocks + 1], [wn_segments], [blocks] (ksc::WIN_NOT_DIRECT: a window block)
   long long wn_blocks = 0, wn_direct_blocks = 0, wn_entries = 0, wn_direct_entries = 0, wn_segments = 0;
+  // Block CSR (KS_MAT_LAYOUT_BSR, only from ks_mat_create_bsr; the plan: ks_csr.h): the diagonal block as bsr_nb block rows of bsr_bs x bsr_bs blocks - one
+  // int per block row, one LOCAL block column per block, the values block after block in stored order, every block row-major. No per-entry index:
+  // d_col and d_val are released
+  int bsr_bs = 0, bsr_nb = 0; long long bsr_blocks = 0;
+  int *bsr_rowptr = nullptr, *bsr_col = nullptr;    // [bsr_nb + 1], [bsr_blocks + CW_PAD]
+  double *bsr_val = nullptr;                        // [bsr_blocks bs bs + CW_PAD]
   // off-diagonal block (columns owned by other ranks), compressed to ghost indices [0,nghost)
   int *o_rowptr = nullptr; int *o_col = nullptr; double *o_val = nullptr; long long nnz_o = 0;
   int nghost = 0;
@@ -253,10 +259,18 @@ static inline size_t ks_binned_lds2(int wr) { return (size_t)4 * (wr + 1) * 8; }
 constexpr int WIN_ROWS = KS_WIN_ROWS, WIN_SMAX = KS_WIN_SMAX;
 static_assert(WIN_ROWS == 256 || WIN_ROWS == 64, "a block is one workgroup of four waves or one wave");
 static_assert(WIN_SMAX >= 1 && WIN_SMAX * 64 <= 65536, "a code is slot * 64 + (col & 63) in 16 bits");
+// Block CSR: a wave takes the block rows that fill at most 64 scalar rows, a workgroup four waves' worth per step; the values stream in chunks of whole
+// blocks that fit 512 scalars (one more for the aligned start of an odd block size): four 16-byte loads per lane - and of at most 64 blocks, one block
+// column per lane (bs = 2: 256 scalars). The choice: DESIGN section 31.
+constexpr int BSR_BS_MIN = 2, BSR_BS_MAX = 8;
+constexpr int bsr_wave_rows(int bs) { return 64 / bs; }
+constexpr int bsr_group_rows(int bs) { return 4 * bsr_wave_rows(bs); }
+constexpr int bsr_chunk_blocks(int bs) { return 512 / (bs * bs) < 64 ? 512 / (bs * bs) : 64; }
 int ks_binned_prepare(size_t lds1, size_t lds2);            // lets the two kernels have that much dynamic LDS (they live in ks_spmv.hip)
 // `variant` of a KS_K_SPMV profile record: which product kernel ran (bench.py and the profiles key on the values)
 enum KsSpmvVariant { KS_SPMV_CSR = 0, KS_SPMV_SELL = 8, KS_SPMV_DICT = 16, KS_SPMV_ODICT = 17, KS_SPMV_BINNED = 18, KS_SPMV_WINDOW = 19,      // k_spmv_csr*, k_spmv_sell<4>, k_spmv_dict, k_spmv_odict, k_binned_*, k_spmv_window
-                     KS_SPMM_DICT = 20, KS_SPMM_ODICT = 21, KS_SPMM_SELL = 22, KS_SPMM_CSR = 23, KS_SPMM_CSR_IL = 24 };    // k_spmm_*; 24: k_spmm_pack + k_spmm_csr (interleaved)
+                     KS_SPMM_DICT = 20, KS_SPMM_ODICT = 21, KS_SPMM_SELL = 22, KS_SPMM_CSR = 23, KS_SPMM_CSR_IL = 24,    // k_spmm_*; 24: k_spmm_pack + k_spmm_csr (interleaved)
+                     KS_SPMV_BSR = 25, KS_SPMM_BSR = 26 };                                                                 // k_spmv_bsr, k_spmm_bsr
 int ks_mat_get_diagonal_internal(ks_mat A, double *d_dev);
 int ks_mat_mult_transpose_internal(ks_mat A, const double *x, double *y);
 int ks_st_apply_transpose_internal(ks_st st, const double *x, double *y);
